@@ -14,6 +14,11 @@
 One process per GPU; for N>1 launch with torch.distributed.run (RCCL): independent graphs shard
 across ranks with no data-path collective ("scaling": "weak"); the barrier + max-over-ranks timing
 uses torch.distributed.
+
+A plain run does only what `value` needs: set up, warm up, time the `--steps` LM iterations of the batch (as a stream group, see
+`--streams`), write the outputs if `--dump-outputs DIR` is given, print the JSON line.  `--full` adds everything else this script
+measures: the per-kernel pass and its rooflines, the frontend, the tick replays, single-graph latency, Schur + PCG, plane landmarks
+and the CPU baselines.
 """
 import argparse
 import json
@@ -26,6 +31,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_HBM_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E ~8 TB/s
+HOST_WORKERS = 16       # host processes / threads of the setup: a GPU host shares its cores, more than this only slows setup down
+DUMP_GRAPHS = 32        # graphs whose final estimates --dump-outputs writes (a fixed, seeded sample of the batch)
 
 
 def pmc_traffic(name, algorithmic_bytes):
@@ -51,7 +58,7 @@ def generate_graphs(kind, poses, landmarks, seeds, cache_dir):
     jobs = [(int(sd), os.path.join(cache_dir, f"{kind}_{poses}_{landmarks}_{int(sd)}.g2o")) for sd in seeds]
     todo = [sd for sd, p in jobs if not (os.path.exists(p) and os.path.getsize(p) > 0)]
     if todo:
-        nproc = max(1, min(len(todo), len(os.sched_getaffinity(0)), 48))
+        nproc = max(1, min(len(todo), len(os.sched_getaffinity(0)), HOST_WORKERS))
         procs = []
         for w in range(nproc):
             mine = todo[w::nproc]
@@ -64,18 +71,51 @@ def generate_graphs(kind, poses, landmarks, seeds, cache_dir):
     return [p for _, p in jobs]
 
 
-def build_batch(paths, n, dev, solver):
-    from semantic_slam_amd import GraphSLAM, GraphBatch
-    graphs = []
-    for k in range(n):
+def load_graphs(paths, n, dev, solver):
+    """`n` graphs from the .g2o files (tiled), parsed by a pool of threads: the C parser runs without the GIL."""
+    from concurrent.futures import ThreadPoolExecutor
+    from semantic_slam_amd import GraphSLAM
+
+    def one(k):
         G = GraphSLAM(False, dev)
         G.load(paths[k % len(paths)])
         if solver >= 0:
             G.set_option("solver", solver)
-        graphs.append(G)
-    batch = GraphBatch(graphs)
+        return G
+    with ThreadPoolExecutor(max_workers=max(1, min(n, len(os.sched_getaffinity(0)), HOST_WORKERS))) as ex:
+        return list(ex.map(one, range(n)))
+
+
+def build_batch(paths, n, dev, solver):
+    from semantic_slam_amd import GraphBatch
+    batch = GraphBatch(load_graphs(paths, n, dev, solver))
     batch.upload()
     return batch
+
+
+def edge_counts(path):
+    """(SE3 edges, landmark edges) of one .g2o file"""
+    eo = el = 0
+    with open(path) as f:
+        for ln in f:
+            if ln.startswith("EDGE_SE3:QUAT "):
+                eo += 1
+            elif ln.startswith("EDGE_"):
+                el += 1
+    return eo, el
+
+
+def dump_outputs(out_dir, batch, stats):
+    """What the timed path hands its caller after the last step, as float64 .npy files: the per-graph results of the optimisation
+    and the final estimates ([graphs, vertices, 7], point landmarks zero-padded) of a fixed, seeded sample of the batch's graphs."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name in ("iterations", "trials", "status", "chi2_before", "chi2_after", "lambda_", "solver_iterations"):
+        np.save(os.path.join(out_dir, f"{name.rstrip('_')}.npy"), np.array([getattr(s, name) for s in stats], np.float64))
+    batch.download()
+    pick = np.sort(np.random.default_rng(0).choice(len(batch.graphs), size=min(DUMP_GRAPHS, len(batch.graphs)), replace=False))
+    np.save(os.path.join(out_dir, "estimates.npy"), np.stack([batch.graphs[int(g)].estimates() for g in pick]))
+    np.save(os.path.join(out_dir, "estimates_graph_index.npy"), pick.astype(np.float64))
 
 
 def timed_optimize(batch, steps, warmup, sync_all):
@@ -450,6 +490,11 @@ def main():
     ap.add_argument("--edge-sharded", action="store_true",
                     help="N > 1: every rank holds the SAME batch, builds the partial normal equations of its edge shard and the ranks "
                          "all-reduce [H || b] over RCCL each LM step (SURVEY 8e mode E / BASELINE.json configs[4]); strong scaling")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: per-kernel pass + rooflines, frontend, tick replays, single graph, "
+                         "Schur + PCG, plane landmarks, CPU baselines (the --no-* / --plane-* options below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (float64; rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-frontend", action="store_true")
     ap.add_argument("--no-single", action="store_true", help="skip the single-graph latency section (used under rocprofv3 --pmc)")
@@ -493,6 +538,13 @@ def main():
     dev = local_rank if world > 1 else 0
     ddev = "cuda" if dist is not None else None
 
+    # one process: the interval and the count are the whole job's (D's helpers would load torch just to return them)
+    def max_over_ranks(seconds):
+        return D.max_over_ranks(seconds, device=ddev) if dist is not None else seconds
+
+    def aggregate_throughput(units, seconds):
+        return D.aggregate_throughput(units, seconds, device=ddev) if dist is not None else units / seconds
+
     def sync_all():
         if dist is not None:
             import torch
@@ -508,17 +560,26 @@ def main():
     t_setup = time.time()
     n_distinct = args.batch if args.distinct < 0 else max(1, min(args.distinct, args.batch))
     paths = generate_graphs("point", args.poses, args.landmarks, seeds_of(n_distinct), args.cache_dir)
-    # the first graphs again as flat arrays: problem sizes for the byte accounting and the cpu_baseline leg
-    problems = [GraphProblem.from_synth(make_graph(args.poses, args.landmarks, seed=sd)) for sd in seeds_of(min(n_distinct, 4))]
-    batch = build_batch(paths, args.batch, dev, args.solver)
-    if sharded:
-        D.init_edge_sharded(batch, device=ddev)   # RCCL communicator inside the library; all-reduce issued from the C++ LM loop
+    Eo, El = edge_counts(paths[0])
+    n_streams = 1 if (sharded or args.streams <= 1 or args.solver in (0, 2)) else min(args.streams, args.batch)
+    graphs = load_graphs(paths, args.batch, dev, args.solver)
+
+    def make_batch(streams):
+        b = GraphBatch(graphs, streams=streams) if streams > 1 else GraphBatch(graphs)
+        b.upload()
+        if sharded:
+            D.init_edge_sharded(b, device=ddev)   # RCCL communicator inside the library; all-reduce issued from the C++ LM loop
+        return b
+    if args.full:
+        # the first graphs again as flat arrays: the cpu_baseline leg
+        problems = [GraphProblem.from_synth(make_graph(args.poses, args.landmarks, seed=sd)) for sd in seeds_of(min(n_distinct, 4))]
+        batch = make_batch(1)
     setup_s = time.time() - t_setup
 
     # ---- warmup (untimed), reset to the initial estimates, K timed steps ---------------------------
-    # Two passes over the same graphs.  (1) kernel pass: ONE batch-synchronous batch on one stream with hipEvents round every kernel
-    # group -> kernel_ms and the rooflines (launches that overlap on the chip cannot be timed one by one).  (2) the timed region of
-    # `value`: the same batch as a stream group (--streams parts, each on its own stream + host thread, events off); identical results.
+    # The timed region of `value`: the batch as a stream group (--streams parts, each on its own stream + host thread, events off).
+    # --full runs a kernel pass before it over the same graphs: ONE batch-synchronous batch on one stream with hipEvents round every
+    # kernel group -> kernel_ms and the rooflines (launches that overlap on the chip cannot be timed one by one); identical results.
     def timed(bt, profiling):
         if args.warmup > 0:
             bt.optimize(args.warmup)
@@ -528,92 +589,111 @@ def main():
         t0_ = time.perf_counter()
         st_ = bt.optimize(args.steps)       # blocks until every stream of the batch is idle
         sync_all()
-        return st_, D.max_over_ranks(time.perf_counter() - t0_, device=ddev)
+        return st_, max_over_ranks(time.perf_counter() - t0_)
 
-    stats, dt_single = timed(batch, True)
-    iters = [int(s.iterations) for s in stats]
-    iters_total = float(sum(iters))
-    steps_done = max(iters) if iters else 0
-    n_streams = 1 if (sharded or args.streams <= 1 or args.solver in (0, 2)) else min(args.streams, args.batch)
-    dt = dt_single
     single_stream = None
-    if n_streams > 1:
+    if not args.full:
+        group_error = None
         try:
-            group = GraphBatch(batch.graphs, streams=n_streams)
-            gstats, dt = timed(group, False)
-            if [int(s.iterations) for s in gstats] != iters or [int(s.trials) for s in gstats] != [int(s.trials) for s in stats]:
-                raise RuntimeError("stream group and single-stream batch disagree on iterations / trials")
-            single_stream = {"value": round(D.aggregate_throughput(iters_total, dt_single, device=ddev), 3),
-                             "ms_per_step": round(1e3 * dt_single / max(steps_done, 1), 4),
-                             "note": "the same steps by one batch-synchronous batch on one stream, hipEvents round every kernel group on: "
-                                     "the pass kernel_ms and the rooflines are taken from"}
-            del group
-        except Exception as e:   # the headline falls back to the single-stream pass (multi-rank runs must not diverge: re-raise there)
-            if dist is not None:
+            batch = make_batch(n_streams)
+            stats, dt = timed(batch, False)
+        except Exception as e:   # the headline falls back to a single-stream batch (multi-rank runs must not diverge: re-raise there)
+            if dist is not None or n_streams <= 1:
                 raise
-            n_streams, dt = 1, dt_single
-            single_stream = {"error": f"stream group failed, value is the single-stream pass: {str(e)[:160]}"}
+            group_error = f"stream group failed, value is the single-stream pass: {str(e)[:160]}"
+        if group_error is not None:
+            batch, n_streams = None, 1
+            batch = make_batch(1)
+            stats, dt = timed(batch, False)
+            single_stream = {"error": group_error}
+        timed_batch, timed_stats = batch, stats
+        iters = [int(s.iterations) for s in stats]
+        iters_total = float(sum(iters))
+        steps_done = max(iters) if iters else 0
+    else:
+        stats, dt_single = timed(batch, True)
+        iters = [int(s.iterations) for s in stats]
+        iters_total = float(sum(iters))
+        steps_done = max(iters) if iters else 0
+        dt = dt_single
+        timed_batch, timed_stats = batch, stats
+        if n_streams > 1:
+            try:
+                group = GraphBatch(batch.graphs, streams=n_streams)
+                gstats, dt = timed(group, False)
+                if [int(s.iterations) for s in gstats] != iters or [int(s.trials) for s in gstats] != [int(s.trials) for s in stats]:
+                    raise RuntimeError("stream group and single-stream batch disagree on iterations / trials")
+                single_stream = {"value": round(aggregate_throughput(iters_total, dt_single), 3),
+                                 "ms_per_step": round(1e3 * dt_single / max(steps_done, 1), 4),
+                                 "note": "the same steps by one batch-synchronous batch on one stream, hipEvents round every kernel group on: "
+                                         "the pass kernel_ms and the rooflines are taken from"}
+                timed_batch, timed_stats = group, gstats
+            except Exception as e:   # the headline falls back to the single-stream pass (multi-rank runs must not diverge: re-raise there)
+                if dist is not None:
+                    raise
+                n_streams, dt = 1, dt_single
+                single_stream = {"error": f"stream group failed, value is the single-stream pass: {str(e)[:160]}"}
     # whole-job value: graph-iterations actually performed by ALL ranks / max-over-ranks time (replicas: no data-path collective)
-    value = iters_total / dt if sharded else D.aggregate_throughput(iters_total, dt, device=ddev)
+    value = iters_total / dt if sharded else aggregate_throughput(iters_total, dt)
 
-    # ---- kernel times (hipEvents on the batch's stream, inside the timed region) -------------------
-    # The LM rounds of a batch of distinct graphs mix full launches with partial ones (a round in which only the graphs that retry a
-    # rejected trial take part): `achieved` = algorithmic bytes of the work ACTUALLY done in the timed region (per-graph bytes x graph
-    # builds / graph factorisations performed) / the kernels' total time there.  The same kernels timed on the whole batch
-    # (every graph taking part) are reported next to it as `full_batch`.
-    names = ["linearize", "chi2", "spmv", "pcg_update", "precond", "oplus", "factor", "solve"]
-    ktimes = {n: batch.kernel_time(n) for n in names}
-    batch.set_profiling(False)
-    dominant = max(ktimes, key=lambda n: ktimes[n][0])
-    Eo = int((problems[0].etype == 0).sum()); El = problems[0].ne - Eo
-    jac_bytes = batch.linearize_bytes()            # whole batch, one build of every graph
     trials_total = int(sum(int(s.trials) for s in stats))
-    lin_ms, lin_n = ktimes["linearize"]
-    jac_done = jac_bytes / args.batch * iters_total            # every LM iteration of a graph builds its system once
-    jac_gbs = jac_done / (lin_ms * 1e-3) / 1e9 if lin_ms > 0 else 0.0
-    full_lin_ms = batch.time_linearize(10)
-    roof_jac = {"bound": "hbm", "kernel": "jacobian_build", "achieved": round(jac_gbs, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                "frac": round(jac_gbs / PEAK_HBM_GBS, 4), "traffic": None, "measured_in": "single-stream pass of the same steps (hipEvents per kernel group)",
-                "bytes_per_launch": jac_bytes, "graph_builds_in_region": int(iters_total), "ms_in_region": round(lin_ms, 3), "launches": lin_n,
-                "full_batch": {"ms_per_launch": round(full_lin_ms, 5), "achieved": round(jac_bytes / (full_lin_ms * 1e-3) / 1e9, 2),
-                               "frac": round(jac_bytes / (full_lin_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4), "ms_per_512_graphs": round(full_lin_ms * 512 / args.batch, 5)}}
-    t, raw, src = pmc_traffic("jacobian_build", jac_bytes)
-    if t is not None:
-        roof_jac.update({"traffic": t, "traffic_raw_counters": raw, "traffic_source": src,
-                         "traffic_kind": f"static: the committed rocprofv3 PMC passes over one launch of the same {args.batch}-graph workload, not collected in this run"})
-    roofline = roof_jac
-    roof_factor = None
-    if ktimes["factor"][1] > 0:
-        fbytes = int(batch.info("factor_bytes"))   # whole batch, one factorisation of every graph
-        f_done = fbytes / args.batch * trials_total
-        gbs = f_done / (ktimes["factor"][0] * 1e-3) / 1e9
-        full_f_ms, full_s_ms = batch.time_solver(5)
-        roof_factor = {"bound": "hbm", "kernel": "block_cholesky_factor (all kernels of one numeric factorisation + fused forward solve)",
-                       "achieved": round(gbs, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": None,
-                       "measured_in": "single-stream pass of the same steps (hipEvents per kernel group)", "bytes_per_launch": fbytes, "graph_factorisations_in_region": trials_total, "ms_in_region": round(ktimes["factor"][0], 3),
-                       "launches": ktimes["factor"][1],
-                       "full_batch": {"ms_per_launch": round(full_f_ms, 4), "achieved": round(fbytes / (full_f_ms * 1e-3) / 1e9, 2),
-                                      "frac": round(fbytes / (full_f_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4), "backward_solve_ms": round(full_s_ms, 4),
-                                      "ms_per_512_graphs": round(full_f_ms * 512 / args.batch, 4), "backward_solve_ms_per_512_graphs": round(full_s_ms * 512 / args.batch, 4)},
-                       "levels": int(batch.info("factor_levels")), "factor_doubles": int(batch.info("factor_lnz")),
-                       "note": "algorithmic bytes = read H, b once + write L, y once per graph factorisation"}
-        t, raw, src = pmc_traffic("factor", fbytes)
+    if args.full:
+        # ---- kernel times (hipEvents on the batch's stream, inside the timed region) -------------------
+        # The LM rounds of a batch of distinct graphs mix full launches with partial ones (a round in which only the graphs that retry a
+        # rejected trial take part): `achieved` = algorithmic bytes of the work ACTUALLY done in the timed region (per-graph bytes x graph
+        # builds / graph factorisations performed) / the kernels' total time there.  The same kernels timed on the whole batch
+        # (every graph taking part) are reported next to it as `full_batch`.
+        names = ["linearize", "chi2", "spmv", "pcg_update", "precond", "oplus", "factor", "solve"]
+        ktimes = {n: batch.kernel_time(n) for n in names}
+        batch.set_profiling(False)
+        dominant = max(ktimes, key=lambda n: ktimes[n][0])
+        jac_bytes = batch.linearize_bytes()            # whole batch, one build of every graph
+        lin_ms, lin_n = ktimes["linearize"]
+        jac_done = jac_bytes / args.batch * iters_total            # every LM iteration of a graph builds its system once
+        jac_gbs = jac_done / (lin_ms * 1e-3) / 1e9 if lin_ms > 0 else 0.0
+        full_lin_ms = batch.time_linearize(10)
+        roof_jac = {"bound": "hbm", "kernel": "jacobian_build", "achieved": round(jac_gbs, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": round(jac_gbs / PEAK_HBM_GBS, 4), "traffic": None, "measured_in": "single-stream pass of the same steps (hipEvents per kernel group)",
+                    "bytes_per_launch": jac_bytes, "graph_builds_in_region": int(iters_total), "ms_in_region": round(lin_ms, 3), "launches": lin_n,
+                    "full_batch": {"ms_per_launch": round(full_lin_ms, 5), "achieved": round(jac_bytes / (full_lin_ms * 1e-3) / 1e9, 2),
+                                   "frac": round(jac_bytes / (full_lin_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4), "ms_per_512_graphs": round(full_lin_ms * 512 / args.batch, 5)}}
+        t, raw, src = pmc_traffic("jacobian_build", jac_bytes)
         if t is not None:
-            roof_factor.update({"traffic": t, "traffic_raw_counters": raw, "traffic_source": src,
-                                "traffic_kind": f"static: the committed rocprofv3 PMC passes over one launch of the same {args.batch}-graph workload, not collected in this run"})
-        if dominant == "factor":
-            roofline = roof_factor
-    if dominant == "spmv" and ktimes["spmv"][1] > 0:
-        # H bytes + 3 vectors x 8*dim per block-SpMV
-        Np, Nl = args.poses - 1, args.landmarks
-        h_bytes = 8 * (36 * Np + 9 * Nl + 36 * Eo + 18 * El)
-        spmv_bytes = args.batch * (h_bytes + 3 * 8 * (6 * Np + 3 * Nl))
-        ms = ktimes["spmv"][0] / ktimes["spmv"][1]
-        gbs = spmv_bytes / (ms * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "kernel": "pcg_block_spmv", "achieved": round(gbs, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": None, "bytes_per_launch": spmv_bytes,
-                    "ms_per_launch": round(ms, 5), "launches": ktimes["spmv"][1],
-                    "note": "bytes assume every still-active graph; converged graphs early-exit"}
+            roof_jac.update({"traffic": t, "traffic_raw_counters": raw, "traffic_source": src,
+                             "traffic_kind": f"static: the committed rocprofv3 PMC passes over one launch of the same {args.batch}-graph workload, not collected in this run"})
+        roofline = roof_jac
+        roof_factor = None
+        if ktimes["factor"][1] > 0:
+            fbytes = int(batch.info("factor_bytes"))   # whole batch, one factorisation of every graph
+            f_done = fbytes / args.batch * trials_total
+            gbs = f_done / (ktimes["factor"][0] * 1e-3) / 1e9
+            full_f_ms, full_s_ms = batch.time_solver(5)
+            roof_factor = {"bound": "hbm", "kernel": "block_cholesky_factor (all kernels of one numeric factorisation + fused forward solve)",
+                           "achieved": round(gbs, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": None,
+                           "measured_in": "single-stream pass of the same steps (hipEvents per kernel group)", "bytes_per_launch": fbytes, "graph_factorisations_in_region": trials_total, "ms_in_region": round(ktimes["factor"][0], 3),
+                           "launches": ktimes["factor"][1],
+                           "full_batch": {"ms_per_launch": round(full_f_ms, 4), "achieved": round(fbytes / (full_f_ms * 1e-3) / 1e9, 2),
+                                          "frac": round(fbytes / (full_f_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4), "backward_solve_ms": round(full_s_ms, 4),
+                                          "ms_per_512_graphs": round(full_f_ms * 512 / args.batch, 4), "backward_solve_ms_per_512_graphs": round(full_s_ms * 512 / args.batch, 4)},
+                           "levels": int(batch.info("factor_levels")), "factor_doubles": int(batch.info("factor_lnz")),
+                           "note": "algorithmic bytes = read H, b once + write L, y once per graph factorisation"}
+            t, raw, src = pmc_traffic("factor", fbytes)
+            if t is not None:
+                roof_factor.update({"traffic": t, "traffic_raw_counters": raw, "traffic_source": src,
+                                    "traffic_kind": f"static: the committed rocprofv3 PMC passes over one launch of the same {args.batch}-graph workload, not collected in this run"})
+            if dominant == "factor":
+                roofline = roof_factor
+        if dominant == "spmv" and ktimes["spmv"][1] > 0:
+            # H bytes + 3 vectors x 8*dim per block-SpMV
+            Np, Nl = args.poses - 1, args.landmarks
+            h_bytes = 8 * (36 * Np + 9 * Nl + 36 * Eo + 18 * El)
+            spmv_bytes = args.batch * (h_bytes + 3 * 8 * (6 * Np + 3 * Nl))
+            ms = ktimes["spmv"][0] / ktimes["spmv"][1]
+            gbs = spmv_bytes / (ms * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "kernel": "pcg_block_spmv", "achieved": round(gbs, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                        "frac": round(gbs / PEAK_HBM_GBS, 4), "traffic": None, "bytes_per_launch": spmv_bytes,
+                        "ms_per_launch": round(ms, 5), "launches": ktimes["spmv"][1],
+                        "note": "bytes assume every still-active graph; converged graphs early-exit"}
 
     out = {
         "metric": "graph-optimize LM iters/sec (5k poses, 1k landmarks)",
@@ -628,28 +708,31 @@ def main():
                    "solver": int(args.solver), "streams": n_streams,
                    "parallelism": (f"edge-sharded x{world}: RCCL all-reduce of [H || b] per LM step" if sharded else f"replicas x{world}")},
         "steps_done": steps_done, "iters_min": min(iters), "iters_max": max(iters),
-        "trial_rounds": int(ktimes["factor"][1] or ktimes["spmv"][1] and ktimes["precond"][1]),
         "lm_trials_total": trials_total, "distinct_graphs": len(paths),
         "graphs_terminated": int(sum(1 for s in stats if s.status == 1)),
         "timed_seconds": round(dt, 4), "single_stream": single_stream,
         "keyframes_landmarks_per_sec": round(value * (args.poses + args.landmarks), 1),
         "chi2_after": stats[0].chi2_after, "lm_trials": stats[0].trials, "solver_iterations": stats[0].solver_iterations,
-        "roofline": roofline, "roofline_jacobian_build": roof_jac,
-        "kernel_ms": {n: [round(v[0], 3), v[1]] for n, v in ktimes.items() if v[1]},
         "setup_seconds": round(setup_s, 1),
     }
-    if roof_factor is not None:
-        out["roofline_factor"] = roof_factor
+    if args.full:
+        out.update({"trial_rounds": int(ktimes["factor"][1] or ktimes["spmv"][1] and ktimes["precond"][1]),
+                    "roofline": roofline, "roofline_jacobian_build": roof_jac,
+                    "kernel_ms": {n: [round(v[0], 3), v[1]] for n, v in ktimes.items() if v[1]}})
+        if roof_factor is not None:
+            out["roofline_factor"] = roof_factor
     if sharded:
         # evidence that RCCL saw `world` ranks: the all-reduce calls this rank issued inside the LM loop and what each of them summed
         out["collective"] = {"backend": "rccl (ncclAllReduce, ncclDouble, sum, out of place)", "world": world,
                              "allreduce_calls": int(batch.info("allreduce_calls")),
                              "bytes_per_call": int(8 * (batch.info("h_doubles") + batch.info("dim"))),
                              "note": "one call per Jacobian build of the batch: [H || b] of every graph, rank-partial buffer -> full system"}
-    del batch
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_batch, timed_stats)
+    del batch, timed_batch, graphs
 
     frontend = None
-    if not args.no_frontend:   # every rank: the frames shard across ranks
+    if args.full and not args.no_frontend:   # every rank: the frames shard across ranks
         try:
             frontend = bench_frontend(dev, cpu_baseline=(not args.no_cpu_baseline and world == 1 and rank == 0), dist=dist, ddev=ddev)
         except Exception as e:
@@ -659,7 +742,7 @@ def main():
     if rank == 0:
         if frontend is not None:
             out["frontend"] = frontend
-        if not args.no_single:
+        if args.full and not args.no_single:
             try:
                 out["tick_replay"] = bench_tick(dev, cpu_baseline=not args.no_cpu_baseline)
                 # the same node loop on a run four times as long (the graph grows to ~450 keyframes): where the per-tick cost of the
@@ -682,7 +765,7 @@ def main():
             out["single_graph"] = {"iters_per_sec": round(n1 / d1, 2), "ms_per_iter": round(1e3 * d1 / n1, 3), "iterations": n1,
                                    "regime": "latency-bound (working set < L2/MALL)", "chi2_after": s1[0].chi2_after}
             del b1
-        if not args.no_single and world == 1:
+        if args.full and not args.no_single and world == 1:
             # ---- north_star's "Schur-complement + PCG" (solver 2) on the same L graph: what it costs per LM trial -------------
             try:
                 b2 = build_batch(paths[:1], 1, dev, 2)
@@ -697,7 +780,7 @@ def main():
                 del b2
             except Exception as e:
                 out["schur_pcg"] = {"error": str(e)[:200]}
-        if args.plane_batch > 0 and world == 1:
+        if args.full and args.plane_batch > 0 and world == 1:
             # ---- plane landmarks (BASELINE.json metric: "5k poses, 1k planes"): VertexPlane + EdgeSE3Plane, numeric Jacobians
             try:
                 n_pd = args.plane_batch if args.plane_distinct < 0 else max(1, min(args.plane_distinct, args.plane_batch))
@@ -718,7 +801,7 @@ def main():
                                  f"plane landmarks {out['plane_landmarks']['value'] / 1e3:.1f}k")
             except Exception as e:   # the headline line must still be printed
                 out["plane_landmarks"] = {"error": str(e)[:200]}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # ---- CPU baseline: the oracle (restated reference algorithm), 1 core, bounded sample ----
             reps, cpu_t, cpu_it, budget = 0, 0.0, 0, 15.0
             while cpu_t < budget:

@@ -2185,14 +2185,19 @@ sslam_batch* sslam_batch_create_streams(sslam_graph* const* graphs, int n, int n
   }
   sslam_batch* h = new sslam_batch();
   h->b.device = graphs[0]->g.device;
+  // the parts are independent batches (own tables, allocations and stream): compiled on one host thread each, as they are optimised
+  h->parts.assign(K, nullptr);
+  std::vector<std::string> errs(K);
+  std::vector<std::thread> th;
   for (int k = 0; k < K; ++k) {
     const int lo = (int)((int64_t)n * k / K), hi = (int)((int64_t)n * (k + 1) / K);
-    sslam_batch* part = batch_create_single(graphs + lo, hi - lo);
-    if (!part) { delete h; return nullptr; }
-    h->parts.push_back(part);
     h->part0.push_back(lo);
+    th.emplace_back([&, k, lo, hi] { h->parts[k] = batch_create_single(graphs + lo, hi - lo); if (!h->parts[k]) errs[k] = last_error_ref(); });
   }
+  for (auto& t : th) t.join();
   h->part0.push_back(n);
+  for (int k = 0; k < K; ++k)
+    if (!h->parts[k]) { last_error_ref() = errs[k]; delete h; return nullptr; }   // (deletes the parts that were built)
   return h;
 }
 static sslam_batch* batch_create_single(sslam_graph* const* graphs, int n) {

@@ -235,16 +235,31 @@ class GraphSLAM:
     def from_synth(cls, g, device: int = 0) -> "GraphSLAM":
         """Build a graph from a synth.SynthGraph: poses 0..Np-1 (the first fixed, graph_slam.cpp:109-111), then landmarks."""
         G = cls(False, device)
-        Np = g.n_poses
-        for i in range(Np):
-            G.add_se3_node(g.poses_init[i])
+        lib, h, Np = G._lib, G._h, g.n_poses
         plane = g.landmark_kind == "plane"
-        for l in range(g.n_landmarks):
-            (G.add_plane_node if plane else G.add_point_xyz_node)(g.lms_init[l])
-        for k in range(len(g.odom_ij)):
-            G.add_se3_edge(int(g.odom_ij[k, 0]), int(g.odom_ij[k, 1]), g.odom_z[k], g.odom_info[k])
-        for k in range(len(g.lm_ij)):
-            (G.add_se3_plane_edge if plane else G.add_se3_point_xyz_edge)(int(g.lm_ij[k, 0]), Np + int(g.lm_ij[k, 1]), g.lm_z[k], g.lm_info[k])
+        nl = 4 if plane else 3
+
+        def rows(a, width):   # pointers to the rows of a C-contiguous float64 copy (kept alive by the caller's name)
+            a = np.ascontiguousarray(np.asarray(a, np.float64).reshape(len(a), width))
+            base, step = a.ctypes.data, a.strides[0]
+            return a, [C.cast(base + k * step, C.POINTER(C.c_double)) for k in range(len(a))]
+        # the add_* calls above without their per-call conversions (thousands per graph): the same values in the same order
+        pa, pp = rows(g.poses_init, 7)
+        for p in pp:
+            _check(lib, lib.sslam_graph_add_vertex_se3(h, p, -1))
+        la, lp = rows(g.lms_init, nl)
+        add_lm = lib.sslam_graph_add_vertex_plane if plane else lib.sslam_graph_add_vertex_point
+        for p in lp:
+            _check(lib, add_lm(h, p))
+        za, zp = rows(g.odom_z, 7)
+        wa, wp = rows(g.odom_info, 36)
+        for (i, j), z, w in zip(g.odom_ij.tolist(), zp, wp):
+            _check(lib, lib.sslam_graph_add_edge_se3(h, i, j, z, w))
+        ya, yp = rows(g.lm_z, nl)
+        va, vp = rows(g.lm_info, 9)
+        add_e = lib.sslam_graph_add_edge_se3_plane if plane else lib.sslam_graph_add_edge_se3_point
+        for (i, l), z, w in zip(g.lm_ij.tolist(), yp, vp):
+            _check(lib, add_e(h, i, Np + l, z, w))
         return G
 
     def estimates(self) -> np.ndarray:

@@ -19,6 +19,8 @@ Quaternions are stored ``(qx, qy, qz, qw)`` like g2o's ``VERTEX_SE3:QUAT`` rows.
 from __future__ import annotations
 
 import dataclasses
+import math
+
 import numpy as np
 
 # ----------------------------------------------------------------------------
@@ -93,6 +95,23 @@ def pose_compose(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     q = quat_mul(a[..., 3:], b[..., 3:])
     q = q / np.linalg.norm(q, axis=-1, keepdims=True)
     return np.concatenate([t, q], axis=-1)
+
+
+def _pose_compose_scalar(a, b):
+    """pose_compose of ONE pair of poses given as lists: the same float operations in the same order (np.cross, quat_mul, a norm
+    summed x, y, z, w), hence the same bits, without NumPy's per-call cost (a graph integrates thousands of them in sequence)."""
+    tx, ty, tz, ax, ay, az, aw = a
+    vx, vy, vz, bx, by, bz, bw = b
+    t0, t1, t2 = 2.0 * (ay * vz - az * vy), 2.0 * (az * vx - ax * vz), 2.0 * (ax * vy - ay * vx)
+    r0 = vx + aw * t0 + (ay * t2 - az * t1)
+    r1 = vy + aw * t1 + (az * t0 - ax * t2)
+    r2 = vz + aw * t2 + (ax * t1 - ay * t0)
+    qx = aw * bx + ax * bw + ay * bz - az * by
+    qy = aw * by - ax * bz + ay * bw + az * bx
+    qz = aw * bz + ax * by - ay * bx + az * bw
+    qw = aw * bw - ax * bx - ay * by - az * bz
+    n = math.sqrt(qx * qx + qy * qy + qz * qz + qw * qw)
+    return [tx + r0, ty + r1, tz + r2, qx / n, qy / n, qz / n, qw / n]
 
 
 def pose_inverse(a: np.ndarray) -> np.ndarray:
@@ -184,8 +203,11 @@ def make_graph(n_poses: int, n_landmarks: int, seed: int = 0, *, landmark_kind: 
     # (chunked brute force; Np*Nl <= 5e6 for the L config)
     obs_p, obs_l = [], []
     kk = min(k_obs, Nl)
+    # squared distances summed x, y, z in that order: bit for bit what ((p - l) ** 2).sum(-1) gives, without the strided reduction
+    dx, dy, dz = (pos[:, None, c] - lm_pts[None, :, c] for c in range(3))
+    d2_all = dx * dx + dy * dy + dz * dz
     for c0 in range(0, Np, 1024):
-        d2 = ((pos[c0:c0 + 1024, None, :] - lm_pts[None, :, :]) ** 2).sum(-1)
+        d2 = d2_all[c0:c0 + 1024]
         idx = np.argpartition(d2, kk - 1, axis=1)[:, :kk]
         dsel = np.take_along_axis(d2, idx, axis=1)
         order = np.argsort(dsel, axis=1, kind="stable")
@@ -200,7 +222,7 @@ def make_graph(n_poses: int, n_landmarks: int, seed: int = 0, *, landmark_kind: 
     # pose in place of that pose's farthest observation, if that does not orphan another.
     cnt = np.bincount(obs_l, minlength=Nl)
     for l in np.nonzero(cnt == 0)[0]:
-        order_p = np.argsort(((pos - lm_pts[l]) ** 2).sum(-1), kind="stable")
+        order_p = np.argsort(d2_all[:, l], kind="stable")
         for p in order_p:
             slot = p * kk + (kk - 1)
             if cnt[obs_l[slot]] > 1:
@@ -235,8 +257,10 @@ def make_graph(n_poses: int, n_landmarks: int, seed: int = 0, *, landmark_kind: 
     # --- initial pose estimates: integrate the noisy sequential odometry ---------------
     poses_init = np.empty_like(poses_true)
     poses_init[0] = poses_true[0]
+    cur, zs = poses_true[0].tolist(), odom_z[:Np - 1].tolist()
     for i in range(Np - 1):
-        poses_init[i + 1] = pose_compose(poses_init[i], odom_z[i])
+        cur = _pose_compose_scalar(cur, zs[i])
+        poses_init[i + 1] = cur
 
     # --- landmark measurements + initial estimates -------------------------------------
     lm_info = np.broadcast_to(np.eye(3) / LAND_NOISE, (El, 3, 3)).copy()
@@ -248,11 +272,10 @@ def make_graph(n_poses: int, n_landmarks: int, seed: int = 0, *, landmark_kind: 
         lm_zm = z_true + rng.normal(0.0, 0.05 * noise_scale, (El, 3))
         lms_init = np.zeros((Nl, 3))
         seen = np.zeros(Nl, bool)
-        for e in range(El):
-            l = li[e]
-            if not seen[l]:
-                seen[l] = True
-                lms_init[l] = poses_init[pi[e], :3] + quat_rotate(poses_init[pi[e], 3:], lm_zm[e])
+        first_l, first_e = np.unique(li, return_index=True)     # each landmark from the first edge that observes it
+        pf = pi[first_e]
+        lms_init[first_l] = poses_init[pf, :3] + quat_rotate(poses_init[pf, 3:], lm_zm[first_e])
+        seen[first_l] = True
         lms_init[~seen] = lm_pts[~seen]
     elif landmark_kind == "plane":
         nrm = rng.normal(0.0, 1.0, (Nl, 3))

@@ -14,12 +14,12 @@ if has tests; then
   python -m pytest $R/tests -m gpu -q > $O/r6_pytest_gpu.txt 2>&1; tail -3 $O/r6_pytest_gpu.txt
 fi
 if has bench; then
-  python $R/bench.py $DRV > $O/bench_stdout.txt 2> $O/bench_stderr.txt; tail -1 $O/bench_stdout.txt > $O/r6_bench.json; cut -c1-400 $O/r6_bench.json
+  python $R/bench.py $DRV --full > $O/bench_stdout.txt 2> $O/bench_stderr.txt; tail -1 $O/bench_stdout.txt > $O/r6_bench.json; cut -c1-400 $O/r6_bench.json
 fi
 if has stats; then
   # kernel stats of the pass the rooflines come from: one batch-synchronous batch on one stream (--streams 1); in the stream-group
   # region the launches of four parts overlap on the chip and a per-launch duration says nothing about a kernel
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py $DRV --streams 1 --no-cpu-baseline --no-frontend --no-single --plane-batch 0 > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py $DRV --full --streams 1 --no-cpu-baseline --no-frontend --no-single --plane-batch 0 > /dev/null 2>&1
   cp $(ls $O/stats/*/*kernel_stats.csv | head -1) $O/r6_bench_kernel_stats.csv; head -12 $O/r6_bench_kernel_stats.csv | cut -c1-160
   rm -rf $O/stats
 fi
