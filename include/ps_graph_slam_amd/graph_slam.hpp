@@ -19,6 +19,7 @@
 #include <array>
 #include <chrono>
 #include <cmath>
+#include <deque>
 #include <iostream>
 #include <map>
 #include <memory>
@@ -91,6 +92,9 @@ class VertexPlane : public VertexHandle {
   std::array<double, 4> estimate() const { double p[7]; sslam_graph_get_vertex(g_, id_, p); return {p[0], p[1], p[2], p[3]}; }
 };
 struct EdgeHandle { int id; };
+// what add_se3_prior_xy(z)_edge return: like g2o's edge pointers they stay valid for the life of the graph
+struct EdgeSE3PriorXY { int id; };
+struct EdgeSE3PriorXYZ { int id; };
 
 // What the caller reads out of g2o::SparseBlockMatrix<Eigen::MatrixXd> after computeMarginals
 // (semantic_graph_slam.cpp:196-203: `spinv.block(r, c)->eval().cast<float>()`): blocks of H^-1 addressed by hessian indices.
@@ -160,6 +164,18 @@ class GraphSLAM {
   sslam::EdgeHandle add_se3_plane_edge(const sslam::VertexSE3* v_se3, const sslam::VertexPlane* v_plane,
                                        const std::array<double, 4>& plane_coeffs, const double* information_matrix) {
     return {check(sslam_graph_add_edge_se3_plane(graph.get(), v_se3->id(), v_plane->id(), plane_coeffs.data(), information_matrix))};
+  }
+  /** add_se3_prior_xy_edge (graph_slam.hpp:122-123, commented out upstream; hdl_graph_slam's EdgeSE3PriorXY): e = t.xy - xy;
+   *  information_matrix: 4 doubles row-major 2x2 */
+  sslam::EdgeSE3PriorXY* add_se3_prior_xy_edge(const sslam::VertexSE3* v_se3, const std::array<double, 2>& xy, const double* information_matrix) {
+    priors_xy_.push_back({check(sslam_graph_add_edge_se3_prior_xy(graph.get(), v_se3->id(), xy.data(), information_matrix))});
+    return &priors_xy_.back();
+  }
+  /** add_se3_prior_xyz_edge (graph_slam.hpp:125-126, commented out upstream; hdl_graph_slam's EdgeSE3PriorXYZ): e = t - xyz;
+   *  information_matrix: 9 doubles row-major 3x3 */
+  sslam::EdgeSE3PriorXYZ* add_se3_prior_xyz_edge(const sslam::VertexSE3* v_se3, const std::array<double, 3>& xyz, const double* information_matrix) {
+    priors_xyz_.push_back({check(sslam_graph_add_edge_se3_prior_xyz(graph.get(), v_se3->id(), xyz.data(), information_matrix))});
+    return &priors_xyz_.back();
   }
 
   /** The robust kernel graph_slam.cpp:155,161 means to install on the landmark edges (g2o::RobustKernelDCS; the reference passes an
@@ -236,6 +252,14 @@ class GraphSLAM {
     double W[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) W[r * 3 + c] = info(r, c);
     return add_se3_point_xyz_edge(v, p, std::array<double, 3>{xyz[0], xyz[1], xyz[2]}, W);
   }
+  sslam::EdgeSE3PriorXY* add_se3_prior_xy_edge(const sslam::VertexSE3* v, const Eigen::Vector2d& xy, const Eigen::MatrixXd& info) {
+    double W[4]; for (int r = 0; r < 2; ++r) for (int c = 0; c < 2; ++c) W[r * 2 + c] = info(r, c);
+    return add_se3_prior_xy_edge(v, std::array<double, 2>{xy[0], xy[1]}, W);
+  }
+  sslam::EdgeSE3PriorXYZ* add_se3_prior_xyz_edge(const sslam::VertexSE3* v, const Eigen::Vector3d& xyz, const Eigen::MatrixXd& info) {
+    double W[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) W[r * 3 + c] = info(r, c);
+    return add_se3_prior_xyz_edge(v, std::array<double, 3>{xyz[0], xyz[1], xyz[2]}, W);
+  }
 #endif
 
  public:
@@ -246,6 +270,8 @@ class GraphSLAM {
  private:
   template <typename T> T* own(T* v) { vertices_.emplace_back(v); return v; }
   std::vector<std::unique_ptr<sslam::VertexHandle>> vertices_;   // the graph owns its vertices, as g2o's optimizer does
+  std::deque<sslam::EdgeSE3PriorXY> priors_xy_;                   // ... and the prior edges it handed out (stable addresses)
+  std::deque<sslam::EdgeSE3PriorXYZ> priors_xyz_;
   static int check(int rc) {
     if (rc < 0) throw std::runtime_error(std::string("sslam: ") + sslam_last_error());
     return rc;

@@ -93,6 +93,16 @@ int sslam_graph_add_edge_se3_plane(sslam_graph* g, int i, int l, const double z[
  * (Schur complement on the landmarks) refuses the graph, the Cholesky solvers and solver 0 take it as it is. */
 int sslam_graph_add_edge_point_point(sslam_graph* g, int l1, int l2, const double z[3], const double info[9]);
 
+/* add_se3_prior_xyz_edge (commented out in the reference, graph_slam.hpp:115-126, the declaration :125-126; g2o registration EDGE_SE3_PRIORXYZ, graph_slam.cpp:32):
+ * hdl_graph_slam's EdgeSE3PriorXYZ, a unary edge on the SE3 vertex v with e = t(v) - z and a 3 x 3 information matrix -- an absolute
+ * position (GNSS, a motion-capture fix, a surveyed marker).  Analytic Jacobian [R | 0] (g2o differentiates it numerically; DESIGN.md
+ * section 2).  Never robustified ("robust_kernel_dcs" stays on the landmark edges).  Returns the edge id (same counter as the binary
+ * edges); a prior counts as an edge for the < 10 edges rule and gives its vertex a hessian index. */
+int sslam_graph_add_edge_se3_prior_xyz(sslam_graph* g, int v, const double z[3], const double info[9]);
+/* add_se3_prior_xy_edge (commented out, graph_slam.hpp:115-123, the declaration :122-123; EDGE_SE3_PRIORXY, graph_slam.cpp:31): EdgeSE3PriorXY, e = t(v).xy - z,
+ * 2 x 2 information matrix; otherwise as sslam_graph_add_edge_se3_prior_xyz. */
+int sslam_graph_add_edge_se3_prior_xy(sslam_graph* g, int v, const double z[2], const double info[4]);
+
 int sslam_graph_num_vertices(const sslam_graph* g);
 int sslam_graph_num_edges(const sslam_graph* g);
 

@@ -62,6 +62,8 @@ def load_library():
         "sslam_graph_add_edge_se3_point": (ci, [vp, ci, ci, dp, dp]),
         "sslam_graph_add_edge_se3_plane": (ci, [vp, ci, ci, dp, dp]),
         "sslam_graph_add_edge_point_point": (ci, [vp, ci, ci, dp, dp]),
+        "sslam_graph_add_edge_se3_prior_xyz": (ci, [vp, ci, dp, dp]),
+        "sslam_graph_add_edge_se3_prior_xy": (ci, [vp, ci, dp, dp]),
         "sslam_graph_num_vertices": (ci, [vp]),
         "sslam_graph_num_edges": (ci, [vp]),
         "sslam_graph_get_vertex": (ci, [vp, ci, dp]),

@@ -10,6 +10,10 @@ namespace sslam {
 
 enum { VT_SE3 = 0, VT_POINT = 1, VT_PLANE = 2 };
 enum { ET_SE3 = 0, ET_SE3_POINT = 1, ET_SE3_PLANE = 2, ET_POINT_POINT = 3 };   // 3: g2o::EdgePointXYZ (graph_slam.cpp:168-180)
+// unary position priors on a VertexSE3 (hdl_graph_slam's EdgeSE3PriorXY / EdgeSE3PriorXYZ; graph_slam.hpp:115-126, commented out in the
+// reference): evj = -1, the measurement is the position (2 / 3 doubles), the information matrix 2 x 2 / 3 x 3
+enum { ET_SE3_PRIOR_XY = 4, ET_SE3_PRIOR_XYZ = 5 };
+inline bool is_prior_edge(int t) { return t == ET_SE3_PRIOR_XY || t == ET_SE3_PRIOR_XYZ; }
 
 struct Options {
   int solver = 1;            // 0 PCG, 1 sparse block Cholesky
@@ -38,11 +42,11 @@ inline int vertex_dim(int t) { return t == VT_SE3 ? 6 : 3; }
 inline int vertex_est_len(int t) { return t == VT_SE3 ? 7 : (t == VT_POINT ? 3 : 4); }
 
 // g2o initializeOptimization ordering: non-fixed vertices that own >= 1 edge get
-// consecutive scalar offsets by id.  Returns the total dimension.
+// consecutive scalar offsets by id (a unary prior is an edge of its vertex).  Returns the total dimension.
 inline int hessian_indices(const HostGraph& g, std::vector<int>& hidx) {
   const int nv = g.nv();
   std::vector<char> has(nv, 0);
-  for (int k = 0; k < g.ne(); ++k) { has[g.evi[k]] = 1; has[g.evj[k]] = 1; }
+  for (int k = 0; k < g.ne(); ++k) { has[g.evi[k]] = 1; if (g.evj[k] >= 0) has[g.evj[k]] = 1; }
   hidx.assign(nv, -1);
   int off = 0;
   for (int v = 0; v < nv; ++v)

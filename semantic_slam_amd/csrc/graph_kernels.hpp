@@ -27,6 +27,7 @@ struct GraphSeg {
   int pose0, npose;  // all SE3 vertices (incl. fixed)
   int lm0, nlm;      // all landmark vertices
   int ell0, nell;    // point-point edges (g2o::EdgePointXYZ)
+  int ep0, nep;      // position priors (EdgeSE3PriorXY / EdgeSE3PriorXYZ)
 };
 
 struct LmState {
@@ -95,6 +96,13 @@ struct BatchView {
   int* pcg_done;    // [2][B] double-buffered by iteration parity
   int* pcg_fail;    // [B]
   int* flags;       // [0] any_in_trial, [1] all_pcg_done
+  // position priors (hdl_graph_slam's EdgeSE3PriorXY / EdgeSE3PriorXYZ, unary on a VertexSE3): e = t(X) - z on the first ep_dim components,
+  // J = [R | 0] -> only the pose's diagonal block and rhs.  SoA, grouped by graph in edge order: z[3][nEp], upper triangle of Omega [6][nEp]
+  // (the third row / column zero for an XY prior)
+  int nEp, nEpRows;
+  const int* ep_pose; const int* ep_dim; const double* ep_z; const double* ep_w;
+  const int* ep_id;                                  // graph-local edge id (edge-sharded mode)
+  const int* ep_row; const int* ep_ptr; const int* ep_edge;   // [nEpRows] pose rows that carry priors, CSR over them: their priors in edge order
 };
 
 // g2o::RobustKernelDCS::robustify: rho[1], the factor on Omega; rho[0] = rho[1] * e2
@@ -191,7 +199,8 @@ __device__ __forceinline__ RowRef row_ref(const BatchView& V, const GraphSeg& sg
 }
 
 __device__ __forceinline__ int row_chunks(const GraphSeg& sg) { return (sg.nprow * 6 + sg.nlrow * 3 + kRowChunk - 1) / kRowChunk; }
-__device__ __forceinline__ int edge_chunks(const GraphSeg& sg) { return (sg.neo + sg.nel + sg.nell + kEdgeChunk - 1) / kEdgeChunk; }
+__device__ __forceinline__ int edge_count(const GraphSeg& sg) { return sg.neo + sg.nel + sg.nell + sg.nep; }
+__device__ __forceinline__ int edge_chunks(const GraphSeg& sg) { return (edge_count(sg) + kEdgeChunk - 1) / kEdgeChunk; }
 
 
 // x [+] dx of one block row t (pose rows first, then landmark rows) of a graph that is in a trial -> the trial estimates
@@ -265,7 +274,24 @@ __device__ __forceinline__ void lm_control_apply(LmState& S, double tchi, double
   }
 }
 
-// chi2 term of the graph-local edge e of graph segment sg (SE3 edges, then landmark edges, then point-point edges; 0 beyond the last):
+// position prior k (batch index): its error e = t(X) - z (the first ep_dim components; the rest 0) and Omega
+__device__ __forceinline__ void prior_error(const BatchView& V, int k, const Pose& X, double err[3], double W[9]) {
+  const size_t n = V.nEp;
+  const int dim = V.ep_dim[k];
+  err[0] = X.t.x - V.ep_z[0 * n + k];
+  err[1] = X.t.y - V.ep_z[1 * n + k];
+  err[2] = dim == 3 ? X.t.z - V.ep_z[2 * n + k] : 0.0;
+  load_sym3(V.ep_w, (int)n, k, W);
+}
+// its chi2 term.  Out of line: the persistent solver kernels inline edge_chi2, and the prior branch must not move their register budget.
+__device__ __forceinline__ double prior_chi2(const BatchView& V, int k, const double* __restrict__ pose) {
+  double err[3], W[9];
+  prior_error(V, k, load_pose(pose, V.ep_pose[k]), err, W);
+  return quad3(W, err);
+}
+
+// chi2 term of the graph-local edge e of graph segment sg (SE3 edges, then landmark edges, then point-point edges, then position priors;
+// 0 beyond the last):
 // g2o computeActiveErrors + the robust kernel's rho[0]
 __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& sg, int e, const double* __restrict__ pose, const double* __restrict__ lmk) {
   double c = 0;
@@ -318,6 +344,8 @@ __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& 
     for (int r = 0; r < 3; ++r) err[r] = (pb[r] - pa[r]) - V.ell_z[r * n + k];
     load_sym3(V.ell_w, (int)n, k, W);
     c = quad3(W, err);
+  } else if (e < edge_count(sg)) {
+    c = prior_chi2(V, sg.ep0 + (e - sg.neo - sg.nel - sg.nell), pose);
   }
   return c;
 }

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kEdgeChunk) void k_chi2(BatchView V, const double* 
   if (mask_mode == 2 && !S.active) return;
   const GraphSeg sg = V.seg[g];
   const int e = blockIdx.x * kEdgeChunk + threadIdx.x;
-  if (blockIdx.x * kEdgeChunk >= sg.neo + sg.nel + sg.nell) return;
+  if (blockIdx.x * kEdgeChunk >= edge_count(sg)) return;
   const double c = edge_chi2(V, sg, e, pose, lmk);
   const double s = block_sum<kEdgeChunk>(c, red);
   if (threadIdx.x == 0) part[(size_t)g * V.maxEdgeChunks + blockIdx.x] = s;
@@ -367,6 +367,59 @@ __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchVie
   for (int c = 0; c < 6; c += 2) store2(Bv + c, accD[21 + c][tid], accD[22 + c][tid]);
 }
 
+// Position priors (hdl_graph_slam's EdgeSE3PriorXY / EdgeSE3PriorXYZ): e = t(X) - z, J = [R | 0] with X <- X exp(delta), so a prior adds
+// R^T Omega R to the upper-left 3 x 3 of its pose's diagonal block and -R^T Omega e to the first three entries of the rhs.  One thread per
+// pose row that carries priors: the pose is read once, its priors summed in edge order, and the sums added onto the block and rhs that
+// k_linearize_rowthread wrote before it in stream order.  No atomics: bitwise deterministic.  A separate launch (and only for a batch that
+// has priors) rather than a slot kind of the row kernel, whose live set is what bounds it (comment above k_linearize_rowthread).
+template <bool SHARD>
+__global__ __launch_bounds__(64) void k_linearize_priors(BatchView V) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= V.nEpRows) return;
+  const int row = V.ep_row[t];
+  const int g = V.prow_graph[row];
+  if (!V.lm[g].lin) return;
+  const Pose X = load_pose(V.pose, V.prow_pose[row]);
+  const Mat3 R = qmat(X.q);
+  double h[6] = {0, 0, 0, 0, 0, 0}, bb[3] = {0, 0, 0};   // upper triangle of the 3 x 3 block (tri3 order), rhs
+  for (int s = V.ep_ptr[t]; s < V.ep_ptr[t + 1]; ++s) {
+    const int k = V.ep_edge[s];
+    double err[3], W[9];
+    prior_error(V, k, X, err, W);
+    if (SHARD && !(V.ep_id[k] >= V.shard_lo[g] && V.ep_id[k] < V.shard_hi[g])) {
+#pragma unroll
+      for (int q = 0; q < 9; ++q) W[q] = 0.0;
+    }
+    double M[9], We[3];   // M = R^T Omega (3 x 3), We = Omega e
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      We[a] = W[a * 3 + 0] * err[0] + W[a * 3 + 1] * err[1] + W[a * 3 + 2] * err[2];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) M[a * 3 + c] = R.m[0 * 3 + a] * W[0 * 3 + c] + R.m[1 * 3 + a] * W[1 * 3 + c] + R.m[2 * 3 + a] * W[2 * 3 + c];
+    }
+    int q = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+      for (int c = a; c < 3; ++c) h[q++] += M[a * 3 + 0] * R.m[0 * 3 + c] + M[a * 3 + 1] * R.m[1 * 3 + c] + M[a * 3 + 2] * R.m[2 * 3 + c];
+      bb[a] -= R.m[0 * 3 + a] * We[0] + R.m[1 * 3 + a] * We[1] + R.m[2 * 3 + a] * We[2];
+    }
+  }
+  double* P = V.Hpp_diag + (size_t)row * 36;
+  double* Bv = V.bvec + (size_t)row * 6;
+  int q = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int c = a; c < 3; ++c) {
+      P[a * 6 + c] += h[q];
+      if (c != a) P[c * 6 + a] += h[q];
+      ++q;
+    }
+    Bv[a] += bb[a];
+  }
+}
+
 // landmark rows: 16 lanes per landmark, each lane walks a strided subset of the incident edges,
 // butterfly reduction in a fixed order.
 template <bool PL, bool SHARD>
@@ -604,7 +657,7 @@ __global__ void k_lm_init(BatchView V, const double* __restrict__ part_chi, int 
   const GraphSeg sg = V.seg[g];
   const double c = wave_sum_partials(part_chi + (size_t)g * V.maxEdgeChunks, edge_chunks(sg));
   if (threadIdx.x == 0) {
-    const bool few = sg.neo + sg.nel + sg.nell < min_edges;
+    const bool few = edge_count(sg) < min_edges;   // position priors count: g2o counts graph->edges()
     S.cur_chi = c; S.chi_before = c; S.iter = 0; S.trials = 0; S.pcg_iters = 0;
     S.status = few ? -5 : 0; S.active = few ? 0 : 1; S.lin = few ? 0 : 1;
     S.in_trial = 0; S.accept = 0; S.lambda = 0; S.nu = 2; S.rho = 0; S.q = 0; S.solve_failed = 0;
@@ -1023,6 +1076,7 @@ static int batch_build(Batch& b, bool host_only = false) {
   std::vector<int> eo_src, el_src;  // (graph-local edge id) for SoA fill
   std::vector<int> eo_g, el_g;
   std::vector<int> ell_a, ell_b, ell_src, ell_g, ell_blk;   // point-point edges (g2o::EdgePointXYZ)
+  std::vector<int> ep_pose, ep_dim, ep_src, ep_g;          // position priors (EdgeSE3PriorXY / XYZ)
   std::vector<int> shard_lo(b.graphs.size(), 0), shard_hi(b.graphs.size(), 0x7fffffff);
   int maxRow = 1, maxEdge = 1;
   for (int g = 0; g < B; ++g) {
@@ -1032,7 +1086,7 @@ static int batch_build(Batch& b, bool host_only = false) {
     GraphSeg& sg = b.seg[g];
     sg.pose0 = (int)b.pose_row.size(); sg.lm0 = (int)b.lm_row.size();
     sg.prow0 = (int)b.prow_pose.size(); sg.lrow0 = (int)b.lrow_lm.size();
-    sg.eo0 = (int)eo_i.size(); sg.el0 = (int)el_p.size(); sg.ell0 = (int)ell_a.size();
+    sg.eo0 = (int)eo_i.size(); sg.el0 = (int)el_p.size(); sg.ell0 = (int)ell_a.size(); sg.ep0 = (int)ep_pose.size();
     auto& vp = b.v2pose[g]; auto& vl = b.v2lm[g];
     vp.assign(G.nv(), -1); vl.assign(G.nv(), -1);
     for (int v = 0; v < G.nv(); ++v) {
@@ -1054,14 +1108,15 @@ static int batch_build(Batch& b, bool host_only = false) {
     for (int k = 0; k < G.ne(); ++k) {
       if (G.etype[k] == ET_SE3) { eo_i.push_back(vp[G.evi[k]]); eo_j.push_back(vp[G.evj[k]]); eo_src.push_back(k); eo_g.push_back(g); }
       else if (G.etype[k] == ET_POINT_POINT) { ell_a.push_back(vl[G.evi[k]]); ell_b.push_back(vl[G.evj[k]]); ell_src.push_back(k); ell_g.push_back(g); }
+      else if (is_prior_edge(G.etype[k])) { ep_pose.push_back(vp[G.evi[k]]); ep_dim.push_back(G.etype[k] == ET_SE3_PRIOR_XYZ ? 3 : 2); ep_src.push_back(k); ep_g.push_back(g); }
       else { el_p.push_back(vp[G.evi[k]]); el_l.push_back(vl[G.evj[k]]); el_src.push_back(k); el_g.push_back(g); }
     }
-    sg.neo = (int)eo_i.size() - sg.eo0; sg.nel = (int)el_p.size() - sg.el0; sg.nell = (int)ell_a.size() - sg.ell0;
+    sg.neo = (int)eo_i.size() - sg.eo0; sg.nel = (int)el_p.size() - sg.el0; sg.nell = (int)ell_a.size() - sg.ell0; sg.nep = (int)ep_pose.size() - sg.ep0;
     maxRow = std::max(maxRow, (sg.nprow * 6 + sg.nlrow * 3 + kRowChunk - 1) / kRowChunk);
-    maxEdge = std::max(maxEdge, (sg.neo + sg.nel + sg.nell + kEdgeChunk - 1) / kEdgeChunk);
+    maxEdge = std::max(maxEdge, (sg.neo + sg.nel + sg.nell + sg.nep + kEdgeChunk - 1) / kEdgeChunk);
   }
   const int nPr = (int)b.prow_pose.size(), nLr = (int)b.lrow_lm.size();
-  const int nEo = (int)eo_i.size(), nEl = (int)el_p.size(), nEll = (int)ell_a.size();
+  const int nEo = (int)eo_i.size(), nEl = (int)el_p.size(), nEll = (int)ell_a.size(), nEp = (int)ep_pose.size();
   // unique off-diagonal blocks
   std::unordered_map<uint64_t, int> ppmap, plmap, llmap;
   std::vector<std::vector<int>> llblk_edges;                 // per landmark-landmark block: its edges
@@ -1245,6 +1300,26 @@ static int batch_build(Batch& b, bool host_only = false) {
   std::vector<int2> llslot_rec;
   for (int r = 0; r < nLr; ++r) { for (auto& q : llslots[r]) llslot_rec.push_back(make_int2(q.first, q.second)); llslot_ptr[r + 1] = (int)llslot_rec.size(); }
   for (int i = 0; i < nLL; ++i) { for (int k : llblk_edges[i]) llblk_edge.push_back(k); llblk_ptr[i + 1] = (int)llblk_edge.size(); }
+  // position priors: SoA payload, and the pose rows that carry them (a prior on a fixed pose adds to chi2 only)
+  std::vector<double> ep_z((size_t)3 * nEp), ep_w((size_t)6 * nEp);
+  for (int k = 0; k < nEp; ++k) {
+    const HostGraph& G = *b.graphs[ep_g[k]];
+    const int s = ep_src[k], d = ep_dim[k];
+    for (int c = 0; c < 3; ++c) ep_z[(size_t)c * nEp + k] = c < d ? G.meas[(size_t)s * 7 + c] : 0.0;
+    int q = 0;
+    for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) ep_w[(size_t)(q++) * nEp + k] = (r < d && c < d) ? G.info[(size_t)s * 36 + r * d + c] : 0.0;
+  }
+  std::vector<int> ep_row, ep_ptr(1, 0), ep_edge;
+  {
+    std::vector<std::vector<int>> per_row(nPr);
+    for (int k = 0; k < nEp; ++k) { const int r = b.pose_row[ep_pose[k]]; if (r >= 0) per_row[r].push_back(k); }
+    for (int r = 0; r < nPr; ++r) {
+      if (per_row[r].empty()) continue;
+      ep_row.push_back(r);
+      for (int k : per_row[r]) ep_edge.push_back(k);
+      ep_ptr.push_back((int)ep_edge.size());
+    }
+  }
   // ---- device allocation
   BatchView& V = b.V;
   memset(&V, 0, sizeof V);
@@ -1265,6 +1340,11 @@ static int batch_build(Batch& b, bool host_only = false) {
   UP(eo_src, eo_id); UP(el_src, el_id); UP(shard_lo, shard_lo); UP(shard_hi, shard_hi);
   UP(ell_a, ell_a); UP(ell_b, ell_b); UP(ell_z, ell_z); UP(ell_w, ell_w); UP(ell_src, ell_id);
   UP(llslot_ptr, llslot_ptr); UP(llslot_rec, llslot_rec); UP(llblk_ptr, llblk_ptr); UP(llblk_edge, llblk_edge);
+  V.nEp = nEp; V.nEpRows = (int)ep_row.size();
+  if (nEp > 0) {   // a batch without priors uploads nothing more than before
+    UP(ep_pose, ep_pose); UP(ep_dim, ep_dim); UP(ep_z, ep_z); UP(ep_w, ep_w); UP(ep_src, ep_id);
+    UP(ep_row, ep_row); UP(ep_ptr, ep_ptr); UP(ep_edge, ep_edge);
+  }
   V.nDupEo = (int)b.dup_eo.size(); V.nDupEl = (int)b.dup_el.size();
   V.nTiles = (int)tile_row0.size();
 #undef UP
@@ -1388,6 +1468,7 @@ static int batch_linearize(Batch& b) {
       hipLaunchKernelGGL(k_plane_jacobians, dim3((unsigned)(bA + bB)), dim3(256), 0, b.stream, V, (int)bA);                              \
     }                                                                                                                                 \
     if (V.nPr > 0) hipLaunchKernelGGL((k_linearize_rowthread<PLV, SHV>), dim3(nblk), dim3(kRowThreads), 0, b.stream, V);               \
+    if (V.nEpRows > 0) hipLaunchKernelGGL((k_linearize_priors<SHV>), dim3((V.nEpRows + 63) / 64), dim3(64), 0, b.stream, V);          \
     if (V.nLr > 0) hipLaunchKernelGGL((k_linearize_lm_rows<PLV, SHV>), dim3((V.nLr + 15) / 16), dim3(256), 0, b.stream, V);            \
     if (V.nLL > 0) hipLaunchKernelGGL((k_linearize_ll<SHV>), dim3((V.nLL + 63) / 64), dim3(64), 0, b.stream, V);                       \
   }
@@ -1716,13 +1797,19 @@ int sslam_graph_add_vertex_plane(sslam_graph* h, const double n_d[4]) {
   return add_vertex(h, VT_PLANE, p, 4, 0);
 }
 
+// j = -1 for a unary edge (position prior)
 static int add_edge(sslam_graph* h, int type, int i, int j, const double* z, int nz, const double* info, int d) {
   if (!h || !z || !info) return set_error(SSLAM_ERR_INVALID, "null argument");
   HostGraph& G = h->g;
-  if (i < 0 || j < 0 || i >= G.nv() || j >= G.nv() || i == j) return set_error(SSLAM_ERR_INVALID, "edge vertex ids (%d,%d) invalid", i, j);
-  if (G.vtype[i] != (type == ET_POINT_POINT ? VT_POINT : VT_SE3)) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", i);
-  const int want = type == ET_SE3 ? VT_SE3 : ((type == ET_SE3_POINT || type == ET_POINT_POINT) ? VT_POINT : VT_PLANE);
-  if (G.vtype[j] != want) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", j);
+  if (is_prior_edge(type)) {
+    if (i < 0 || i >= G.nv() || j != -1) return set_error(SSLAM_ERR_INVALID, "prior vertex id %d invalid", i);
+    if (G.vtype[i] != VT_SE3) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", i);
+  } else {
+    if (i < 0 || j < 0 || i >= G.nv() || j >= G.nv() || i == j) return set_error(SSLAM_ERR_INVALID, "edge vertex ids (%d,%d) invalid", i, j);
+    if (G.vtype[i] != (type == ET_POINT_POINT ? VT_POINT : VT_SE3)) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", i);
+    const int want = type == ET_SE3 ? VT_SE3 : ((type == ET_SE3_POINT || type == ET_POINT_POINT) ? VT_POINT : VT_PLANE);
+    if (G.vtype[j] != want) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", j);
+  }
   // only the upper triangle of the information matrix travels to the device: an asymmetric one would be symmetrised silently
   double amax = 0;
   for (int k = 0; k < d * d; ++k) { if (!std::isfinite(info[k])) return set_error(SSLAM_ERR_INVALID, "information matrix has a non-finite entry"); amax = std::max(amax, std::fabs(info[k])); }
@@ -1753,6 +1840,13 @@ int sslam_graph_add_edge_se3_plane(sslam_graph* h, int i, int l, const double z[
 
 int sslam_graph_add_edge_point_point(sslam_graph* h, int l1, int l2, const double z[3], const double info[9]) {
   return add_edge(h, ET_POINT_POINT, l1, l2, z, 3, info, 3);
+}
+
+int sslam_graph_add_edge_se3_prior_xyz(sslam_graph* h, int v, const double z[3], const double info[9]) {
+  return add_edge(h, ET_SE3_PRIOR_XYZ, v, -1, z, 3, info, 3);
+}
+int sslam_graph_add_edge_se3_prior_xy(sslam_graph* h, int v, const double z[2], const double info[4]) {
+  return add_edge(h, ET_SE3_PRIOR_XY, v, -1, z, 2, info, 2);
 }
 
 int sslam_graph_num_vertices(const sslam_graph* h) { return h ? h->g.nv() : SSLAM_ERR_INVALID; }
@@ -2111,6 +2205,11 @@ int sslam_graph_save_g2o(const sslam_graph* h, const char* path) {
       fprintf(f, "EDGE_POINTXYZ %d %d", G.evi[k], G.evj[k]);
       for (int c = 0; c < 3; ++c) fprintf(f, " %.17g", z[c]);
       for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) fprintf(f, " %.17g", W[r * 3 + c]);
+    } else if (is_prior_edge(G.etype[k])) {   // hdl_graph_slam's EdgeSE3PriorXY(Z)::write: vertex, z, upper triangle of Omega
+      const int d = G.etype[k] == ET_SE3_PRIOR_XYZ ? 3 : 2;
+      fprintf(f, d == 3 ? "EDGE_SE3_PRIORXYZ %d" : "EDGE_SE3_PRIORXY %d", G.evi[k]);
+      for (int c = 0; c < d; ++c) fprintf(f, " %.17g", z[c]);
+      for (int r = 0; r < d; ++r) for (int c = r; c < d; ++c) fprintf(f, " %.17g", W[r * d + c]);
     } else {  // row format of the in-tree EdgeSE3Plane::write (edge_se3_plane.hpp:40-47)
       fprintf(f, "EDGE_SE3_PLANE %d %d", G.evi[k], G.evj[k]);
       for (int c = 0; c < 4; ++c) fprintf(f, " %.17g", z[c]);
@@ -2157,6 +2256,12 @@ int sslam_graph_load_g2o(sslam_graph* h, const char* path) {
       if (fscanf(f, "%d %d", &i, &j) != 2 || !rd(z, 4) || !rd(u, 6) || !idmap.count(i) || !idmap.count(j)) { rc = -1; break; }
       int q = 0; for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) { W[r * 3 + c] = u[q]; W[c * 3 + r] = u[q]; ++q; }
       if (add_edge(h, ET_SE3_PLANE, idmap[i], idmap[j], z, 4, W, 3) < 0) { rc = -1; break; }
+    } else if (t == "EDGE_SE3_PRIORXYZ" || t == "EDGE_SE3_PRIORXY") {
+      const int d = t == "EDGE_SE3_PRIORXYZ" ? 3 : 2;
+      int i; double z[3], u[6], W[9];
+      if (fscanf(f, "%d", &i) != 1 || !rd(z, d) || !rd(u, d * (d + 1) / 2) || !idmap.count(i)) { rc = -1; break; }
+      int q = 0; for (int r = 0; r < d; ++r) for (int c = r; c < d; ++c) { W[r * d + c] = u[q]; W[c * d + r] = u[q]; ++q; }
+      if (add_edge(h, d == 3 ? ET_SE3_PRIOR_XYZ : ET_SE3_PRIOR_XY, idmap[i], -1, z, d, W, d) < 0) { rc = -1; break; }
     } else {  // PARAMS_SE3OFFSET and unknown rows: skip to end of line
       int ch; while ((ch = fgetc(f)) != EOF && ch != '\n') {}
     }
@@ -2407,13 +2512,16 @@ int64_t sslam_batch_linearize_bytes(const sslam_batch* h) {
   if (!h->parts.empty()) { int64_t t = 0; for (const sslam_batch* p : h->parts) t += sslam_batch_linearize_bytes(p); return t; }
   const Batch& b = h->b;
   // 344*Eo + 160*El(176 plane) + 288*Np + 72*Nl + 288*Eo + 144*El + 48*Np + 24*Nl
+  // position priors (k_linearize_priors): 80 per prior (z 24, Omega 48, dim 4, slot 4) + 268 per pose row that carries one (pose 64, row
+  // and CSR entries 8 + 4, the 9 + 3 doubles of H and b it adds to read 96 and written 96)
   int64_t bytes = 0;
   for (size_t g = 0; g < b.graphs.size(); ++g) {
     const HostGraph& G = *b.graphs[g];
     for (int k = 0; k < G.ne(); ++k)
-      bytes += G.etype[k] == ET_SE3 ? 344 + 288 : (G.etype[k] == ET_SE3_POINT ? 160 + 144 : (G.etype[k] == ET_SE3_PLANE ? 176 + 144 : 8 + 24 + 48 + 48 + 72));
+      bytes += G.etype[k] == ET_SE3 ? 344 + 288 : (G.etype[k] == ET_SE3_POINT ? 160 + 144 : (G.etype[k] == ET_SE3_PLANE ? 176 + 144 :
+               (is_prior_edge(G.etype[k]) ? 80 : 8 + 24 + 48 + 48 + 72)));
   }
-  bytes += (int64_t)b.V.nPr * (288 + 48) + (int64_t)b.V.nLr * (72 + 24);
+  bytes += (int64_t)b.V.nPr * (288 + 48) + (int64_t)b.V.nLr * (72 + 24) + (int64_t)b.V.nEpRows * 268;
   return bytes;
 }
 int sslam_batch_info(sslam_batch* h, const char* key, double* value) {

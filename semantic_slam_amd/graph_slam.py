@@ -3,6 +3,7 @@
 Method names, argument meaning and return conventions follow the reference class
 (reference include/ps_graph_slam/graph_slam.hpp:35-152, src/ps_graph_slam/graph_slam.cpp):
 ``add_se3_node``, ``add_point_xyz_node``, ``add_se3_edge``, ``add_se3_point_xyz_edge``,
+``add_se3_prior_xy_edge`` / ``add_se3_prior_xyz_edge`` (declared in comments upstream),
 ``optimize`` (returns ``False`` iff the graph has fewer than 10 edges, graph_slam.cpp:184-186),
 ``computeLandmarkMarginals``, ``save``.  Vertex handles are plain integer ids.
 """
@@ -97,6 +98,18 @@ class GraphSLAM:
         z = np.ascontiguousarray(xyz, np.float64).reshape(3)
         w = np.ascontiguousarray(information_matrix, np.float64).reshape(9)
         return _check(self._lib, self._lib.sslam_graph_add_edge_point_point(self._h, v1_xyz, v2_xyz, _dptr(z), _dptr(w)))
+
+    def add_se3_prior_xy_edge(self, v_se3: int, xy, information_matrix) -> int:
+        """graph_slam.hpp:122-123 (commented out upstream): hdl_graph_slam's EdgeSE3PriorXY, e = t.xy - xy (information must be 2x2)"""
+        z = np.ascontiguousarray(xy, np.float64).reshape(2)
+        w = np.ascontiguousarray(information_matrix, np.float64).reshape(4)
+        return _check(self._lib, self._lib.sslam_graph_add_edge_se3_prior_xy(self._h, v_se3, _dptr(z), _dptr(w)))
+
+    def add_se3_prior_xyz_edge(self, v_se3: int, xyz, information_matrix) -> int:
+        """graph_slam.hpp:125-126 (commented out upstream): hdl_graph_slam's EdgeSE3PriorXYZ, e = t - xyz (information must be 3x3)"""
+        z = np.ascontiguousarray(xyz, np.float64).reshape(3)
+        w = np.ascontiguousarray(information_matrix, np.float64).reshape(9)
+        return _check(self._lib, self._lib.sslam_graph_add_edge_se3_prior_xyz(self._h, v_se3, _dptr(z), _dptr(w)))
 
     # -- queries -----------------------------------------------------------------------------
     def num_vertices(self) -> int:
