@@ -160,9 +160,10 @@ struct CholOpts {
   int cap_mid = 1800;      // doubles of L per mid piece (512 L graphs: 1800 / 2400 / 3600 -> 9.14 / 9.47 / 10.2 ms per factorisation, 9.55 without the class)
   int nt_mid = 128;        // its workgroup.  Round 6, front kernels, 512 L graphs, mid launches per factorisation: 512 threads 3.87 ms, 256 1.91, 128 1.54, 64 1.89
                            // (a piece's phases hold a few hundred lanes of work at most; every further wave adds its share of the barriers and idle passes)
-  int nt_ftail = 256;      // workgroup of k_front_tail (the front tables do not depend on it): 128 | 256 | 512 | 1024; tail launch 1.12 / 0.84 / 1.13 ms at 128 / 256 / 512
+  int nt_ftail = 256;      // workgroup of k_front_tail: 128 | 256 | 512 | 1024 (1024 with nt_tail 1024); tail launch 1.12 / 0.84 / 1.13 ms at 128 / 256 / 512
   int pcap_mid = 16;
-  int nt_bleaf = 0, nt_bmid = 0, nt_btail = 0;   // workgroups of the backward-substitution launches (0: those of the factorisation; the kernels do not depend on the cut)
+  int nt_bleaf = 0, nt_bmid = 0, nt_btail = 0;   // workgroups of the backward-substitution launches (the kernels do not depend on the cut); nt_bleaf /
+                                                  // nt_bmid 0: those of the factorisation; nt_btail: 128 | 256 | 512 (anything else)
   int nt_leaf = -1, nt_tail = 512;    // workgroup sizes the items are cut for; nt_leaf -1: 128 for batches >= 32 (groups of pieces, below), else 64
   int min_chunk = 4;       // a list of <= min_chunk updates is never split
   int split_min = 4096;    // a depth with at least this many pieces is launched in up to four parts, by LDS need
@@ -193,8 +194,8 @@ struct CholOpts {
                            // kernels (chol_piece); -1: 1 for batches >= 32, else 0.  Measured (round 6): 512 L graphs 7.85 vs 8.0 ms per
                            // factorisation with a fifth of the table bytes; the orchestrator's tick (latency-bound: the LDS digest of the blob
                            // sits on the chain of pieces) 5.53-5.70 vs 5.27-5.30 ms at 110 keyframes, 8.0 vs 7.64 at 436 -> record kernels there
-  int flow = 1;            // small batches: 0 a launch per depth; 1 the dependency-driven single launch (k_chol_flow) when the tree is narrower than its
-                           // grid; 2 also on wide trees (per-depth launches for the bottom, measured slower: tests only)
+  int flow = 1;            // small batches: 0 a launch per depth; 1 the dependency-driven single launch (k_chol_flow) when the bottom depth of the tree
+                           // is no wider than its grid; 2 the single launch on any tree (a wide one is walked in rounds, measured slower: tests only)
   // SSLAM_CHOL_OPTS="key=value,key=value,...": every plan option above by its field name (tests force the piece shapes of a 5000-pose graph
   // onto small graphs with it; tuning sweeps), plus order=mmd|mindeg and dump=1.  The ONE environment switch of the plan.
   void from_env() {
@@ -247,10 +248,19 @@ struct CholOpts {
 // 1.96 k -> 2.04 k / 2.71 k -> 2.93 k / 3.39 k -> 3.81 k / 7.75 k -> 9.60 k LM iterations/s against the plans small batches took before; one such
 // graph is as fast either way and keeps its 512-thread pieces).
 inline bool chol_throughput_regime(int B, int block_rows) { return B >= 32 || (B >= 2 && block_rows >= 8000); }
+// Every workgroup width option lands in the set of widths its kernels are instantiated for (sslam_chol.hip Widths): the launches take the
+// widths as they are, and the plan (the team capacity of the front tables) sees the same ones.
 inline bool chol_opts_normalise(CholOpts& opt, int B, int block_rows) {
+  auto one_of = [](int v, std::initializer_list<int> set) { return std::find(set.begin(), set.end(), v) != set.end(); };
   if (opt.nt_tail != 1024) opt.nt_tail = 512;
-  if (opt.nt_leaf != -1 && opt.nt_leaf != 128 && opt.nt_leaf != 256 && opt.nt_leaf != 512 && opt.nt_leaf != 1024) opt.nt_leaf = 64;   // -1: by batch size (chol_symbolic)
-  if (opt.nt_mid != 256 && opt.nt_mid != 512) opt.nt_mid = 128;
+  if (!one_of(opt.nt_leaf, {-1, 128, 256, 512, 1024})) opt.nt_leaf = 64;   // -1: by batch size (chol_symbolic)
+  if (!one_of(opt.nt_mid, {256, 512})) opt.nt_mid = 128;
+  if (opt.nt_tail == 1024) opt.nt_ftail = 1024;   // (k_front_tail runs the 1024-thread tail with 1024 threads)
+  else if (!one_of(opt.nt_ftail, {128, 256, 1024})) opt.nt_ftail = 512;
+  if (!one_of(opt.nt_btail, {128, 256})) opt.nt_btail = 512;
+  for (int* nt : {&opt.nt_bleaf, &opt.nt_bmid})
+    if (*nt <= 0) *nt = 0;   // 0: the workgroup of the factorisation
+    else if (!one_of(*nt, {128, 256, 512, 1024})) *nt = 64;
   const bool want_flow = opt.flow != 0 && B < 8 && !chol_throughput_regime(B, block_rows) && opt.nt_tail == 512 && opt.group_cap <= 0 && !opt.nt_leaf_set;
   if (want_flow) { opt.nt_leaf = opt.nt_tail; opt.mid_width = 0; }
   return want_flow;
@@ -1216,7 +1226,7 @@ inline int chol_symbolic(const SymIn& in, CholOpts opt, CholHost& out) {
     front_build(FrontIn{ncol, npiece, ncomp, bp, brow, boff, bsrc, bfmt, col_comp, col_piece, col_dim, col_xoff, col_yoff, col_il, comp_parent, comp_R}, out.piece, out.ilv, F);
     // the kernels keep the diagonal blocks of a level in registers of 8-lane teams, up to two columns per team (front_kernels.hpp)
     for (int p = 0; p < npiece && F.ok; ++p) {
-      const int nt = piece_tail[p] ? (opt.nt_tail == 1024 ? 1024 : opt.nt_ftail) : (piece_cls[p] == 1 ? opt.nt_mid : opt.nt_leaf);   // the workgroup k_front_* runs the piece with
+      const int nt = piece_tail[p] ? opt.nt_ftail : (piece_cls[p] == 1 ? opt.nt_mid : opt.nt_leaf);   // the workgroup k_front_* runs the piece with
       for (int l = 0; l < out.piece[p].nilv; ++l) {
         const ILevel& lv = out.ilv[out.piece[p].ilv0 + l];
         if (lv.c1 - lv.c0 > 2 * (nt / 8)) { F.ok = false; F.why = "a level of a piece has more columns than the workgroup's teams hold"; break; }

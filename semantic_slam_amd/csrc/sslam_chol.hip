@@ -74,7 +74,7 @@ struct SpecLanes {
   int* err = nullptr;         // ONE timeout flag for all lanes (the plan's own: d_flow + 3 * npiece) -- chol_flow_check reads a single word
   const double *pose_cur = nullptr, *lmk_cur = nullptr;   // the current estimates (V.pose / V.lmk)
   long long sL = 0, sU = 0, sy = 0, sx = 0, spose = 0, slmk = 0, spe = 0, spa = 0, sflow = 0;   // lane strides (elements)
-  int g0 = 0, g1 = 0;         // workgroups of lane 0 / of every other lane in the (one-dimensional) grid of k_chol_flow
+  int g0 = 0, g1 = 0;         // workgroups of lane 0 / of every other lane in the (one-dimensional) grid of k_chol_spec_round
   int after = 0;              // lanes 1.. take part once `after` trials of the iteration have been rejected (0: always; 1: adaptive)
   int* ctl = nullptr;         // k_chol_spec_round: [0] rounds begun, [1] lanes at work in this round, [2] lanes finished in this round,
                               // [8 + k] end tickets of lane k, [8 + K + k] rounds lane k has run (its epoch)
@@ -87,7 +87,7 @@ struct CholPlan {
   std::vector<int> plv_lds_ff;  // front kernels (front_kernels.hpp): LDS doubles per launch; front: the per-depth launches run them
   int tail_lds_ff = 0;
   bool front = false;
-  int tail_lds_f = 0, tail_lds_b = 0, tail_total = 0, nt_tail = 512, nt_ftail = 256, nt_bleaf = 0, nt_bmid = 0, nt_btail = 0, nt_leaf = 64, ustage = 0;
+  int tail_lds_f = 0, tail_lds_b = 0, tail_total = 0, nt_tail = 512, nt_ftail = 256, nt_bleaf = 0, nt_bmid = 0, nt_btail = 0, ustage = 0;
   std::vector<void*> allocs;
   DevArena* arena = nullptr;    // the owning batch's arena (single-graph handles), else hipMalloc
   int64_t lnz = 0, unz = 0;
@@ -105,11 +105,10 @@ struct CholPlan {
   int flow_grid = 0;            // persistent workgroups
   int spec_grid = 0;            // workgroups of a speculative round (all lanes)
   double flow_need = 1.0, spec_need = 1.0;   // the share of the device those grids occupy when resident (workgroups / what the device holds of them)
-  int flow_first = 0;           // first launch-order piece of the single launch; the per-depth launches [0, flow_launch0) come before it
-  int flow_launch0 = 0;
-  int flow_epoch = 0;           // launches so far: the counters are never reset, a launch waits for epoch * (children)
-  int lm_epoch = 0;             // launches that carried the LM halves of a trial (k_chol_flow, bit 2)
-  int spec_epoch = 0;           // the same for the lanes' own counters (speculative trials)
+  bool flow_narrow = false;     // the bottom depth of the tree is no wider than flow_grid (the speculative lanes and the fused LM halves need it)
+  int flow_epoch = 0;          // launches so far: the counters are never reset, a launch waits for epoch * (children)
+  int lm_epoch = 0;             // launches that carried the LM halves of a trial (k_chol_flow, lmstep)
+  int spec_epoch = 0;           // rounds of the speculative lanes (k_chol_spec_round)
   int2* d_dep = nullptr;        // per launch-order piece: {parent (launch order) or -1, children}
   int* d_flow = nullptr;        // [children done | backward done | forward done] per piece, then [0] error flag at 3 * npiece
   // marginals along the elimination-tree paths (k_chol_marginal_paths)
@@ -1274,6 +1273,30 @@ __device__ __forceinline__ void lm_begin_small(const BatchView& V, const CholVie
   __threadfence_block();
   __syncthreads();
 }
+// the partial sums of graph g's trial (x [+] dx in V.pose_trial / V.lmk_trial): chi2 by edge chunks (k_chi2) into part_e and
+// dx . (lambda dx + b) by row chunks (k_scale) into V.part_a
+template <int NT>
+__device__ __forceinline__ void trial_partial_sums(const BatchView& V, const GraphSeg& sg, int g, double* __restrict__ part_e, double* red) {
+  const int tid = threadIdx.x;
+  const int nec = edge_chunks(sg), nrc = row_chunks(sg);
+  for (int c0 = 0; c0 < nec; c0 += NT / kEdgeChunk) {
+    const int chunk = c0 + tid / kEdgeChunk;
+    const double c = chunk < nec ? edge_chi2(V, sg, chunk * kEdgeChunk + tid % kEdgeChunk, V.pose_trial, V.lmk_trial) : 0.0;
+    vblock_store_sum<kEdgeChunk, NT>(c, red, part_e + (size_t)g * V.maxEdgeChunks + chunk, chunk < nec);
+  }
+  const double lambda = V.lm[g].lambda;
+  constexpr int NV = NT / kRowChunk;
+  for (int c0 = 0; c0 < nrc; c0 += NV) {
+    const int vb = tid / kRowChunk, chunk = c0 + vb;
+    const bool live = vb < NV && chunk < nrc;
+    double v = 0;
+    if (live) {
+      const RowRef R = row_ref(V, sg, chunk * kRowChunk + tid % kRowChunk);
+      if (R.valid) { const double d = V.x[R.xoff]; v = d * (lambda * d + V.bvec[R.xoff]); }
+    }
+    vblock_store_sum<kRowChunk, NT>(v, red, V.part_a + (size_t)g * V.maxRowChunks + chunk, live);
+  }
+}
 template <int NT>
 __device__ __forceinline__ void lm_end_small(const BatchView& V, const CholView& C, int g, double* __restrict__ part_e, int max_iters, double* red) {
   // k_chol_end + k_oplus + k_chi2 + k_scale + k_lm_control + k_commit for graph g (in a trial)
@@ -1285,25 +1308,7 @@ __device__ __forceinline__ void lm_end_small(const BatchView& V, const CholView&
   for (int i = tid; i < sg.nprow + sg.nlrow; i += NT) oplus_row(V, i < sg.nprow ? sg.prow0 + i : V.nPr + sg.lrow0 + (i - sg.nprow), V.x);
   __threadfence_block();
   __syncthreads();
-  for (int c0 = 0; c0 < nec; c0 += NT / kEdgeChunk) {   // the chunks of k_chi2
-    const int chunk = c0 + tid / kEdgeChunk;
-    const double c = chunk < nec ? edge_chi2(V, sg, chunk * kEdgeChunk + tid % kEdgeChunk, V.pose_trial, V.lmk_trial) : 0.0;
-    vblock_store_sum<kEdgeChunk, NT>(c, red, part_e + (size_t)g * V.maxEdgeChunks + chunk, chunk < nec);
-  }
-  {   // dx . (lambda dx + b): the chunks of k_scale
-    const double lambda = S.lambda;
-    constexpr int NV = NT / kRowChunk;
-    for (int c0 = 0; c0 < nrc; c0 += NV) {
-      const int vb = tid / kRowChunk, chunk = c0 + vb;
-      const bool live = vb < NV && chunk < nrc;
-      double v = 0;
-      if (live) {
-        const RowRef R = row_ref(V, sg, chunk * kRowChunk + tid % kRowChunk);
-        if (R.valid) { const double d = V.x[R.xoff]; v = d * (lambda * d + V.bvec[R.xoff]); }
-      }
-      vblock_store_sum<kRowChunk, NT>(v, red, V.part_a + (size_t)g * V.maxRowChunks + chunk, live);
-    }
-  }
+  trial_partial_sums<NT>(V, sg, g, part_e, red);
   __threadfence_block();
   __syncthreads();
   if (tid < 64) {   // accept / reject (k_lm_control)
@@ -1357,11 +1362,8 @@ __device__ __forceinline__ void spec_lane_end(BatchView V, const SpecLanes& SL, 
   const int tid = threadIdx.x;
   V.lm = SL.lm + k * V.B; V.x = SL.x + k * SL.sx; V.pose_trial = SL.pose_trial + k * SL.spose; V.lmk_trial = SL.lmk_trial + k * SL.slmk;
   V.part_a = SL.part_a + k * SL.spa;
-  double* part_e = SL.part_e + k * SL.spe;
-  const LmState& S = V.lm[g];
-  if (!S.active || !S.in_trial) return;
+  if (!V.lm[g].active || !V.lm[g].in_trial) return;
   const GraphSeg sg = V.seg[g];
-  const int nec = edge_chunks(sg), nrc = row_chunks(sg);
   for (int i = tid; i < sg.nprow + sg.nlrow; i += NT) oplus_row(V, i < sg.nprow ? sg.prow0 + i : V.nPr + sg.lrow0 + (i - sg.nprow), V.x);
   // vertices without a row (fixed: the gauge vertex) keep their estimate in the lane's trial arrays too
   const double* __restrict__ cur_pose = SL.pose_cur;
@@ -1370,23 +1372,7 @@ __device__ __forceinline__ void spec_lane_end(BatchView V, const SpecLanes& SL, 
   for (int i = tid; i < sg.nlm; i += NT) if (V.lm_row[sg.lm0 + i] < 0) for (int q = 0; q < 4; ++q) V.lmk_trial[(size_t)(sg.lm0 + i) * 4 + q] = cur_lmk[(size_t)(sg.lm0 + i) * 4 + q];
   __threadfence_block();
   __syncthreads();
-  for (int c0 = 0; c0 < nec; c0 += NT / kEdgeChunk) {
-    const int chunk = c0 + tid / kEdgeChunk;
-    const double c = chunk < nec ? edge_chi2(V, sg, chunk * kEdgeChunk + tid % kEdgeChunk, V.pose_trial, V.lmk_trial) : 0.0;
-    vblock_store_sum<kEdgeChunk, NT>(c, red, part_e + (size_t)g * V.maxEdgeChunks + chunk, chunk < nec);
-  }
-  const double lambda = S.lambda;
-  constexpr int NV = NT / kRowChunk;
-  for (int c0 = 0; c0 < nrc; c0 += NV) {
-    const int vb = tid / kRowChunk, chunk = c0 + vb;
-    const bool live = vb < NV && chunk < nrc;
-    double v = 0;
-    if (live) {
-      const RowRef R = row_ref(V, sg, chunk * kRowChunk + tid % kRowChunk);
-      if (R.valid) { const double d = V.x[R.xoff]; v = d * (lambda * d + V.bvec[R.xoff]); }
-    }
-    vblock_store_sum<kRowChunk, NT>(v, red, V.part_a + (size_t)g * V.maxRowChunks + chunk, live);
-  }
+  trial_partial_sums<NT>(V, sg, g, SL.part_e + k * SL.spe, red);   // (V.lm, V.x, V.part_a: the lane's)
 }
 // OptimizationAlgorithmLevenberg's do { ... } while (rho < 0 && q < 10) over the finished lanes, in order, and the commit of the accepted one
 template <int NT>
@@ -1455,32 +1441,78 @@ __device__ __forceinline__ bool flow_wait(const int* p, int target, int* err, in
 #include "front_kernels.hpp"
 namespace sslam {
 
+// The two walks of a persistent launch over the pieces of the plan (k_chol_flow, k_chol_spec_round): workgroup wg of nwg takes the
+// launch-order pieces wg, wg + nwg, ...  flow: [children done | backward done | forward done] per piece.  check_trial: a piece whose graph
+// is not in a trial is not computed but still waits and signals (its parent's count includes it); false: every piece is (a lane in a
+// trial -- the constant folds the test away).
 template <int NT, bool USTAGE>
-__global__ __launch_bounds__(NT) void k_chol_flow(BatchView V, CholView C, int q_first, int np, int epoch, const int2* __restrict__ dep, int* flow, SpecLanes SL,
-                                                  int do_backward, double* __restrict__ part_e, int max_iters, int lm_epoch) {
+__device__ __forceinline__ void flow_forward(const BatchView& V, const CholView& C, int np, const int2* __restrict__ dep, int* flow, int wg, int nwg,
+                                             int epoch, int* err, double* sm, bool check_trial) {
+  const int tid = threadIdx.x;
+  int* child_done = flow;
+  int* fwd_done = flow + 2 * np;
+  for (int q = wg; q < np; q += nwg) {
+    const PieceMeta pm = C.lpiece[q];
+    const int2 d = dep[q];
+    const int* wp = d.y > 0 ? child_done + q : nullptr;   // the pieces fetch their tables and H before the wait for the children
+    if (check_trial && !V.lm[pm.graph].in_trial) {   // (set by the begin kernel of the step: not touched inside the launch)
+      if (wp) {
+        if (tid == 0) flow_wait(wp, d.y * epoch, err, C.fail + pm.graph);
+        __syncthreads();
+      }
+    } else if (C.fblob) {   // front tables (front_kernels.hpp)
+      if (q >= C.ltail0) front_piece<NT, true>(V, C, pm, C.lfgrp[q], sm, nullptr, wp, d.y * epoch, err);
+      else front_piece<NT, false>(V, C, pm, C.lfgrp[q], sm, nullptr, wp, d.y * epoch, err);
+    } else if (q >= C.ltail0) {
+      if (C.rupd) chol_piece<NT, false, true, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
+      else chol_piece<NT, false, false, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
+    } else chol_piece<NT, USTAGE, false, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
+    __syncthreads();   // every thread's stores of L, y and the update matrix are issued ...
+    if (tid == 0) {    // ... and released to the other CUs together with the signal
+      __threadfence();
+      if (d.x >= 0) __hip_atomic_fetch_add(child_done + d.x, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      else __hip_atomic_store(fwd_done + q, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+template <int NT>
+__device__ __forceinline__ void flow_backward(const BatchView& V, const CholView& C, int np, const int2* __restrict__ dep, int* flow, int wg, int nwg,
+                                              int epoch, int* err, double* sm, bool check_trial) {
+  const int tid = threadIdx.x;
+  int* back_done = flow + np;
+  int* fwd_done = flow + 2 * np;
+  for (int i = wg; i < np; i += nwg) {
+    const int q = np - 1 - i;
+    const PieceMeta pm = C.lpiece[q];
+    const int2 d = dep[q];
+    if (tid == 0) {
+      if (d.x >= 0) flow_wait(back_done + d.x, epoch, err, C.fail + pm.graph);
+      else flow_wait(fwd_done + q, epoch, err, C.fail + pm.graph);
+    }
+    __syncthreads();
+    if (!check_trial || V.lm[pm.graph].in_trial) chol_piece_backward<NT>(C, pm, C.y, V.x, sm, nullptr);
+    __syncthreads();
+    if (tid == 0) {
+      __threadfence();
+      __hip_atomic_store(back_done + q, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// backward: x = L^-T y after the factorisation (false: the flat factor of the marginals, L only).  lmstep: a whole damping trial in this
+// launch -- what k_lm_begin_small does before the factorisation (workgroup g for graph g, everybody waits for it: lambda and in_trial are
+// read by every piece) and what k_lm_end_small does after the backward substitution (the workgroup that finishes last, by a ticket).  Two
+// launches less per trial of the orchestrator's graphs (measured: 0.02 - 0.15 ms per tick -- a trial waits for the chain of pieces inside
+// this launch, not for launches).
+template <int NT, bool USTAGE>
+__global__ __launch_bounds__(NT) void k_chol_flow(BatchView V, CholView C, int np, int epoch, const int2* __restrict__ dep, int* flow, int backward,
+                                                  int lmstep, double* __restrict__ part_e, int max_iters, int lm_epoch) {
   extern __shared__ double sm[];
   __shared__ double red[NT / 64];
   __shared__ int s_last;
   const int tid = threadIdx.x;
-  const bool defer = do_backward & 2;   // bit 1: tables and H before the wait for the children (chol_piece DEFER)
-  // bit 2: a whole damping trial in this launch -- what k_lm_begin_small does before the factorisation (workgroup g for graph g, everybody
-  // waits for it: lambda and in_trial are read by every piece) and what k_lm_end_small does after the backward substitution (the
-  // workgroup that finishes last, by a ticket).  Two launches less per trial of the orchestrator's graphs (measured: 0.02 - 0.15 ms per
-  // tick -- a trial waits for the chain of pieces inside this launch, not for launches).
-  const bool lmstep = (do_backward & 4) && SL.K == 0;
-  int wg = blockIdx.x, nwg = gridDim.x;
-  if (SL.K > 0) {   // speculative damping trials: a lane = a range of workgroups, with its own factor, vectors, counters and lambda
-    long long k = 0;
-    if (wg < SL.g0) nwg = SL.g0;
-    else { const int r = wg - SL.g0; k = 1 + r / SL.g1; wg = r - (int)(k - 1) * SL.g1; nwg = SL.g1; }
-    V.lm = SL.lm + k * V.B; V.x = SL.x + k * SL.sx;
-    C.Lval = SL.Lval + k * SL.sL; C.Uval = SL.Uval + k * SL.sU; C.y = SL.y + k * SL.sy; C.fail = SL.fail + k * V.B;
-    flow = SL.flow + k * SL.sflow;
-  }
-  int* child_done = flow;
-  int* back_done = flow + np;
-  int* fwd_done = flow + 2 * np;
-  int* err = SL.K > 0 ? SL.err : flow + 3 * np;
+  const int wg = blockIdx.x, nwg = gridDim.x;
+  int* err = flow + 3 * np;
   int* begin_done = flow + 3 * np + 1;
   int* end_ticket = flow + 3 * np + 2;
   if (lmstep) {
@@ -1492,58 +1524,9 @@ __global__ __launch_bounds__(NT) void k_chol_flow(BatchView V, CholView C, int q
     if (tid == 0) flow_wait(begin_done, V.B * lm_epoch, err);   // (its own count: solves without the LM halves share the counters of the pieces)
     __syncthreads();
   }
-  // ---- (H + lambda I) = L L^T and y = L^-1 b, leaves to roots
-  // (pieces before q_first -- the wide bottom of a large graph's tree -- were factored by per-depth launches before this one; dep[].y counts
-  // the children inside [q_first, np) only)
-  for (int q = q_first + wg; q < np; q += nwg) {
-    const PieceMeta pm = C.lpiece[q];
-    const int2 d = dep[q];
-    const bool run = V.lm[pm.graph].in_trial;   // (set by the begin kernel of the step: not touched inside this launch)
-    if (d.y > 0 && !(defer && run)) {
-      if (tid == 0) flow_wait(child_done + q, d.y * epoch, err, C.fail + pm.graph);
-      __syncthreads();
-    }
-    if (run && C.fblob) {   // front tables (front_kernels.hpp): tables before the wait whenever the piece waits
-      const int* wp = (d.y > 0 && defer) ? child_done + q : nullptr;
-      if (q >= C.ltail0) front_piece<NT, true>(V, C, pm, C.lfgrp[q], sm, nullptr, wp, d.y * epoch, err);
-      else front_piece<NT, false>(V, C, pm, C.lfgrp[q], sm, nullptr, wp, d.y * epoch, err);
-    } else if (run) {
-      const int* wp = d.y > 0 ? child_done + q : nullptr;
-      if (defer) {
-        if (q >= C.ltail0) {
-          if (C.rupd) chol_piece<NT, false, true, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
-          else chol_piece<NT, false, false, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
-        } else chol_piece<NT, USTAGE, false, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
-      } else if (q >= C.ltail0) {
-        if (C.rupd) chol_piece<NT, false, true>(V, C, pm, sm, nullptr);
-        else chol_piece<NT, false, false>(V, C, pm, sm, nullptr);
-      } else chol_piece<NT, USTAGE, false>(V, C, pm, sm, nullptr);
-    }
-    __syncthreads();   // every thread's stores of L, y and the update matrix are issued ...
-    if (tid == 0) {    // ... and released to the other CUs together with the signal
-      __threadfence();
-      if (d.x >= 0) __hip_atomic_fetch_add(child_done + d.x, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      else __hip_atomic_store(fwd_done + q, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (!(do_backward & 1)) return;   // the flat factor of the marginals: L only
-  // ---- x = L^-T y, roots to leaves
-  for (int i = wg; i < np - q_first; i += nwg) {
-    const int q = np - 1 - i;
-    const PieceMeta pm = C.lpiece[q];
-    const int2 d = dep[q];
-    if (tid == 0) {
-      if (d.x >= 0) flow_wait(back_done + d.x, epoch, err, C.fail + pm.graph);
-      else flow_wait(fwd_done + q, epoch, err, C.fail + pm.graph);
-    }
-    __syncthreads();
-    if (V.lm[pm.graph].in_trial) chol_piece_backward<NT>(C, pm, C.y, V.x, sm, nullptr);
-    __syncthreads();
-    if (tid == 0) {
-      __threadfence();
-      __hip_atomic_store(back_done + q, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  flow_forward<NT, USTAGE>(V, C, np, dep, flow, wg, nwg, epoch, err, sm, true);   // (H + lambda I) = L L^T and y = L^-1 b, leaves to roots
+  if (!backward) return;
+  flow_backward<NT>(V, C, np, dep, flow, wg, nwg, epoch, err, sm, true);           // x = L^-T y, roots to leaves
   if (lmstep) {   // the rest of the trial: x [+] dx, chi2, accept / reject, commit -- by the workgroup that finishes last
     __syncthreads();
     if (tid == 0) {
@@ -1559,13 +1542,13 @@ __global__ __launch_bounds__(NT) void k_chol_flow(BatchView V, CholView C, int q
   }
 }
 
-// One LM ITERATION'S WORTH of damping trials of a single small graph in ONE launch (speculative_trials): what k_lm_begin_spec, k_chol_flow over
-// the lanes, k_lm_end_spec and k_lm_control_spec did in four.  Workgroup 0 begins the step and sets the lanes up (lane k: the lambda after k
-// rejected trials; the adaptive form puts lanes 1.. to work only once a trial of the iteration has been rejected); everybody waits for
-// that.  The workgroups of a lane that is not at work leave at once -- a lane counts its own rounds (ctl[8 + K + k]) and waits on its own
-// counters with that number, so rounds it sits out cost it nothing.  A lane's workgroups factor and solve as in k_chol_flow (fetch before
-// the wait); the one that takes the lane's last ticket forms the lane's chi2 / scale partial sums; the lane that finishes last replays
-// g2o's accept / reject sequence over the lanes in order and commits the accepted one.  Same sums, same order: bitwise the sequential loop.
+// One LM ITERATION'S WORTH of damping trials of a single small graph in ONE launch (speculative_trials).  Workgroup 0 begins the step and
+// sets the lanes up (lane k: the lambda after k rejected trials; the adaptive form puts lanes 1.. to work only once a trial of the iteration
+// has been rejected); everybody waits for that.  The workgroups of a lane that is not at work leave at once -- a lane counts its own rounds
+// (ctl[8 + K + k]) and waits on its own counters with that number, so rounds it sits out cost it nothing.  A lane's workgroups factor and
+// solve with the walks of k_chol_flow; the one that takes the lane's last ticket forms the lane's chi2 / scale partial sums; the lane that
+// finishes last replays g2o's accept / reject sequence over the lanes in order and commits the accepted one.  Same sums, same order:
+// bitwise the sequential loop.
 template <int NT, bool USTAGE>
 __global__ __launch_bounds__(NT) void k_chol_spec_round(BatchView V, CholView C, int np, const int2* __restrict__ dep, SpecLanes SL, int round, int max_iters) {
   extern __shared__ double sm[];
@@ -1594,45 +1577,9 @@ __global__ __launch_bounds__(NT) void k_chol_spec_round(BatchView V, CholView C,
   C.Lval = SL.Lval + k * SL.sL; C.Uval = SL.Uval + k * SL.sU; C.y = SL.y + k * SL.sy; C.fail = SL.fail + k * V.B;
   if (!V.lm[g].in_trial) return;   // this lane sits the round out (uniform over the lane)
   int* flow = SL.flow + k * SL.sflow;
-  int* child_done = flow;
-  int* back_done = flow + np;
-  int* fwd_done = flow + 2 * np;
-  int* err = SL.err;
   const int epoch = ctl[8 + SL.K + k] + 1;
-  for (int q = wg; q < np; q += nwg) {
-    const PieceMeta pm = C.lpiece[q];
-    const int2 d = dep[q];
-    const int* wp = d.y > 0 ? child_done + q : nullptr;
-    if (C.fblob) {
-      if (q >= C.ltail0) front_piece<NT, true>(V, C, pm, C.lfgrp[q], sm, nullptr, wp, d.y * epoch, err);
-      else front_piece<NT, false>(V, C, pm, C.lfgrp[q], sm, nullptr, wp, d.y * epoch, err);
-    } else if (q >= C.ltail0) {
-      if (C.rupd) chol_piece<NT, false, true, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
-      else chol_piece<NT, false, false, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
-    } else chol_piece<NT, USTAGE, false, true>(V, C, pm, sm, nullptr, wp, d.y * epoch, err);
-    __syncthreads();
-    if (tid == 0) {
-      __threadfence();
-      if (d.x >= 0) __hip_atomic_fetch_add(child_done + d.x, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      else __hip_atomic_store(fwd_done + q, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  for (int i = wg; i < np; i += nwg) {
-    const int q = np - 1 - i;
-    const PieceMeta pm = C.lpiece[q];
-    const int2 d = dep[q];
-    if (tid == 0) {
-      if (d.x >= 0) flow_wait(back_done + d.x, epoch, err, C.fail + pm.graph);
-      else flow_wait(fwd_done + q, epoch, err, C.fail + pm.graph);
-    }
-    __syncthreads();
-    chol_piece_backward<NT>(C, pm, C.y, V.x, sm, nullptr);
-    __syncthreads();
-    if (tid == 0) {
-      __threadfence();
-      __hip_atomic_store(back_done + q, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  flow_forward<NT, USTAGE>(V, C, np, dep, flow, wg, nwg, epoch, SL.err, sm, false);
+  flow_backward<NT>(V, C, np, dep, flow, wg, nwg, epoch, SL.err, sm, false);
   // ---- the lane's last workgroup: its partial sums
   __syncthreads();
   if (tid == 0) {
@@ -1668,6 +1615,23 @@ __global__ void k_chol_end(BatchView V, CholView C) {  // publish failures throu
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
+// The workgroup widths the kernels exist for.  chol_opts_normalise (chol_plan.hpp) maps every width option onto its set; a launch calls
+// f(std::integral_constant<int, W>) through with_width, and a width outside the set is an error, never another width.
+template <int... W> struct Widths {};
+using LeafWidths = Widths<64, 128, 256, 512, 1024>;   // k_chol_pieces, k_front_pieces, k_chol_back_pieces
+using MidWidths = Widths<128, 256, 512>;              // k_chol_pieces of the mid class (RIGHT)
+using TailWidths = Widths<512, 1024>;                 // k_chol_tail
+using FrontTailWidths = Widths<128, 256, 512, 1024>;  // k_front_tail
+using BackTailWidths = Widths<128, 256, 512>;         // k_chol_back_tail
+using Flag = Widths<0, 1>;                            // a bool template argument
+template <int... W, class F>
+static int with_width(Widths<W...>, int v, F&& f) {
+  if (((v == W && (f(std::integral_constant<int, W>{}), true)) || ...)) return 0;
+  return set_error(SSLAM_ERR_INVALID, "sparse Cholesky: no kernel for workgroup width %d (chol_opts_normalise maps every width option)", v);
+}
+template <int... W, class F>
+static void for_each_width(Widths<W...>, F&& f) { (f(std::integral_constant<int, W>{}), ...); }
+
 namespace {
 template <typename T>
 int up_to_dev(CholPlan& P, hipStream_t s, const std::vector<T>& h, const T** out) {
@@ -1725,7 +1689,7 @@ int chol_plan_build(Batch& b) {
   CholView& C = P->C;
   C.ncol = H.ncol; C.nlevels = H.nlevels; C.dim = H.dim; C.npiece = H.npiece;
   P->lvl_ptr = H.lvl_ptr; P->plv_ptr = H.plv_ptr; P->plv_lds_f = H.plv_lds_f; P->plv_lds_b = H.plv_lds_b; P->plv_nt = H.plv_nt; P->plv_cls = H.plv_cls;
-  P->tail_lds_f = H.tail_lds_f; P->tail_lds_b = H.tail_lds_b; P->tail_total = (int)H.tail_pieces.size(); P->nt_tail = H.nt_tail; P->nt_ftail = H.nt_ftail; P->nt_bleaf = H.nt_bleaf; P->nt_bmid = H.nt_bmid; P->nt_btail = H.nt_btail; P->nt_leaf = H.nt_leaf; P->ustage = H.ustage;
+  P->tail_lds_f = H.tail_lds_f; P->tail_lds_b = H.tail_lds_b; P->tail_total = (int)H.tail_pieces.size(); P->nt_tail = H.nt_tail; P->nt_ftail = H.nt_ftail; P->nt_bleaf = H.nt_bleaf; P->nt_bmid = H.nt_bmid; P->nt_btail = H.nt_btail; P->ustage = H.ustage;
   P->lnz = H.lnz;
   {   // elimination-tree parents (first block below the diagonal) and the vertex -> column map, for the path marginals
     std::vector<int> yoff_col(H.dim + 1, -1);
@@ -1841,23 +1805,18 @@ int chol_plan_build(Batch& b) {
     static std::vector<int> done;
     std::lock_guard<std::mutex> lk(mu);
     if (std::find(done.begin(), done.end(), b.device) == done.end()) {
-      const int v = lds_lim;
-      const void* fns[] = {(const void*)k_chol_pieces<64, true>, (const void*)k_chol_pieces<128, true>, (const void*)k_chol_pieces<256, true>,
-                           (const void*)k_chol_pieces<512, true>, (const void*)k_chol_pieces<1024, true>,
-                           (const void*)k_chol_pieces<64, false>, (const void*)k_chol_pieces<128, false>, (const void*)k_chol_pieces<256, false>,
-                           (const void*)k_chol_pieces<512, false>, (const void*)k_chol_pieces<1024, false>,
-                           (const void*)k_chol_pieces<128, false, true>, (const void*)k_chol_pieces<256, false, true>, (const void*)k_chol_pieces<512, false, true>,
-                           (const void*)k_chol_tail<512>, (const void*)k_chol_tail<1024>,
-                           (const void*)k_chol_back_pieces<64>, (const void*)k_chol_back_pieces<128>, (const void*)k_chol_back_pieces<256>,
-                           (const void*)k_chol_back_pieces<512>, (const void*)k_chol_back_pieces<1024>, (const void*)k_chol_back_tail<128>, (const void*)k_chol_back_tail<256>, (const void*)k_chol_back_tail<512>,
-                           (const void*)k_chol_flow<512, true>, (const void*)k_chol_flow<512, false>,
-                           (const void*)k_chol_spec_round<512, true>, (const void*)k_chol_spec_round<512, false>,
-                           (const void*)k_front_pieces<64, false>, (const void*)k_front_pieces<128, false>, (const void*)k_front_pieces<256, false>,
-                           (const void*)k_front_pieces<512, false>, (const void*)k_front_pieces<1024, false>,
-                           (const void*)k_front_pieces<64, true>, (const void*)k_front_pieces<128, true>, (const void*)k_front_pieces<256, true>,
-                           (const void*)k_front_pieces<512, true>, (const void*)k_front_pieces<1024, true>,
-                           (const void*)k_front_tail<128>, (const void*)k_front_tail<256>, (const void*)k_front_tail<512>, (const void*)k_front_tail<1024>};
-      for (const void* f : fns) SSLAM_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, v));
+      std::vector<const void*> fns = {(const void*)k_chol_flow<512, true>, (const void*)k_chol_flow<512, false>,
+                                      (const void*)k_chol_spec_round<512, true>, (const void*)k_chol_spec_round<512, false>};
+      for_each_width(LeafWidths{}, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        fns.insert(fns.end(), {(const void*)k_chol_pieces<NT, true>, (const void*)k_chol_pieces<NT, false>, (const void*)k_chol_back_pieces<NT>,
+                               (const void*)k_front_pieces<NT, false>, (const void*)k_front_pieces<NT, true>});
+      });
+      for_each_width(MidWidths{}, [&](auto nt) { fns.push_back((const void*)k_chol_pieces<decltype(nt)::value, false, true>); });
+      for_each_width(TailWidths{}, [&](auto nt) { fns.push_back((const void*)k_chol_tail<decltype(nt)::value>); });
+      for_each_width(FrontTailWidths{}, [&](auto nt) { fns.push_back((const void*)k_front_tail<decltype(nt)::value>); });
+      for_each_width(BackTailWidths{}, [&](auto nt) { fns.push_back((const void*)k_chol_back_tail<decltype(nt)::value>); });
+      for (const void* f : fns) SSLAM_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_lim));
       done.push_back(b.device);
     }
   }
@@ -1869,25 +1828,18 @@ int chol_plan_build(Batch& b) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 512, lds_max) != hipSuccess || per_cu < 1 ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b.device) != hipSuccess || cus < 1) P->flow = false;
     else {
-      // the wide bottom of a large tree keeps its per-depth launches (hundreds of independent pieces fill the chip at once; a persistent
-      // grid would walk them in rounds): the single launch starts at the first depth that is no wider than its grid
+      // Every workgroup of the grid is resident (at most half of what the device holds at once), workgroup w takes the pieces w, w + G, ...
+      // in increasing order and children come before their parents in launch order: the lowest unfinished piece always has its children
+      // done, so the walk progresses whatever the width of the tree.  But a wide tree is walked in rounds, with an agent-scope release /
+      // acquire per piece: measured on one 5000-pose graph (733 / 358 / 148 / ... pieces per depth), per-depth launches for the wide depths
+      // + the single launch for the rest 1.56 ms per LM iteration, a launch per depth 1.01 ms.  The single launch is for trees that are
+      // no wider than the grid at the bottom depth (the orchestrator's graphs: 5.1 vs 5.7 ms per tick at 110 keyframes); flow=2 takes it
+      // on any tree (tests: a persistent workgroup walks many pieces)
       const int cap = std::max(1, per_cu * cus / 2);
-      int l0 = 0;
-      while (l0 < (int)P->plv_lds_f.size() && P->plv_ptr[l0 + 1] - P->plv_ptr[l0] > cap) ++l0;
-      P->flow_launch0 = l0;
-      // measured on one 5000-pose graph (733 / 358 / 148 / ... pieces per depth): launches for the wide depths + the single launch for the
-      // rest 1.56 ms per LM iteration, a launch per depth 1.01 ms (both with 512-thread pieces; 1.50 ms with round 3's 64-thread pieces) --
-      // a persistent grid walks a wide tree in rounds and pays an agent-scope release / acquire per piece.  The single launch is for trees
-      // that are narrower than the grid at every depth (the orchestrator's graphs: 5.1 vs 5.7 ms per tick at 110 keyframes)
-      if (l0 > 0 && flow_mode != 2) P->flow = false;
-      P->flow_first = l0 < (int)P->plv_ptr.size() ? P->plv_ptr[l0] : 0;
-      P->flow_grid = std::max(1, std::min((int)dep.size() - P->flow_first, cap));
+      P->flow_narrow = P->plv_lds_f.empty() || P->plv_ptr[1] - P->plv_ptr[0] <= cap;
+      if (!P->flow_narrow && flow_mode != 2) P->flow = false;
+      P->flow_grid = std::max(1, std::min((int)dep.size(), cap));
       P->flow_need = std::min(1.0, (double)P->flow_grid / (double)(per_cu * cus));
-      if (!P->flow) { /* launch-per-depth path */ }
-      else if (P->flow_first > 0) {   // children that the launches finish are not waited for
-        for (auto& d2 : dep) d2.y = 0;
-        for (int i = P->flow_first; i < (int)dep.size(); ++i) if (dep[i].x >= 0) dep[dep[i].x].y++;
-      }
       if ((rc = up_to_dev(*P, b.stream, dep, (const int2**)&P->d_dep))) return rc;
       const size_t nints = 3 * dep.size() + 8;
       if ((rc = plan_alloc(&p, nints * sizeof(int)))) return rc;
@@ -1897,7 +1849,7 @@ int chol_plan_build(Batch& b) {
       // speculative damping trials: one small graph whose ten lanes of pieces are all on the chip at once
       const int K = 10;
       const int spec_mode = chol_spec_mode(b);
-      if (spec_mode && b.V.B == 1 && P->flow_launch0 == 0) {   // (the lanes cost three allocations + memsets per rebuild)
+      if (spec_mode && b.V.B == 1 && P->flow_narrow) {   // (the lanes cost three allocations + memsets per rebuild)
         // K lanes of persistent workgroups, all of them on the chip at once.  Lane 0 -- the only one at work until a trial of the iteration
         // has been rejected (adaptive form) -- gets a workgroup per piece like the plain single-launch solve, the others share the rest
         SpecLanes& SL = P->spec;
@@ -1915,7 +1867,7 @@ int chol_plan_build(Batch& b) {
           SL.after = spec_mode == 2 ? 0 : 1;
           P->spec_grid = SL.g0 + (K - 1) * SL.g1;
           P->spec_need = std::min(1.0, (double)P->spec_grid / (double)(per_cu_s * cus));
-          SL.sL = (H.lnz + 64 + 1) & ~1LL; SL.sU = (H.unz + 64 + 1) & ~1LL; SL.sy = (C.dim + 8 + 1) & ~1LL; SL.sx = (C.dim + 8 + 1) & ~1LL;
+          SL.sL = (H.lnz + 64 + 1) & ~1LL; SL.sU = (unz_all + 64 + 1) & ~1LL; SL.sy = (C.dim + 8 + 1) & ~1LL; SL.sx = (C.dim + 8 + 1) & ~1LL;
           SL.spose = (long long)b.V.nPose * 8; SL.slmk = (long long)b.V.nLm * 4; SL.spe = (long long)b.V.B * b.V.maxEdgeChunks; SL.spa = (long long)b.V.B * b.V.maxRowChunks;
           SL.sflow = (long long)nints;
           const size_t nd = (size_t)K * (SL.sL + SL.sU + SL.sy + SL.sx + SL.spose + SL.slmk + SL.spe + SL.spa);
@@ -2022,43 +1974,25 @@ static size_t plan_flow_lds(const CholPlan& P) {
 
 // (H + lambda I) dx = b in ONE launch (k_chol_flow) for plans that allow it; false: the caller takes the launch-per-depth path
 bool chol_plan_flow(const Batch& b) { return b.chol && b.chol->flow && !b.chol->compact; }
-// the launches of one solve: per-depth launches over the wide bottom of the tree, the dependency-driven launch over the rest (factor and
-// both substitutions), per-depth launches of the backward substitution over the bottom again
-static void flow_launches(Batch& b, bool spec = false, bool backward = true, bool lmstep = false, int max_iters = 0) {
+// the single launch of one solve: factor and forward substitution, then (backward) the backward substitution, (lmstep) inside the LM
+// halves of a damping trial
+static int flow_launch(Batch& b, bool backward, bool lmstep = false, int max_iters = 0) {
   CholPlan& P = *b.chol;
-  const CholView& C = P.C;
-  const size_t lds = plan_flow_lds(P);
-  const int np = (int)P.lp_graph.size();
-  for (int l = 0; l < P.flow_launch0; ++l) {
-    const int n = P.plv_ptr[l + 1] - P.plv_ptr[l];
-    if (P.ustage) hipLaunchKernelGGL((k_chol_pieces<512, true>), dim3(n), dim3(512), (size_t)P.plv_lds_f[l] * sizeof(double), b.stream, b.V, C, P.plv_ptr[l], (const int*)nullptr);
-    else hipLaunchKernelGGL((k_chol_pieces<512, false>), dim3(n), dim3(512), (size_t)P.plv_lds_f[l] * sizeof(double), b.stream, b.V, C, P.plv_ptr[l], (const int*)nullptr);
-  }
-  const int epoch = spec ? ++P.spec_epoch : ++P.flow_epoch;   // the lanes count on their own counters
-  const SpecLanes SL = spec ? P.spec : SpecLanes{};
+  const int epoch = ++P.flow_epoch;
   const int lm_epoch = lmstep ? ++P.lm_epoch : 0;
-  const dim3 grid(spec ? P.spec_grid : P.flow_grid);
-  const int defer = 2;   // tables + H before the wait for the children (round 4: -0.43 ms per tick)
-  {
-    PersistScope gate(b.device, b.stream, spec ? P.spec_need : P.flow_need);
-    if (P.ustage) hipLaunchKernelGGL((k_chol_flow<512, true>), grid, dim3(512), lds, b.stream, b.V, C, P.flow_first, np, epoch, (const int2*)P.d_dep, P.d_flow, SL, (backward ? 1 : 0) | defer | (lmstep ? 4 : 0), b.d_part_e, max_iters, lm_epoch);
-    else hipLaunchKernelGGL((k_chol_flow<512, false>), grid, dim3(512), lds, b.stream, b.V, C, P.flow_first, np, epoch, (const int2*)P.d_dep, P.d_flow, SL, (backward ? 1 : 0) | defer | (lmstep ? 4 : 0), b.d_part_e, max_iters, lm_epoch);
-  }
-  for (int l = P.flow_launch0 - 1; l >= 0 && backward; --l) {
-    const int n = P.plv_ptr[l + 1] - P.plv_ptr[l];
-    hipLaunchKernelGGL(k_chol_back_pieces<512>, dim3(n), dim3(512), (size_t)P.plv_lds_b[l] * sizeof(double), b.stream, C, P.plv_ptr[l], (const double*)C.y, b.V.x, (const LmState*)b.V.lm, (const int*)nullptr);
-  }
+  PersistScope gate(b.device, b.stream, P.flow_need);
+  return with_width(Flag{}, P.ustage ? 1 : 0, [&](auto us) {
+    hipLaunchKernelGGL((k_chol_flow<512, (bool)decltype(us)::value>), dim3(P.flow_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C, (int)P.lp_graph.size(),
+                       epoch, (const int2*)P.d_dep, P.d_flow, backward ? 1 : 0, lmstep ? 1 : 0, b.d_part_e, max_iters, lm_epoch);
+  });
 }
 int chol_solve_flow(Batch& b) {
   CholPlan& P = *b.chol;
   P.C.flat_L = 0;
-  const CholView& C = P.C;
   ScopedTimer t(b, "factor");
-  const size_t lds = plan_flow_lds(P);
-  const int np = (int)P.lp_graph.size();
-  hipLaunchKernelGGL(k_chol_begin, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, C);
-  flow_launches(b);
-  hipLaunchKernelGGL(k_chol_end, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, C);
+  hipLaunchKernelGGL(k_chol_begin, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, P.C);
+  if (int rc = flow_launch(b, true)) return rc;
+  hipLaunchKernelGGL(k_chol_end, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, P.C);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "cholesky flow launch: %s", hipGetErrorString(e));
   return 0;
@@ -2068,7 +2002,7 @@ int chol_factor_flat_flow(Batch& b) {
   CholPlan& P = *b.chol;
   P.C.flat_L = 1;
   hipLaunchKernelGGL(k_chol_begin, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, P.C);
-  flow_launches(b, false, false);
+  if (int rc = flow_launch(b, false)) return rc;
   hipLaunchKernelGGL(k_chol_end, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, P.C);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "cholesky flow launch: %s", hipGetErrorString(e));
@@ -2078,16 +2012,15 @@ int chol_factor_flat_flow(Batch& b) {
 int chol_lm_step_flow(Batch& b, int max_iters) {
   CholPlan& P = *b.chol;
   P.C.flat_L = 0;
-  const CholView& C = P.C;
-  const size_t lds = plan_flow_lds(P);
-  const int np = (int)P.lp_graph.size();
-  // the begin / end halves of the trial inside the launch when it covers the whole tree and has a workgroup per graph
-  if (P.flow_launch0 == 0 && P.flow_grid >= b.V.B) { flow_launches(b, false, true, true, max_iters); }
+  int rc;
+  // the begin / end halves of the trial inside the launch when the tree is narrow and the grid has a workgroup per graph
+  if (P.flow_narrow && P.flow_grid >= b.V.B) rc = flow_launch(b, true, true, max_iters);
   else {
-    hipLaunchKernelGGL(k_lm_begin_small<512>, dim3(b.V.B), dim3(512), 0, b.stream, b.V, C);
-    flow_launches(b);
-    hipLaunchKernelGGL(k_lm_end_small<512>, dim3(b.V.B), dim3(512), 0, b.stream, b.V, C, b.d_part_e, max_iters);
+    hipLaunchKernelGGL(k_lm_begin_small<512>, dim3(b.V.B), dim3(512), 0, b.stream, b.V, P.C);
+    rc = flow_launch(b, true);
+    hipLaunchKernelGGL(k_lm_end_small<512>, dim3(b.V.B), dim3(512), 0, b.stream, b.V, P.C, b.d_part_e, max_iters);
   }
+  if (rc) return rc;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "LM step launch: %s", hipGetErrorString(e));
   return 0;
@@ -2097,14 +2030,16 @@ bool chol_plan_spec(const Batch& b) { return chol_plan_flow(b) && b.chol->spec.K
 int chol_lm_step_spec(Batch& b, int max_iters) {
   CholPlan& P = *b.chol;
   P.C.flat_L = 0;
-  const size_t lds = plan_flow_lds(P);
-  const int np = (int)P.lp_graph.size();
   const int round = ++P.spec_epoch;
+  int rc;
   {
     PersistScope gate(b.device, b.stream, P.spec_need);
-    if (P.ustage) hipLaunchKernelGGL((k_chol_spec_round<512, true>), dim3(P.spec_grid), dim3(512), lds, b.stream, b.V, P.C, np, (const int2*)P.d_dep, P.spec, round, max_iters);
-    else hipLaunchKernelGGL((k_chol_spec_round<512, false>), dim3(P.spec_grid), dim3(512), lds, b.stream, b.V, P.C, np, (const int2*)P.d_dep, P.spec, round, max_iters);
+    rc = with_width(Flag{}, P.ustage ? 1 : 0, [&](auto us) {
+      hipLaunchKernelGGL((k_chol_spec_round<512, (bool)decltype(us)::value>), dim3(P.spec_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C,
+                         (int)P.lp_graph.size(), (const int2*)P.d_dep, P.spec, round, max_iters);
+    });
   }
+  if (rc) return rc;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "speculative LM step launch: %s", hipGetErrorString(e));
   return 0;
@@ -2176,57 +2111,42 @@ int chol_factor_and_forward(Batch& b, bool flat) {
     const int n = P.compact ? P.c_ptr[l + 1] - P.c_ptr[l] : P.plv_ptr[l + 1] - P.plv_ptr[l];
     if (n <= 0) continue;
     const int* idx = P.compact ? P.d_idx + P.c_ptr[l] : nullptr;
+    const int begin = P.plv_ptr[l];
+    const bool mid = P.plv_cls[l] == 1;
+    int rc;
     if (P.front) {   // front tables: one kernel for every class, the workgroup size the launch was cut for
-      const size_t ldf = (size_t)P.plv_lds_ff[l] * sizeof(double);
-#define SSLAM_LAUNCH_FRONT(NTV)                                                                                                     \
-  if (P.plv_cls[l] == 1) hipLaunchKernelGGL((k_front_pieces<NTV, true>), dim3(n), dim3(NTV), ldf, b.stream, b.V, C, P.plv_ptr[l], idx);   \
-  else hipLaunchKernelGGL((k_front_pieces<NTV, false>), dim3(n), dim3(NTV), ldf, b.stream, b.V, C, P.plv_ptr[l], idx);
-      switch (P.plv_nt[l]) {
-        case 128: SSLAM_LAUNCH_FRONT(128) break;
-        case 256: SSLAM_LAUNCH_FRONT(256) break;
-        case 512: SSLAM_LAUNCH_FRONT(512) break;
-        case 1024: SSLAM_LAUNCH_FRONT(1024) break;
-        default: SSLAM_LAUNCH_FRONT(64) break;
-      }
-#undef SSLAM_LAUNCH_FRONT
-      continue;
+      const size_t lds = (size_t)P.plv_lds_ff[l] * sizeof(double);
+      rc = with_width(LeafWidths{}, P.plv_nt[l], [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (mid) hipLaunchKernelGGL((k_front_pieces<NT, true>), dim3(n), dim3(NT), lds, b.stream, b.V, C, begin, idx);
+        else hipLaunchKernelGGL((k_front_pieces<NT, false>), dim3(n), dim3(NT), lds, b.stream, b.V, C, begin, idx);
+      });
+    } else if (mid) {   // mid pieces: wider workgroups, right-looking internal updates, update-matrix records from HBM
+      const size_t lds = (size_t)P.plv_lds_f[l] * sizeof(double);
+      rc = with_width(MidWidths{}, P.plv_nt[l], [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (C.rupd) hipLaunchKernelGGL((k_chol_pieces<NT, false, true>), dim3(n), dim3(NT), lds, b.stream, b.V, C, begin, idx);
+        else hipLaunchKernelGGL((k_chol_pieces<NT, false, false>), dim3(n), dim3(NT), lds, b.stream, b.V, C, begin, idx);
+      });
+    } else {
+      const size_t lds = (size_t)P.plv_lds_f[l] * sizeof(double);
+      rc = with_width(LeafWidths{}, P.plv_nt[l], [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (P.ustage) hipLaunchKernelGGL((k_chol_pieces<NT, true>), dim3(n), dim3(NT), lds, b.stream, b.V, C, begin, idx);
+        else hipLaunchKernelGGL((k_chol_pieces<NT, false>), dim3(n), dim3(NT), lds, b.stream, b.V, C, begin, idx);
+      });
     }
-    const size_t lds = (size_t)P.plv_lds_f[l] * sizeof(double);
-#define SSLAM_LAUNCH_PIECES(NTV)                                                                                                   \
-  if (P.ustage) hipLaunchKernelGGL((k_chol_pieces<NTV, true>), dim3(n), dim3(NTV), lds, b.stream, b.V, C, P.plv_ptr[l], idx);       \
-  else hipLaunchKernelGGL((k_chol_pieces<NTV, false>), dim3(n), dim3(NTV), lds, b.stream, b.V, C, P.plv_ptr[l], idx);
-#define SSLAM_LAUNCH_MID(NTV)                                                                                                      \
-  if (C.rupd) hipLaunchKernelGGL((k_chol_pieces<NTV, false, true>), dim3(n), dim3(NTV), lds, b.stream, b.V, C, P.plv_ptr[l], idx);  \
-  else hipLaunchKernelGGL((k_chol_pieces<NTV, false, false>), dim3(n), dim3(NTV), lds, b.stream, b.V, C, P.plv_ptr[l], idx);
-    if (P.plv_cls[l] == 1) {   // mid pieces: wider workgroups, right-looking internal updates, update-matrix records from HBM
-      switch (P.plv_nt[l]) {
-        case 128: SSLAM_LAUNCH_MID(128) break;
-        case 512: SSLAM_LAUNCH_MID(512) break;
-        default: SSLAM_LAUNCH_MID(256) break;
-      }
-    } else switch (P.nt_leaf) {
-      case 128: SSLAM_LAUNCH_PIECES(128) break;
-      case 512: SSLAM_LAUNCH_PIECES(512) break;
-      case 1024: SSLAM_LAUNCH_PIECES(1024) break;
-      case 256: SSLAM_LAUNCH_PIECES(256) break;
-      default: SSLAM_LAUNCH_PIECES(64) break;
-    }
-#undef SSLAM_LAUNCH_PIECES
-#undef SSLAM_LAUNCH_MID
+    if (rc) return rc;
   }
-  if (P.tail_total > 0) {
-    const int n = P.compact ? P.c_ptr[nplv + 1] - P.c_ptr[nplv] : b.V.B;
+  const int n = P.compact ? P.c_ptr[nplv + 1] - P.c_ptr[nplv] : b.V.B;
+  if (P.tail_total > 0 && n > 0) {
     const int* idx = P.compact ? P.d_idx + P.c_ptr[nplv] : nullptr;
-    if (n > 0 && P.front) {
-      const int ntf = P.nt_tail == 1024 ? 1024 : P.nt_ftail;
-      if (ntf == 1024) hipLaunchKernelGGL(k_front_tail<1024>, dim3(n), dim3(1024), (size_t)P.tail_lds_ff * sizeof(double), b.stream, b.V, C, idx);
-      else if (ntf == 128) hipLaunchKernelGGL(k_front_tail<128>, dim3(n), dim3(128), (size_t)P.tail_lds_ff * sizeof(double), b.stream, b.V, C, idx);
-      else if (ntf == 256) hipLaunchKernelGGL(k_front_tail<256>, dim3(n), dim3(256), (size_t)P.tail_lds_ff * sizeof(double), b.stream, b.V, C, idx);
-      else hipLaunchKernelGGL(k_front_tail<512>, dim3(n), dim3(512), (size_t)P.tail_lds_ff * sizeof(double), b.stream, b.V, C, idx);
-    } else if (n > 0) {
-      if (P.nt_tail == 1024) hipLaunchKernelGGL(k_chol_tail<1024>, dim3(n), dim3(1024), (size_t)P.tail_lds_f * sizeof(double), b.stream, b.V, C, idx);
-      else hipLaunchKernelGGL(k_chol_tail<512>, dim3(n), dim3(512), (size_t)P.tail_lds_f * sizeof(double), b.stream, b.V, C, idx);
-    }
+    const int rc = P.front ? with_width(FrontTailWidths{}, P.nt_ftail, [&](auto nt) {
+      hipLaunchKernelGGL(k_front_tail<decltype(nt)::value>, dim3(n), dim3(nt), (size_t)P.tail_lds_ff * sizeof(double), b.stream, b.V, C, idx);
+    }) : with_width(TailWidths{}, P.nt_tail, [&](auto nt) {
+      hipLaunchKernelGGL(k_chol_tail<decltype(nt)::value>, dim3(n), dim3(nt), (size_t)P.tail_lds_f * sizeof(double), b.stream, b.V, C, idx);
+    });
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(k_chol_end, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, C);
   hipError_t e = hipGetLastError();
@@ -2240,29 +2160,25 @@ int chol_backward(Batch& b) {
   if (C.flat_L) return set_error(SSLAM_ERR_INVALID, "chol_backward needs the class-interleaved factor (the last factorisation was a flat one)");
   ScopedTimer t(b, "solve");
   const int nplv = (int)P.plv_lds_b.size();
-  if (P.tail_total > 0) {
-    const int n = P.compact ? P.c_ptr[nplv + 1] - P.c_ptr[nplv] : b.V.B;
+  const int ntail = P.compact ? P.c_ptr[nplv + 1] - P.c_ptr[nplv] : b.V.B;
+  if (P.tail_total > 0 && ntail > 0) {
     const int* idx = P.compact ? P.d_idx + P.c_ptr[nplv] : nullptr;
-    const int ntb = P.nt_btail == 128 || P.nt_btail == 256 ? P.nt_btail : 512;
-    if (n > 0 && ntb == 128) hipLaunchKernelGGL(k_chol_back_tail<128>, dim3(n), dim3(128), (size_t)P.tail_lds_b * sizeof(double), b.stream, C, (const double*)C.y, b.V.x, (const LmState*)b.V.lm, idx);
-    else if (n > 0 && ntb == 256) hipLaunchKernelGGL(k_chol_back_tail<256>, dim3(n), dim3(256), (size_t)P.tail_lds_b * sizeof(double), b.stream, C, (const double*)C.y, b.V.x, (const LmState*)b.V.lm, idx);
-    else if (n > 0) hipLaunchKernelGGL(k_chol_back_tail<512>, dim3(n), dim3(512), (size_t)P.tail_lds_b * sizeof(double), b.stream, C, (const double*)C.y, b.V.x, (const LmState*)b.V.lm, idx);
+    const int rc = with_width(BackTailWidths{}, P.nt_btail, [&](auto w) {
+      hipLaunchKernelGGL(k_chol_back_tail<decltype(w)::value>, dim3(ntail), dim3(w), (size_t)P.tail_lds_b * sizeof(double), b.stream, C, (const double*)C.y, b.V.x,
+                         (const LmState*)b.V.lm, idx);
+    });
+    if (rc) return rc;
   }
   for (int l = nplv - 1; l >= 0; --l) {
     const int n = P.compact ? P.c_ptr[l + 1] - P.c_ptr[l] : P.plv_ptr[l + 1] - P.plv_ptr[l];
     if (n <= 0) continue;
     const int* idx = P.compact ? P.d_idx + P.c_ptr[l] : nullptr;
-    const size_t lds = (size_t)P.plv_lds_b[l] * sizeof(double);
-#define SSLAM_LAUNCH_BACK(NTV) hipLaunchKernelGGL(k_chol_back_pieces<NTV>, dim3(n), dim3(NTV), lds, b.stream, C, P.plv_ptr[l], (const double*)C.y, b.V.x, (const LmState*)b.V.lm, idx);
-    const int ovr = P.plv_cls[l] == 1 ? P.nt_bmid : P.nt_bleaf;
-    switch (ovr > 0 ? ovr : P.plv_nt[l]) {
-      case 128: SSLAM_LAUNCH_BACK(128) break;
-      case 512: SSLAM_LAUNCH_BACK(512) break;
-      case 1024: SSLAM_LAUNCH_BACK(1024) break;
-      case 256: SSLAM_LAUNCH_BACK(256) break;
-      default: SSLAM_LAUNCH_BACK(64) break;
-    }
-#undef SSLAM_LAUNCH_BACK
+    const int ovr = P.plv_cls[l] == 1 ? P.nt_bmid : P.nt_bleaf;   // 0: the workgroup of the factorisation
+    const int rc = with_width(LeafWidths{}, ovr > 0 ? ovr : P.plv_nt[l], [&](auto w) {
+      hipLaunchKernelGGL(k_chol_back_pieces<decltype(w)::value>, dim3(n), dim3(w), (size_t)P.plv_lds_b[l] * sizeof(double), b.stream, C, P.plv_ptr[l],
+                         (const double*)C.y, b.V.x, (const LmState*)b.V.lm, idx);
+    });
+    if (rc) return rc;
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "cholesky solve launch: %s", hipGetErrorString(e));

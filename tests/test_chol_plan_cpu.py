@@ -268,6 +268,24 @@ def test_front_tables_are_a_fraction_of_the_record_tables(hip_lib):
     assert any(plan.front_group(p)["n2"] > 0 for p in range(plan.npiece))     # blocks with a second child source exist (the rank lists are exercised)
 
 
+def test_out_of_set_workgroup_widths_plan_as_their_normalised_values(hip_lib):
+    """chol_opts_normalise maps every workgroup width option onto the widths the kernels exist for, so the plan (the front tables'
+    team capacity is sized by nt_ftail) sees the width the launch runs: nt_ftail=2048 plans exactly as its launch width 512, and the
+    backward-substitution widths, which only the launches read, leave the plan alone."""
+    names = ("col", "blk", "upd", "item", "mb", "ilv", "piece", "lvl_ptr", "lvl_cols", "plv_ptr", "plv_pieces", "ppoff", "plblk", "tail_ptr",
+             "tail_pieces", "plv_lds_f", "plv_lds_b", "scalars", "asrc", "usrc", "fwd", "uitem", "umb", "rcol", "rupd", "plv_nt", "plv_cls",
+             "fblob", "fgrp", "plv_lds_ff")
+    g = make_graph(150, 30, seed=5)
+    base = {"cap_leaf": 400, "cap_tail": 700, "tail_width": 2}
+    a, _, _ = _plan_and_system(hip_lib, g, False, dict(base, nt_ftail=2048, nt_btail=100, nt_bleaf=100, nt_bmid=-3))
+    b, _, _ = _plan_and_system(hip_lib, g, False, dict(base, nt_ftail=512))
+    assert a.front and b.front and len(a.tail_pieces) > 0
+    for name in names:
+        x, y = getattr(a, name), getattr(b, name)
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), name
+    assert (a.front, a.funz, a.tail_lds_ff) == (b.front, b.funz, b.tail_lds_ff)   # fscalars
+
+
 def test_parent_links_and_both_orderings_factor(hip_lib):
     """Every piece names the piece its update matrix goes to (what the dependency-driven launch k_chol_flow waits on); both elimination
     orders (multiple minimum degree over independent sets, round 4; lowest-index minimum degree) give a valid plan, and the new one a

@@ -159,6 +159,8 @@ def test_cholesky_solve_matches_oracle_cholesky(gpu_lib, lam):
     {"front": "1", "flow": "0", "cap_leaf": "400", "tail_width": "2", "mid_width": "12", "cap_mid": "1200"},
     {"front": "1", "flow": "0", "cap_leaf": "300", "group_cap": "1200", "nt_leaf": "128", "tail_width": "0", "mid_width": "8", "cap_mid": "1500"},
     {"front": "1", "cap_leaf": "400", "cap_tail": "700", "tail_width": "2"},
+    # widths outside the instantiated sets: planned and launched as their normalised values (chol_opts_normalise)
+    {"front": "1", "flow": "0", "cap_leaf": "400", "cap_tail": "700", "tail_width": "2", "nt_ftail": "2048", "nt_btail": "100", "nt_bleaf": "100"},
 ])
 def test_cholesky_pieces_of_every_shape(gpu_lib, monkeypatch, env):
     """The piece plan is cut by LDS capacity; caps far below the defaults force what the 5000-pose graph has (pieces with
@@ -662,8 +664,8 @@ def _optimize_variant(gp, iters, env, fused, spec=1):
 
 def test_single_launch_solve_and_fused_steps_equal_the_stand_alone_kernels(gpu_lib):
     """Round 4's launch-count work on small batches, against the round-3 launch sequence:
-    (s) opt-in for a single small graph ("speculative_trials"): the (up to ten) damping trials of an LM iteration side by side in the lanes of one k_chol_flow
-        launch, then the accept / reject replay (k_lm_control_spec) -> bitwise (a), same iteration AND trial counts;
+    (s) opt-in for a single small graph ("speculative_trials"): the (up to ten) damping trials of an LM iteration side by side in the lanes of one
+        k_chol_spec_round launch, which also replays the accept / reject sequence -> bitwise (a), same iteration AND trial counts;
     (a) Jacobian kernels + k_lm_begin_small + k_chol_flow (factor and both solves in one dependency-driven launch) + k_lm_end_small;
     (b) the same plan with the stand-alone LM kernels round the single-launch solve -> bitwise (a);
     (c) SSLAM_CHOL_OPTS flow=0: a launch per depth of the tree (other work-item cuts: same result up to rounding);
@@ -708,13 +710,13 @@ def test_front_tables_through_every_launch_form(gpu_lib):
 
 
 def test_single_launch_solve_on_the_L_graph_and_a_small_batch(gpu_lib):
-    """k_chol_flow with more pieces than workgroups (one 5000-pose graph: ~1500 pieces over a persistent grid) and on a batch of four
+    """k_chol_flow with more pieces than workgroups (one 5000-pose graph: ~1500 pieces over a persistent grid, walked in rounds) and on a batch of four
     distinct graphs: same chi2 / estimates as the launch-per-depth path up to rounding."""
     import os
     from semantic_slam_amd import GraphSLAM, GraphBatch
     g = make_graph(5000, 1000, seed=2)
     gp = GraphProblem.from_synth(g)
-    a = _optimize_variant(gp, 4, {"flow": 2}, 1)     # 2: the single launch on a wide tree too (by default such a graph keeps its per-depth launches: measured faster)
+    a = _optimize_variant(gp, 4, {"flow": 2}, 1)     # 2: the single launch over the whole wide tree (by default such a graph keeps its per-depth launches: measured faster)
     c = _optimize_variant(gp, 4, {"flow": 0}, 0)
     assert a[0] == c[0] and abs(a[2] - c[2]) <= 1e-9 * c[2]
     assert np.abs(a[3] - c[3]).max() <= 1e-7 * np.abs(c[3]).max()
