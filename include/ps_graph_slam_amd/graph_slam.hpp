@@ -182,6 +182,13 @@ class GraphSLAM {
    *  uninitialised pointer, so the default here is "none").  phi > 0 switches it on for every landmark edge, 0 off. */
   void setRobustKernelDCS(double phi = 1.0) { check(sslam_graph_set_option(graph.get(), "robust_kernel_dcs", phi)); }
 
+  /** hdl_graph_slam's GraphSLAM::add_robust_kernel(edge, kernel_type, kernel_size) -- what graph_slam.cpp:155-161 means to do per edge.  g2o's
+   *  RobustKernelFactory names: "NONE" (removes the kernel), "Huber", "PseudoHuber", "Cauchy", "Welsch", "Fair", "Saturated", "DCS"; an
+   *  unknown name throws.  Any edge handle type.  A value change: the next optimize() keeps its symbolic factorisation. */
+  void add_robust_kernel(const sslam::EdgeHandle& edge, const std::string& kernel_type, double kernel_size) { set_robust_kernel(edge.id, kernel_type, kernel_size); }
+  void add_robust_kernel(const sslam::EdgeSE3PriorXY* edge, const std::string& kernel_type, double kernel_size) { set_robust_kernel(edge->id, kernel_type, kernel_size); }
+  void add_robust_kernel(const sslam::EdgeSE3PriorXYZ* edge, const std::string& kernel_type, double kernel_size) { set_robust_kernel(edge->id, kernel_type, kernel_size); }
+
   /** perform graph optimization (graph_slam.cpp:182-219): false iff the graph has fewer than 10 edges */
   bool optimize(int max_iterations = 1024) {
     sslam_opt_stats st;
@@ -275,6 +282,12 @@ class GraphSLAM {
   static int check(int rc) {
     if (rc < 0) throw std::runtime_error(std::string("sslam: ") + sslam_last_error());
     return rc;
+  }
+  void set_robust_kernel(int edge_id, const std::string& kernel_type, double kernel_size) {
+    static const char* const names[8] = {"NONE", "Huber", "PseudoHuber", "Cauchy", "Welsch", "Fair", "Saturated", "DCS"};
+    for (int k = 0; k < 8; ++k)
+      if (kernel_type == names[k]) { check(sslam_graph_set_edge_robust_kernel(graph.get(), edge_id, k, kernel_size)); return; }
+    throw std::runtime_error("sslam: unknown robust kernel type '" + kernel_type + "'");
   }
 };
 

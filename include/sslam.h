@@ -96,7 +96,8 @@ int sslam_graph_add_edge_point_point(sslam_graph* g, int l1, int l2, const doubl
 /* add_se3_prior_xyz_edge (commented out in the reference, graph_slam.hpp:115-126, the declaration :125-126; g2o registration EDGE_SE3_PRIORXYZ, graph_slam.cpp:32):
  * hdl_graph_slam's EdgeSE3PriorXYZ, a unary edge on the SE3 vertex v with e = t(v) - z and a 3 x 3 information matrix -- an absolute
  * position (GNSS, a motion-capture fix, a surveyed marker).  Analytic Jacobian [R | 0] (g2o differentiates it numerically; DESIGN.md
- * section 2).  Never robustified ("robust_kernel_dcs" stays on the landmark edges).  Returns the edge id (same counter as the binary
+ * section 2).  Not touched by "robust_kernel_dcs" (that option stays on the landmark edges); a kernel of its own -- a GNSS fix under multipath --
+ * comes from sslam_graph_set_edge_robust_kernel.  Returns the edge id (same counter as the binary
  * edges); a prior counts as an edge for the < 10 edges rule and gives its vertex a hessian index. */
 int sslam_graph_add_edge_se3_prior_xyz(sslam_graph* g, int v, const double z[3], const double info[9]);
 /* add_se3_prior_xy_edge (commented out, graph_slam.hpp:115-123, the declaration :122-123; EDGE_SE3_PRIORXY, graph_slam.cpp:31): EdgeSE3PriorXY, e = t(v).xy - z,
@@ -140,6 +141,49 @@ int sslam_graph_hessian_index(sslam_graph* g, int id);
  * in round 5) and is never slower with the lanes-fit rule: the default.  SSLAM_LM_SPEC=0/1/2 in the environment overrides the option for
  * every graph of the process. */
 int sslam_graph_set_option(sslam_graph* g, const char* key, double value);
+
+/* Per-edge robust kernels (hdl_graph_slam's GraphSLAM::add_robust_kernel(edge, type, size); what graph_slam.cpp:155,161 of the reference means to
+ * do, quirk B1).  g2o semantics (BaseEdge::robustInformation): with e2 = e^T Omega e and d = delta, H += J^T (rho1 Omega) J,
+ * b -= J^T (rho1 Omega) e, and the edge's chi2 term is rho0.  g2o's second-order term (rho[2]) is commented out upstream and stays out.
+ *
+ *   id  name         rho0                                        rho1
+ *   0   none         e2                                          1
+ *   1   Huber        e2 if e2 <= d^2, else 2 d sqrt(e2) - d^2    1, else d / sqrt(e2)
+ *   2   PseudoHuber  2 d^2 (sqrt(1 + e2/d^2) - 1)                1 / sqrt(1 + e2/d^2)
+ *   3   Cauchy       d^2 log(1 + e2/d^2)                         1 / (1 + e2/d^2)
+ *   4   Welsch       d^2 (1 - exp(-e2/d^2))                      exp(-e2/d^2)
+ *   5   Fair         2 d^2 (a - log1p(a)), a = sqrt(e2)/d        1 / (1 + a)
+ *   6   Saturated    e2 if e2 <= d^2, else d^2                   1, else 0
+ *   7   DCS          e2 s, s = min(1, (2d/(d+e2))^2)             s
+ *
+ * These are the g2o kernels whose formulas are the same in every g2o release.  GemanMcClure and Tukey changed between releases and are left
+ * out on purpose.  Any edge id of the shared counter, any edge class.  kind outside 0..7, delta <= 0 or non-finite with kind != 0, or an
+ * unknown edge id: SSLAM_ERR_INVALID, graph untouched.  kind = 0 removes the kernel.
+ * Precedence: an edge with a kernel of its own uses it; a landmark edge without one still follows "robust_kernel_dcs"; every other edge
+ * without one is plain least squares.
+ * A kernel is a VALUE of the edge, not structure: setting one keeps the batch tables and the symbolic factorisation (host_plan_us stays 0 on
+ * the next sslam_graph_optimize of an already planned graph), and a live sslam_batch picks the new values up at sslam_batch_upload.  Members
+ * of a batch may carry different per-edge kernels; the "same options" rule of sslam_batch_create is about the options only.
+ * A graph none of whose edges has a kernel launches the same kernels as before this call existed; one that has takes the robust
+ * instantiations of the linearisation / chi2 kernels and of every LM launch form ("fused_small_graph", "speculative_trials": same results,
+ * bitwise, as without them).
+ * The .g2o text format has no place for robust kernels and g2o does not write them: sslam_graph_save_g2o drops them, a loaded graph has none. */
+#define SSLAM_ROBUST_NONE 0
+#define SSLAM_ROBUST_HUBER 1
+#define SSLAM_ROBUST_PSEUDOHUBER 2
+#define SSLAM_ROBUST_CAUCHY 3
+#define SSLAM_ROBUST_WELSCH 4
+#define SSLAM_ROBUST_FAIR 5
+#define SSLAM_ROBUST_SATURATED 6
+#define SSLAM_ROBUST_DCS 7
+int sslam_graph_set_edge_robust_kernel(sslam_graph* g, int edge_id, int kind, double delta);
+/* kind / delta may be NULL; delta is 0 for an edge without a kernel */
+int sslam_graph_get_edge_robust_kernel(const sslam_graph* g, int edge_id, int* kind, double* delta);
+/* Per listed edge, at the current estimates: the raw e2 = e^T Omega e, the robustified rho0 (the edge's chi2 term; their sum over all edges is
+ * sslam_graph_chi2) and the weight rho1 of the kernel the edge is under (precedence above) -- how a caller finds the loop closures the optimiser
+ * has switched off.  Evaluated on the device, one thread per requested edge.  Any output may be NULL.  edge_ids = NULL: all edges in id
+ * order (n is ignored; the outputs hold sslam_graph_num_edges values).  n = 0: nothing to do, returns 0.  An unknown id: SSLAM_ERR_INVALID. */
+int sslam_graph_edge_chi2(sslam_graph* g, const int* edge_ids, int n, double* e2_out, double* rho0_out, double* weight_out);
 
 /* GraphSLAM::optimize (graph_slam.cpp:182-219) with the iteration cap as a parameter (the
  * reference hard-codes 1024, graph_slam.cpp:205).  Fewer than 10 edges: returns

@@ -70,6 +70,9 @@ def load_library():
         "sslam_graph_set_vertex": (ci, [vp, ci, dp]),
         "sslam_graph_hessian_index": (ci, [vp, ci]),
         "sslam_graph_set_option": (ci, [vp, C.c_char_p, cd]),
+        "sslam_graph_set_edge_robust_kernel": (ci, [vp, ci, ci, cd]),
+        "sslam_graph_get_edge_robust_kernel": (ci, [vp, ci, C.POINTER(ci), dp]),
+        "sslam_graph_edge_chi2": (ci, [vp, C.POINTER(ci), ci, dp, dp, dp]),
         "sslam_graph_optimize": (ci, [vp, ci, C.POINTER(OptStats)]),
         "sslam_graph_chi2": (ci, [vp, dp]),
         "sslam_graph_marginals": (ci, [vp, C.POINTER(ci), ci, dp]),

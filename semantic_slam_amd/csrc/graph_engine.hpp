@@ -145,6 +145,13 @@ struct Batch {
   double* d_hb_part = nullptr; // edge-sharded mode: this rank's partial [H || b] (send buffer of the out-of-place all-reduce)
   int64_t allreduce_calls = 0; // ncclAllReduce calls issued so far (tests: the collective really ran)
   int shard_rank = 0, shard_world = 1;
+  // per-edge robust kernels: (graph, graph-local edge id) of every edge of the four storage classes (SE3, landmark, point-point, prior) as
+  // batch_build ordered them, the device arrays (allocated when a kernel is first seen) and the sum of the graphs' robust_version they hold
+  std::vector<int> cls_src[4], cls_g[4];
+  unsigned char* d_rk[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* d_rd[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool robust_synced = false, has_robust = false;
+  uint64_t robust_ver = 0;
 
   ~Batch() { release(); }
   void release() {
@@ -236,6 +243,9 @@ int chol_solve_multi(Batch& b, const double* rhs_host, int nrhs, double* x_host)
 bool chol_plan_flow(const Batch& b);        // the plan runs factor + both solves in one dependency-driven launch (small batches)
 int chol_solve_flow(Batch& b);              // (H + lambda I) dx = b for in_trial graphs -> V.x, one launch
 int chol_lm_step_flow(Batch& b, int max_iters);   // begin step + one-launch solve + update / chi2 / accept-reject / commit: 3 launches per damping trial
+int chol_plan_lm_launches(const Batch& b, bool spec);   // launches so far that ran LM trials inside a persistent kernel (fused halves / speculative rounds)
+bool chol_plan_flow_rk(const Batch& b);     // ... and its fused LM halves may take a batch with per-edge robust kernels
+bool chol_plan_spec_rk(const Batch& b);     // ... and so may the speculative lanes
 bool chol_plan_spec(const Batch& b);        // one small graph: the damping trials of an LM iteration can run side by side
 int chol_spec_mode(const Batch& b);               // 0 off, 1 adaptive (lanes join after the first rejected trial of an iteration), 2 always
 int chol_lm_step_spec(Batch& b, int max_iters);   // one LM iteration: up to ten speculative trials + the accept / reject replay

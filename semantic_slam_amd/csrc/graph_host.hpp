@@ -32,6 +32,12 @@ struct HostGraph {
   std::vector<int> etype, evi, evj;
   std::vector<double> meas;  // 7 per edge
   std::vector<double> info;  // 36 per edge (leading d*d used, row-major)
+  // per-edge robust kernels (sslam_graph_set_edge_robust_kernel): kind 0..7 (SSLAM_ROBUST_*) and width delta per edge.  Edge DATA like meas /
+  // info, not structure: a change bumps robust_version, which a batch compares at its next upload.
+  std::vector<unsigned char> rk_kind;
+  std::vector<double> rk_delta;
+  int n_robust = 0;                // edges with kind != 0
+  uint64_t robust_version = 0;
   Options opt;
   uint64_t structure_version = 0;  // bumped on every add_*
   int nv() const { return (int)vtype.size(); }

@@ -103,12 +103,71 @@ struct BatchView {
   const int* ep_pose; const int* ep_dim; const double* ep_z; const double* ep_w;
   const int* ep_id;                                  // graph-local edge id (edge-sharded mode)
   const int* ep_row; const int* ep_ptr; const int* ep_edge;   // [nEpRows] pose rows that carry priors, CSR over them: their priors in edge order
+  // per-edge robust kernels (sslam_graph_set_edge_robust_kernel): kind (SSLAM_ROBUST_*, 0 = none) and width delta of every edge, next to each
+  // class's Omega.  All eight pointers are nullptr when no edge of the batch has a kernel of its own; the host then launches the <RK = false>
+  // instantiations, which are the kernels as they were before per-edge kernels existed.
+  const unsigned char* eo_rk; const unsigned char* el_rk; const unsigned char* ell_rk; const unsigned char* ep_rk;
+  const double* eo_rd; const double* el_rd; const double* ell_rd; const double* ep_rd;
 };
 
 // g2o::RobustKernelDCS::robustify: rho[1], the factor on Omega; rho[0] = rho[1] * e2
 __device__ __forceinline__ double dcs_rho1(double phi, double e2) {
   const double scale = (2.0 * phi) / (phi + e2);
   return scale >= 1.0 ? 1.0 : scale * scale;
+}
+// Per-edge robust kernels, g2o semantics (BaseEdge::robustInformation): e2 = e^T Omega e -> rho0 (the edge's chi2 term) and rho1 (the factor
+// on Omega in H and b).  The table of include/sslam.h; g2o's second-order term rho[2] stays out, as upstream.  Only the <RK = true>
+// instantiations call this: FP64 sqrt / log / exp are multi-instruction sequences on CDNA and do not belong in the kernel-free build.
+enum { RK_NONE = 0, RK_HUBER = 1, RK_PSEUDOHUBER = 2, RK_CAUCHY = 3, RK_WELSCH = 4, RK_FAIR = 5, RK_SATURATED = 6, RK_DCS = 7 };
+__device__ __forceinline__ void robust_rho(int kind, double d, double e2, double& rho0, double& rho1) {
+  const double d2 = d * d;
+  rho0 = e2; rho1 = 1.0;
+  switch (kind) {
+    case RK_HUBER:
+      if (e2 > d2) { const double s = sqrt(e2); rho0 = 2.0 * d * s - d2; rho1 = d / s; }
+      break;
+    case RK_PSEUDOHUBER: {
+      const double a = sqrt(1.0 + e2 / d2);
+      rho0 = 2.0 * d2 * (a - 1.0); rho1 = 1.0 / a;
+    } break;
+    case RK_CAUCHY: {
+      const double a = 1.0 + e2 / d2;
+      rho0 = d2 * log(a); rho1 = 1.0 / a;
+    } break;
+    case RK_WELSCH: {
+      const double a = exp(-e2 / d2);
+      rho0 = d2 * (1.0 - a); rho1 = a;
+    } break;
+    case RK_FAIR: {
+      const double a = sqrt(e2) / d;
+      rho0 = 2.0 * d2 * (a - log1p(a)); rho1 = 1.0 / (1.0 + a);
+    } break;
+    case RK_SATURATED:
+      if (e2 > d2) { rho0 = d2; rho1 = 0.0; }
+      break;
+    case RK_DCS:
+      rho1 = dcs_rho1(d, e2); rho0 = e2 * rho1;
+      break;
+    default: break;
+  }
+}
+// e^T Omega e of EdgeSE3 k from the 21 upper-triangular entries of its Omega (SoA, stride n).  ONE form for every robust instantiation -- the
+// two endpoint rows, a duplicate's off-diagonal block, the chi2 term, sslam_graph_edge_chi2 -- so that an edge at a Huber / Saturated
+// threshold lands on the same side everywhere.
+__device__ __forceinline__ double se3_e2(const double* __restrict__ w, int n, int k, const double ev[6]) {
+  double e2 = 0;
+  int q = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) { e2 += (r == c ? 1.0 : 2.0) * w[(size_t)q * n + k] * (ev[r] * ev[c]); ++q; }
+  return e2;
+}
+// rho1 of an edge that may carry a kernel of its own (kind 0: none)
+__device__ __forceinline__ double robust_rho1(int kind, double d, double e2) {
+  double r0, r1;
+  robust_rho(kind, d, e2, r0, r1);
+  return r1;
 }
 __device__ __forceinline__ double quad3(const double W[9], const double e[3]) {
   double c = 0;
@@ -292,7 +351,9 @@ __device__ __forceinline__ double prior_chi2(const BatchView& V, int k, const do
 
 // chi2 term of the graph-local edge e of graph segment sg (SE3 edges, then landmark edges, then point-point edges, then position priors;
 // 0 beyond the last):
-// g2o computeActiveErrors + the robust kernel's rho[0]
+// g2o computeActiveErrors + the robust kernel's rho[0].  RK: the batch carries per-edge kernels (an edge with one uses it; a
+// landmark edge without one still follows dcs_phi); RK = false is the code as it was without them.  RAW: e^T Omega e, no kernel at all.
+template <bool RK = false, bool RAW = false>
 __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& sg, int e, const double* __restrict__ pose, const double* __restrict__ lmk) {
   double c = 0;
   if (e < sg.neo) {
@@ -303,6 +364,11 @@ __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& 
                  {V.eo_z[3 * (size_t)n + k], V.eo_z[4 * (size_t)n + k], V.eo_z[5 * (size_t)n + k], V.eo_z[6 * (size_t)n + k]}};
     Se3Lin L;
     se3_error(Xi, Xj, Z, L);
+    if constexpr (RK || RAW) {   // the e2 the robust linearisation forms (se3_e2), then the edge's own kernel
+      c = se3_e2(V.eo_w, n, k, L.e);
+      if constexpr (!RAW) { const int rk = V.eo_rk[k]; if (rk) { double r1; const double e2 = c; robust_rho(rk, V.eo_rd[k], e2, c, r1); } }
+      return c;
+    }
     double W[36];
     load_sym6(V.eo_w, n, k, W);
     for (int r = 0; r < 6; ++r) {
@@ -333,6 +399,11 @@ __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& 
       for (int s = 0; s < 3; ++s) a += W[r * 3 + s] * err[s];
       c += err[r] * a;
     }
+    if constexpr (RAW) return c;
+    if constexpr (RK) {
+      const int rk = V.el_rk[k];
+      if (rk) { double r1; const double e2 = c; robust_rho(rk, V.el_rd[k], e2, c, r1); return c; }
+    }
     if (V.dcs_phi > 0) c *= dcs_rho1(V.dcs_phi, c);
   } else if (e < sg.neo + sg.nel + sg.nell) {   // g2o::EdgePointXYZ: e = (p_b - p_a) - z
     const int k = sg.ell0 + (e - sg.neo - sg.nel);
@@ -344,10 +415,25 @@ __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& 
     for (int r = 0; r < 3; ++r) err[r] = (pb[r] - pa[r]) - V.ell_z[r * n + k];
     load_sym3(V.ell_w, (int)n, k, W);
     c = quad3(W, err);
+    if constexpr (RK && !RAW) { const int rk = V.ell_rk[k]; if (rk) { double r1; const double e2 = c; robust_rho(rk, V.ell_rd[k], e2, c, r1); } }
   } else if (e < edge_count(sg)) {
-    c = prior_chi2(V, sg.ep0 + (e - sg.neo - sg.nel - sg.nell), pose);
+    const int k = sg.ep0 + (e - sg.neo - sg.nel - sg.nell);
+    c = prior_chi2(V, k, pose);
+    if constexpr (RK && !RAW) { const int rk = V.ep_rk[k]; if (rk) { double r1; const double e2 = c; robust_rho(rk, V.ep_rd[k], e2, c, r1); } }
   }
   return c;
+}
+// the kernel that edge e of segment sg is under: its own, else DCS(dcs_phi) on a landmark edge, else none
+__device__ __forceinline__ void edge_kernel_of(const BatchView& V, const GraphSeg& sg, int e, int& kind, double& delta) {
+  kind = 0; delta = 0.0;
+  const bool own = V.eo_rk != nullptr;
+  if (e < sg.neo) { if (own) { kind = V.eo_rk[sg.eo0 + e]; delta = V.eo_rd[sg.eo0 + e]; } }
+  else if (e < sg.neo + sg.nel) {
+    const int k = sg.el0 + (e - sg.neo);
+    if (own) { kind = V.el_rk[k]; delta = V.el_rd[k]; }
+    if (!kind && V.dcs_phi > 0) { kind = RK_DCS; delta = V.dcs_phi; }
+  } else if (e < sg.neo + sg.nel + sg.nell) { const int k = sg.ell0 + (e - sg.neo - sg.nel); if (own) { kind = V.ell_rk[k]; delta = V.ell_rd[k]; } }
+  else if (e < edge_count(sg)) { const int k = sg.ep0 + (e - sg.neo - sg.nel - sg.nell); if (own) { kind = V.ep_rk[k]; delta = V.ep_rd[k]; } }
 }
 
 }  // namespace sslam

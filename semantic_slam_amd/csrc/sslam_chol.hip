@@ -105,6 +105,7 @@ struct CholPlan {
   int flow_grid = 0;            // persistent workgroups
   int spec_grid = 0;            // workgroups of a speculative round (all lanes)
   double flow_need = 1.0, spec_need = 1.0;   // the share of the device those grids occupy when resident (workgroups / what the device holds of them)
+  bool rk_flow_ok = false, rk_spec_ok = false;   // the <RK = true> instantiations of the persistent kernels are as resident as the plain ones the grids were sized for
   bool flow_narrow = false;     // the bottom depth of the tree is no wider than flow_grid (the speculative lanes and the fused LM halves need it)
   int flow_epoch = 0;          // launches so far: the counters are never reset, a launch waits for epoch * (children)
   int lm_epoch = 0;             // launches that carried the LM halves of a trial (k_chol_flow, lmstep)
@@ -1275,13 +1276,14 @@ __device__ __forceinline__ void lm_begin_small(const BatchView& V, const CholVie
 }
 // the partial sums of graph g's trial (x [+] dx in V.pose_trial / V.lmk_trial): chi2 by edge chunks (k_chi2) into part_e and
 // dx . (lambda dx + b) by row chunks (k_scale) into V.part_a
-template <int NT>
+// RK: the batch carries per-edge robust kernels (edge_chi2<true>); RK = false is the code as it was without them
+template <int NT, bool RK = false>
 __device__ __forceinline__ void trial_partial_sums(const BatchView& V, const GraphSeg& sg, int g, double* __restrict__ part_e, double* red) {
   const int tid = threadIdx.x;
   const int nec = edge_chunks(sg), nrc = row_chunks(sg);
   for (int c0 = 0; c0 < nec; c0 += NT / kEdgeChunk) {
     const int chunk = c0 + tid / kEdgeChunk;
-    const double c = chunk < nec ? edge_chi2(V, sg, chunk * kEdgeChunk + tid % kEdgeChunk, V.pose_trial, V.lmk_trial) : 0.0;
+    const double c = chunk < nec ? edge_chi2<RK>(V, sg, chunk * kEdgeChunk + tid % kEdgeChunk, V.pose_trial, V.lmk_trial) : 0.0;
     vblock_store_sum<kEdgeChunk, NT>(c, red, part_e + (size_t)g * V.maxEdgeChunks + chunk, chunk < nec);
   }
   const double lambda = V.lm[g].lambda;
@@ -1297,7 +1299,7 @@ __device__ __forceinline__ void trial_partial_sums(const BatchView& V, const Gra
     vblock_store_sum<kRowChunk, NT>(v, red, V.part_a + (size_t)g * V.maxRowChunks + chunk, live);
   }
 }
-template <int NT>
+template <int NT, bool RK = false>
 __device__ __forceinline__ void lm_end_small(const BatchView& V, const CholView& C, int g, double* __restrict__ part_e, int max_iters, double* red) {
   // k_chol_end + k_oplus + k_chi2 + k_scale + k_lm_control + k_commit for graph g (in a trial)
   const int tid = threadIdx.x;
@@ -1308,7 +1310,7 @@ __device__ __forceinline__ void lm_end_small(const BatchView& V, const CholView&
   for (int i = tid; i < sg.nprow + sg.nlrow; i += NT) oplus_row(V, i < sg.nprow ? sg.prow0 + i : V.nPr + sg.lrow0 + (i - sg.nprow), V.x);
   __threadfence_block();
   __syncthreads();
-  trial_partial_sums<NT>(V, sg, g, part_e, red);
+  trial_partial_sums<NT, RK>(V, sg, g, part_e, red);
   __threadfence_block();
   __syncthreads();
   if (tid < 64) {   // accept / reject (k_lm_control)
@@ -1333,11 +1335,11 @@ __global__ __launch_bounds__(NT) void k_lm_begin_small(BatchView V, CholView C) 
   if (!V.lm[blockIdx.x].active) return;
   lm_begin_small<NT>(V, C, blockIdx.x, red);
 }
-template <int NT>
+template <int NT, bool RK = false>
 __global__ __launch_bounds__(NT) void k_lm_end_small(BatchView V, CholView C, double* __restrict__ part_e, int max_iters) {
   __shared__ double red[NT / 64];
   if (!V.lm[blockIdx.x].active || !V.lm[blockIdx.x].in_trial) return;
-  lm_end_small<NT>(V, C, blockIdx.x, part_e, max_iters, red);
+  lm_end_small<NT, RK>(V, C, blockIdx.x, part_e, max_iters, red);
 }
 
 // ---- speculative damping trials (SpecLanes): begin / per-lane end / replay of the accept-reject sequence + commit ----------------
@@ -1357,7 +1359,7 @@ __device__ __forceinline__ int spec_setup_lanes(const BatchView& V, const SpecLa
   return n;
 }
 // x [+] dx, chi2 and dx . (lambda dx + b) of lane k (one workgroup)
-template <int NT>
+template <int NT, bool RK = false>
 __device__ __forceinline__ void spec_lane_end(BatchView V, const SpecLanes& SL, const long long k, const int g, double* red) {
   const int tid = threadIdx.x;
   V.lm = SL.lm + k * V.B; V.x = SL.x + k * SL.sx; V.pose_trial = SL.pose_trial + k * SL.spose; V.lmk_trial = SL.lmk_trial + k * SL.slmk;
@@ -1372,7 +1374,7 @@ __device__ __forceinline__ void spec_lane_end(BatchView V, const SpecLanes& SL, 
   for (int i = tid; i < sg.nlm; i += NT) if (V.lm_row[sg.lm0 + i] < 0) for (int q = 0; q < 4; ++q) V.lmk_trial[(size_t)(sg.lm0 + i) * 4 + q] = cur_lmk[(size_t)(sg.lm0 + i) * 4 + q];
   __threadfence_block();
   __syncthreads();
-  trial_partial_sums<NT>(V, sg, g, SL.part_e + k * SL.spe, red);   // (V.lm, V.x, V.part_a: the lane's)
+  trial_partial_sums<NT, RK>(V, sg, g, SL.part_e + k * SL.spe, red);   // (V.lm, V.x, V.part_a: the lane's)
 }
 // OptimizationAlgorithmLevenberg's do { ... } while (rho < 0 && q < 10) over the finished lanes, in order, and the commit of the accepted one
 template <int NT>
@@ -1504,7 +1506,7 @@ __device__ __forceinline__ void flow_backward(const BatchView& V, const CholView
 // read by every piece) and what k_lm_end_small does after the backward substitution (the workgroup that finishes last, by a ticket).  Two
 // launches less per trial of the orchestrator's graphs (measured: 0.02 - 0.15 ms per tick -- a trial waits for the chain of pieces inside
 // this launch, not for launches).
-template <int NT, bool USTAGE>
+template <int NT, bool USTAGE, bool RK = false>
 __global__ __launch_bounds__(NT) void k_chol_flow(BatchView V, CholView C, int np, int epoch, const int2* __restrict__ dep, int* flow, int backward,
                                                   int lmstep, double* __restrict__ part_e, int max_iters, int lm_epoch) {
   extern __shared__ double sm[];
@@ -1537,7 +1539,7 @@ __global__ __launch_bounds__(NT) void k_chol_flow(BatchView V, CholView C, int n
     __syncthreads();
     if (s_last) {
       for (int g = 0; g < V.B; ++g)
-        if (V.lm[g].active && V.lm[g].in_trial) lm_end_small<NT>(V, C, g, part_e, max_iters, red);
+        if (V.lm[g].active && V.lm[g].in_trial) lm_end_small<NT, RK>(V, C, g, part_e, max_iters, red);
     }
   }
 }
@@ -1549,7 +1551,7 @@ __global__ __launch_bounds__(NT) void k_chol_flow(BatchView V, CholView C, int n
 // solve with the walks of k_chol_flow; the one that takes the lane's last ticket forms the lane's chi2 / scale partial sums; the lane that
 // finishes last replays g2o's accept / reject sequence over the lanes in order and commits the accepted one.  Same sums, same order:
 // bitwise the sequential loop.
-template <int NT, bool USTAGE>
+template <int NT, bool USTAGE, bool RK = false>
 __global__ __launch_bounds__(NT) void k_chol_spec_round(BatchView V, CholView C, int np, const int2* __restrict__ dep, SpecLanes SL, int round, int max_iters) {
   extern __shared__ double sm[];
   __shared__ double red[NT / 64];
@@ -1589,7 +1591,7 @@ __global__ __launch_bounds__(NT) void k_chol_spec_round(BatchView V, CholView C,
   }
   __syncthreads();
   if (!s_flag) return;
-  spec_lane_end<NT>(V0, SL, k, g, red);
+  spec_lane_end<NT, RK>(V0, SL, k, g, red);
   __syncthreads();
   if (tid == 0) {
     ctl[8 + SL.K + k] = epoch;
@@ -1806,7 +1808,9 @@ int chol_plan_build(Batch& b) {
     std::lock_guard<std::mutex> lk(mu);
     if (std::find(done.begin(), done.end(), b.device) == done.end()) {
       std::vector<const void*> fns = {(const void*)k_chol_flow<512, true>, (const void*)k_chol_flow<512, false>,
-                                      (const void*)k_chol_spec_round<512, true>, (const void*)k_chol_spec_round<512, false>};
+                                      (const void*)k_chol_spec_round<512, true>, (const void*)k_chol_spec_round<512, false>,
+                                      (const void*)k_chol_flow<512, true, true>, (const void*)k_chol_flow<512, false, true>,
+                                      (const void*)k_chol_spec_round<512, true, true>, (const void*)k_chol_spec_round<512, false, true>};
       for_each_width(LeafWidths{}, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
         fns.insert(fns.end(), {(const void*)k_chol_pieces<NT, true>, (const void*)k_chol_pieces<NT, false>, (const void*)k_chol_back_pieces<NT>,
@@ -1836,6 +1840,11 @@ int chol_plan_build(Batch& b) {
       // no wider than the grid at the bottom depth (the orchestrator's graphs: 5.1 vs 5.7 ms per tick at 110 keyframes); flow=2 takes it
       // on any tree (tests: a persistent workgroup walks many pieces)
       const int cap = std::max(1, per_cu * cus / 2);
+      {   // a batch with per-edge robust kernels launches the <RK = true> form into the same grid: only if the device holds as many of it
+        int per_cu_rk = 0;
+        const void* fn_rk = P->ustage ? (const void*)k_chol_flow<512, true, true> : (const void*)k_chol_flow<512, false, true>;
+        P->rk_flow_ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_rk, fn_rk, 512, lds_max) == hipSuccess && per_cu_rk >= per_cu;
+      }
       P->flow_narrow = P->plv_lds_f.empty() || P->plv_ptr[1] - P->plv_ptr[0] <= cap;
       if (!P->flow_narrow && flow_mode != 2) P->flow = false;
       P->flow_grid = std::max(1, std::min((int)dep.size(), cap));
@@ -1856,6 +1865,11 @@ int chol_plan_build(Batch& b) {
         int per_cu_s = 0;   // what the device holds at once of the round's own kernel (ten lanes at work must all be resident)
         const void* fn_s = P->ustage ? (const void*)k_chol_spec_round<512, true> : (const void*)k_chol_spec_round<512, false>;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, fn_s, 512, lds_max) != hipSuccess || per_cu_s < 1) per_cu_s = 1;
+        {
+          int per_cu_rk = 0;
+          const void* fn_rk = P->ustage ? (const void*)k_chol_spec_round<512, true, true> : (const void*)k_chol_spec_round<512, false, true>;
+          P->rk_spec_ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_rk, fn_rk, 512, lds_max) == hipSuccess && per_cu_rk >= per_cu_s;
+        }
         const int full = std::max(K, std::min(2 * cap, per_cu_s * cus));
         SL.g0 = std::max(1, std::min((int)dep.size(), std::min(cap, full / 2)));
         SL.g1 = std::max(1, std::min((int)dep.size(), (full - SL.g0) / (K - 1)));
@@ -1974,6 +1988,10 @@ static size_t plan_flow_lds(const CholPlan& P) {
 
 // (H + lambda I) dx = b in ONE launch (k_chol_flow) for plans that allow it; false: the caller takes the launch-per-depth path
 bool chol_plan_flow(const Batch& b) { return b.chol && b.chol->flow && !b.chol->compact; }
+// the fused LM halves / the speculative lanes may take a batch with per-edge robust kernels (their <RK = true> forms fit the sized grids)
+int chol_plan_lm_launches(const Batch& b, bool spec) { return !b.chol ? 0 : (spec ? b.chol->spec_epoch : b.chol->lm_epoch); }
+bool chol_plan_flow_rk(const Batch& b) { return chol_plan_flow(b) && b.chol->rk_flow_ok; }
+bool chol_plan_spec_rk(const Batch& b) { return chol_plan_flow(b) && b.chol->rk_spec_ok; }
 // the single launch of one solve: factor and forward substitution, then (backward) the backward substitution, (lmstep) inside the LM
 // halves of a damping trial
 static int flow_launch(Batch& b, bool backward, bool lmstep = false, int max_iters = 0) {
@@ -1982,6 +2000,10 @@ static int flow_launch(Batch& b, bool backward, bool lmstep = false, int max_ite
   const int lm_epoch = lmstep ? ++P.lm_epoch : 0;
   PersistScope gate(b.device, b.stream, P.flow_need);
   return with_width(Flag{}, P.ustage ? 1 : 0, [&](auto us) {
+    if (lmstep && b.has_robust)   // (only the LM halves read edges; a plain solve stays on the plain form)
+      hipLaunchKernelGGL((k_chol_flow<512, (bool)decltype(us)::value, true>), dim3(P.flow_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C, (int)P.lp_graph.size(),
+                         epoch, (const int2*)P.d_dep, P.d_flow, backward ? 1 : 0, 1, b.d_part_e, max_iters, lm_epoch);
+    else
     hipLaunchKernelGGL((k_chol_flow<512, (bool)decltype(us)::value>), dim3(P.flow_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C, (int)P.lp_graph.size(),
                        epoch, (const int2*)P.d_dep, P.d_flow, backward ? 1 : 0, lmstep ? 1 : 0, b.d_part_e, max_iters, lm_epoch);
   });
@@ -2014,11 +2036,12 @@ int chol_lm_step_flow(Batch& b, int max_iters) {
   P.C.flat_L = 0;
   int rc;
   // the begin / end halves of the trial inside the launch when the tree is narrow and the grid has a workgroup per graph
-  if (P.flow_narrow && P.flow_grid >= b.V.B) rc = flow_launch(b, true, true, max_iters);
+  if (P.flow_narrow && P.flow_grid >= b.V.B && (!b.has_robust || P.rk_flow_ok)) rc = flow_launch(b, true, true, max_iters);
   else {
     hipLaunchKernelGGL(k_lm_begin_small<512>, dim3(b.V.B), dim3(512), 0, b.stream, b.V, P.C);
     rc = flow_launch(b, true);
-    hipLaunchKernelGGL(k_lm_end_small<512>, dim3(b.V.B), dim3(512), 0, b.stream, b.V, P.C, b.d_part_e, max_iters);
+    if (b.has_robust) hipLaunchKernelGGL((k_lm_end_small<512, true>), dim3(b.V.B), dim3(512), 0, b.stream, b.V, P.C, b.d_part_e, max_iters);
+    else hipLaunchKernelGGL(k_lm_end_small<512>, dim3(b.V.B), dim3(512), 0, b.stream, b.V, P.C, b.d_part_e, max_iters);
   }
   if (rc) return rc;
   hipError_t e = hipGetLastError();
@@ -2035,6 +2058,10 @@ int chol_lm_step_spec(Batch& b, int max_iters) {
   {
     PersistScope gate(b.device, b.stream, P.spec_need);
     rc = with_width(Flag{}, P.ustage ? 1 : 0, [&](auto us) {
+      if (b.has_robust)
+        hipLaunchKernelGGL((k_chol_spec_round<512, (bool)decltype(us)::value, true>), dim3(P.spec_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C,
+                           (int)P.lp_graph.size(), (const int2*)P.d_dep, P.spec, round, max_iters);
+      else
       hipLaunchKernelGGL((k_chol_spec_round<512, (bool)decltype(us)::value>), dim3(P.spec_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C,
                          (int)P.lp_graph.size(), (const int2*)P.d_dep, P.spec, round, max_iters);
     });

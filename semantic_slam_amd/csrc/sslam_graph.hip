@@ -29,6 +29,7 @@ namespace sslam {
 // =============================================================================================
 
 // ---- residual / chi2 (g2o computeActiveErrors): per-graph partial sums, deterministic ---------
+template <bool RK>
 __global__ __launch_bounds__(kEdgeChunk) void k_chi2(BatchView V, const double* __restrict__ pose,
                                                     const double* __restrict__ lmk, int mask_mode,
                                                     double* __restrict__ part) {
@@ -40,9 +41,23 @@ __global__ __launch_bounds__(kEdgeChunk) void k_chi2(BatchView V, const double* 
   const GraphSeg sg = V.seg[g];
   const int e = blockIdx.x * kEdgeChunk + threadIdx.x;
   if (blockIdx.x * kEdgeChunk >= edge_count(sg)) return;
-  const double c = edge_chi2(V, sg, e, pose, lmk);
+  const double c = edge_chi2<RK>(V, sg, e, pose, lmk);
   const double s = block_sum<kEdgeChunk>(c, red);
   if (threadIdx.x == 0) part[(size_t)g * V.maxEdgeChunks + blockIdx.x] = s;
+}
+
+// sslam_graph_edge_chi2: one thread per requested edge (loc: its graph-local index in edge_chi2's order) -> e^T Omega e, rho0 and rho1 of the
+// kernel the edge is under, at the current estimates.  out: [3][n].  No atomics, no reduction.
+__global__ __launch_bounds__(64) void k_edge_chi2(BatchView V, int g, const int* __restrict__ loc, int n, double* __restrict__ out) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= n) return;
+  const GraphSeg sg = V.seg[g];
+  const int e = loc[t];
+  const double e2 = edge_chi2<false, true>(V, sg, e, V.pose, V.lmk);
+  int kind; double delta, r0, r1;
+  edge_kernel_of(V, sg, e, kind, delta);
+  robust_rho(kind, delta, e2, r0, r1);
+  out[t] = e2; out[(size_t)n + t] = r0; out[2 * (size_t)n + t] = r1;
 }
 
 // off-diagonal block codes: >= 0 owner edge, <= -2 a further edge on the same vertex pair, -1 none
@@ -146,7 +161,9 @@ __global__ __launch_bounds__(256) void k_plane_jacobians(BatchView V, int blocks
 // slot) compiles to 231 VGPRs -- two waves per SIMD, no spill -- and ran 2.33 vs 2.10 ms per 512-graph build.  By the raw counters the build
 // moves ~13 MB per graph (both endpoint rows read an EdgeSE3, the landmark rows read every landmark edge again) at ~3.2 TB/s of mixed reads
 // and scattered 16-byte writes: it sits at what HBM gives such a mix, and only fewer bytes would make it faster.
-template <bool PL, bool SHARD>
+// RK: the batch carries per-edge robust kernels; an edge's Omega is scaled by its rho1 (e2 from the unmasked Omega: shards scale alike, and both
+// endpoint rows of an EdgeSE3 form the same value).  RK = false is the kernel above, untouched: its live ranges are what bounds it.
+template <bool PL, bool SHARD, bool RK>
 __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchView V) {
   __shared__ double accD[27][kRowThreads];   // this row's diagonal block (upper triangle) and rhs: a thread-private LDS column, conflict free
   const int tid = threadIdx.x;
@@ -177,8 +194,12 @@ __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchVie
       // edge-sharded mode: an edge outside this rank's range contributes nothing (everything below is linear in Omega; the owner
       // of an off-diagonal block still writes it, as zeros)
       const int eid = SHARD ? V.eo_id[e] : 0;
-      const double mk = (!SHARD || (eid >= sh_lo && eid < sh_hi)) ? 1.0 : 0.0;
+      double mk = (!SHARD || (eid >= sh_lo && eid < sh_hi)) ? 1.0 : 0.0;
       auto w21 = [&](int q) { return V.eo_w[(size_t)q * n + e]; };
+      if constexpr (RK) {
+        const int rk = V.eo_rk[e];
+        if (rk) mk *= robust_rho1(rk, V.eo_rd[e], se3_e2(V.eo_w, n, e, L.e));
+      }
 #pragma unroll
       for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -315,13 +336,15 @@ __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchVie
       double W[9];
       load_sym3(V.el_w, n, e, W);
       double dcs = 1.0;
-      if (V.dcs_phi > 0) dcs = dcs_rho1(V.dcs_phi, quad3(W, err));   // from the unmasked Omega: every rank scales its share alike
+      const int rk = RK ? V.el_rk[e] : 0;
+      if (RK && rk) dcs = robust_rho1(rk, V.el_rd[e], quad3(W, err));
+      else if (V.dcs_phi > 0) dcs = dcs_rho1(V.dcs_phi, quad3(W, err));   // from the unmasked Omega: every rank scales its share alike
       const int lid = SHARD ? V.el_id[e] : 0;
       if (SHARD && !(lid >= sh_lo && lid < sh_hi)) {
 #pragma unroll
         for (int q = 0; q < 9; ++q) W[q] = 0.0;
       }
-      if (V.dcs_phi > 0) {
+      if ((RK && rk) || V.dcs_phi > 0) {
 #pragma unroll
         for (int q = 0; q < 9; ++q) W[q] *= dcs;
       }
@@ -372,7 +395,7 @@ __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchVie
 // pose row that carries priors: the pose is read once, its priors summed in edge order, and the sums added onto the block and rhs that
 // k_linearize_rowthread wrote before it in stream order.  No atomics: bitwise deterministic.  A separate launch (and only for a batch that
 // has priors) rather than a slot kind of the row kernel, whose live set is what bounds it (comment above k_linearize_rowthread).
-template <bool SHARD>
+template <bool SHARD, bool RK>
 __global__ __launch_bounds__(64) void k_linearize_priors(BatchView V) {
   const int t = blockIdx.x * 64 + threadIdx.x;
   if (t >= V.nEpRows) return;
@@ -386,6 +409,14 @@ __global__ __launch_bounds__(64) void k_linearize_priors(BatchView V) {
     const int k = V.ep_edge[s];
     double err[3], W[9];
     prior_error(V, k, X, err, W);
+    if constexpr (RK) {
+      const int rk = V.ep_rk[k];
+      if (rk) {
+        const double r1 = robust_rho1(rk, V.ep_rd[k], quad3(W, err));
+#pragma unroll
+        for (int q = 0; q < 9; ++q) W[q] *= r1;
+      }
+    }
     if (SHARD && !(V.ep_id[k] >= V.shard_lo[g] && V.ep_id[k] < V.shard_hi[g])) {
 #pragma unroll
       for (int q = 0; q < 9; ++q) W[q] = 0.0;
@@ -422,7 +453,7 @@ __global__ __launch_bounds__(64) void k_linearize_priors(BatchView V) {
 
 // landmark rows: 16 lanes per landmark, each lane walks a strided subset of the incident edges,
 // butterfly reduction in a fixed order.
-template <bool PL, bool SHARD>
+template <bool PL, bool SHARD, bool RK>
 __global__ __launch_bounds__(256) void k_linearize_lm_rows(BatchView V) {
   const int l = blockIdx.x * 16 + (threadIdx.x >> 4);
   const int lane = threadIdx.x & 15;
@@ -457,7 +488,12 @@ __global__ __launch_bounds__(256) void k_linearize_lm_rows(BatchView V) {
       }
       double W[9];
       load_sym3(V.el_w, n, e, W);
-      if (V.dcs_phi > 0) {
+      const int rk = RK ? V.el_rk[e] : 0;
+      if (RK && rk) {
+        const double r1 = robust_rho1(rk, V.el_rd[e], quad3(W, err));
+#pragma unroll
+        for (int q = 0; q < 9; ++q) W[q] *= r1;
+      } else if (V.dcs_phi > 0) {
         const double r1 = dcs_rho1(V.dcs_phi, quad3(W, err));
 #pragma unroll
         for (int q = 0; q < 9; ++q) W[q] *= r1;
@@ -496,6 +532,14 @@ __global__ __launch_bounds__(256) void k_linearize_lm_rows(BatchView V) {
 #pragma unroll
       for (int r = 0; r < 3; ++r) err[r] = (pb[r] - pa[r]) - V.ell_z[r * n + k];
       load_sym3(V.ell_w, (int)n, k, W);
+      if constexpr (RK) {
+        const int rk = V.ell_rk[k];
+        if (rk) {
+          const double r1 = robust_rho1(rk, V.ell_rd[k], quad3(W, err));
+#pragma unroll
+          for (int q = 0; q < 9; ++q) W[q] *= r1;
+        }
+      }
       if (SHARD) {
         const int g = V.lrow_graph[l];
         if (!(V.ell_id[k] >= V.shard_lo[g] && V.ell_id[k] < V.shard_hi[g])) {
@@ -527,7 +571,7 @@ __global__ __launch_bounds__(256) void k_linearize_lm_rows(BatchView V) {
 }
 
 // landmark-landmark blocks of the point-point edges: block (a, b) = sum over the edges on that pair of J_a^T Omega J_b = -Omega
-template <bool SHARD>
+template <bool SHARD, bool RK>
 __global__ __launch_bounds__(64) void k_linearize_ll(BatchView V) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= V.nLL) return;
@@ -540,6 +584,20 @@ __global__ __launch_bounds__(64) void k_linearize_ll(BatchView V) {
     if (SHARD && !(V.ell_id[k] >= V.shard_lo[g] && V.ell_id[k] < V.shard_hi[g])) continue;
     double W[9];
     load_sym3(V.ell_w, V.nEll, k, W);
+    if constexpr (RK) {
+      const int rk = V.ell_rk[k];
+      if (rk) {   // the same e2 from the same inputs as the two landmark rows of the edge form
+        const size_t n = V.nEll;
+        const double* pa = V.lmk + (size_t)V.ell_a[k] * 4;
+        const double* pb = V.lmk + (size_t)V.ell_b[k] * 4;
+        double err[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) err[r] = (pb[r] - pa[r]) - V.ell_z[r * n + k];
+        const double r1 = robust_rho1(rk, V.ell_rd[k], quad3(W, err));
+#pragma unroll
+        for (int q = 0; q < 9; ++q) W[q] *= r1;
+      }
+    }
 #pragma unroll
     for (int q = 0; q < 9; ++q) acc[q] -= W[q];
   }
@@ -549,6 +607,7 @@ __global__ __launch_bounds__(64) void k_linearize_ll(BatchView V) {
 
 // Further edges on an already-owned vertex pair (e.g. a repeated loop closure): their off-diagonal
 // contributions are added serially, in edge order, after the owners have written the blocks.
+template <bool RK>
 __global__ void k_linearize_dups(BatchView V) {
   // the host orders the duplicate lists by block; thread t owns the run of entries that share its block
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -565,6 +624,13 @@ __global__ void k_linearize_dups(BatchView V) {
     double Ji[36], Jj[36], W[36], WJ[36];
     se3_full_jacobians(L, Ji, Jj);
     load_sym6(V.eo_w, V.nEo, k, W);
+    if constexpr (RK) {
+      const int rk = V.eo_rk[k];
+      if (rk) {
+        const double r1 = robust_rho1(rk, V.eo_rd[k], se3_e2(V.eo_w, V.nEo, k, L.e));
+        for (int q = 0; q < 36; ++q) W[q] *= r1;
+      }
+    }
     for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) { double a = 0; for (int s = 0; s < 6; ++s) a += W[r * 6 + s] * Jj[s * 6 + c]; WJ[r * 6 + c] = a; }
     const int blk = decode_blk(V.eo_blk[k]);
     double* O = V.Hpp_off + (size_t)(blk >> 1) * 36;
@@ -595,7 +661,8 @@ __global__ void k_linearize_dups(BatchView V) {
                       Plane{{V.el_z[0 * (size_t)n + k], V.el_z[1 * (size_t)n + k], V.el_z[2 * (size_t)n + k]}, V.el_z[3 * (size_t)n + k]}, Ji, Jl);
     }
     load_sym3(V.el_w, n, k, W);
-    if (V.dcs_phi > 0) {
+    const int rk = RK ? V.el_rk[k] : 0;
+    if ((RK && rk) || V.dcs_phi > 0) {
       double err[3];
       if (V.lm_kind[li] == VT_POINT) {
         PointLin L;
@@ -605,7 +672,7 @@ __global__ void k_linearize_dups(BatchView V) {
         plane_error(Xi, Plane{{lp[0], lp[1], lp[2]}, lp[3]},
                     Plane{{V.el_z[0 * (size_t)n + k], V.el_z[1 * (size_t)n + k], V.el_z[2 * (size_t)n + k]}, V.el_z[3 * (size_t)n + k]}, err);
       }
-      const double r1 = dcs_rho1(V.dcs_phi, quad3(W, err));
+      const double r1 = (RK && rk) ? robust_rho1(rk, V.el_rd[k], quad3(W, err)) : dcs_rho1(V.dcs_phi, quad3(W, err));
       for (int q = 0; q < 9; ++q) W[q] *= r1;
     }
     double WJl[9];
@@ -1383,11 +1450,54 @@ static int batch_build(Batch& b, bool host_only = false) {
   b.versions.resize(B);
   for (int g = 0; g < B; ++g) b.versions[g] = b.graphs[g]->structure_version;
   b.uploaded = false;
+  b.cls_src[0] = std::move(eo_src); b.cls_g[0] = std::move(eo_g); b.cls_src[1] = std::move(el_src); b.cls_g[1] = std::move(el_g);
+  b.cls_src[2] = std::move(ell_src); b.cls_g[2] = std::move(ell_g); b.cls_src[3] = std::move(ep_src); b.cls_g[3] = std::move(ep_g);
+  b.robust_synced = false; b.has_robust = false;
+  return 0;
+}
+
+// Per-edge robust kernels are edge data: when a graph's kernels changed since this batch last looked (robust_version), the kind / delta arrays
+// of the four edge classes are written again -- no table, no plan, no structure is touched.  A batch none of whose edges has a kernel holds
+// null pointers and runs the <RK = false> kernels.  Their memory does not come from a handle's arena (whose blocks travel with one flush at
+// build time): a kernel may arrive long after the batch was built.
+static int batch_sync_robust(Batch& b) {
+  uint64_t ver = 0;
+  int any = 0;
+  for (const HostGraph* G : b.graphs) { ver += G->robust_version; any += G->n_robust; }
+  if (b.robust_synced && ver == b.robust_ver) return 0;
+  BatchView& V = b.V;
+  if (any) {
+    for (int c = 0; c < 4; ++c) {
+      const size_t n = b.cls_src[c].size();
+      std::vector<unsigned char> kind(std::max<size_t>(n, 1), 0);
+      std::vector<double> delta(std::max<size_t>(n, 1), 0.0);
+      for (size_t k = 0; k < n; ++k) {
+        const HostGraph& G = *b.graphs[b.cls_g[c][k]];
+        kind[k] = G.rk_kind[b.cls_src[c][k]]; delta[k] = G.rk_delta[b.cls_src[c][k]];
+      }
+      if (!b.d_rk[c]) {
+        void* p = nullptr;
+        SSLAM_HIP_TRY(hipMalloc(&p, kind.size())); b.allocs.push_back(p); b.d_rk[c] = (unsigned char*)p;
+        SSLAM_HIP_TRY(hipMalloc(&p, delta.size() * sizeof(double))); b.allocs.push_back(p); b.d_rd[c] = (double*)p;
+      }
+      SSLAM_HIP_TRY(hipMemcpyAsync(b.d_rk[c], kind.data(), kind.size(), hipMemcpyHostToDevice, b.stream));
+      SSLAM_HIP_TRY(hipMemcpyAsync(b.d_rd[c], delta.data(), delta.size() * sizeof(double), hipMemcpyHostToDevice, b.stream));
+      SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // (the host vectors go out of scope)
+    }
+    V.eo_rk = b.d_rk[0]; V.el_rk = b.d_rk[1]; V.ell_rk = b.d_rk[2]; V.ep_rk = b.d_rk[3];
+    V.eo_rd = b.d_rd[0]; V.el_rd = b.d_rd[1]; V.ell_rd = b.d_rd[2]; V.ep_rd = b.d_rd[3];
+  } else {
+    V.eo_rk = V.el_rk = V.ell_rk = V.ep_rk = nullptr;
+    V.eo_rd = V.el_rd = V.ell_rd = V.ep_rd = nullptr;
+  }
+  b.has_robust = any != 0;
+  b.robust_ver = ver; b.robust_synced = true;
   return 0;
 }
 
 static int batch_upload_estimates(Batch& b) {
   SSLAM_HIP_TRY(hipSetDevice(b.device));
+  if (int rc = batch_sync_robust(b)) return rc;
   const size_t np = (size_t)b.V.nPose * 8, nl = (size_t)b.V.nLm * 4;
   std::vector<double> fallback;
   double* stage = reinterpret_cast<double*>(b.pin->get((np + nl) * sizeof(double)));   // page-locked: four asynchronous copies, no staged blits
@@ -1461,17 +1571,20 @@ static int batch_linearize(Batch& b) {
   b.V.dcs_phi = b.graphs[0]->opt.dcs_phi;   // read live like pcg_tol / solver: an option set after the batch was built must not be ignored
   const BatchView& V = b.V;
   const int nblk = (V.nPr + kRowThreads - 1) / kRowThreads;
-#define SSLAM_LAUNCH_LIN(PLV, SHV)                                                                                                    \
+#define SSLAM_LAUNCH_LIN(PLV, SHV, RKV)                                                                                               \
   {                                                                                                                                   \
     if (PLV && V.nEl > 0) {                                                                                                           \
       const long long bA = ((long long)V.nEl * 14 + 255) / 256, bB = ((long long)V.nEl * 6 + 255) / 256;                                \
       hipLaunchKernelGGL(k_plane_jacobians, dim3((unsigned)(bA + bB)), dim3(256), 0, b.stream, V, (int)bA);                              \
     }                                                                                                                                 \
-    if (V.nPr > 0) hipLaunchKernelGGL((k_linearize_rowthread<PLV, SHV>), dim3(nblk), dim3(kRowThreads), 0, b.stream, V);               \
-    if (V.nEpRows > 0) hipLaunchKernelGGL((k_linearize_priors<SHV>), dim3((V.nEpRows + 63) / 64), dim3(64), 0, b.stream, V);          \
-    if (V.nLr > 0) hipLaunchKernelGGL((k_linearize_lm_rows<PLV, SHV>), dim3((V.nLr + 15) / 16), dim3(256), 0, b.stream, V);            \
-    if (V.nLL > 0) hipLaunchKernelGGL((k_linearize_ll<SHV>), dim3((V.nLL + 63) / 64), dim3(64), 0, b.stream, V);                       \
+    if (V.nPr > 0) hipLaunchKernelGGL((k_linearize_rowthread<PLV, SHV, RKV>), dim3(nblk), dim3(kRowThreads), 0, b.stream, V);          \
+    if (V.nEpRows > 0) hipLaunchKernelGGL((k_linearize_priors<SHV, RKV>), dim3((V.nEpRows + 63) / 64), dim3(64), 0, b.stream, V);     \
+    if (V.nLr > 0) hipLaunchKernelGGL((k_linearize_lm_rows<PLV, SHV, RKV>), dim3((V.nLr + 15) / 16), dim3(256), 0, b.stream, V);       \
+    if (V.nLL > 0) hipLaunchKernelGGL((k_linearize_ll<SHV, RKV>), dim3((V.nLL + 63) / 64), dim3(64), 0, b.stream, V);                  \
+    if (V.nDupEo + V.nDupEl > 0) hipLaunchKernelGGL(k_linearize_dups<RKV>, dim3((std::max(V.nDupEo, V.nDupEl) + 63) / 64), dim3(64), 0, b.stream, V); \
   }
+  // a batch with per-edge robust kernels takes the <RK = true> instantiations; every other batch the kernels as they always were
+#define SSLAM_LAUNCH_LIN_RK(PLV, SHV) { if (b.has_robust) SSLAM_LAUNCH_LIN(PLV, SHV, true) else SSLAM_LAUNCH_LIN(PLV, SHV, false) }
   // (Round 4 could run the landmark-row kernel on a second stream next to the pose-row kernel: +4 % on one stream, -24 % inside a stream
   // group, where every part forked and joined its own second stream at every step -- removed in round 5.)
   if (b.sharded) {
@@ -1484,8 +1597,7 @@ static int batch_linearize(Batch& b) {
     Vp.Hpl = b.d_hb_part + b.hpl_base; Vp.Hll_off = b.d_hb_part + b.hll_off_base; Vp.bvec = b.d_hb_part + (V.bvec - V.Hpp_diag);
     {
       const BatchView& V = Vp;
-      if (b.has_planes) SSLAM_LAUNCH_LIN(true, true) else SSLAM_LAUNCH_LIN(false, true)
-      if (V.nDupEo + V.nDupEl > 0) hipLaunchKernelGGL(k_linearize_dups, dim3((std::max(V.nDupEo, V.nDupEl) + 63) / 64), dim3(64), 0, b.stream, V);
+      if (b.has_planes) SSLAM_LAUNCH_LIN_RK(true, true) else SSLAM_LAUNCH_LIN_RK(false, true)
     }
     if (b.comm) {
       // the partial [H || b] arrays of all ranks -> their sum on every rank: ONE all-reduce over xGMI (RCCL), in stream order;
@@ -1497,9 +1609,9 @@ static int batch_linearize(Batch& b) {
       SSLAM_HIP_TRY(hipMemcpyAsync(V.Hpp_diag, b.d_hb_part, (size_t)b.hb_doubles * sizeof(double), hipMemcpyDeviceToDevice, b.stream));
     }
   } else {
-    if (b.has_planes) SSLAM_LAUNCH_LIN(true, false) else SSLAM_LAUNCH_LIN(false, false)
-    if (V.nDupEo + V.nDupEl > 0) hipLaunchKernelGGL(k_linearize_dups, dim3((std::max(V.nDupEo, V.nDupEl) + 63) / 64), dim3(64), 0, b.stream, V);
+    if (b.has_planes) SSLAM_LAUNCH_LIN_RK(true, false) else SSLAM_LAUNCH_LIN_RK(false, false)
   }
+#undef SSLAM_LAUNCH_LIN_RK
 #undef SSLAM_LAUNCH_LIN
   return launch_check("linearize");
 }
@@ -1561,7 +1673,8 @@ static int batch_solve(Batch& b) {
 static int batch_chi2(Batch& b, const double* pose, const double* lmk, int mask_mode) {
   ScopedTimer t(b, "chi2");
   b.V.dcs_phi = b.graphs[0]->opt.dcs_phi;
-  hipLaunchKernelGGL(k_chi2, edge_grid(b), dim3(kEdgeChunk), 0, b.stream, b.V, pose, lmk, mask_mode, b.d_part_e);
+  if (b.has_robust) hipLaunchKernelGGL(k_chi2<true>, edge_grid(b), dim3(kEdgeChunk), 0, b.stream, b.V, pose, lmk, mask_mode, b.d_part_e);
+  else hipLaunchKernelGGL(k_chi2<false>, edge_grid(b), dim3(kEdgeChunk), 0, b.stream, b.V, pose, lmk, mask_mode, b.d_part_e);
   return launch_check("chi2");
 }
 
@@ -1590,7 +1703,10 @@ static int batch_optimize(Batch& b, int max_iters, sslam_opt_stats* out) {
       flow_steps = chol_plan_flow(b);
     }
   }
-  const bool spec_steps = flow_steps && chol_spec_mode(b) && chol_plan_spec(b);
+  // a batch with per-edge robust kernels takes the <RK = true> forms of the persistent kernels, which were compiled apart so that the plain
+  // forms stay what they were; should the device hold fewer of them than the grids were sized for, the lanes are left out (the LM halves
+  // then run as k_lm_begin_small / k_lm_end_small<RK> around the single-launch solve: chol_lm_step_flow) -- same results, bitwise
+  const bool spec_steps = flow_steps && chol_spec_mode(b) && chol_plan_spec(b) && (!b.has_robust || chol_plan_spec_rk(b));
   long long budget = 10LL * std::max(max_iters, 0) + 8;    // hard bound: <= 10 trials per iteration
   int need = max_iters;
   if ((rc = chol_set_active(b, nullptr))) return rc;
@@ -1821,6 +1937,7 @@ static int add_edge(sslam_graph* h, int type, int i, int j, const double* z, int
   G.etype.push_back(type); G.evi.push_back(i); G.evj.push_back(j);
   for (int k = 0; k < 7; ++k) G.meas.push_back(k < nz ? z[k] : 0.0);
   for (int k = 0; k < 36; ++k) G.info.push_back(k < d * d ? info[k] : 0.0);
+  G.rk_kind.push_back(0); G.rk_delta.push_back(0.0);
   G.structure_version++;
   return id;
 }
@@ -1885,6 +2002,72 @@ int sslam_graph_set_option(sslam_graph* h, const char* key, double value) {
   else if (k == "pcg_max_iters") o.pcg_max_iters = (int)value;
   else if (k == "deterministic") { if (value == 0) return set_error(SSLAM_ERR_UNSUPPORTED, "the Jacobian build is always deterministic (gather form); the FP64-atomics variant was removed"); }
   else return set_error(SSLAM_ERR_INVALID, "unknown option '%s'", key);
+  return 0;
+}
+
+// ---- per-edge robust kernels ---------------------------------------------------------------------
+int sslam_graph_set_edge_robust_kernel(sslam_graph* h, int edge_id, int kind, double delta) {
+  if (!h) return set_error(SSLAM_ERR_INVALID, "null graph");
+  HostGraph& G = h->g;
+  if (edge_id < 0 || edge_id >= G.ne()) return set_error(SSLAM_ERR_INVALID, "bad edge id %d", edge_id);
+  if (kind < SSLAM_ROBUST_NONE || kind > SSLAM_ROBUST_DCS) return set_error(SSLAM_ERR_INVALID, "robust kernel kind %d: 0 .. 7 (SSLAM_ROBUST_*)", kind);
+  if (kind != SSLAM_ROBUST_NONE && !(std::isfinite(delta) && delta > 0)) return set_error(SSLAM_ERR_INVALID, "robust kernel width must be finite and > 0");
+  if (kind == SSLAM_ROBUST_NONE) delta = 0.0;
+  G.n_robust += (kind != 0) - (G.rk_kind[edge_id] != 0);
+  G.rk_kind[edge_id] = (unsigned char)kind; G.rk_delta[edge_id] = delta;
+  G.robust_version++;   // a value change: structure_version, the batch tables and the symbolic factorisation stay
+  if (h->batch) h->batch->uploaded = false;
+  h->linearized = false;
+  return 0;
+}
+int sslam_graph_get_edge_robust_kernel(const sslam_graph* h, int edge_id, int* kind, double* delta) {
+  if (!h || edge_id < 0 || edge_id >= h->g.ne()) return set_error(SSLAM_ERR_INVALID, "bad edge id %d", edge_id);
+  if (kind) *kind = h->g.rk_kind[edge_id];
+  if (delta) *delta = h->g.rk_delta[edge_id];
+  return 0;
+}
+int sslam_graph_edge_chi2(sslam_graph* h, const int* edge_ids, int n, double* e2_out, double* rho0_out, double* weight_out) {
+  if (!h) return set_error(SSLAM_ERR_INVALID, "null graph");
+  const HostGraph& G = h->g;
+  if (!edge_ids) n = G.ne();   // all edges, in id order
+  if (n < 0) return set_error(SSLAM_ERR_INVALID, "negative edge count");
+  if (n == 0) return 0;
+  // edge id -> graph-local index in the order of edge_chi2: SE3 edges, landmark edges, point-point edges, priors, each in id order
+  std::vector<int> pos(G.ne());
+  int cnt[4] = {0, 0, 0, 0};
+  auto cls = [&](int k) { return G.etype[k] == ET_SE3 ? 0 : (G.etype[k] == ET_POINT_POINT ? 2 : (is_prior_edge(G.etype[k]) ? 3 : 1)); };
+  for (int k = 0; k < G.ne(); ++k) pos[k] = cnt[cls(k)]++;
+  const int off[4] = {0, cnt[0], cnt[0] + cnt[1], cnt[0] + cnt[1] + cnt[2]};
+  std::vector<int> loc(n);
+  for (int t = 0; t < n; ++t) {
+    const int k = edge_ids ? edge_ids[t] : t;
+    if (k < 0 || k >= G.ne()) return set_error(SSLAM_ERR_INVALID, "bad edge id %d", k);
+    loc[t] = off[cls(k)] + pos[k];
+  }
+  int rc = ensure_batch(h);
+  if (rc) return rc;
+  Batch& b = *h->batch;
+  if ((rc = batch_upload_estimates(b))) return rc;
+  b.V.dcs_phi = G.opt.dcs_phi;
+  int* d_loc = nullptr; double* d_out = nullptr;
+  std::vector<double> out((size_t)3 * n);
+  hipError_t e = hipMalloc((void**)&d_loc, (size_t)n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, out.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpyAsync(d_loc, loc.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, b.stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_edge_chi2, dim3((n + 63) / 64), dim3(64), 0, b.stream, b.V, 0, (const int*)d_loc, n, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, b.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+  if (d_loc) (void)hipFree(d_loc);
+  if (d_out) (void)hipFree(d_out);
+  if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "edge chi2: %s", hipGetErrorString(e));
+  for (int t = 0; t < n; ++t) {
+    if (e2_out) e2_out[t] = out[t];
+    if (rho0_out) rho0_out[t] = out[(size_t)n + t];
+    if (weight_out) weight_out[t] = out[2 * (size_t)n + t];
+  }
   return 0;
 }
 
@@ -2551,6 +2734,8 @@ int sslam_batch_info(sslam_batch* h, const char* key, double* value) {
   else if (k == "h_doubles") *value = (double)b.V.h_total;
   else if (k == "dim") *value = dim;
   else if (k == "allreduce_calls") *value = (double)b.allreduce_calls;
+  else if (k == "lm_fused_launches") *value = (double)chol_plan_lm_launches(b, false);   // k_chol_flow launches that carried the halves of a damping trial
+  else if (k == "lm_spec_rounds") *value = (double)chol_plan_lm_launches(b, true);       // k_chol_spec_round launches
   else if (k == "factor_bytes") *value = 8.0 * ((double)b.V.h_total + dim + (double)chol_plan_lnz(b) + dim);
   else return set_error(SSLAM_ERR_INVALID, "unknown info key '%s'", key);
   return 0;

@@ -46,6 +46,10 @@ def _pose7(pose) -> np.ndarray:
     raise ValueError("pose must be 7 numbers [t, q(xyzw)] or a 4x4 isometry")
 
 
+# g2o's RobustKernelFactory names -> SSLAM_ROBUST_* (include/sslam.h; GemanMcClure and Tukey are left out there on purpose)
+ROBUST_KERNELS = {"NONE": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "Welsch": 4, "Fair": 5, "Saturated": 6, "DCS": 7}
+
+
 class GraphSLAM:
     """``ps_graph_slam::GraphSLAM`` on one MI355X (graph_slam.cpp:40-97)."""
 
@@ -112,6 +116,34 @@ class GraphSLAM:
         return _check(self._lib, self._lib.sslam_graph_add_edge_se3_prior_xyz(self._h, v_se3, _dptr(z), _dptr(w)))
 
     # -- queries -----------------------------------------------------------------------------
+    # ---- per-edge robust kernels (hdl_graph_slam's GraphSLAM::add_robust_kernel)
+    def add_robust_kernel(self, edge_id: int, kernel_type: str, kernel_size: float = 1.0) -> None:
+        """Put the g2o kernel `kernel_type` ("NONE", "Huber", "PseudoHuber", "Cauchy", "Welsch", "Fair", "Saturated", "DCS") of width
+        `kernel_size` on an edge of any class; "NONE" removes it.  A value change: the symbolic factorisation is kept."""
+        if kernel_type not in ROBUST_KERNELS:
+            raise ValueError(f"unknown robust kernel type '{kernel_type}' (known: {', '.join(ROBUST_KERNELS)})")
+        _check(self._lib, self._lib.sslam_graph_set_edge_robust_kernel(self._h, int(edge_id), ROBUST_KERNELS[kernel_type], float(kernel_size)))
+
+    def edge_robust_kernel(self, edge_id: int):
+        """(type name, size) of the edge's own kernel; ("NONE", 0.0) without one."""
+        kind, delta = C.c_int(0), C.c_double(0.0)
+        _check(self._lib, self._lib.sslam_graph_get_edge_robust_kernel(self._h, int(edge_id), C.byref(kind), C.byref(delta)))
+        return [k for k, v in ROBUST_KERNELS.items() if v == kind.value][0], delta.value
+
+    def edge_chi2(self, edge_ids=None):
+        """Per edge at the current estimates: (e2, rho0, weight) arrays -- the raw e^T Omega e, the robustified chi2 term and the kernel's
+        rho1.  edge_ids None: all edges in id order."""
+        if edge_ids is None:
+            n, ids = self.num_edges(), None
+        else:
+            ids = np.ascontiguousarray(edge_ids, np.int32)
+            n = int(ids.size)
+        e2, r0, w = np.zeros(n), np.zeros(n), np.zeros(n)
+        if n:
+            _check(self._lib, self._lib.sslam_graph_edge_chi2(self._h, ids.ctypes.data_as(C.POINTER(C.c_int)) if ids is not None else None,
+                                                              n, _dptr(e2), _dptr(r0), _dptr(w)))
+        return e2, r0, w
+
     def num_vertices(self) -> int:
         return self._lib.sslam_graph_num_vertices(self._h)
 

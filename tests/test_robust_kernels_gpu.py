@@ -1,0 +1,479 @@
+"""Per-edge robust kernels on the GPU against tests/robust_ref.py: the robust instantiations of the linearisation and chi2 kernels on every
+edge class, sslam_graph_edge_chi2, LM to termination, an independent optimum (scipy), false loop closures, every solver / launch form,
+edge shards, batches, and kernels as values (no new symbolic factorisation)."""
+import copy
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import robust_ref as R
+from oracle.oracle import GraphProblem
+from prior_ref import add_priors, make_priors
+from semantic_slam_amd.synth import make_graph
+
+pytestmark = pytest.mark.gpu
+
+KINDS = [R.HUBER, R.PSEUDOHUBER, R.CAUCHY, R.WELSCH, R.FAIR, R.SATURATED, R.DCS]
+
+
+def _full(U):
+    return (U + sp.triu(U, 1).T).tocsc()
+
+
+def _with_outliers(g, pri, seed, every=4):
+    """a copy of (g, priors) with gross errors on every `every`-th loop closure, landmark observation and prior; returns the copy and the
+    edge ids (GraphProblem.from_synth order: EdgeSE3, landmark edges, priors) that were corrupted"""
+    rng = np.random.default_rng(seed)
+    g = copy.copy(g)
+    g.odom_z = g.odom_z.copy(); g.lm_z = g.lm_z.copy()
+    Eo, El, Np = len(g.odom_ij), len(g.lm_ij), g.n_poses
+    bad = []
+    for k in range(Np - 1, Eo, 2):                                   # loop closures sit behind the Np - 1 odometry edges
+        g.odom_z[k, :3] += rng.uniform(2.0, 4.0, 3) * rng.choice([-1, 1], 3); bad.append(k)
+    for k in range(1, El, every):
+        if g.landmark_kind == "point":
+            g.lm_z[k, :3] += rng.uniform(1.0, 2.0, 3)
+        else:
+            g.lm_z[k, 3] += rng.uniform(1.0, 2.0)
+        bad.append(Eo + k)
+    pri = [(p, z.copy(), W) for p, z, W in pri]
+    for k in range(0, len(pri), 3):
+        pri[k][1][:] += rng.uniform(3.0, 6.0, len(pri[k][1])); bad.append(Eo + El + k)
+    return g, pri, np.asarray(bad)
+
+
+def _graph(g, pri, gauge_free=False):
+    from semantic_slam_amd import GraphSLAM
+    gp = GraphProblem.from_synth(g)
+    if gauge_free:
+        gp.vfixed[:] = 0
+    G = GraphSLAM.from_problem(gp)
+    add_priors(G, pri)
+    return G
+
+
+def _widths(ref, q=0.6, bad=()):
+    """a width per edge class: the q quantile of the class's e2 at the initial estimates, taken over the edges that were NOT corrupted
+    (`bad`), so that the gross outliers sit far beyond the threshold.  The initial poses integrate the odometry, so those edges start at
+    e2 ~ 1e-28: they are left out of the quantile (a threshold down there would be decided by the last bit of e2), which then is the
+    loop closures' """
+    e2 = ref.e2()
+    keep = np.ones(len(e2), bool); keep[np.asarray(bad, int)] = False
+    out = np.ones(len(e2))
+    for lo, hi in ((0, ref.Eo), (ref.Eo, ref.Eo + ref.El), (ref.Eo + ref.El, len(e2))):
+        v = e2[lo:hi][(e2[lo:hi] > 1e-6) & keep[lo:hi]]
+        if len(v):
+            out[lo:hi] = np.sqrt(np.quantile(v, q))
+    return out
+
+
+def _set_all(G, ref, kinds, widths, edges=None):
+    """the same kernels on the GPU graph and on the reference; kinds: one id or an array per edge"""
+    n = ref.Eo + ref.El + ref.Ep
+    kinds = np.broadcast_to(np.asarray(kinds), (n,))
+    for e in (range(n) if edges is None else edges):
+        if kinds[e] != R.NONE:
+            if G is not None:
+                G.add_robust_kernel(int(e), R.NAMES[kinds[e]], float(widths[e]))
+            ref.set_kernel(int(e), int(kinds[e]), float(widths[e]))
+
+
+def _check_active(ref, kinds_used):
+    """both sides of the threshold are populated in every edge class, at the reference's current estimates (tests call it before and after
+    the optimisation): no test passes with the kernel idle"""
+    _, _, r1 = ref.edge_chi2()
+    for lo, hi in ((0, ref.Eo), (ref.Eo, ref.Eo + ref.El), (ref.Eo + ref.El, len(r1))):
+        w = r1[lo:hi][ref.rk[lo:hi] != R.NONE]
+        assert np.count_nonzero(w < 1) > 0, (lo, hi)
+        if set(kinds_used) & {R.HUBER, R.SATURATED, R.DCS}:
+            assert np.count_nonzero(r1[lo:hi] == 1) > 0, (lo, hi)
+
+
+def _assert_system(G, ref, tol):
+    U, b = G.linearize()
+    Ho, bo = ref.build()
+    assert U.shape == Ho.shape
+    dH = abs(_full(U) - Ho).max() / abs(Ho).max()
+    db = np.abs(b - bo).max() / max(1.0, np.abs(bo).max())
+    dc = abs(G.chi2() - ref.chi2()) / ref.chi2()
+    print(f"linearise: dH {dH:.3e} db {db:.3e} dchi2 {dc:.3e}")
+    assert dH <= tol and db <= tol
+    assert G.chi2() == pytest.approx(ref.chi2(), rel=1e-12)
+    return Ho
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_linearize_each_kind_on_every_edge_class(gpu_lib, kind):
+    g, pri, _ = _with_outliers(make_graph(60, 12, seed=3, loop_every=6), make_priors(make_graph(60, 12, seed=3, loop_every=6), seed=1), seed=kind)
+    G = _graph(g, pri)
+    ref = R.NpRobustGraph(g, pri)
+    _set_all(G, ref, kind, _widths(ref, 0.9 if kind == R.SATURATED else 0.6))
+    _check_active(ref, [kind])
+    Ho = _assert_system(G, ref, 1e-11)
+    if kind == R.SATURATED:                                          # rho1 = 0 beyond the threshold: the inliers keep H positive definite
+        assert np.linalg.eigvalsh(Ho.toarray()).min() > 0
+
+
+@pytest.mark.parametrize("lk,tol", [("point", 1e-11), ("plane", 2e-5)])
+def test_linearize_mixed_kinds(gpu_lib, lk, tol):
+    g0 = make_graph(60, 12, seed=4, landmark_kind=lk, loop_every=6)
+    g, pri, _ = _with_outliers(g0, make_priors(g0, seed=2, xyz_every=5, xy_offset=2), seed=9)
+    G = _graph(g, pri)
+    ref = R.NpRobustGraph(g, pri)
+    n = ref.Eo + ref.El + ref.Ep
+    kinds = np.arange(n) % 8                                         # every kind, "none" included, in every class
+    _set_all(G, ref, kinds, _widths(ref))
+    _check_active(ref, KINDS)
+    _assert_system(G, ref, tol)
+    e2, r0, w = G.edge_chi2()
+    f2, f0, fw = ref.edge_chi2()
+    for a, f in ((e2, f2), (r0, f0), (w, fw)):                       # (the odometry edges start at e2 ~ 1e-28: relative to the largest term)
+        assert np.abs(a - f).max() <= (1e-9 if lk == "point" else 1e-6) * np.abs(f).max()
+
+
+def test_point_point_edges_take_kernels(gpu_lib):
+    """g2o::EdgePointXYZ (the fourth storage class): H, b and chi2 of a small graph against a dense NumPy build"""
+    from semantic_slam_amd import GraphSLAM
+    rng = np.random.default_rng(5)
+    G = GraphSLAM()
+    G.add_se3_node([0, 0, 0, 0, 0, 0, 1])
+    P = rng.normal(size=(6, 3))
+    ids = [G.add_point_xyz_node(p) for p in P]
+    W0 = np.eye(3) * 2.0
+    for l, p in zip(ids, P):
+        G.add_se3_point_xyz_edge(0, l, p + 0.01, W0)                # ties every point to the fixed pose
+    edges = []
+    for a in range(6):
+        for b in range(a + 1, 6):
+            Q = rng.normal(size=(3, 3)); W = Q @ Q.T + np.eye(3)
+            z = P[b] - P[a] + rng.normal(0, 0.05, 3) + (3.0 if (a + b) % 4 == 0 else 0.0)
+            edges.append((a, b, z, W, G.add_point_xyz_point_xyz_edge(ids[a], ids[b], z, W)))
+    edges.append(edges[0][:4] + (G.add_point_xyz_point_xyz_edge(ids[0], ids[1], edges[0][2], edges[0][3]),))   # a second edge on one pair
+    kinds = [KINDS[k % 7] for k in range(len(edges))]
+    for (a, b, z, W, e), k in zip(edges, kinds):
+        G.add_robust_kernel(e, R.NAMES[k], 1.5)
+    H = np.zeros((18, 18)); bb = np.zeros(18); chi = 0.0
+    for l, p in enumerate(P):
+        e = -0.01 * np.ones(3)
+        H[3 * l:3 * l + 3, 3 * l:3 * l + 3] += W0; bb[3 * l:3 * l + 3] -= W0 @ e; chi += e @ W0 @ e
+    n_down = 0
+    for (a, b, z, W, _), k in zip(edges, kinds):
+        e = P[b] - P[a] - z
+        r0, r1 = R.rho(k, 1.5, e @ W @ e)
+        n_down += r1 < 1
+        Ws = W * r1; chi += r0
+        sa, sb = slice(3 * a, 3 * a + 3), slice(3 * b, 3 * b + 3)
+        H[sa, sa] += Ws; H[sb, sb] += Ws; H[sa, sb] -= Ws; H[sb, sa] -= Ws
+        bb[sa] += Ws @ e; bb[sb] -= Ws @ e
+    assert 0 < n_down < len(edges)
+    U, b = G.linearize()
+    assert abs(_full(U).toarray() - H).max() <= 1e-11 * abs(H).max()
+    assert np.abs(b - bb).max() <= 1e-11 * max(1.0, np.abs(bb).max())
+    assert G.chi2() == pytest.approx(chi, rel=1e-12)
+    e2, r0, w = G.edge_chi2([e[4] for e in edges])
+    for (a, b, z, W, _), k, x2, x0, xw in zip(edges, kinds, e2, r0, w):
+        e = P[b] - P[a] - z
+        f0, f1 = R.rho(k, 1.5, e @ W @ e)
+        assert x2 == pytest.approx(e @ W @ e, rel=1e-12) and x0 == pytest.approx(float(f0), rel=1e-12) and xw == pytest.approx(float(f1), rel=1e-12)
+
+
+def test_edge_chi2_before_and_after_optimisation(gpu_lib):
+    g0 = make_graph(120, 24, seed=7, loop_every=10)
+    g, pri, bad = _with_outliers(g0, make_priors(g0, seed=3, xyz_every=10, xy_offset=5), seed=1)
+    G = _graph(g, pri)
+    ref = R.NpRobustGraph(g, pri)
+    n = ref.Eo + ref.El + ref.Ep
+    _set_all(G, ref, 1 + np.arange(n) % 7, _widths(ref))
+    for stage in range(2):
+        e2, r0, w = G.edge_chi2()
+        f2, f0, fw = ref.edge_chi2()
+        assert len(e2) == n == G.num_edges()
+        for a, f in ((e2, f2), (r0, f0), (w, fw)):
+            assert np.abs(a - f).max() <= 1e-9 * np.abs(f).max()
+        assert r0.sum() == pytest.approx(G.chi2(), rel=1e-12)
+        sub = np.array([n - 1, 0, ref.Eo + 3, ref.Eo - 1, 0])        # any order, repeats allowed
+        s2, s0, sw = G.edge_chi2(sub)
+        assert np.array_equal(s2, e2[sub]) and np.array_equal(s0, r0[sub]) and np.array_equal(sw, w[sub])
+        if stage == 0:
+            assert G.optimize(15)
+            E = G.estimates()
+            ref.poses = E[:g.n_poses].copy(); ref.lms = E[g.n_poses:, :3].copy()
+    assert np.median(w[bad]) < np.median(np.delete(w, bad))         # the corrupted edges are the ones the kernels distrust
+
+
+def _s_config(kind):
+    g0 = make_graph(500, 100, seed=0)
+    g, pri, bad = _with_outliers(g0, make_priors(g0, seed=2), seed=3, every=10)
+    G = _graph(g, pri)
+    ref = R.NpRobustGraph(g, pri)
+    _set_all(G, ref, kind, _widths(ref, 0.9, bad))
+    _check_active(ref, [kind])
+    return G, ref, bad
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_S_config_with_outliers_matches_reference_lm(gpu_lib, kind):
+    """BASELINE.json configs[1] (500 poses / 100 landmarks) + priors + gross outliers, the kernel on every edge (widths from the inliers):
+    the first ten LM iterations against the reference's, then run to LM's termination both land on the same optimum -- at which edges are
+    still beyond their thresholds (the kernels are at work where the comparison is made, not only at the start)."""
+    G, ref, _ = _s_config(kind)
+    assert G.optimize(10)
+    its, hist = ref.optimize(10)
+    s = G.last_stats
+    print(f"kind {kind}: ten iterations chi2 {s.chi2_after!r} ref {hist[-1][0]!r} trials {s.trials} ref trials {sum(q for _, _, q in hist)}")
+    assert s.iterations == its == 10
+    assert s.chi2_after == pytest.approx(hist[-1][0], rel=1e-6)
+    G2, ref2, bad = _s_config(kind)
+    assert G2.optimize(1024)
+    its2, _ = ref2.optimize(1024)
+    s = G2.last_stats
+    E = ref2.estimates()
+    _, _, w = G2.edge_chi2()
+    print(f"kind {kind}: to termination chi2 {s.chi2_after!r} ref {ref2.chi2()!r} iterations {s.iterations} ref {its2} status {s.status} "
+          f"d_est {np.abs(G2.estimates() - E).max() / np.abs(E).max():.3e} edges with weight < 1: {np.count_nonzero(w < 1)} of {len(w)}")
+    assert s.status == 1
+    assert s.chi2_after == pytest.approx(ref2.chi2(), rel=1e-9)
+    assert np.abs(G2.estimates() - E).max() <= 1e-6 * np.abs(E).max()
+    assert np.count_nonzero(w < 1) > 0                               # the kernels are at work at the optimum too
+
+
+def test_huber_optimum_is_scipys(gpu_lib):
+    """the minimum of sum rho0 by an independent solver: least_squares on sqrt(rho0(e2) / e2) L^T e (Omega = L L^T), every pose free"""
+    from scipy.optimize import least_squares
+    from oracle.np_graph import se3_error_jac, point_error_jac, pose_oplus
+    g0 = make_graph(150, 30, seed=5, loop_every=10)
+    g, pri, _ = _with_outliers(g0, make_priors(g0, seed=3, xyz_every=15, xy_offset=7), seed=2, every=6)
+    G = _graph(g, pri, gauge_free=True)
+    ref = R.NpRobustGraph(g, pri, fixed=[])
+    d = _widths(ref, 0.8)
+    _set_all(G, ref, R.HUBER, d)
+    _check_active(ref, [R.HUBER])
+    assert G.optimize(1024)
+    Np, Nl = g.n_poses, g.n_landmarks
+    Lo = np.linalg.cholesky(g.odom_info).transpose(0, 2, 1)
+    Ll = np.linalg.cholesky(g.lm_info).transpose(0, 2, 1)
+    Lp = [np.linalg.cholesky(W).T for _, _, W in pri]
+
+    def fun(x):
+        P = pose_oplus(g.poses_init, x[:6 * Np].reshape(Np, 6))
+        L = g.lms_init + x[6 * Np:].reshape(Nl, 3)
+        eo = se3_error_jac(P[g.odom_ij[:, 0]], P[g.odom_ij[:, 1]], g.odom_z, False)
+        el = point_error_jac(P[g.lm_ij[:, 0]], L[g.lm_ij[:, 1]], g.lm_z, False)
+        rs = [np.einsum('eij,ej->ei', Lo, eo), np.einsum('eij,ej->ei', Ll, el)] + [(Lp[k] @ (P[p, :len(z)] - z))[None] for k, (p, z, _) in enumerate(pri)]
+        out, o = [], 0
+        for r in rs:
+            e2 = np.sum(r * r, axis=1)
+            r0, _ = R.rho(R.HUBER, d[o:o + len(r)], e2)
+            out.append((r * np.sqrt(r0 / np.maximum(e2, 1e-300))[:, None]).ravel()); o += len(r)
+        return np.concatenate(out)
+    res = least_squares(fun, np.zeros(6 * Np + 3 * Nl), method="trf", tr_solver="exact", ftol=1e-15, xtol=1e-15, gtol=1e-15, max_nfev=200)
+    assert res.status > 0
+    P = pose_oplus(g.poses_init, res.x[:6 * Np].reshape(Np, 6))
+    L = g.lms_init + res.x[6 * Np:].reshape(-1, 3)
+    E = G.estimates()
+    print(f"huber: chi2 {G.last_stats.chi2_after!r} scipy {2 * res.cost!r}")
+    assert G.last_stats.chi2_after == pytest.approx(2 * res.cost, rel=1e-8)
+    assert np.abs(E[:Np, :3] - P[:, :3]).max() <= 1e-6 * np.abs(P[:, :3]).max()
+    assert np.abs(E[Np:, :3] - L).max() <= 1e-6 * np.abs(L).max()
+
+
+def _ate(P, g):
+    return float(np.sqrt(np.mean(np.sum((P[:, :3] - g.poses_true[:, :3]) ** 2, axis=1))))
+
+
+@pytest.mark.parametrize("name,kind", [("Huber", R.HUBER), ("DCS", R.DCS)])
+def test_false_loop_closures_are_switched_off(gpu_lib, name, kind):
+    """a pose graph (plus its landmarks) with gross false loop closures: a kernel on the EdgeSE3 loop closures gives a trajectory closer to
+    the truth than plain least squares, on the GPU and in the reference alike, and the injected edges get the lowest weights"""
+    g0 = make_graph(300, 60, seed=8, loop_every=15)
+    g = copy.copy(g0); g.odom_z = g0.odom_z.copy()
+    Np, Eo = g.n_poses, len(g.odom_ij)
+    loops = np.arange(Np - 1, Eo)
+    bad = loops[::4]
+    rng = np.random.default_rng(0)
+    g.odom_z[bad, :3] += rng.uniform(3.0, 5.0, (len(bad), 3))
+    good = np.setdiff1d(loops, bad)
+    assert len(bad) >= 3 and len(good) >= 3
+    plain = _graph(g, [])
+    assert plain.optimize(1024)
+    G = _graph(g, [])
+    ref = R.NpRobustGraph(g)
+    rplain = R.NpRobustGraph(g); rplain.optimize(40)
+    for e in loops:
+        G.add_robust_kernel(int(e), name, 1.0); ref.set_kernel(int(e), kind, 1.0)
+    assert G.optimize(1024)
+    ref.optimize(40)
+    a_plain, a_rob = _ate(plain.estimates()[:Np], g), _ate(G.estimates()[:Np], g)
+    print(f"{name}: ATE plain {a_plain:.4f} robust {a_rob:.4f}; reference plain {_ate(rplain.poses, g):.4f} robust {_ate(ref.poses, g):.4f}")
+    assert a_rob < a_plain
+    assert _ate(ref.poses, g) < _ate(rplain.poses, g)
+    _, _, w = G.edge_chi2()
+    assert w[bad].max() < w[good].min()
+    assert np.all(w[:Np - 1] == 1.0)                                 # the odometry edges carry no kernel
+
+
+def _mixed(g, pri, dcs=0.0, opts=()):
+    G = _graph(g, pri)
+    ref = R.NpRobustGraph(g, pri, dcs_phi=dcs)
+    n = ref.Eo + ref.El + ref.Ep
+    _set_all(G, ref, 1 + np.arange(n) % 7, _widths(ref, 0.8))
+    for k, v in opts:
+        G.set_option(k, v)
+    return G, ref
+
+
+def test_other_solvers_reach_the_same_optimum(gpu_lib):
+    g0 = make_graph(500, 100, seed=0)
+    g, pri, _ = _with_outliers(g0, make_priors(g0, seed=2), seed=3, every=10)
+    G1, _ = _mixed(g, pri)
+    assert G1.optimize(1024)
+    for solver in (0, 2):
+        G, _ = _mixed(g, pri, opts=[("solver", solver), ("pcg_tol", 1e-10)])
+        assert G.optimize(200)
+        assert G.last_stats.chi2_after == pytest.approx(G1.last_stats.chi2_after, rel=1e-8)
+        assert np.abs(G.estimates() - G1.estimates()).max() <= 1e-5 * np.abs(G1.estimates()).max()
+
+
+def test_launch_forms_are_bitwise_equal_and_runs_repeat(gpu_lib):
+    """The robust instantiations of every LM launch form -- stand-alone kernels, the halves of a trial inside k_chol_flow, the speculative
+    lanes of k_chol_spec_round -- give the same bits, trial counts included.  Each form runs as a batch of one so that the batch's
+    counters show which persistent kernels really carried the trials."""
+    from semantic_slam_amd import GraphBatch
+    g0 = make_graph(120, 24, seed=11, loop_every=10)
+    g, pri, bad = _with_outliers(g0, make_priors(g0, seed=4, xyz_every=10, xy_offset=5), seed=6)
+
+    def build(fused, spec):
+        G = _graph(g, pri)
+        ref = R.NpRobustGraph(g, pri)
+        n = ref.Eo + ref.El + ref.Ep
+        _set_all(G, ref, 1 + np.arange(n) % 7, _widths(ref, 0.8, bad))
+        G.set_option("fused_small_graph", fused); G.set_option("speculative_trials", spec)
+        return G
+    runs, counts = [], {}
+    for fused, spec in [(0, 0), (0, 0), (1, 0), (1, 1), (1, 2), (0, 1), (0, 2)]:
+        G = build(fused, spec)
+        B = GraphBatch([G]); B.upload()
+        st = B.optimize(1024)[0]
+        B.download()
+        counts[(fused, spec)] = (int(B.info("lm_fused_launches")), int(B.info("lm_spec_rounds")))
+        runs.append(((st.iterations, st.trials, st.chi2_after), G.estimates().copy()))
+    print("launch forms (fused launches, speculative rounds):", counts)
+    for r in runs[1:]:
+        assert r[0] == runs[0][0] and np.array_equal(r[1], runs[0][1])
+    # the forms are distinct code paths: no persistent kernel without the option, the fused halves with it, the lanes with speculation
+    assert counts[(0, 0)] == (0, 0) and counts[(0, 2)] == (0, 0)
+    assert counts[(1, 0)][0] > 0 and counts[(1, 0)][1] == 0
+    assert counts[(1, 2)][1] > 0 and counts[(1, 1)][0] + counts[(1, 1)][1] > 0   # (the adaptive lanes join only after a rejected trial)
+    S = build(1, 1)                                                  # and the single handle (the default form) gives the same bits
+    assert S.optimize(1024)
+    assert (S.last_stats.iterations, S.last_stats.trials, S.last_stats.chi2_after) == runs[0][0] and np.array_equal(S.estimates(), runs[0][1])
+
+
+def test_eight_edge_shards_sum_to_the_full_system(gpu_lib):
+    from semantic_slam_amd import GraphBatch
+    gs = [make_graph(80, 15, seed=31), make_graph(50, 9, seed=32, landmark_kind="plane")]
+    built = []
+    for k, g0 in enumerate(gs):
+        g, pri, _ = _with_outliers(g0, make_priors(g0, seed=5 + k, xyz_every=9, xy_offset=4), seed=k)
+        built.append(_mixed(g, pri)[0])
+    B = GraphBatch(built); B.upload()
+    full = B.linearize_hb()
+    parts = []
+    for r in range(8):
+        B.set_edge_shard(r, 8)
+        parts.append(B.linearize_hb())
+    assert np.abs(np.sum(parts, axis=0) - full).max() <= 1e-12 * np.abs(full).max()
+    assert all(np.abs(p).max() > 0 for p in parts)
+    B.set_edge_shard(0, 1)
+    assert np.array_equal(B.linearize_hb(), full)
+
+
+def test_batch_members_with_different_kernels_match_single_handles(gpu_lib):
+    """40 members (>= 32: the front kernels of the batched factorisation run), every member with kernels of its own -- one of them with
+    none -- equal their single-handle runs"""
+    from semantic_slam_amd import GraphBatch
+    M = 40
+    cases = []
+    for m in range(M):
+        g0 = make_graph(120, 24, seed=100 + m)
+        g, pri, _ = _with_outliers(g0, make_priors(g0, seed=m, xyz_every=10, xy_offset=5), seed=m)
+        cases.append((g, pri, m))
+
+    def build(c):
+        g, pri, m = c
+        G = _graph(g, pri)
+        if m != 3:
+            ref = R.NpRobustGraph(g, pri)
+            n = ref.Eo + ref.El + ref.Ep
+            _set_all(G, ref, 1 + (np.arange(n) + m) % 7, _widths(ref, 0.8))
+        return G
+    singles = [build(c) for c in cases]
+    for G in singles:
+        assert G.optimize(6)
+    graphs = [build(c) for c in cases]
+    B = GraphBatch(graphs); B.upload()
+    stats = B.optimize(6)
+    B.download()
+    for G1, G2, st in zip(singles, graphs, stats):
+        assert st.chi2_after == pytest.approx(G1.last_stats.chi2_after, rel=1e-9)
+        assert np.abs(G1.estimates() - G2.estimates()).max() < 1e-9 * max(1.0, np.abs(G1.estimates()).max())
+    # a live batch picks a changed kernel up at upload: member 3 gets member 4's kind of kernels and then matches a fresh handle built so
+    g, pri, _ = cases[3]
+    ref = R.NpRobustGraph(g, pri)
+    w = _widths(ref, 0.8)
+    fresh = _graph(g, pri)
+    for v in range(graphs[3].num_vertices()):
+        graphs[3].set_estimate(v, fresh.estimate(v))
+    _set_all(graphs[3], ref, R.CAUCHY, w); _set_all(fresh, R.NpRobustGraph(g, pri), R.CAUCHY, w)
+    B.upload()
+    st3 = B.optimize(6)[3]
+    assert fresh.optimize(6)
+    assert st3.chi2_after == pytest.approx(fresh.last_stats.chi2_after, rel=1e-9)
+
+
+def test_kernel_change_is_a_value_change(gpu_lib):
+    g0 = make_graph(120, 24, seed=13)
+    g, pri, bad = _with_outliers(g0, make_priors(g0, seed=1, xyz_every=10, xy_offset=5), seed=4)
+    G = _graph(g, pri)
+    init = [G.estimate(v).copy() for v in range(G.num_vertices())]
+    assert G.optimize(10)
+    assert G.last_stats.host_plan_us > 0                             # the first call planned the structure
+    chi_plain = G.last_stats.chi2_after
+    for v, e in enumerate(init):
+        G.set_estimate(v, e)
+    for e in bad:
+        G.add_robust_kernel(int(e), "Cauchy", 2.0)
+    assert G.optimize(10)
+    assert G.last_stats.host_plan_us == 0                            # ... and a kernel is a value: nothing was planned again
+    assert G.last_stats.chi2_after < chi_plain
+    F = _graph(g, pri)
+    for e in bad:
+        F.add_robust_kernel(int(e), "Cauchy", 2.0)
+    assert F.optimize(10)
+    assert (F.last_stats.chi2_after, F.last_stats.iterations, F.last_stats.trials) == (G.last_stats.chi2_after, G.last_stats.iterations, G.last_stats.trials)
+    assert np.array_equal(F.estimates(), G.estimates())
+    for e in bad:                                                    # removing every kernel returns to the plain kernels and the plain result
+        G.add_robust_kernel(int(e), "NONE", 0.0)
+    for v, e in enumerate(init):
+        G.set_estimate(v, e)
+    assert G.optimize(10) and G.last_stats.host_plan_us == 0
+    assert G.last_stats.chi2_after == chi_plain
+
+
+def test_global_dcs_option_and_per_edge_kernels(gpu_lib):
+    """"robust_kernel_dcs" = 1 plus Huber on some landmark edges: those use Huber, the other landmark edges DCS, everything else plain"""
+    g0 = make_graph(60, 12, seed=3, loop_every=6)
+    g, pri, _ = _with_outliers(g0, make_priors(g0, seed=1), seed=2)
+    G = _graph(g, pri)
+    G.set_option("robust_kernel_dcs", 1.0)
+    ref = R.NpRobustGraph(g, pri, dcs_phi=1.0)
+    hub = np.arange(ref.Eo, ref.Eo + ref.El, 3)
+    _set_all(G, ref, R.HUBER, _widths(ref), edges=hub)
+    _, _, r1 = ref.edge_chi2()
+    rest = np.setdiff1d(np.arange(ref.Eo, ref.Eo + ref.El), hub)
+    assert np.count_nonzero(r1[hub] < 1) > 0 and np.count_nonzero(r1[rest] < 1) > 0
+    _assert_system(G, ref, 1e-11)
+    e2, r0, w = G.edge_chi2()
+    assert np.abs(w - r1).max() <= 1e-9
+    assert np.all(w[:ref.Eo] == 1.0) and np.all(w[ref.Eo + ref.El:] == 1.0)
