@@ -247,6 +247,24 @@ int sslam_batch_upload(sslam_batch* b);
 /* copy optimised estimates back into the host graphs */
 int sslam_batch_download(sslam_batch* b);
 int sslam_batch_optimize(sslam_batch* b, int max_iters, sslam_opt_stats* out /* [n] */);
+/* Blocks of H^-1 of the graphs of a batch.  H is the undamped system at the estimates the batch currently holds on
+ * the device (after sslam_batch_upload / sslam_batch_optimize), NOT at the host graphs' estimates.
+ * req = 3n ints: (graph index in the batch, row vertex id, column vertex id).
+ * out = packed row-major d(row) x d(col) blocks in request order.
+ * Diagonal and off-diagonal pairs; both vertices belong to the named graph.
+ * A fixed or edge-less vertex on either side gives a block of zeros, and so do two vertices in different connected components of their
+ * graph.  n == 0 returns 0.  SSLAM_ERR_INVALID, with out_blocks unwritten: a NULL handle, a NULL req or out_blocks with n > 0, a graph
+ * index or vertex id out of range, a structure change since creation.  SSLAM_ERR_NUMERIC when a factorisation of the undamped H breaks
+ * down -- the rule of sslam_graph_marginals; ONE graph of the batch that is not positive definite fails the whole call (per-graph
+ * failure flags are future work).  SSLAM_ERR_UNSUPPORTED: solver 0 or 2, a batch in edge-sharded mode.  A stream group works: every
+ * request goes to the part that holds its graph, and the parts run one after the other from the calling thread.
+ * One linearisation and one flat factorisation of the whole batch, then ONE WAVE PER REQUEST (k_chol_marginal_pairs): a forward
+ * substitution along the elimination-tree path of the row vertex and, for an off-diagonal pair, of the column vertex, and the product of
+ * the two over the columns the paths share -- no right-hand side matrix, no backward substitution, only the requested blocks cross PCIe.
+ * Paths of any length (the L configuration included): what fits the LDS of a wave runs there, the rest in a device scratch buffer, with
+ * bitwise the same result; SSLAM_MARGINAL_LDS_BYTES in the environment (read per call, default and ceiling 61440) lowers the LDS budget.
+ * The call leaves the batch as it found it: sslam_batch_optimize / sslam_batch_download after it give, bitwise, what they give without it. */
+int sslam_batch_marginals(sslam_batch* b, const int32_t* req, int n, double* out_blocks);
 /* Edge-sharded mode (SURVEY 8e mode E, BASELINE.json configs[4]): every graph's edge list is split contiguously over `world` ranks
  * (one process per GPU, each holding the whole batch); a rank builds the partial normal equations of its edges, ONE RCCL all-reduce
  * (ncclDouble, sum, over xGMI) of the contiguous [H || b] device buffer gives every rank the full system, and the solve / update /
@@ -270,7 +288,8 @@ int sslam_batch_time_linearize(sslam_batch* b, int repeats, double* ms_per_build
 int sslam_batch_time_solver(sslam_batch* b, int repeats, double* factor_ms, double* solve_ms);
 /* algorithmic bytes of one Jacobian build over the whole batch (SURVEY §8d formula) */
 int64_t sslam_batch_linearize_bytes(const sslam_batch* b);
-/* structural facts of a batch (doubles): "factor_lnz" (doubles in the Cholesky factor), "factor_levels",
+/* structural facts of a batch (doubles): "factor_lnz" (doubles in the Cholesky factor), "factor_levels", "factor_front" (1: the
+ * factorisation runs the front kernels, the default of batches of 32 graphs and more),
  * "h_doubles" (doubles in H), "dim" (scalar unknowns), "factor_bytes" = algorithmic HBM bytes of one numeric
  * factorisation + fused forward solve: read H and b once, write L and y once */
 int sslam_batch_info(sslam_batch* b, const char* key, double* value);

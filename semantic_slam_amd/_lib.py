@@ -91,6 +91,7 @@ def load_library():
         "sslam_batch_upload": (ci, [vp]),
         "sslam_batch_download": (ci, [vp]),
         "sslam_batch_optimize": (ci, [vp, ci, C.POINTER(OptStats)]),
+        "sslam_batch_marginals": (ci, [vp, C.POINTER(C.c_int32), ci, dp]),
         "sslam_comm_unique_id": (ci, [C.c_char_p]),
         "sslam_batch_comm_init": (ci, [vp, C.c_char_p, ci, ci]),
         "sslam_batch_set_edge_shard": (ci, [vp, ci, ci]),

@@ -133,6 +133,7 @@ struct Batch {
   std::vector<Pending> pending;
   std::vector<hipEvent_t> event_pool;
   bool uploaded = false;
+  LmState* d_lm_save = nullptr;   // [B] sslam_batch_marginals: the per-graph LM states while the call borrows them (allocated at its first use)
   bool has_duplicate_blocks = false;
   bool has_planes = false;
   std::vector<int> dup_eo, dup_el;
@@ -239,6 +240,7 @@ int chol_backward(Batch& b);             // x = L^-T y  -> V.x
 int chol_set_active(Batch& b, const std::vector<char>* active);   // LM endgame: size the launches for the graphs still active (nullptr: all)
 int64_t chol_plan_lnz(const Batch& b);
 int chol_plan_levels(const Batch& b);
+bool chol_plan_front(const Batch& b);       // the factorisation runs the front kernels (front_kernels.hpp)
 int chol_solve_multi(Batch& b, const double* rhs_host, int nrhs, double* x_host);  // uses the last factorisation
 bool chol_plan_flow(const Batch& b);        // the plan runs factor + both solves in one dependency-driven launch (small batches)
 int chol_solve_flow(Batch& b);              // (H + lambda I) dx = b for in_trial graphs -> V.x, one launch
@@ -252,6 +254,8 @@ int chol_lm_step_spec(Batch& b, int max_iters);   // one LM iteration: up to ten
 int chol_factor_flat_flow(Batch& b);        // flat factor (marginals) through the single launch
 int chol_flow_check(Batch& b);              // error flag of that launch (synchronises the stream)
 int chol_marginal_diag(Batch& b, const std::vector<int>& xoff, const std::vector<int>& dims, double* out36);  // diagonal blocks of H^-1 along the tree paths, one launch
+struct MarginalReq { int xoff_u, dim_u, xoff_v, dim_v; };   // first unknown (internal row order) and dimension of the row / column vertex; xoff_v == xoff_u: a diagonal block
+int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double* out36);   // blocks Z(u, v) of H^-1 for pairs of vertices of a batch, paths of any length
 
 
 }  // namespace sslam

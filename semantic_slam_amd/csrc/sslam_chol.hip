@@ -118,6 +118,8 @@ struct CholPlan {
   int* d_mpath = nullptr;       // [path_ptr | dims | path columns] of a request
   double* d_mout = nullptr;     // [requests][36]
   size_t mpath_cap = 0, mout_cap = 0;
+  char* d_mscratch = nullptr;   // k_chol_marginal_pairs: the Y slices of the requests whose paths LDS does not hold
+  size_t mscratch_cap = 0;      // bytes
 };
 
 void chol_plan_free(CholPlan* p) {
@@ -148,6 +150,7 @@ void chol_plan_free(CholPlan* p) {
   if (p->d_multi_x) (void)hipFree(p->d_multi_x);
   if (p->d_mpath && !p->arena) (void)hipFree(p->d_mpath);
   if (p->d_mout && !p->arena) (void)hipFree(p->d_mout);
+  if (p->d_mscratch && !p->arena) (void)hipFree(p->d_mscratch);
   delete p;
 }
 
@@ -1223,6 +1226,113 @@ __global__ __launch_bounds__(64) void k_chol_marginal_paths(CholView C, const in
 }
 
 // ------------------------------------------------------------------------------------------------
+// Blocks Z(u, v) of H^-1 for (row vertex, column vertex) PAIRS of the graphs of a batch (sslam_batch_marginals), diagonal or not, and for
+// paths of any length.  Z(u, v) = E_u^T L^-T L^-1 E_v = Y_u^T Y_v with Y_w = L^-1 E_w, and Y_w lives on the path of w's column to the root of
+// the elimination tree: the product runs over the columns the two paths share -- in a tree their common suffix, from the lowest common
+// ancestor to the root (none when u and v lie in different components: zeros).  One wave per request: the forward substitution of
+// k_chol_marginal_paths along path(u) -- the same operations in the same order -- then, for u != v, along path(v), then the sum over the
+// suffix.  A request with u == v keeps ONE Y (the whole LDS budget for its one path) and is the arithmetic of k_chol_marginal_paths.
+// SCRATCH = false: Y and the path records in LDS [diagonal block 36 | Y: ylen x 36 | records ylen x int4 | y offsets ylen x int].
+// SCRATCH = true: the same three arrays in the request's slice of a device buffer (req[7], in units of 16 bytes), for paths that LDS does
+// not hold; only the diagonal block stays in LDS.  Same body, same order of operations: the two placements agree bitwise.  The wave is the
+// whole workgroup, its lanes hand Y to one another between the phases of a step: the workgroup-scope release / acquire of __syncthreads()
+// orders plain global stores and loads of one workgroup as it orders LDS (its waves share the CU's L1; the compiler waits for the stores
+// before the barrier).
+// req: 8 ints per request {first entry of path(u) in path_cols, its length, the same for path(v) (length 0: u == v), d(u), d(v), length of
+// the common suffix, scratch slice}.  out: [requests][36], the leading d(u) x d(v) entries row-major.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void marginal_path_forward(const CholView& C, const int* __restrict__ cols, int P, int D, double* Y, double* sD,
+                                                      int4* prec, int* pyoff) {
+  const int lane = threadIdx.x;
+  const double* __restrict__ L = C.Lval;
+  for (int t = lane; t < P; t += 64) {
+    const ColMeta cm = C.col[cols[t]];
+    prec[t] = make_int4(cm.b0, cm.nb, cm.base, cm.dim);
+    pyoff[t] = cm.yoff;
+  }
+  for (int e = lane; e < P * 36; e += 64) Y[e] = 0.0;
+  __syncthreads();
+  if (lane < D) Y[lane * 6 + lane] = 1.0;   // E_w: identity in the vertex' own rows (path entry 0)
+  __syncthreads();
+  for (int s = 0; s < P; ++s) {
+    const int4 pr = prec[s];
+    const int da = pr.w;
+    if (lane < da * da) sD[lane] = L[pr.z + lane];
+    __syncthreads();
+    if (lane < D) {   // one lane per right-hand side column: Y_s = L_ss^-1 acc_s
+      double yv[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        if (i < da) {
+          double a = Y[s * 36 + i * 6 + lane];
+#pragma unroll
+          for (int m = 0; m < 6; ++m) if (m < i) a -= sD[i * da + m] * yv[m];
+          yv[i] = a / sD[i * da + i];
+          Y[s * 36 + i * 6 + lane] = yv[i];
+        }
+      }
+    }
+    __syncthreads();
+    for (int bq = lane; bq < pr.y - 1; bq += 64) {   // the blocks below the diagonal: acc_t -= L(t, s) Y_s
+      const BlkMeta bm = C.blk[pr.x + 1 + bq];
+      const int di = bm.info & 15;
+      int lo = s + 1, hi = P - 1;                    // the row's place on the path (y offsets ascend along it)
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (pyoff[mid] < bm.yoff_row) lo = mid + 1; else hi = mid; }
+      const double* Lb = L + bm.off;
+      double* acc = Y + lo * 36;
+      for (int i = 0; i < di; ++i) {
+        double lrow[6];
+#pragma unroll
+        for (int m = 0; m < 6; ++m) lrow[m] = m < da ? Lb[i * da + m] : 0.0;
+        for (int c = 0; c < D; ++c) {
+          double a = 0;
+#pragma unroll
+          for (int m = 0; m < 6; ++m) a += lrow[m] * Y[s * 36 + m * 6 + c];   // rows >= da of Y_s are zero
+          acc[i * 6 + c] -= a;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <bool SCRATCH>
+__global__ __launch_bounds__(64) void k_chol_marginal_pairs(CholView C, const int* __restrict__ req, const int* __restrict__ path_cols,
+                                                            double* __restrict__ out, int ylen, char* scratch) {
+  extern __shared__ double sm[];
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int* __restrict__ q = req + (size_t)r * 8;
+  const int Pu = q[1], Pv = q[3], Du = q[4], Dv = q[5], nc = q[6];
+  double* sD = sm;
+  double* Y;
+  int4* prec;
+  int* pyoff;
+  if (SCRATCH) {
+    const int yl = Pu + Pv;
+    Y = reinterpret_cast<double*>(scratch + (size_t)q[7] * 16);
+    prec = reinterpret_cast<int4*>(Y + (size_t)yl * 36);
+    pyoff = reinterpret_cast<int*>(prec + yl);
+  } else {
+    Y = sm + 36;
+    prec = reinterpret_cast<int4*>(Y + (size_t)ylen * 36);
+    pyoff = reinterpret_cast<int*>(prec + ylen);
+  }
+  marginal_path_forward(C, path_cols + q[0], Pu, Du, Y, sD, prec, pyoff);
+  if (Pv > 0) marginal_path_forward(C, path_cols + q[2], Pv, Dv, Y + (size_t)Pu * 36, sD, prec + Pu, pyoff + Pu);
+  // the common suffix: its first entry in either path (u == v: the whole path, nc == Pu)
+  const double* Yu = Y + (size_t)(Pu - nc) * 36;
+  const double* Yv = Pv > 0 ? Y + (size_t)(Pu + Pv - nc) * 36 : Yu;
+  if (lane < Du * Dv) {
+    const int rr = lane / Dv, cc = lane - rr * Dv;
+    double z = 0;
+    for (int t = 0; t < nc; ++t)
+#pragma unroll
+      for (int i = 0; i < 6; ++i) z += Yu[t * 36 + i * 6 + rr] * Yv[t * 36 + i * 6 + cc];
+    out[(size_t)r * 36 + lane] = z;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // One LM iteration of a SMALL graph after its linearisation, in ONE launch (the orchestrator's tick re-optimises a
 // graph of a few hundred vertices 25-40 trials per tick, and ~65 launches per trial made the MI355X slower than one host core).
 // One workgroup per graph whose whole elimination tree is walked by the tail kernels (plans with no per-depth launches):
@@ -2090,6 +2200,7 @@ int chol_flow_check(Batch& b) {
 
 int64_t chol_plan_lnz(const Batch& b) { return b.chol ? b.chol->lnz : 0; }
 int chol_plan_levels(const Batch& b) { return b.chol ? b.chol->C.nlevels : 0; }
+bool chol_plan_front(const Batch& b) { return b.chol && b.chol->front; }
 int chol_plan_launches(const Batch& b) { return b.chol ? (int)b.chol->plv_lds_f.size() + (b.chol->tail_total > 0 ? 1 : 0) : 0; }
 
 // LM endgame: from now on only the graphs flagged in `active` can be in a trial (a terminated graph never comes back within an
@@ -2294,6 +2405,99 @@ int chol_marginal_diag(Batch& b, const std::vector<int>& xoff, const std::vector
   if (stage) memcpy(out, stage + in_bytes, out_bytes);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "path marginals launch: %s", hipGetErrorString(e));
+  return 0;
+}
+
+// Z(u, v) of (L L^T)^-1 for pairs of vertices of the graphs of a batch (k_chol_marginal_pairs), from the last FLAT factorisation; out:
+// [n][36], the leading dim_u x dim_v entries row-major.  Any path length: a request whose Y fits the LDS budget (SSLAM_MARGINAL_LDS_BYTES,
+// read per call; default and ceiling 60 KB) runs out of LDS, every other one out of its slice of a device scratch buffer -- one upload, at
+// most one launch per placement and one download, through the page-locked staging buffer.  (Requests beyond 64 MB of path lists or 1 GB of
+// scratch go in further rounds of the same: the memory of a call is bounded, whatever the batch.)
+int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double* out) {
+  CholPlan& P = *b.chol;
+  const CholView& C = P.C;
+  const size_t n = reqs.size();
+  if (n == 0) return 0;
+  if (!C.flat_L) return set_error(SSLAM_ERR_INVALID, "chol_marginal_blocks needs the flat factor (chol_factor_and_forward(b, true))");
+  size_t budget = 60 * 1024;
+  if (const char* e = getenv("SSLAM_MARGINAL_LDS_BYTES")) budget = (size_t)std::min<long long>(std::max<long long>(atoll(e), 0), 60 * 1024);
+  auto col_of = [&](int xo) { return (xo >= 0 && xo < (int)P.h_xoff_col.size()) ? P.h_xoff_col[xo] : -1; };
+  for (const MarginalReq& rq : reqs)
+    if (col_of(rq.xoff_u) < 0 || col_of(rq.xoff_v) < 0) return set_error(SSLAM_ERR_INVALID, "marginal of an unknown that is not the start of a block row");
+  // device scratch: out of the graph handle's arena when there is one, else the plan's own allocations (as chol_marginal_diag)
+  auto grow = [&](void** p, size_t& cap, size_t bytes) -> int {
+    if (cap >= bytes) return 0;
+    bytes += bytes / 4 + 4096;
+    if (P.arena) { *p = P.arena->take(bytes, true); cap = *p ? bytes : 0; if (!*p) return set_error(SSLAM_ERR_HIP, "device allocation of %zu bytes failed", bytes); }
+    else { if (*p) (void)hipFree(*p); *p = nullptr; cap = 0; SSLAM_HIP_TRY(hipMalloc(p, bytes)); cap = bytes; }
+    return 0;
+  };
+  constexpr size_t kPathCap = (size_t)16 << 20, kScratchCap = (size_t)1 << 30;   // ints of path lists, bytes of Y slices per round
+  constexpr size_t kEntry = 36 * sizeof(double) + sizeof(int4) + sizeof(int);      // Y block, path record, y offset of one path entry
+  struct Rec { int v[8]; size_t src; bool scratch; };
+  std::vector<Rec> recs;
+  std::vector<int> cols, up;
+  for (size_t k0 = 0; k0 < n;) {
+    recs.clear(); cols.clear();
+    size_t scr_bytes = 0, k = k0;
+    int ylen_lds = 0, n_lds = 0;
+    for (; k < n && (k == k0 || (cols.size() < kPathCap && scr_bytes < kScratchCap)); ++k) {
+      const MarginalReq& rq = reqs[k];
+      Rec q{};
+      q.src = k;
+      q.v[0] = (int)cols.size();
+      for (int j = col_of(rq.xoff_u); j >= 0; j = P.h_cparent[j]) cols.push_back(j);
+      q.v[1] = (int)cols.size() - q.v[0];
+      q.v[2] = q.v[0]; q.v[3] = 0; q.v[4] = rq.dim_u; q.v[5] = rq.dim_u; q.v[6] = q.v[1];
+      if (rq.xoff_v != rq.xoff_u) {
+        q.v[2] = (int)cols.size();
+        for (int j = col_of(rq.xoff_v); j >= 0; j = P.h_cparent[j]) cols.push_back(j);
+        q.v[3] = (int)cols.size() - q.v[2];
+        q.v[5] = rq.dim_v;
+        int nc = 0;   // common suffix of the two paths: from the root down to their lowest common ancestor
+        while (nc < q.v[1] && nc < q.v[3] && cols[q.v[0] + q.v[1] - 1 - nc] == cols[q.v[2] + q.v[3] - 1 - nc]) ++nc;
+        q.v[6] = nc;
+      }
+      const int ylen = q.v[1] + q.v[3];
+      q.scratch = 36 * sizeof(double) + (size_t)ylen * kEntry + 16 > budget;
+      if (q.scratch) { q.v[7] = (int)(scr_bytes / 16); scr_bytes += ((size_t)ylen * kEntry + 15) & ~(size_t)15; }
+      else { ylen_lds = std::max(ylen_lds, ylen); ++n_lds; }
+      recs.push_back(q);
+    }
+    const int m = (int)recs.size(), n_scr = m - n_lds;
+    std::stable_partition(recs.begin(), recs.end(), [](const Rec& r) { return !r.scratch; });   // [LDS requests | scratch requests]
+    up.resize((size_t)m * 8 + cols.size());
+    for (int i = 0; i < m; ++i) std::copy(recs[i].v, recs[i].v + 8, up.begin() + (size_t)i * 8);
+    std::copy(cols.begin(), cols.end(), up.begin() + (size_t)m * 8);
+    int rc;
+    size_t mpath_bytes = P.mpath_cap * sizeof(int), mout_bytes = P.mout_cap * sizeof(double);
+    if ((rc = grow((void**)&P.d_mpath, mpath_bytes, up.size() * sizeof(int)))) return rc;
+    P.mpath_cap = mpath_bytes / sizeof(int);
+    if ((rc = grow((void**)&P.d_mout, mout_bytes, (size_t)m * 36 * sizeof(double)))) return rc;
+    P.mout_cap = mout_bytes / sizeof(double);
+    if (n_scr > 0 && (rc = grow((void**)&P.d_mscratch, P.mscratch_cap, scr_bytes))) return rc;
+    const size_t in_bytes = (up.size() * sizeof(int) + 7) & ~(size_t)7, out_bytes = (size_t)m * 36 * sizeof(double);
+    char* stage = b.pin->get(in_bytes + out_bytes);
+    std::vector<double> fallback;
+    const void* src = up.data();
+    double* res;
+    if (stage) { memcpy(stage, up.data(), up.size() * sizeof(int)); src = stage; res = reinterpret_cast<double*>(stage + in_bytes); }
+    else { fallback.resize((size_t)m * 36); res = fallback.data(); }
+    SSLAM_HIP_TRY(hipMemcpyAsync(P.d_mpath, src, up.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
+    const int* d_cols = P.d_mpath + (size_t)m * 8;
+    if (n_lds > 0)
+      hipLaunchKernelGGL(k_chol_marginal_pairs<false>, dim3(n_lds), dim3(64), 36 * sizeof(double) + (size_t)ylen_lds * kEntry + 16, b.stream, C,
+                         (const int*)P.d_mpath, d_cols, P.d_mout, ylen_lds, (char*)nullptr);
+    if (n_scr > 0)
+      hipLaunchKernelGGL(k_chol_marginal_pairs<true>, dim3(n_scr), dim3(64), 36 * sizeof(double), b.stream, C,
+                         (const int*)(P.d_mpath + (size_t)n_lds * 8), d_cols, P.d_mout + (size_t)n_lds * 36, 0, P.d_mscratch);
+    SSLAM_HIP_TRY(hipMemcpyAsync(res, P.d_mout, out_bytes, hipMemcpyDeviceToHost, b.stream));
+    SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // up is reused by the next round
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "pair marginals launch: %s", hipGetErrorString(e));
+    for (int i = 0; i < m; ++i) std::copy(res + (size_t)i * 36, res + (size_t)i * 36 + 36, out + recs[i].src * 36);
+    k0 = k;
+  }
   return 0;
 }
 

@@ -2536,6 +2536,103 @@ int sslam_batch_optimize(sslam_batch* h, int max_iters, sslam_opt_stats* out) {
     return for_each_part(h, true, [&](sslam_batch* p, int k) { return batch_optimize(p->b, max_iters, out + h->part0[k]); });
   return batch_optimize(h->b, max_iters, out);
 }
+// ---- covariance blocks of the graphs of a batch -------------------------------------------------------------------------------
+// Blocks of H^-1 for (graph, row vertex, column vertex) requests of ONE batch (a part of a stream group): linearise once at the estimates the
+// device holds, factor the undamped H flat (the choice of marginal_blocks between the single launch and the launches per depth), then one
+// wave per request along the elimination-tree paths (chol_marginal_blocks).  The per-graph LM states are borrowed -- the linearisation wants
+// every graph at the start of an iteration, the factorisation every graph in a trial at lambda 0 -- and put back; H, b, y and the factor
+// are rebuilt by the first step of whatever runs next, the estimates are only read.  out: [n][36].
+static int batch_marginals(Batch& b, const std::vector<std::array<int, 3>>& req, double* out) {
+  if (req.empty()) return 0;
+  const int solver = b.graphs[0]->opt.solver;
+  if (solver == 0 || solver == 2) return set_error(SSLAM_ERR_UNSUPPORTED, "sslam_batch_marginals: direct solvers only (solver %d)", solver);
+  if (b.sharded) return set_error(SSLAM_ERR_UNSUPPORTED, "sslam_batch_marginals is not available in the edge-sharded mode");
+  SSLAM_HIP_TRY(hipSetDevice(b.device));
+  std::vector<MarginalReq> mr;
+  std::vector<int> slot(req.size(), -1);
+  auto xoff_of = [&](int g, int v) {   // first unknown of the vertex in the batch's internal row order, -1: fixed or without edges
+    const HostGraph& G = *b.graphs[g];
+    if (G.vtype[v] == VT_SE3) { const int r = b.pose_row[b.v2pose[g][v]]; return r < 0 ? -1 : 6 * r; }
+    const int r = b.lm_row[b.v2lm[g][v]];
+    return r < 0 ? -1 : 6 * b.V.nPr + 3 * r;
+  };
+  for (size_t k = 0; k < req.size(); ++k) {
+    const int g = req[k][0], vr = req[k][1], vc = req[k][2];
+    const int xr = xoff_of(g, vr), xc = xoff_of(g, vc);
+    if (xr < 0 || xc < 0) continue;
+    slot[k] = (int)mr.size();
+    mr.push_back({xr, vertex_dim(b.graphs[g]->vtype[vr]), xc, vertex_dim(b.graphs[g]->vtype[vc])});
+  }
+  std::fill(out, out + req.size() * 36, 0.0);
+  if (mr.empty()) return 0;
+  int rc;
+  if (!b.uploaded && (rc = batch_upload_estimates(b))) return rc;
+  if ((rc = chol_set_active(b, nullptr))) return rc;   // a stale compaction (an optimise that failed half way) must not leave graphs out
+  const size_t lm_bytes = sizeof(LmState) * (size_t)b.V.B;
+  if (!b.d_lm_save && (rc = dev_alloc(b, (size_t)b.V.B, &b.d_lm_save, false))) return rc;
+  SSLAM_HIP_TRY(hipMemcpyAsync(b.d_lm_save, b.V.lm, lm_bytes, hipMemcpyDeviceToDevice, b.stream));
+  struct Restore {   // the LM states go back on every return path
+    Batch& b; size_t bytes;
+    ~Restore() { (void)hipMemcpyAsync(b.V.lm, b.d_lm_save, bytes, hipMemcpyDeviceToDevice, b.stream); (void)hipStreamSynchronize(b.stream); b.harvest(); }
+  } restore{b, lm_bytes};
+  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
+  hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
+  if ((rc = batch_linearize(b))) return rc;   // undamped H at the current estimates
+  hipLaunchKernelGGL(k_set_trial_all, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, 0.0);
+  if (!b.chol && (rc = chol_plan_build(b))) return rc;
+  if ((rc = chol_plan_flow(b) ? chol_factor_flat_flow(b) : chol_factor_and_forward(b, /*flat=*/true))) return rc;
+  std::vector<int> fail((size_t)b.V.B, 0);
+  if ((rc = read_device(b, fail.data(), b.V.pcg_fail, fail.size() * sizeof(int)))) return rc;
+  if ((rc = chol_flow_check(b))) return rc;
+  for (int g = 0; g < b.V.B; ++g)
+    if (fail[g]) return set_error(SSLAM_ERR_NUMERIC, "H of graph %d of the batch is not positive definite: no marginals", g);
+  std::vector<double> Z(mr.size() * 36);
+  if ((rc = chol_marginal_blocks(b, mr, Z.data()))) return rc;
+  for (size_t k = 0; k < req.size(); ++k)
+    if (slot[k] >= 0) std::copy(Z.begin() + (size_t)slot[k] * 36, Z.begin() + (size_t)slot[k] * 36 + 36, out + k * 36);
+  return 0;
+}
+
+int sslam_batch_marginals(sslam_batch* h, const int32_t* req, int n, double* out) {
+  if (!h || n < 0 || (n > 0 && (!req || !out))) return set_error(SSLAM_ERR_INVALID, "null argument");
+  int rc = batch_check(h);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  const bool group = !h->parts.empty();
+  const int K = group ? (int)h->parts.size() : 1;
+  const int ng = group ? h->part0.back() : (int)h->b.graphs.size();
+  auto part_batch = [&](int k) -> Batch& { return group ? h->parts[k]->b : h->b; };
+  // every request is checked before anything runs: a bad one leaves out_blocks unwritten
+  std::vector<std::vector<std::array<int, 3>>> preq(K);
+  std::vector<std::vector<int>> psrc(K);
+  std::vector<int> dr(n), dc(n);
+  for (int k = 0; k < n; ++k) {
+    const int g = req[3 * k], vr = req[3 * k + 1], vc = req[3 * k + 2];
+    if (g < 0 || g >= ng) return set_error(SSLAM_ERR_INVALID, "request %d: graph index %d out of range (the batch holds %d graphs)", k, g, ng);
+    int p = 0;
+    if (group) p = (int)(std::upper_bound(h->part0.begin(), h->part0.end(), g) - h->part0.begin()) - 1;
+    const int gl = group ? g - h->part0[p] : g;
+    const HostGraph& G = *part_batch(p).graphs[gl];
+    if (vr < 0 || vr >= G.nv() || vc < 0 || vc >= G.nv()) return set_error(SSLAM_ERR_INVALID, "request %d: bad vertex id (%d, %d) in graph %d", k, vr, vc, g);
+    dr[k] = vertex_dim(G.vtype[vr]); dc[k] = vertex_dim(G.vtype[vc]);
+    preq[p].push_back({gl, vr, vc});
+    psrc[p].push_back(k);
+  }
+  // the parts of a stream group one after the other, from the calling thread
+  std::vector<std::vector<double>> pz(K);
+  auto run = [&](int p) { pz[p].resize(preq[p].size() * 36 + 1); return batch_marginals(part_batch(p), preq[p], pz[p].data()); };
+  if (group) rc = for_each_part(h, false, [&](sslam_batch*, int p) { return run(p); });
+  else rc = run(0);
+  if (rc) return rc;
+  std::vector<size_t> off(n + 1, 0);
+  for (int k = 0; k < n; ++k) off[k + 1] = off[k] + (size_t)dr[k] * dc[k];
+  for (int p = 0; p < K; ++p)
+    for (size_t i = 0; i < psrc[p].size(); ++i) {
+      const int k = psrc[p][i];
+      std::copy(pz[p].begin() + i * 36, pz[p].begin() + i * 36 + (size_t)dr[k] * dc[k], out + off[k]);
+    }
+  return 0;
+}
 // ---- edge-sharded mode (SURVEY 8e mode E; BASELINE.json configs[4]): the edges of every graph of the batch are split
 //      contiguously over the ranks, each rank builds the partial normal equations of its edges, ONE RCCL all-reduce of the
 //      contiguous [H || b] buffer sums them, and the rest of the LM step runs replicated.
@@ -2726,11 +2823,12 @@ int sslam_batch_info(sslam_batch* h, const char* key, double* value) {
   Batch& b = h->b;
   const std::string k(key);
   int rc;
-  if ((k == "factor_lnz" || k == "factor_levels" || k == "factor_launches" || k == "factor_bytes") && !b.chol && (rc = chol_plan_build(b))) return rc;
+  if ((k == "factor_lnz" || k == "factor_levels" || k == "factor_launches" || k == "factor_front" || k == "factor_bytes") && !b.chol && (rc = chol_plan_build(b))) return rc;
   const double dim = 6.0 * b.V.nPr + 3.0 * b.V.nLr;
   if (k == "factor_lnz") *value = (double)chol_plan_lnz(b);
   else if (k == "factor_levels") *value = (double)chol_plan_levels(b);
   else if (k == "factor_launches") *value = (double)chol_plan_launches(b);
+  else if (k == "factor_front") *value = chol_plan_front(b) ? 1.0 : 0.0;
   else if (k == "h_doubles") *value = (double)b.V.h_total;
   else if (k == "dim") *value = dim;
   else if (k == "allreduce_calls") *value = (double)b.allreduce_calls;

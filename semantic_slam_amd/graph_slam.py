@@ -348,6 +348,50 @@ class GraphBatch:
         _check(self._lib, self._lib.sslam_batch_optimize(self._h, max_iterations, st))
         return list(st)
 
+    # -- covariances -----------------------------------------------------------------------------
+    def _request_array(self, requests) -> np.ndarray:
+        """(graph, row vertex, column vertex) triples -> [n, 3] int32, checked against the host graphs before any C call"""
+        rows = []
+        for k, rq in enumerate(requests):
+            try:
+                g, vr, vc = rq
+            except (TypeError, ValueError):
+                raise ValueError(f"request {k}: expected (graph, row_vertex, col_vertex), got {rq!r}") from None
+            for x in (g, vr, vc):
+                if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                    raise TypeError(f"request {k}: graph index and vertex ids are integers, got {rq!r}")
+            if not 0 <= g < len(self.graphs):
+                raise IndexError(f"request {k}: graph index {g} out of range (the batch holds {len(self.graphs)} graphs)")
+            rows.append((int(g), int(vr), int(vc)))
+        return np.ascontiguousarray(rows, np.int32).reshape(-1, 3)
+
+    def marginals(self, requests):
+        """sslam_batch_marginals: blocks of H^-1 at the estimates the batch holds on the device.  ``requests`` is a sequence of
+        (graph, row_vertex, col_vertex); returns the d(row) x d(col) arrays in request order."""
+        req = self._request_array(requests)
+        dims = []
+        for k, (g, vr, vc) in enumerate(req):
+            G = self.graphs[g]
+            nv = G.num_vertices()
+            if not (0 <= vr < nv and 0 <= vc < nv):
+                raise IndexError(f"request {k}: vertex ids ({vr}, {vc}) out of range (graph {g} has {nv} vertices)")
+            dims.append(tuple(6 if len(G.estimate(int(v))) == 7 else 3 for v in (vr, vc)))
+        out = np.zeros(int(sum(a * b for a, b in dims)) + 1)
+        _check(self._lib, self._lib.sslam_batch_marginals(self._h, req.ctypes.data_as(C.POINTER(C.c_int32)), len(req), _dptr(out)))
+        blocks, o = [], 0
+        for a, b in dims:
+            blocks.append(out[o:o + a * b].reshape(a, b).copy())
+            o += a * b
+        return blocks
+
+    def landmark_marginals(self, ids_per_graph):
+        """diagonal blocks of H^-1 for the listed vertices of every graph: ``ids_per_graph[g]`` -> list of blocks, one list per graph"""
+        ids_per_graph = [list(ids) for ids in ids_per_graph]
+        if len(ids_per_graph) != len(self.graphs):
+            raise ValueError(f"one id list per graph: got {len(ids_per_graph)} lists for {len(self.graphs)} graphs")
+        blocks = iter(self.marginals([(g, v, v) for g, ids in enumerate(ids_per_graph) for v in ids]))
+        return [[next(blocks) for _ in ids] for ids in ids_per_graph]
+
     # -- edge-sharded mode (SURVEY 8e mode E) ----------------------------------------------------
     def comm_init(self, unique_id: bytes, rank: int, world: int) -> None:
         """RCCL communicator + edge shard of this rank (every rank holds the whole batch); see distributed.init_edge_sharded."""
