@@ -51,7 +51,7 @@ struct ColMeta { int xoff, yoff, dim, graph, b0, nb, nbi, base, f0, f1, piece, i
 // xoff: offset in the unknown vector (internal row order); yoff: offset in elimination order (the forward-substituted
 // rhs y lives in that order so that a piece's y is contiguous); blocks [b0, b0 + nb), diagonal first, the first nbi
 // (diagonal included) have their row inside the column's own piece; base = Lval offset of the diagonal block;
-// [f0, f1) = the blocks of ROW j (FwdMeta), for the forward substitution of the multi right-hand-side solves
+// [f0, f1) = the blocks of ROW j (FwdMeta): a host table (sslam_debug_plan), no kernel reads it
 
 struct BlkMeta { int off, src, xoff_row, yoff_row, coldiag, colyoff, info, as0; };
 // off: Lval offset; src: H offset or -1; x / y offsets of the block's row; Lval offset of the diagonal block and y offset of
@@ -124,7 +124,7 @@ struct PieceMeta { int graph, c0, nc, b0, nb, lbase, lsize, y0, ysize, ilv0, nil
 // update matrix: U items [uit0, +nuit), split U blocks [umb0, +numb), their update records [uu0, +nuu) and child sources [us0, +nus)
 // (UItem.u0 / .s0 and UMb.s0 are relative to uu0 / us0: the per-depth kernels stage these records in LDS as well)
 
-// Factor storage of a piece.  Flat form (LDS, and HBM when CholView::flat_L is set for the multi right-hand-side kernels): the
+// Factor storage of a piece.  Flat form (LDS, and HBM when CholView::flat_L is set for the marginals kernel): the
 // piece's blocks sorted by size class, [n36 blocks of 36 doubles | n18 of 18 | the rest of 10], each block row-major.  HBM form of
 // the LM loop: every class transposed -- element k of the i-th block of a class at  class start + k * (blocks in the class) + i --
 // so that the backward substitution, which runs one thread per block and touches every element once, reads with consecutive lanes
@@ -274,7 +274,7 @@ struct CholHost {
   std::vector<ILevel> ilv; std::vector<PieceMeta> piece;
   std::vector<AsmSrc> asrc, usrc; std::vector<FwdMeta> fwd; std::vector<UItem> uitem; std::vector<UMb> umb;
   std::vector<RCol> rcol; std::vector<UpdMeta> rupd;   // right-looking update lists of the tail pieces, [ncol] and per piece
-  std::vector<int> lvl_ptr, lvl_cols;       // column levels of the elimination tree (multi right-hand-side solves)
+  std::vector<int> lvl_ptr, lvl_cols;       // column levels of the elimination tree: host tables (sslam_debug_plan), no kernel reads them
   std::vector<int> plv_ptr, plv_pieces;     // pieces grouped by depth (one launch each)
   std::vector<PieceMeta> lpiece;            // piece records in launch order: plv_pieces then tail_pieces (one dependent load less per workgroup)
   std::vector<int> tail_ptr, tail_pieces;   // per graph: its tail pieces in elimination order
@@ -755,7 +755,7 @@ inline int chol_symbolic(const SymIn& in, CholOpts opt, CholHost& out) {
     }
   }
   SSLAM_PT("blocks")
-  // ---- levels of the block elimination tree (multi right-hand-side solves) and inside the pieces --------------------------
+  // ---- levels of the block elimination tree and inside the pieces ---------------------------------------------------------
   std::vector<int> level(ncol, 0), col_il(ncol, 0);
   int nlev = 0;
   for (int j = 0; j < ncol; ++j) {

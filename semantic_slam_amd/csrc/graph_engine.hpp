@@ -138,7 +138,7 @@ struct Batch {
   bool has_planes = false;
   std::vector<int> dup_eo, dup_el;
   int max_row_slots = 0;
-  CholPlan* chol = nullptr;    // piece plan (chol_plan.hpp): multi right-hand-side solves of the marginals; SSLAM_CHOL_LEGACY=1: the LM loop too
+  CholPlan* chol = nullptr;    // piece plan (chol_plan.hpp) of the direct solvers: the LM loop and the flat factor of the marginals
   // edge-sharded mode
   bool sharded = false;        // linearize only the edges of this rank's range
   void* comm = nullptr;        // ncclComm_t (RCCL), or null: partial systems are left unsummed (single-device tests)
@@ -241,7 +241,6 @@ int chol_set_active(Batch& b, const std::vector<char>* active);   // LM endgame:
 int64_t chol_plan_lnz(const Batch& b);
 int chol_plan_levels(const Batch& b);
 bool chol_plan_front(const Batch& b);       // the factorisation runs the front kernels (front_kernels.hpp)
-int chol_solve_multi(Batch& b, const double* rhs_host, int nrhs, double* x_host);  // uses the last factorisation
 bool chol_plan_flow(const Batch& b);        // the plan runs factor + both solves in one dependency-driven launch (small batches)
 int chol_solve_flow(Batch& b);              // (H + lambda I) dx = b for in_trial graphs -> V.x, one launch
 int chol_lm_step_flow(Batch& b, int max_iters);   // begin step + one-launch solve + update / chi2 / accept-reject / commit: 3 launches per damping trial
@@ -253,7 +252,6 @@ int chol_spec_mode(const Batch& b);               // 0 off, 1 adaptive (lanes jo
 int chol_lm_step_spec(Batch& b, int max_iters);   // one LM iteration: up to ten speculative trials + the accept / reject replay
 int chol_factor_flat_flow(Batch& b);        // flat factor (marginals) through the single launch
 int chol_flow_check(Batch& b);              // error flag of that launch (synchronises the stream)
-int chol_marginal_diag(Batch& b, const std::vector<int>& xoff, const std::vector<int>& dims, double* out36);  // diagonal blocks of H^-1 along the tree paths, one launch
 struct MarginalReq { int xoff_u, dim_u, xoff_v, dim_v; };   // first unknown (internal row order) and dimension of the row / column vertex; xoff_v == xoff_u: a diagonal block
 int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double* out36);   // blocks Z(u, v) of H^-1 for pairs of vertices of a batch, paths of any length
 

@@ -7,7 +7,7 @@
 //                          external updates from HBM, internal levels out of LDS, one coalesced write of L and y
 //   k_chol_tail<NT>        one workgroup per graph walks the top pieces of its tree in elimination order
 //   k_chol_back_pieces / k_chol_back_tail   the same pieces top-down for x = L^-T y
-//   k_chol_forward_level / k_chol_backward_level<Q>   level-scheduled multi right-hand-side solves (marginals)
+//   k_chol_marginal_pairs<SCRATCH>   blocks of H^-1 along elimination-tree paths of the flat factor (marginals)
 // Everything is gather-form: every L entry is written by exactly one thread, sums run in a fixed order -> bitwise
 // repeatable.  Forward substitution is fused into the factorisation (b rides along as an extra row of the diagonal block).
 //   k_front_pieces / k_front_tail (front_kernels.hpp, round 6)   the same pieces through the front tables of front_plan.hpp: the default of batches >= 32
@@ -45,8 +45,6 @@ struct CholView {
   const UMb* umb;
   const RCol* rcol;         // tail pieces, right-looking form: per column, its internal updates of later blocks of the piece ...
   const UpdMeta* rupd;      // ... (UpdMeta's right-looking form); nullptr: target-major items
-  const FwdMeta* fwd;       // blocks of every row (multi right-hand-side forward substitution)
-  const int* lvl_cols;      // columns grouped by level of the elimination tree
   const int* plv_pieces;    // pieces grouped by depth
   const int* tail_ptr;      // [B + 1]
   const int* tail_pieces;
@@ -56,7 +54,7 @@ struct CholView {
   int* fail;                // [B]
   const unsigned* fblob;    // front tables (front_plan.hpp): the blobs, and per launch-order piece where its blob is; nullptr: record plan only
   const FrontGrp* lfgrp;
-  int flat_L;               // 1: the factor is written in flat form (multi right-hand-side kernels); 0: class-interleaved (LM loop)
+  int flat_L;               // 1: the factor is written in flat form (marginals kernel); 0: class-interleaved (LM loop)
   long long* dbg;           // SSLAM_CHOL_STAMPS: shader-clock totals per phase of workgroup 0 ([16] tail kernel, [16] per-depth kernels)
 };
 
@@ -83,7 +81,7 @@ struct SpecLanes {
 struct CholPlan {
   CholView C{};
   SpecLanes spec{};
-  std::vector<int> lvl_ptr, plv_ptr, plv_lds_f, plv_lds_b, plv_nt, plv_cls;
+  std::vector<int> plv_ptr, plv_lds_f, plv_lds_b, plv_nt, plv_cls;
   std::vector<int> plv_lds_ff;  // front kernels (front_kernels.hpp): LDS doubles per launch; front: the per-depth launches run them
   int tail_lds_ff = 0;
   bool front = false;
@@ -97,9 +95,6 @@ struct CholPlan {
   int* d_idx = nullptr;         // [pieces of the active graphs, launch by launch | active graphs that have a tail]
   size_t idx_cap = 0;
   bool compact = false;
-  double* d_multi_y = nullptr;  // scratch for multi-rhs solves
-  double* d_multi_x = nullptr;
-  int multi_cap = 0;
   // dependency-driven factorisation + solve in ONE launch (k_chol_flow): small batches only
   bool flow = false;            // the plan can run it (every piece has one parent piece; nt_leaf == nt_tail)
   int flow_grid = 0;            // persistent workgroups
@@ -112,7 +107,7 @@ struct CholPlan {
   int spec_epoch = 0;           // rounds of the speculative lanes (k_chol_spec_round)
   int2* d_dep = nullptr;        // per launch-order piece: {parent (launch order) or -1, children}
   int* d_flow = nullptr;        // [children done | backward done | forward done] per piece, then [0] error flag at 3 * npiece
-  // marginals along the elimination-tree paths (k_chol_marginal_paths)
+  // marginals along the elimination-tree paths (k_chol_marginal_pairs)
   std::vector<int> h_cparent;   // parent column in the elimination tree, -1: root
   std::vector<int> h_xoff_col;  // offset in the unknown vector (internal row order) -> column, -1 elsewhere
   int* d_mpath = nullptr;       // [path_ptr | dims | path columns] of a request
@@ -146,8 +141,6 @@ void chol_plan_free(CholPlan* p) {
   }
   for (void* a : p->allocs) (void)hipFree(a);
   if (p->d_idx) (void)hipFree(p->d_idx);
-  if (p->d_multi_y) (void)hipFree(p->d_multi_y);
-  if (p->d_multi_x) (void)hipFree(p->d_multi_x);
   if (p->d_mpath && !p->arena) (void)hipFree(p->d_mpath);
   if (p->d_mout && !p->arena) (void)hipFree(p->d_mout);
   if (p->d_mscratch && !p->arena) (void)hipFree(p->d_mscratch);
@@ -1067,179 +1060,15 @@ __global__ __launch_bounds__(NT) void k_chol_back_tail(CholView C, const double*
 }
 
 // ------------------------------------------------------------------------------------------------
-// level-scheduled multi right-hand-side solves on the finished factor (marginals): blockIdx.y = right-hand side
-// ------------------------------------------------------------------------------------------------
-// forward: y_j = L_jj^-1 (b_j - sum_k L_jk y_k); rhs in internal row order, y in elimination order
-__global__ __launch_bounds__(64) void k_chol_forward_level(CholView C, int lvl_begin, const double* __restrict__ rhs, double* __restrict__ y) {
-  __shared__ double t[8];
-  const int j = C.lvl_cols[lvl_begin + blockIdx.x];
-  const ColMeta cm = C.col[j];
-  const size_t vo = (size_t)blockIdx.y * C.dim;
-  const int lane = threadIdx.x;
-  const int dj = cm.dim;
-  const double* __restrict__ L = C.Lval;
-  if (lane < dj) {
-    double a = rhs[vo + cm.xoff + lane];
-    for (int u = cm.f0; u < cm.f1; ++u) {   // the blocks of row j, ascending k
-      const FwdMeta fm = C.fwd[u];
-      const int dk = fm.off < 0 ? 6 : 3;
-      const double* pa = L + (fm.off & 0x7FFFFFFF) + lane * dk;
-      const double* yk = y + vo + fm.yoff;
-      for (int q = 0; q < dk; ++q) a -= pa[q] * yk[q];
-    }
-    t[lane] = a;
-  }
-  __syncthreads();
-  if (lane == 0) {
-    const double* D = L + cm.base;
-    for (int r = 0; r < dj; ++r) {
-      double a = t[r];
-      for (int s = 0; s < r; ++s) a -= D[r * dj + s] * t[s];
-      t[r] = a / D[r * dj + r];
-    }
-    for (int r = 0; r < dj; ++r) y[vo + cm.yoff + r] = t[r];
-  }
-}
-
-// backward substitution of one column by a team of 8 * Q lanes:   x_j = L_jj^-T (y_j - sum_i L_ij^T x_i)
-template <int Q>
-__device__ __forceinline__ void chol_backward_column(const CholView& C, const int j, const double* __restrict__ y, double* x,
-                                                     const size_t vo, const int lt) {
-  const int c = lt & 7, q = lt >> 3;
-  const ColMeta cm = C.col[j];
-  const int dj = cm.dim;
-  const double* __restrict__ L = C.Lval;
-  const int cc = min(c, dj - 1);
-  const double* D = L + cm.base;
-  double acc = 0;
-  for (int bi = 1 + q; bi < cm.nb; bi += Q) {
-    const BlkMeta bm = C.blk[cm.b0 + bi];
-    const double* Bk = L + bm.off + cc;
-    const double* xi = x + vo + bm.xoff_row;
-    double s = Bk[0] * xi[0] + Bk[dj] * xi[1] + Bk[2 * dj] * xi[2];
-    if ((bm.info & 15) == 6) s += Bk[3 * dj] * xi[3] + Bk[4 * dj] * xi[4] + Bk[5 * dj] * xi[5];
-    acc += s;
-  }
-  if (Q > 1) acc += __shfl_xor(acc, 8, 64);
-  if (Q > 2) acc += __shfl_xor(acc, 16, 64);
-  if (Q > 4) acc += __shfl_xor(acc, 32, 64);
-  double t = y[vo + cm.yoff + cc] - acc;
-#pragma unroll
-  for (int r = 5; r >= 0; --r) {
-    const int rr = min(r, dj - 1);
-    const double drr = D[rr * dj + rr], drc = D[rr * dj + cc];
-    const double xr = __shfl(t, rr, 8) / drr;
-    if (r < dj) {
-      if (c == r) t = xr;
-      else if (c < r) t -= drc * xr;
-    }
-  }
-  if (q == 0 && c < dj) x[vo + cm.xoff + c] = t;
-}
-
-template <int Q>
-__global__ __launch_bounds__(64) void k_chol_backward_level(CholView C, int lvl_begin, int n, const double* __restrict__ y, double* x) {
-  constexpr int kCols = 8 / Q;
-  const int p = blockIdx.x * kCols + threadIdx.x / (8 * Q);
-  const int j = C.lvl_cols[lvl_begin + min(p, n - 1)];
-  if (p < n) chol_backward_column<Q>(C, j, y, x, (size_t)blockIdx.y * C.dim, threadIdx.x % (8 * Q));
-}
-
-// ------------------------------------------------------------------------------------------------
-// Diagonal blocks of H^-1 = (L L^T)^-1 for a list of vertices in ONE launch (computeLandmarkMarginals, reference
-// src/ps_graph_slam/graph_slam.cpp:221-234 -> g2o MarginalCovarianceCholesky).  Z(v,v) = E_v^T L^-T L^-1 E_v = Y^T Y with Y = L^-1 E_v,
-// and Y is non-zero only on the PATH from v's column to the root of the elimination tree; every off-diagonal block of a column on that
-// path has its row further up the same path (struct(k) is a subset of the ancestors of k).  One wave per vertex walks its path bottom-up
-// with a right-looking forward substitution held in LDS: finalise Y_s = L_ss^-1 acc_s, then every block (i, path[s]) of the column
-// subtracts L(i, s) Y_s from acc_i -- one lane per block, distinct rows, no conflicts, fixed order.  Work O(path^2) per vertex instead of
-// two triangular solves over the whole factor per right-hand side column (round 3: 2 x levels launches, 3 N_l right-hand sides and the
-// whole solution matrix over PCIe).  Needs the flat factor (chol_factor_and_forward(b, true)).
-// LDS: [Y: maxlen x 36 | diagonal block 36 | path records: {first block, blocks, diagonal offset, dim | yoff << 8} maxlen x int4]
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_chol_marginal_paths(CholView C, const int* __restrict__ path_ptr, const int* __restrict__ req_dim,
-                                                            const int* __restrict__ path_cols, double* __restrict__ out, int maxlen) {
-  extern __shared__ double sm[];
-  const int r = blockIdx.x, lane = threadIdx.x;
-  const int p0 = path_ptr[r], P = path_ptr[r + 1] - p0, D = req_dim[r];
-  double* Y = sm;
-  double* sD = Y + (size_t)maxlen * 36;
-  int4* prec = reinterpret_cast<int4*>(sD + 36);
-  int* pyoff = reinterpret_cast<int*>(prec + maxlen);
-  const double* __restrict__ L = C.Lval;
-  for (int t = lane; t < P; t += 64) {
-    const ColMeta cm = C.col[path_cols[p0 + t]];
-    prec[t] = make_int4(cm.b0, cm.nb, cm.base, cm.dim);
-    pyoff[t] = cm.yoff;
-  }
-  for (int e = lane; e < P * 36; e += 64) Y[e] = 0.0;
-  __syncthreads();
-  if (lane < D) Y[lane * 6 + lane] = 1.0;   // E_v: identity in the vertex' own rows (path entry 0)
-  __syncthreads();
-  for (int s = 0; s < P; ++s) {
-    const int4 pr = prec[s];
-    const int da = pr.w;
-    if (lane < da * da) sD[lane] = L[pr.z + lane];
-    __syncthreads();
-    if (lane < D) {   // one lane per right-hand side column: Y_s = L_ss^-1 acc_s
-      double yv[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        if (i < da) {
-          double a = Y[s * 36 + i * 6 + lane];
-#pragma unroll
-          for (int m = 0; m < 6; ++m) if (m < i) a -= sD[i * da + m] * yv[m];
-          yv[i] = a / sD[i * da + i];
-          Y[s * 36 + i * 6 + lane] = yv[i];
-        }
-      }
-    }
-    __syncthreads();
-    for (int bq = lane; bq < pr.y - 1; bq += 64) {   // the blocks below the diagonal: acc_t -= L(t, s) Y_s
-      const BlkMeta bm = C.blk[pr.x + 1 + bq];
-      const int di = bm.info & 15;
-      int lo = s + 1, hi = P - 1;                    // the row's place on the path (y offsets ascend along it)
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (pyoff[mid] < bm.yoff_row) lo = mid + 1; else hi = mid; }
-      const double* Lb = L + bm.off;
-      double* acc = Y + lo * 36;
-      for (int i = 0; i < di; ++i) {
-        double lrow[6];
-#pragma unroll
-        for (int m = 0; m < 6; ++m) lrow[m] = m < da ? Lb[i * da + m] : 0.0;
-        for (int c = 0; c < D; ++c) {
-          double a = 0;
-#pragma unroll
-          for (int m = 0; m < 6; ++m) a += lrow[m] * Y[s * 36 + m * 6 + c];   // rows >= da of Y_s are zero
-          acc[i * 6 + c] -= a;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (lane < D * D) {
-    const int rr = lane / D, cc = lane - rr * D;
-    double z = 0;
-    for (int t = 0; t < P; ++t)
-#pragma unroll
-      for (int i = 0; i < 6; ++i) z += Y[t * 36 + i * 6 + rr] * Y[t * 36 + i * 6 + cc];
-    out[(size_t)r * 36 + lane] = z;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Blocks Z(u, v) of H^-1 for (row vertex, column vertex) PAIRS of the graphs of a batch (sslam_batch_marginals), diagonal or not, and for
-// paths of any length.  Z(u, v) = E_u^T L^-T L^-1 E_v = Y_u^T Y_v with Y_w = L^-1 E_w, and Y_w lives on the path of w's column to the root of
-// the elimination tree: the product runs over the columns the two paths share -- in a tree their common suffix, from the lowest common
-// ancestor to the root (none when u and v lie in different components: zeros).  One wave per request: the forward substitution of
-// k_chol_marginal_paths along path(u) -- the same operations in the same order -- then, for u != v, along path(v), then the sum over the
-// suffix.  A request with u == v keeps ONE Y (the whole LDS budget for its one path) and is the arithmetic of k_chol_marginal_paths.
-// SCRATCH = false: Y and the path records in LDS [diagonal block 36 | Y: ylen x 36 | records ylen x int4 | y offsets ylen x int].
-// SCRATCH = true: the same three arrays in the request's slice of a device buffer (req[7], in units of 16 bytes), for paths that LDS does
-// not hold; only the diagonal block stays in LDS.  Same body, same order of operations: the two placements agree bitwise.  The wave is the
-// whole workgroup, its lanes hand Y to one another between the phases of a step: the workgroup-scope release / acquire of __syncthreads()
-// orders plain global stores and loads of one workgroup as it orders LDS (its waves share the CU's L1; the compiler waits for the stores
-// before the barrier).
-// req: 8 ints per request {first entry of path(u) in path_cols, its length, the same for path(v) (length 0: u == v), d(u), d(v), length of
-// the common suffix, scratch slice}.  out: [requests][36], the leading d(u) x d(v) entries row-major.
+// Blocks of H^-1 = (L L^T)^-1 along elimination-tree paths (computeLandmarkMarginals, reference src/ps_graph_slam/graph_slam.cpp:221-234
+// -> g2o MarginalCovarianceCholesky; sslam_batch_marginals).  Z(w, w) = E_w^T L^-T L^-1 E_w = Y^T Y with Y = L^-1 E_w, and Y is non-zero
+// only on the PATH from w's column to the root of the elimination tree; every off-diagonal block of a column on that path has its row
+// further up the same path (struct(k) is a subset of the ancestors of k).  marginal_path_forward: one wave walks the path bottom-up with a
+// right-looking forward substitution: finalise Y_s = L_ss^-1 acc_s, then every block (i, path[s]) of the column subtracts L(i, s) Y_s from
+// acc_i -- one lane per block, distinct rows, no conflicts, fixed order.  Work O(path^2) per vertex instead of two triangular solves over
+// the whole factor per right-hand side column.  Needs the flat factor (chol_factor_and_forward(b, true)).
+// cols: the P columns of the path; D = d(w); Y: P x 36; sD: the diagonal block of a step, 36; prec: {first block, blocks, diagonal offset,
+// dim} P x int4; pyoff: y offsets P x int.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void marginal_path_forward(const CholView& C, const int* __restrict__ cols, int P, int D, double* Y, double* sD,
                                                       int4* prec, int* pyoff) {
@@ -1296,6 +1125,18 @@ __device__ __forceinline__ void marginal_path_forward(const CholView& C, const i
   }
 }
 
+// Z(u, v) for (row vertex, column vertex) PAIRS, diagonal or not, and for paths of any length.  Z(u, v) = Y_u^T Y_v: the product runs over
+// the columns the two paths share -- in a tree their common suffix, from the lowest common ancestor to the root (none when u and v lie
+// in different components: zeros).  One wave per request: marginal_path_forward along path(u), then, for u != v, along path(v), then the
+// sum over the suffix.  A request with u == v keeps ONE Y (the whole LDS budget for its one path).
+// SCRATCH = false: Y and the path records in LDS [diagonal block 36 | Y: ylen x 36 | records ylen x int4 | y offsets ylen x int].
+// SCRATCH = true: the same three arrays in the request's slice of a device buffer (req[7], in units of 16 bytes), for paths that LDS does
+// not hold; only the diagonal block stays in LDS.  Same body, same order of operations: the two placements agree bitwise.  The wave is the
+// whole workgroup, its lanes hand Y to one another between the phases of a step: the workgroup-scope release / acquire of __syncthreads()
+// orders plain global stores and loads of one workgroup as it orders LDS (its waves share the CU's L1; the compiler waits for the stores
+// before the barrier).
+// req: 8 ints per request {first entry of path(u) in path_cols, its length, the same for path(v) (length 0: u == v), d(u), d(v), length of
+// the common suffix, scratch slice}.  out: [requests][36], the leading d(u) x d(v) entries row-major.
 template <bool SCRATCH>
 __global__ __launch_bounds__(64) void k_chol_marginal_pairs(CholView C, const int* __restrict__ req, const int* __restrict__ path_cols,
                                                             double* __restrict__ out, int ylen, char* scratch) {
@@ -1800,7 +1641,7 @@ int chol_plan_build(Batch& b) {
   P->arena = b.arena;
   CholView& C = P->C;
   C.ncol = H.ncol; C.nlevels = H.nlevels; C.dim = H.dim; C.npiece = H.npiece;
-  P->lvl_ptr = H.lvl_ptr; P->plv_ptr = H.plv_ptr; P->plv_lds_f = H.plv_lds_f; P->plv_lds_b = H.plv_lds_b; P->plv_nt = H.plv_nt; P->plv_cls = H.plv_cls;
+  P->plv_ptr = H.plv_ptr; P->plv_lds_f = H.plv_lds_f; P->plv_lds_b = H.plv_lds_b; P->plv_nt = H.plv_nt; P->plv_cls = H.plv_cls;
   P->tail_lds_f = H.tail_lds_f; P->tail_lds_b = H.tail_lds_b; P->tail_total = (int)H.tail_pieces.size(); P->nt_tail = H.nt_tail; P->nt_ftail = H.nt_ftail; P->nt_bleaf = H.nt_bleaf; P->nt_bmid = H.nt_bmid; P->nt_btail = H.nt_btail; P->ustage = H.ustage;
   P->lnz = H.lnz;
   {   // elimination-tree parents (first block below the diagonal) and the vertex -> column map, for the path marginals
@@ -1852,8 +1693,6 @@ int chol_plan_build(Batch& b) {
       if ((rc = up_to_dev(*P, b.stream, H.rupd, &C.rupd))) return rc;
     }
   }
-  if ((rc = up_to_dev(*P, b.stream, H.fwd, &C.fwd))) return rc;
-  if ((rc = up_to_dev(*P, b.stream, H.lvl_cols, &C.lvl_cols))) return rc;
   if ((rc = up_to_dev(*P, b.stream, H.plv_pieces, &C.plv_pieces))) return rc;
   if ((rc = up_to_dev(*P, b.stream, H.tail_ptr, &C.tail_ptr))) return rc;
   if ((rc = up_to_dev(*P, b.stream, H.tail_pieces, &C.tail_pieces))) return rc;
@@ -2129,7 +1968,7 @@ int chol_solve_flow(Batch& b) {
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "cholesky flow launch: %s", hipGetErrorString(e));
   return 0;
 }
-// the flat factor (multi right-hand-side / path-marginal kernels) through the single launch: L only, no backward substitution
+// the flat factor (marginals kernel) through the single launch: L only, no backward substitution
 int chol_factor_flat_flow(Batch& b) {
   CholPlan& P = *b.chol;
   P.C.flat_L = 1;
@@ -2240,7 +2079,7 @@ int chol_set_active(Batch& b, const std::vector<char>* active) {
 
 int chol_factor_and_forward(Batch& b, bool flat) {
   CholPlan& P = *b.chol;
-  P.C.flat_L = flat ? 1 : 0;   // form of the factor in HBM: flat for the multi right-hand-side kernels, class-interleaved for chol_backward
+  P.C.flat_L = flat ? 1 : 0;   // form of the factor in HBM: flat for the marginals kernel, class-interleaved for chol_backward
   const CholView& C = P.C;
   ScopedTimer t(b, "factor");
   hipLaunchKernelGGL(k_chol_begin, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, C);
@@ -2323,91 +2162,6 @@ int chol_backward(Batch& b) {
   return 0;
 }
 
-// X = (L L^T)^-1 RHS for nrhs right-hand sides (host arrays, internal ordering, [nrhs][dim])
-int chol_solve_multi(Batch& b, const double* rhs_host, int nrhs, double* x_host) {
-  CholPlan& P = *b.chol;
-  const CholView& C = P.C;
-  if (nrhs <= 0) return 0;
-  if (!C.flat_L) return set_error(SSLAM_ERR_INVALID, "chol_solve_multi needs the flat factor (chol_factor_and_forward(b, true))");
-  const int chunk_max = std::max(1, std::min(nrhs, (int)std::min<int64_t>(4096, ((int64_t)1 << 30) / std::max(1, C.dim) / 8)));
-  if (P.multi_cap < chunk_max) {
-    if (P.d_multi_y) (void)hipFree(P.d_multi_y);
-    if (P.d_multi_x) (void)hipFree(P.d_multi_x);
-    SSLAM_HIP_TRY(hipMalloc((void**)&P.d_multi_y, (size_t)chunk_max * C.dim * sizeof(double)));
-    SSLAM_HIP_TRY(hipMalloc((void**)&P.d_multi_x, (size_t)chunk_max * C.dim * sizeof(double)));
-    P.multi_cap = chunk_max;
-  }
-  for (int r0 = 0; r0 < nrhs; r0 += chunk_max) {
-    const int nr = std::min(chunk_max, nrhs - r0);
-    const size_t bytes = (size_t)nr * C.dim * sizeof(double);
-    SSLAM_HIP_TRY(hipMemcpyAsync(P.d_multi_x, rhs_host + (size_t)r0 * C.dim, bytes, hipMemcpyHostToDevice, b.stream));
-    for (int l = 0; l < C.nlevels; ++l) {
-      const int n = P.lvl_ptr[l + 1] - P.lvl_ptr[l];
-      if (n > 0) hipLaunchKernelGGL(k_chol_forward_level, dim3(n, nr), dim3(64), 0, b.stream, C, P.lvl_ptr[l], (const double*)P.d_multi_x, P.d_multi_y);
-    }
-    for (int l = C.nlevels - 1; l >= 0; --l) {
-      const int n = P.lvl_ptr[l + 1] - P.lvl_ptr[l];
-      if (n > 0) hipLaunchKernelGGL(k_chol_backward_level<1>, dim3((n + 7) / 8, nr), dim3(64), 0, b.stream, C, P.lvl_ptr[l], n, (const double*)P.d_multi_y, P.d_multi_x);
-    }
-    SSLAM_HIP_TRY(hipMemcpyAsync(x_host + (size_t)r0 * C.dim, P.d_multi_x, bytes, hipMemcpyDeviceToHost, b.stream));
-    SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));
-  }
-  return 0;
-}
-
-// Z(v, v) of (L L^T)^-1 for the vertices whose unknowns start at xoff[k] (internal row order, dims[k] = 3 | 6), from the last FLAT
-// factorisation; out: [n][36], the leading dims[k]^2 entries row-major.  Returns SSLAM_ERR_UNSUPPORTED when a path does not fit the LDS of
-// one wave (the caller falls back to the multi right-hand-side solves).
-int chol_marginal_diag(Batch& b, const std::vector<int>& xoff, const std::vector<int>& dims, double* out) {
-  CholPlan& P = *b.chol;
-  const CholView& C = P.C;
-  const int n = (int)xoff.size();
-  if (n == 0) return 0;
-  if (!C.flat_L) return set_error(SSLAM_ERR_INVALID, "chol_marginal_diag needs the flat factor (chol_factor_and_forward(b, true))");
-  std::vector<int> hdr(2 * (size_t)n + 1, 0), cols;
-  int maxlen = 1;
-  for (int k = 0; k < n; ++k) {
-    int j = (xoff[k] >= 0 && xoff[k] < (int)P.h_xoff_col.size()) ? P.h_xoff_col[xoff[k]] : -1;
-    if (j < 0) return set_error(SSLAM_ERR_INVALID, "marginal of an unknown that is not the start of a block row");
-    hdr[k] = (int)cols.size();
-    for (; j >= 0; j = P.h_cparent[j]) cols.push_back(j);
-    maxlen = std::max(maxlen, (int)cols.size() - hdr[k]);
-    hdr[n + 1 + k] = dims[k];
-  }
-  hdr[n] = (int)cols.size();
-  const size_t lds = (size_t)maxlen * 36 * sizeof(double) + 36 * sizeof(double) + (size_t)maxlen * (sizeof(int4) + sizeof(int)) + 16;
-  if (lds > 60 * 1024) return SSLAM_ERR_UNSUPPORTED;
-  const size_t ints = hdr.size() + cols.size();
-  // scratch: out of the graph handle's arena when there is one (a plan is rebuilt every tick of the orchestrator: no hipMalloc / hipFree
-  // pair per tick), else the plan's own allocations
-  if (P.mpath_cap < ints) {
-    if (P.arena) { P.d_mpath = (int*)P.arena->take((ints + 1024) * sizeof(int), true); if (!P.d_mpath) return set_error(SSLAM_ERR_HIP, "device allocation failed"); }
-    else { if (P.d_mpath) (void)hipFree(P.d_mpath); P.d_mpath = nullptr; P.mpath_cap = 0; SSLAM_HIP_TRY(hipMalloc((void**)&P.d_mpath, (ints + 1024) * sizeof(int))); }
-    P.mpath_cap = ints + 1024;
-  }
-  if (P.mout_cap < (size_t)n * 36) {
-    if (P.arena) { P.d_mout = (double*)P.arena->take(((size_t)n * 36 + 1024) * sizeof(double), true); if (!P.d_mout) return set_error(SSLAM_ERR_HIP, "device allocation failed"); }
-    else { if (P.d_mout) (void)hipFree(P.d_mout); P.d_mout = nullptr; P.mout_cap = 0; SSLAM_HIP_TRY(hipMalloc((void**)&P.d_mout, ((size_t)n * 36 + 1024) * sizeof(double))); }
-    P.mout_cap = (size_t)n * 36 + 1024;
-  }
-  hdr.insert(hdr.end(), cols.begin(), cols.end());
-  // both copies through the page-locked staging buffer: [paths | results]
-  const size_t in_bytes = (hdr.size() * sizeof(int) + 7) & ~(size_t)7, out_bytes = (size_t)n * 36 * sizeof(double);
-  char* stage = b.pin->get(in_bytes + out_bytes);
-  const void* src = hdr.data();
-  void* dst = out;
-  if (stage) { memcpy(stage, hdr.data(), hdr.size() * sizeof(int)); src = stage; dst = stage + in_bytes; }
-  SSLAM_HIP_TRY(hipMemcpyAsync(P.d_mpath, src, hdr.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
-  hipLaunchKernelGGL(k_chol_marginal_paths, dim3(n), dim3(64), lds, b.stream, C, (const int*)P.d_mpath, (const int*)(P.d_mpath + n + 1),
-                     (const int*)(P.d_mpath + 2 * (size_t)n + 1), P.d_mout, maxlen);
-  SSLAM_HIP_TRY(hipMemcpyAsync(dst, P.d_mout, out_bytes, hipMemcpyDeviceToHost, b.stream));
-  SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // hdr is a local
-  if (stage) memcpy(out, stage + in_bytes, out_bytes);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "path marginals launch: %s", hipGetErrorString(e));
-  return 0;
-}
-
 // Z(u, v) of (L L^T)^-1 for pairs of vertices of the graphs of a batch (k_chol_marginal_pairs), from the last FLAT factorisation; out:
 // [n][36], the leading dim_u x dim_v entries row-major.  Any path length: a request whose Y fits the LDS budget (SSLAM_MARGINAL_LDS_BYTES,
 // read per call; default and ceiling 60 KB) runs out of LDS, every other one out of its slice of a device scratch buffer -- one upload, at
@@ -2424,7 +2178,8 @@ int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double*
   auto col_of = [&](int xo) { return (xo >= 0 && xo < (int)P.h_xoff_col.size()) ? P.h_xoff_col[xo] : -1; };
   for (const MarginalReq& rq : reqs)
     if (col_of(rq.xoff_u) < 0 || col_of(rq.xoff_v) < 0) return set_error(SSLAM_ERR_INVALID, "marginal of an unknown that is not the start of a block row");
-  // device scratch: out of the graph handle's arena when there is one, else the plan's own allocations (as chol_marginal_diag)
+  // device scratch: out of the graph handle's arena when there is one (a plan is rebuilt every tick of the orchestrator: no hipMalloc /
+  // hipFree pair per tick), else the plan's own allocations
   auto grow = [&](void** p, size_t& cap, size_t bytes) -> int {
     if (cap >= bytes) return 0;
     bytes += bytes / 4 + 4096;

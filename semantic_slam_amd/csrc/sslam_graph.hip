@@ -2232,17 +2232,64 @@ int sslam_graph_oplus(sslam_graph* h, const double* dx) {
   return batch_download_estimates(b);
 }
 
-// Blocks (row vertex vr, column vertex vc) of H^-1 at the current linearisation: the columns of H^-1 that belong to the
-// requested column vertices are computed (Cholesky: one multi right-hand-side solve; PCG: one solve per column) and the
-// requested row blocks are read out of them.  out: packed row-major d(vr) x d(vc) blocks, zeros for fixed / edge-less vertices.
+// First unknown of vertex v of graph g in the batch's internal row order, -1: fixed or without edges.
+static int vertex_xoff(const Batch& b, int g, int v) {
+  if (b.graphs[g]->vtype[v] == VT_SE3) { const int r = b.pose_row[b.v2pose[g][v]]; return r < 0 ? -1 : 6 * r; }
+  const int r = b.lm_row[b.v2lm[g][v]];
+  return r < 0 ? -1 : 6 * b.V.nPr + 3 * r;
+}
+
+// The flat factor of the undamped H of every graph of a linearised batch, what chol_marginal_blocks reads: through the single launch
+// where the plan has one, else the launches per depth.  *bad: the first graph whose H is not positive definite, -1: none.
+static int factor_undamped_flat(Batch& b, int* bad) {
+  int rc;
+  hipLaunchKernelGGL(k_set_trial_all, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, 0.0);
+  if (!b.chol && (rc = chol_plan_build(b))) return rc;
+  if ((rc = chol_plan_flow(b) ? chol_factor_flat_flow(b) : chol_factor_and_forward(b, /*flat=*/true))) return rc;
+  std::vector<int> fail((size_t)b.V.B, 0);
+  if ((rc = read_device(b, fail.data(), b.V.pcg_fail, fail.size() * sizeof(int)))) return rc;
+  if ((rc = chol_flow_check(b))) return rc;
+  *bad = -1;
+  for (int g = b.V.B - 1; g >= 0; --g) if (fail[g]) *bad = g;
+  return 0;
+}
+
+// Blocks (row vertex vr, column vertex vc) of H^-1 at the current linearisation.  Direct solvers: the undamped H is factored once, then one
+// wave per pair walks the elimination-tree paths of its two vertices (chol_marginal_blocks) -- no right-hand side matrix, no backward
+// solve, and only the requested blocks cross PCIe.  PCG: the columns of H^-1 that belong to the requested column vertices are solved for
+// one by one and the requested row blocks are read out of them.
+// out: packed row-major d(vr) x d(vc) blocks, zeros for fixed / edge-less vertices.
 static int marginal_blocks(sslam_graph* h, const std::vector<std::pair<int, int>>& pairs, double* out) {
   int rc;
   if ((rc = do_linearize(h))) return rc;  // undamped H at the current estimates
   Batch& b = *h->batch;
-  std::vector<int> hidx;
-  const int dim = hessian_indices(h->g, hidx);
   for (auto& pr : pairs)
     if (pr.first < 0 || pr.first >= h->g.nv() || pr.second < 0 || pr.second >= h->g.nv()) return set_error(SSLAM_ERR_INVALID, "bad vertex id (%d, %d)", pr.first, pr.second);
+  if (h->g.opt.solver != 0) {
+    int bad;
+    if ((rc = factor_undamped_flat(b, &bad))) return rc;
+    if (bad >= 0) return set_error(SSLAM_ERR_NUMERIC, "H is not positive definite: no marginals");
+    std::vector<MarginalReq> mr;
+    std::vector<int> slot(pairs.size(), -1);
+    for (size_t k = 0; k < pairs.size(); ++k) {
+      const int vr = pairs[k].first, vc = pairs[k].second;
+      const int xr = vertex_xoff(b, 0, vr), xc = vertex_xoff(b, 0, vc);
+      if (xr < 0 || xc < 0) continue;
+      slot[k] = (int)mr.size();
+      mr.push_back({xr, vertex_dim(h->g.vtype[vr]), xc, vertex_dim(h->g.vtype[vc])});
+    }
+    std::vector<double> Z(mr.size() * 36 + 1);
+    if ((rc = chol_marginal_blocks(b, mr, Z.data()))) return rc;
+    size_t o = 0;
+    for (size_t k = 0; k < pairs.size(); ++k) {
+      const int n = vertex_dim(h->g.vtype[pairs[k].first]) * vertex_dim(h->g.vtype[pairs[k].second]);
+      for (int e = 0; e < n; ++e) out[o + e] = slot[k] < 0 ? 0.0 : Z[(size_t)slot[k] * 36 + e];
+      o += (size_t)n;
+    }
+    return 0;
+  }
+  std::vector<int> hidx;
+  const int dim = hessian_indices(h->g, hidx);
   // unique column vertices, their scalar columns
   std::vector<int> colv;
   for (auto& pr : pairs) if (hidx[pr.second] >= 0 && hidx[pr.first] >= 0) colv.push_back(pr.second);
@@ -2252,78 +2299,21 @@ static int marginal_blocks(sslam_graph* h, const std::vector<std::pair<int, int>
   int nrhs = 0;
   for (int v : colv) { col0[v] = nrhs; nrhs += vertex_dim(h->g.vtype[v]); }
   const size_t idim = (size_t)6 * b.V.nPr + (size_t)3 * b.V.nLr;
-  std::vector<double> X;   // [scalar column][g2o order]; sized when the general path is taken (11 MB at 450 keyframes: not for the path marginals)
+  std::vector<double> X((size_t)nrhs * dim);   // [scalar column][g2o order]
   std::vector<double> rhs_g2o(dim, 0.0), rhs_int, xi(idim);
-  if (h->g.opt.solver != 0) {
-    // factor the undamped H once, then solve all unit right-hand sides together
-    hipLaunchKernelGGL(k_set_trial_all, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, 0.0);
-    if (!b.chol && (rc = chol_plan_build(b))) return rc;
-    if ((rc = chol_plan_flow(b) ? chol_factor_flat_flow(b) : chol_factor_and_forward(b, /*flat=*/true))) return rc;
-    int fail = 0;
-    SSLAM_HIP_TRY(hipMemcpyAsync(&fail, b.V.pcg_fail, sizeof fail, hipMemcpyDeviceToHost, b.stream));
-    SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));
-    if ((rc = chol_flow_check(b))) return rc;
-    if (fail) return set_error(SSLAM_ERR_NUMERIC, "H is not positive definite: no marginals");
-    // Diagonal blocks only (what computeLandmarkMarginals asks for, semantic_graph_slam.cpp:188-190): one launch, a forward substitution
-    // along each vertex' path of the elimination tree (k_chol_marginal_paths) -- no right-hand side matrix, no backward solve, and only
-    // the requested blocks cross PCIe.  Off-diagonal pairs (or SSLAM_MARGINAL_PATHS=0) take the multi right-hand-side solves below.
-    static const bool paths_on = [] { const char* e = getenv("SSLAM_MARGINAL_PATHS"); return !(e && atoi(e) == 0); }();
-    bool all_diag = paths_on;
-    for (auto& pr : pairs) all_diag = all_diag && pr.first == pr.second;
-    if (all_diag) {
-      std::vector<int> xoffs, dims, slot(pairs.size(), -1);
-      for (size_t k = 0; k < pairs.size(); ++k) {
-        const int v = pairs[k].first;
-        if (hidx[v] < 0) continue;
-        int xo;
-        if (h->g.vtype[v] == VT_SE3) xo = 6 * b.pose_row[b.v2pose[0][v]];
-        else xo = 6 * b.V.nPr + 3 * b.lm_row[b.v2lm[0][v]];
-        slot[k] = (int)xoffs.size();
-        xoffs.push_back(xo); dims.push_back(vertex_dim(h->g.vtype[v]));
-      }
-      std::vector<double> Z(xoffs.size() * 36 + 1);
-      rc = chol_marginal_diag(b, xoffs, dims, Z.data());
-      if (rc == 0) {
-        size_t o = 0;
-        for (size_t k = 0; k < pairs.size(); ++k) {
-          const int d = vertex_dim(h->g.vtype[pairs[k].first]);
-          for (int e = 0; e < d * d; ++e) out[o + e] = slot[k] < 0 ? 0.0 : Z[(size_t)slot[k] * 36 + e];
-          o += (size_t)d * d;
-        }
-        return 0;
-      }
-      if (rc != SSLAM_ERR_UNSUPPORTED) return rc;   // a path longer than one wave's LDS holds: the general path below
+  for (int v : colv)
+    for (int c = 0; c < vertex_dim(h->g.vtype[v]); ++c) {
+      rhs_g2o[hidx[v] + c] = 1.0;
+      from_g2o_order(h, rhs_g2o.data(), rhs_int);
+      rhs_g2o[hidx[v] + c] = 0.0;
+      SSLAM_HIP_TRY(hipMemcpyAsync(b.V.bvec, rhs_int.data(), rhs_int.size() * 8, hipMemcpyHostToDevice, b.stream));
+      hipLaunchKernelGGL(k_set_trial_all, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, 0.0);
+      if ((rc = batch_solve(b))) return rc;
+      SSLAM_HIP_TRY(hipMemcpyAsync(xi.data(), b.V.x, xi.size() * 8, hipMemcpyDeviceToHost, b.stream));
+      SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));
+      to_g2o_order(h, xi, X.data() + (size_t)(col0[v] + c) * dim);
     }
-    X.resize((size_t)nrhs * dim);
-    std::vector<double> R((size_t)nrhs * idim, 0.0), Xi((size_t)nrhs * idim);
-    for (int v : colv)
-      for (int c = 0; c < vertex_dim(h->g.vtype[v]); ++c) {
-        rhs_g2o[hidx[v] + c] = 1.0;
-        from_g2o_order(h, rhs_g2o.data(), rhs_int);
-        rhs_g2o[hidx[v] + c] = 0.0;
-        std::copy(rhs_int.begin(), rhs_int.end(), R.begin() + (size_t)(col0[v] + c) * idim);
-      }
-    if ((rc = chol_solve_multi(b, R.data(), nrhs, Xi.data()))) return rc;
-    for (int q = 0; q < nrhs; ++q) {
-      std::copy(Xi.begin() + (size_t)q * idim, Xi.begin() + (size_t)(q + 1) * idim, xi.begin());
-      to_g2o_order(h, xi, X.data() + (size_t)q * dim);
-    }
-  } else {
-    X.resize((size_t)nrhs * dim);
-    for (int v : colv)
-      for (int c = 0; c < vertex_dim(h->g.vtype[v]); ++c) {
-        rhs_g2o[hidx[v] + c] = 1.0;
-        from_g2o_order(h, rhs_g2o.data(), rhs_int);
-        rhs_g2o[hidx[v] + c] = 0.0;
-        SSLAM_HIP_TRY(hipMemcpyAsync(b.V.bvec, rhs_int.data(), rhs_int.size() * 8, hipMemcpyHostToDevice, b.stream));
-        hipLaunchKernelGGL(k_set_trial_all, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, 0.0);
-        if ((rc = batch_solve(b))) return rc;
-        SSLAM_HIP_TRY(hipMemcpyAsync(xi.data(), b.V.x, xi.size() * 8, hipMemcpyDeviceToHost, b.stream));
-        SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));
-        to_g2o_order(h, xi, X.data() + (size_t)(col0[v] + c) * dim);
-      }
-    h->linearized = false;  // b was overwritten
-  }
+  h->linearized = false;  // b was overwritten
   size_t o = 0;
   for (auto& pr : pairs) {
     const int vr = pr.first, vc = pr.second;
@@ -2538,7 +2528,7 @@ int sslam_batch_optimize(sslam_batch* h, int max_iters, sslam_opt_stats* out) {
 }
 // ---- covariance blocks of the graphs of a batch -------------------------------------------------------------------------------
 // Blocks of H^-1 for (graph, row vertex, column vertex) requests of ONE batch (a part of a stream group): linearise once at the estimates the
-// device holds, factor the undamped H flat (the choice of marginal_blocks between the single launch and the launches per depth), then one
+// device holds, factor the undamped H flat (factor_undamped_flat, shared with the single-graph marginal_blocks), then one
 // wave per request along the elimination-tree paths (chol_marginal_blocks).  The per-graph LM states are borrowed -- the linearisation wants
 // every graph at the start of an iteration, the factorisation every graph in a trial at lambda 0 -- and put back; H, b, y and the factor
 // are rebuilt by the first step of whatever runs next, the estimates are only read.  out: [n][36].
@@ -2550,15 +2540,9 @@ static int batch_marginals(Batch& b, const std::vector<std::array<int, 3>>& req,
   SSLAM_HIP_TRY(hipSetDevice(b.device));
   std::vector<MarginalReq> mr;
   std::vector<int> slot(req.size(), -1);
-  auto xoff_of = [&](int g, int v) {   // first unknown of the vertex in the batch's internal row order, -1: fixed or without edges
-    const HostGraph& G = *b.graphs[g];
-    if (G.vtype[v] == VT_SE3) { const int r = b.pose_row[b.v2pose[g][v]]; return r < 0 ? -1 : 6 * r; }
-    const int r = b.lm_row[b.v2lm[g][v]];
-    return r < 0 ? -1 : 6 * b.V.nPr + 3 * r;
-  };
   for (size_t k = 0; k < req.size(); ++k) {
     const int g = req[k][0], vr = req[k][1], vc = req[k][2];
-    const int xr = xoff_of(g, vr), xc = xoff_of(g, vc);
+    const int xr = vertex_xoff(b, g, vr), xc = vertex_xoff(b, g, vc);
     if (xr < 0 || xc < 0) continue;
     slot[k] = (int)mr.size();
     mr.push_back({xr, vertex_dim(b.graphs[g]->vtype[vr]), xc, vertex_dim(b.graphs[g]->vtype[vc])});
@@ -2578,14 +2562,9 @@ static int batch_marginals(Batch& b, const std::vector<std::array<int, 3>>& req,
   if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
   hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
   if ((rc = batch_linearize(b))) return rc;   // undamped H at the current estimates
-  hipLaunchKernelGGL(k_set_trial_all, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, 0.0);
-  if (!b.chol && (rc = chol_plan_build(b))) return rc;
-  if ((rc = chol_plan_flow(b) ? chol_factor_flat_flow(b) : chol_factor_and_forward(b, /*flat=*/true))) return rc;
-  std::vector<int> fail((size_t)b.V.B, 0);
-  if ((rc = read_device(b, fail.data(), b.V.pcg_fail, fail.size() * sizeof(int)))) return rc;
-  if ((rc = chol_flow_check(b))) return rc;
-  for (int g = 0; g < b.V.B; ++g)
-    if (fail[g]) return set_error(SSLAM_ERR_NUMERIC, "H of graph %d of the batch is not positive definite: no marginals", g);
+  int bad;
+  if ((rc = factor_undamped_flat(b, &bad))) return rc;
+  if (bad >= 0) return set_error(SSLAM_ERR_NUMERIC, "H of graph %d of the batch is not positive definite: no marginals", bad);
   std::vector<double> Z(mr.size() * 36);
   if ((rc = chol_marginal_blocks(b, mr, Z.data()))) return rc;
   for (size_t k = 0; k < req.size(); ++k)

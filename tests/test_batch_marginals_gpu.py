@@ -1,6 +1,7 @@
 """sslam_batch_marginals on the GPU: blocks of H^-1 for (graph, row vertex, column vertex) requests of a batch -- diagonal and
 off-diagonal, one wave per request along the elimination-tree paths (k_chol_marginal_pairs), Y in LDS or in a device scratch buffer.
-References: the dense inverse of the oracle's H at the downloaded estimates, and sslam_graph_marginals of the downloaded host graphs.
+References: the dense inverse of the oracle's H at the downloaded estimates, and sslam_graph_marginals of the downloaded host graphs (the
+same kernel from a batch of one: a check of the plumbing, not an independent reference).
 Tolerance, everywhere a tolerance is used: the project's own for marginals, |a - ref|.max() <= 1e-6 |ref|.max() per block."""
 import ctypes as C
 import os
@@ -122,18 +123,25 @@ def test_front_kernel_family(gpu_lib):
     got = B.landmark_marginals([ids.get(g, []) for g in range(32)])
     assert [len(x) for x in got] == [len(ids.get(g, [])) for g in range(32)]
     for g in sample:
-        ref = graphs[g].computeLandmarkMarginals(ids[g])
+        gps[g].est[:] = graphs[g].estimates()
+        Hinv = _dense_inverse(gps[g])
+        ref = graphs[g].computeLandmarkMarginals(ids[g])   # the same pair kernel on the record kernels' factor: not independent, hence Hinv
         for v, a, r in zip(ids[g], got[g], ref):
             _close(a, r, f"graph {g} vertex {v}")
+            _close(a, _ref_block(gps[g], Hinv, v, v), f"graph {g} vertex {v} against the dense inverse")
     small = GraphBatch([GraphSLAM.from_problem(gp) for gp in gps[:4]])
     assert small.info("factor_front") == 0
 
 
 def test_batch_of_one_against_the_single_graph_handle(gpu_lib):
+    """A handle owns a batch of one: sslam_graph_marginals and sslam_batch_marginals of a batch of one factor and walk identically, the
+    blocks are equal bit for bit.  The dense inverse of the oracle's H is the independent reference."""
     from semantic_slam_amd import GraphSLAM, GraphBatch
     gp = GraphProblem.from_synth(make_graph(40, 8, seed=6), interleave=True)
     G = GraphSLAM.from_problem(gp)
     G.optimize(4)
+    gp.est[:] = G.estimates()
+    Hinv = _dense_inverse(gp)
     ids = [int(v) for v in gp.lm_ids] + [int(gp.pose_ids[k]) for k in (1, 20, 39)]
     ref = G.computeLandmarkMarginals(ids)
     M = GraphSLAM.from_problem(gp)
@@ -142,9 +150,10 @@ def test_batch_of_one_against_the_single_graph_handle(gpu_lib):
     B = GraphBatch([M])
     B.upload()
     got = B.marginals([(0, v, v) for v in ids])
-    print("batch of one bitwise equal to sslam_graph_marginals:", all(np.array_equal(a, r) for a, r in zip(got, ref)))
     for v, a, r in zip(ids, got, ref):
-        _close(a, r, f"vertex {v}")
+        _close(a, _ref_block(gp, Hinv, v, v), f"vertex {v} against the dense inverse")
+        _close(r, _ref_block(gp, Hinv, v, v), f"vertex {v} of the handle against the dense inverse")
+        assert np.array_equal(a, r), f"vertex {v}: max difference {np.abs(a - r).max():.3e}"
 
 
 def test_edge_data_travels(gpu_lib):
