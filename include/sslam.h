@@ -265,6 +265,20 @@ int sslam_batch_optimize(sslam_batch* b, int max_iters, sslam_opt_stats* out /* 
  * bitwise the same result; SSLAM_MARGINAL_LDS_BYTES in the environment (read per call, default and ceiling 61440) lowers the LDS budget.
  * The call leaves the batch as it found it: sslam_batch_optimize / sslam_batch_download after it give, bitwise, what they give without it. */
 int sslam_batch_marginals(sslam_batch* b, const int32_t* req, int n, double* out_blocks);
+/* Parity hook.  (H_g + lambda[g] I) x_g = b_g for every graph of the batch at the estimates the device holds, through the launches the
+ * LM loop takes.
+ * lambda[g] >= 0: graph g takes part.  lambda[g] < 0: it sits out exactly as a terminated graph does in the LM endgame (in_trial = active
+ * = 0, and the launches are sized for the graphs that take part as sslam_batch_optimize sizes them for the graphs still active: index
+ * lists once at most half of a batch of 8 graphs and more is left; SSLAM_CHOL_OPTS "compact=0" keeps the full ranges, with bitwise the
+ * same results; sslam_batch_info "compact_rounds" counts the times the index lists were switched on).
+ * x: the graphs' unknowns one after the other in batch order, each in its own hessian-index order (sslam_graph_hessian_index); zeros
+ * for a graph that sat out.  Returns the number of doubles; x == NULL only reports it.  solver_iterations ([n] or NULL): PCG iterations
+ * per graph (solvers 0 and 2), 0 for the direct solvers.
+ * SSLAM_ERR_INVALID: a NULL handle, a NULL lambda with x given, capacity below the size, a lambda that is not finite, a structure change
+ * since creation.  SSLAM_ERR_UNSUPPORTED: a batch in edge-sharded mode.  SSLAM_ERR_NUMERIC: the solve of a graph that took part broke
+ * down.  A stream group works: the parts run one after the other from the calling thread.
+ * The batch is left as it was found: sslam_batch_optimize / sslam_batch_marginals after it give, bitwise, what they give without it. */
+int64_t sslam_batch_solve(sslam_batch* b, const double* lambda, double* x, int64_t capacity, int64_t* solver_iterations /* [n] or NULL */);
 /* Edge-sharded mode (SURVEY 8e mode E, BASELINE.json configs[4]): every graph's edge list is split contiguously over `world` ranks
  * (one process per GPU, each holding the whole batch); a rank builds the partial normal equations of its edges, ONE RCCL all-reduce
  * (ncclDouble, sum, over xGMI) of the contiguous [H || b] device buffer gives every rank the full system, and the solve / update /
@@ -290,6 +304,8 @@ int sslam_batch_time_solver(sslam_batch* b, int repeats, double* factor_ms, doub
 int64_t sslam_batch_linearize_bytes(const sslam_batch* b);
 /* structural facts of a batch (doubles): "factor_lnz" (doubles in the Cholesky factor), "factor_levels", "factor_front" (1: the
  * factorisation runs the front kernels, the default of batches of 32 graphs and more),
+ * "compact_rounds" (times so far that the LM endgame, or sslam_batch_solve with graphs sitting out, sized the factor / solve launches by
+ * index lists of the graphs still taking part; summed over the parts of a stream group),
  * "h_doubles" (doubles in H), "dim" (scalar unknowns), "factor_bytes" = algorithmic HBM bytes of one numeric
  * factorisation + fused forward solve: read H and b once, write L and y once */
 int sslam_batch_info(sslam_batch* b, const char* key, double* value);

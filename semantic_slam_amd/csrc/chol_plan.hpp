@@ -196,6 +196,8 @@ struct CholOpts {
                            // sits on the chain of pieces) 5.53-5.70 vs 5.27-5.30 ms at 110 keyframes, 8.0 vs 7.64 at 436 -> record kernels there
   int flow = 1;            // small batches: 0 a launch per depth; 1 the dependency-driven single launch (k_chol_flow) when the bottom depth of the tree
                            // is no wider than its grid; 2 the single launch on any tree (a wide one is walked in rounds, measured slower: tests only)
+  int compact = 1;         // LM endgame: 1: once at most half of a batch of >= 8 graphs is still active, the launches are sized by index lists of the
+                           // active graphs' pieces (chol_set_active); 0: always the full ranges (tests: same results, bitwise).  Not part of the plan tables.
   // SSLAM_CHOL_OPTS="key=value,key=value,...": every plan option above by its field name (tests force the piece shapes of a 5000-pose graph
   // onto small graphs with it; tuning sweeps), plus order=mmd|mindeg and dump=1.  The ONE environment switch of the plan.
   void from_env() {
@@ -229,7 +231,7 @@ struct CholOpts {
       else if (k == "min_chunk") min_chunk = std::max(1, iv); else if (k == "split_min") split_min = std::max(2, iv);
       else if (k == "pcap_leaf") pcap_leaf = iv; else if (k == "pcap_mid") pcap_mid = iv; else if (k == "pcap_tail") pcap_tail = iv;
       else if (k == "group_cap") group_cap = iv; else if (k == "group_blocks") group_blocks = iv; else if (k == "ustage") ustage = iv;
-      else if (k == "order_bits_max") order_bits_max = iv; else if (k == "flow") flow = iv; else if (k == "front") front = iv; else if (k == "dump") dump = iv != 0;
+      else if (k == "order_bits_max") order_bits_max = iv; else if (k == "flow") flow = iv; else if (k == "front") front = iv; else if (k == "compact") compact = iv; else if (k == "dump") dump = iv != 0;
       else if (k == "order") order = (v == "mindeg" || v == "0") ? 0 : 1;
       else if (k == "order_mul") order_mul = atof(v.c_str()); else if (k == "order_add") order_add = iv;
       else fprintf(stderr, "[sslam] SSLAM_CHOL_OPTS: unknown key '%s'\n", k.c_str());

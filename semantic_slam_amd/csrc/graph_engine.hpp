@@ -133,7 +133,7 @@ struct Batch {
   std::vector<Pending> pending;
   std::vector<hipEvent_t> event_pool;
   bool uploaded = false;
-  LmState* d_lm_save = nullptr;   // [B] sslam_batch_marginals: the per-graph LM states while the call borrows them (allocated at its first use)
+  LmState* d_lm_save = nullptr;   // [B] sslam_batch_marginals / sslam_batch_solve: the per-graph LM states while the call borrows them (allocated at its first use)
   bool has_duplicate_blocks = false;
   bool has_planes = false;
   std::vector<int> dup_eo, dup_el;
@@ -146,6 +146,7 @@ struct Batch {
   double* d_hb_part = nullptr; // edge-sharded mode: this rank's partial [H || b] (send buffer of the out-of-place all-reduce)
   int64_t allreduce_calls = 0; // ncclAllReduce calls issued so far (tests: the collective really ran)
   int shard_rank = 0, shard_world = 1;
+  int64_t compact_rounds = 0;  // chol_set_active calls so far that left the launches sized by index lists (tests: the compacted forms really ran)
   // per-edge robust kernels: (graph, graph-local edge id) of every edge of the four storage classes (SE3, landmark, point-point, prior) as
   // batch_build ordered them, the device arrays (allocated when a kernel is first seen) and the sum of the graphs' robust_version they hold
   std::vector<int> cls_src[4], cls_g[4];

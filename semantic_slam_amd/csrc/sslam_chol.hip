@@ -95,6 +95,7 @@ struct CholPlan {
   int* d_idx = nullptr;         // [pieces of the active graphs, launch by launch | active graphs that have a tail]
   size_t idx_cap = 0;
   bool compact = false;
+  bool allow_compact = true;    // CholOpts::compact (SSLAM_CHOL_OPTS compact=0: chol_set_active never switches the index lists on)
   // dependency-driven factorisation + solve in ONE launch (k_chol_flow): small batches only
   bool flow = false;            // the plan can run it (every piece has one parent piece; nt_leaf == nt_tail)
   int flow_grid = 0;            // persistent workgroups
@@ -1639,6 +1640,7 @@ int chol_plan_build(Batch& b) {
   CholPlan* P = new CholPlan();
   b.chol = P;
   P->arena = b.arena;
+  P->allow_compact = opt.compact != 0;
   CholView& C = P->C;
   C.ncol = H.ncol; C.nlevels = H.nlevels; C.dim = H.dim; C.npiece = H.npiece;
   P->plv_ptr = H.plv_ptr; P->plv_lds_f = H.plv_lds_f; P->plv_lds_b = H.plv_lds_b; P->plv_nt = H.plv_nt; P->plv_cls = H.plv_cls;
@@ -2053,7 +2055,7 @@ int chol_set_active(Batch& b, const std::vector<char>* active) {
   const int B = b.V.B;
   int na = 0;
   for (int g = 0; g < B; ++g) na += (*active)[g] ? 1 : 0;
-  if (B < 8 || na == 0 || 2 * na > B) return 0;
+  if (!P.allow_compact || B < 8 || na == 0 || 2 * na > B) return 0;
   const int nplv = (int)P.plv_lds_f.size();
   std::vector<int> idx;
   idx.reserve(P.lp_graph.size() * (size_t)na / B + 64);
@@ -2074,6 +2076,7 @@ int chol_set_active(Batch& b, const std::vector<char>* active) {
   if (!idx.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(P.d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // idx is a local
   P.compact = true;
+  b.compact_rounds++;
   return 0;
 }
 

@@ -1080,6 +1080,10 @@ __global__ void k_set_trial_all(BatchView V, double lambda) {  // used by the so
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g < V.B) { V.lm[g].in_trial = 1; V.lm[g].lambda = lambda; V.lm[g].active = 1; }
 }
+__global__ void k_set_trial_each(BatchView V, const double* __restrict__ lambda) {  // sslam_batch_solve: every graph its own damping; lambda < 0: the graph sits out
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < V.B) { const int on = lambda[g] >= 0 ? 1 : 0; V.lm[g].in_trial = on; V.lm[g].lambda = on ? lambda[g] : 0.0; V.lm[g].active = on; }
+}
 
 }  // namespace sslam
 
@@ -2612,6 +2616,109 @@ int sslam_batch_marginals(sslam_batch* h, const int32_t* req, int n, double* out
     }
   return 0;
 }
+// ---- one linear solve of every graph of a batch (parity hook) --------------------------------------------------------------------
+// (H_g + lambda[g] I) x_g = b_g of ONE batch (a part of a stream group) at the estimates the device holds, through the launches the LM loop
+// takes: the LM states are borrowed as batch_marginals borrows them, every graph gets its own damping (k_set_trial_each), and the graphs
+// with lambda < 0 sit out as terminated graphs do in the LM endgame -- the launches are sized by chol_set_active with that mask.
+// x: V.x in the batch's internal row order; iters / fail: per graph.
+static int batch_solve_each(Batch& b, const double* lambda, std::vector<double>& x, std::vector<long long>& iters, std::vector<int>& fail) {
+  SSLAM_HIP_TRY(hipSetDevice(b.device));
+  const int B = b.V.B;
+  int rc;
+  if (!b.uploaded && (rc = batch_upload_estimates(b))) return rc;
+  if ((rc = chol_set_active(b, nullptr))) return rc;
+  const size_t lm_bytes = sizeof(LmState) * (size_t)B;
+  if (!b.d_lm_save && (rc = dev_alloc(b, (size_t)B, &b.d_lm_save, false))) return rc;
+  SSLAM_HIP_TRY(hipMemcpyAsync(b.d_lm_save, b.V.lm, lm_bytes, hipMemcpyDeviceToDevice, b.stream));
+  struct Restore {   // the LM states and the full launch ranges go back on every return path
+    Batch& b; size_t bytes;
+    ~Restore() {
+      (void)chol_set_active(b, nullptr);
+      (void)hipMemcpyAsync(b.V.lm, b.d_lm_save, bytes, hipMemcpyDeviceToDevice, b.stream); (void)hipStreamSynchronize(b.stream); b.harvest();
+    }
+  } restore{b, lm_bytes};
+  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
+  hipLaunchKernelGGL(k_lm_init, dim3(B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
+  if ((rc = batch_linearize(b))) return rc;
+  // the lambdas travel through the max-diagonal partials (B doubles at least), which nothing reads between here and the solve
+  std::vector<char> mask((size_t)B);
+  for (int g = 0; g < B; ++g) mask[g] = lambda[g] >= 0 ? 1 : 0;
+  SSLAM_HIP_TRY(hipMemcpyAsync(b.d_part_m, lambda, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, b.stream));
+  hipLaunchKernelGGL(k_set_trial_each, dim3((B + 63) / 64), dim3(64), 0, b.stream, b.V, b.d_part_m);
+  SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // `lambda` is the caller's
+  x.assign((size_t)6 * b.V.nPr + (size_t)3 * b.V.nLr, 0.0);
+  iters.assign((size_t)B, 0); fail.assign((size_t)B, 0);
+  if (std::find(mask.begin(), mask.end(), (char)1) == mask.end()) return launch_check("solve");   // nobody takes part: nothing to launch
+  const int solver = b.graphs[0]->opt.solver;
+  if (solver != 0 && solver != 2 && !b.chol && (rc = chol_plan_build(b))) return rc;   // chol_set_active needs the plan
+  if ((rc = chol_set_active(b, &mask))) return rc;
+  if ((rc = batch_solve(b))) return rc;
+  std::vector<LmState> st((size_t)B);
+  if (!x.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(x.data(), b.V.x, x.size() * 8, hipMemcpyDeviceToHost, b.stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(fail.data(), b.V.pcg_fail, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, b.stream));
+  if ((rc = read_lm_state(b, st))) return rc;
+  for (int g = 0; g < B; ++g) { iters[g] = st[g].pcg_iters; if (!mask[g]) fail[g] = 0; }
+  if ((rc = chol_set_active(b, nullptr))) return rc;
+  if ((rc = launch_check("solve"))) return rc;
+  return chol_flow_check(b);
+}
+
+int64_t sslam_batch_solve(sslam_batch* h, const double* lambda, double* x, int64_t capacity, int64_t* solver_iterations) {
+  if (!h) return set_error(SSLAM_ERR_INVALID, "null batch");
+  int rc = batch_check(h);
+  if (rc) return rc;
+  const bool group = !h->parts.empty();
+  const int K = group ? (int)h->parts.size() : 1;
+  auto part_batch = [&](int k) -> Batch& { return group ? h->parts[k]->b : h->b; };
+  // every graph's unknowns in its own hessian-index order, one graph after the other
+  std::vector<int64_t> goff;
+  std::vector<std::vector<int>> hidx;
+  int64_t total = 0;
+  for (int k = 0; k < K; ++k)
+    for (HostGraph* G : part_batch(k).graphs) {
+      hidx.emplace_back();
+      goff.push_back(total);
+      total += hessian_indices(*G, hidx.back());
+    }
+  if (!x) return total;
+  if (!lambda) return set_error(SSLAM_ERR_INVALID, "null argument");
+  if (capacity < total) return set_error(SSLAM_ERR_INVALID, "buffer of %lld doubles needed", (long long)total);
+  for (int k = 0; k < K; ++k)
+    if (part_batch(k).sharded) return set_error(SSLAM_ERR_UNSUPPORTED, "sslam_batch_solve is not available in the edge-sharded mode");
+  std::vector<int> first(K + 1, 0);
+  for (int k = 0; k < K; ++k) first[k + 1] = first[k] + (int)part_batch(k).graphs.size();
+  for (int g = 0; g < first[K]; ++g)
+    if (!(lambda[g] == lambda[g]) || std::isinf(lambda[g])) return set_error(SSLAM_ERR_INVALID, "lambda of graph %d is not finite", g);
+  std::fill(x, x + total, 0.0);
+  if (solver_iterations) std::fill(solver_iterations, solver_iterations + first[K], (int64_t)0);
+  // the parts of a stream group one after the other, from the calling thread
+  auto run = [&](int p) {
+    Batch& b = part_batch(p);
+    std::vector<double> xi;
+    std::vector<long long> iters;
+    std::vector<int> fail;
+    int rc2 = batch_solve_each(b, lambda + first[p], xi, iters, fail);
+    if (rc2) return rc2;
+    for (int gl = 0; gl < (int)b.graphs.size(); ++gl) {
+      const int g = first[p] + gl;
+      if (!(lambda[g] >= 0)) continue;
+      if (fail[gl]) return set_error(SSLAM_ERR_NUMERIC, "linear solve of graph %d of the batch broke down", g);
+      if (solver_iterations) solver_iterations[g] = iters[gl];
+      const HostGraph& G = *b.graphs[gl];
+      double* xo = x + goff[g];
+      for (int v = 0; v < G.nv(); ++v) {
+        const int xr = vertex_xoff(b, gl, v), o = hidx[g][v];
+        if (xr < 0 || o < 0) continue;
+        const int d = vertex_dim(G.vtype[v]);
+        for (int a = 0; a < d; ++a) xo[o + a] = xi[(size_t)xr + a];
+      }
+    }
+    return 0;
+  };
+  if (group) rc = for_each_part(h, false, [&](sslam_batch*, int p) { return run(p); });
+  else rc = run(0);
+  return rc ? rc : total;
+}
 // ---- edge-sharded mode (SURVEY 8e mode E; BASELINE.json configs[4]): the edges of every graph of the batch are split
 //      contiguously over the ranks, each rank builds the partial normal equations of its edges, ONE RCCL all-reduce of the
 //      contiguous [H || b] buffer sums them, and the rest of the LM step runs replicated.
@@ -2811,6 +2918,7 @@ int sslam_batch_info(sslam_batch* h, const char* key, double* value) {
   else if (k == "h_doubles") *value = (double)b.V.h_total;
   else if (k == "dim") *value = dim;
   else if (k == "allreduce_calls") *value = (double)b.allreduce_calls;
+  else if (k == "compact_rounds") *value = (double)b.compact_rounds;   // chol_set_active calls that sized the launches by index lists
   else if (k == "lm_fused_launches") *value = (double)chol_plan_lm_launches(b, false);   // k_chol_flow launches that carried the halves of a damping trial
   else if (k == "lm_spec_rounds") *value = (double)chol_plan_lm_launches(b, true);       // k_chol_spec_round launches
   else if (k == "factor_bytes") *value = 8.0 * ((double)b.V.h_total + dim + (double)chol_plan_lnz(b) + dim);

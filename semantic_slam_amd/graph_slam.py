@@ -392,6 +392,33 @@ class GraphBatch:
         blocks = iter(self.marginals([(g, v, v) for g, ids in enumerate(ids_per_graph) for v in ids]))
         return [[next(blocks) for _ in ids] for ids in ids_per_graph]
 
+    # -- one linear solve per graph (parity hook) -------------------------------------------------
+    def solve(self, lambdas):
+        """sslam_batch_solve: (H_g + lambdas[g] I) x_g = b_g for every graph at the estimates the batch holds on the device.  A graph with
+        lambdas[g] < 0 sits out as a terminated graph does in the LM endgame.  Returns one array per graph in hessian-index order, None for
+        a graph that sat out; ``last_solver_iterations`` holds the PCG iterations per graph (0 for the direct solvers)."""
+        lam = np.ascontiguousarray(lambdas, np.float64).reshape(-1)
+        if len(lam) != len(self.graphs):
+            raise ValueError(f"one lambda per graph: got {len(lam)} for {len(self.graphs)} graphs")
+        n = int(self._lib.sslam_batch_solve(self._h, None, None, 0, None))
+        _check(self._lib, min(n, 0))
+        x = np.zeros(n + 1)
+        it = (C.c_int64 * len(lam))()
+        _check(self._lib, min(int(self._lib.sslam_batch_solve(self._h, _dptr(lam), _dptr(x), n, it)), 0))
+        self.last_solver_iterations = list(it)
+        if not hasattr(self, "_dims"):   # scalar unknowns per graph (the structure of a batch's graphs is fixed at its creation)
+            self._dims = []
+            for G in self.graphs:
+                hv = [(G.hessian_index(v), v) for v in range(G.num_vertices())]
+                h, v = max(hv) if hv else (-1, -1)
+                self._dims.append(0 if h < 0 else h + (6 if len(G.estimate(v)) == 7 else 3))
+        out, o = [], 0
+        for g, d in enumerate(self._dims):
+            out.append(x[o:o + d].copy() if lam[g] >= 0 else None)
+            o += d
+        assert o == n, (o, n)
+        return out
+
     # -- edge-sharded mode (SURVEY 8e mode E) ----------------------------------------------------
     def comm_init(self, unique_id: bytes, rank: int, world: int) -> None:
         """RCCL communicator + edge shard of this rank (every rank holds the whole batch); see distributed.init_edge_sharded."""

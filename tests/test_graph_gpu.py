@@ -524,6 +524,122 @@ def test_stream_group_matches_the_single_stream_batch(gpu_lib):
         assert np.abs(G1.estimates() - G3.estimates()).max() < 1e-9
 
 
+def _endgame_run(gps, build, iters, monkeypatch, compact):
+    """one batch through optimize(iters) with the compaction of the LM endgame on or off (SSLAM_CHOL_OPTS compact, read when the plan is built)"""
+    from semantic_slam_amd import GraphBatch
+    if compact:
+        monkeypatch.delenv("SSLAM_CHOL_OPTS", raising=False)
+    else:
+        monkeypatch.setenv("SSLAM_CHOL_OPTS", "compact=0")
+    graphs = build(gps)
+    B = GraphBatch(graphs); B.upload()
+    stats = B.optimize(iters)
+    B.download()
+    monkeypatch.delenv("SSLAM_CHOL_OPTS", raising=False)
+    return graphs, stats, B.info("compact_rounds")
+
+
+def _assert_runs_bitwise_equal(run_a, run_b):
+    (ga, sa, _), (gb, sb, _) = run_a, run_b
+    for k, (a, b, Ga, Gb) in enumerate(zip(sa, sb, ga, gb)):
+        assert (a.status, a.iterations, a.trials) == (b.status, b.iterations, b.trials), k
+        assert a.chi2_before == b.chi2_before and a.chi2_after == b.chi2_after, k
+        assert np.array_equal(Ga.estimates(), Gb.estimates()), k
+
+
+def test_lm_endgame_compacts_once_most_of_the_batch_is_done(gpu_lib, monkeypatch):
+    """batch_optimize looks at the LM states every 8 steps and, once at most half of a batch of >= 8 graphs is still active, sizes the
+    factor / solve launches by index lists of the active graphs' pieces (chol_set_active).  Deterministic trigger: eight of twelve members
+    have 9 edges -- TOO_FEW_EDGES, inactive from k_lm_init on, yet owners of pieces in the plan -- so the first look finds 4 of 12 active and
+    steps 9 .. 24 of the four noisy graphs run off the index lists.  Against the oracle at the bars of the batch-regime test, and bitwise
+    against the same batch with the compaction switched off (SSLAM_CHOL_OPTS compact=0).
+    The noisy graphs are far from converged after 24 iterations (noise_scale 25 for points, 3 for planes: the oracle needs all 24, with
+    rejected trials on the way, and its counts do not move under 1e-13 perturbations of the measurements): iteration and trial counts at
+    the noise floor are decided by last bits (test_L_config_termination_iteration) and are not what this test is about."""
+    from semantic_slam_amd import GraphSLAM
+    noisy = [(80, 16, 840, 25.0), (110, 22, 860, 3.0), (140, 28, 843, 25.0), (170, 34, 867, 3.0)]
+    gps = [GraphProblem.from_synth(make_graph(a, b, seed=s, noise_scale=ns, landmark_kind="plane" if i & 1 else "point"), interleave=bool(i & 1))
+           for i, (a, b, s, ns) in enumerate(noisy)]
+
+    def small(k):
+        """a 5-pose chain (4 odometry edges) and one landmark seen from all five poses: 9 edges"""
+        G = GraphSLAM()
+        ps = [G.add_se3_node([1.0 * j + 0.05 * k, 0.02 * j * j, 0, 0, 0, 0, 1]) for j in range(5)]
+        l = G.add_point_xyz_node([2.0, 1.0 + 0.1 * k, 0.5])
+        for j in range(4):
+            G.add_se3_edge(ps[j], ps[j + 1], [1, 0, 0, 0, 0, 0, 1], np.eye(6))
+        for j in range(5):
+            G.add_se3_point_xyz_edge(ps[j], l, [2.0 - j, 1.0, 0.5], np.eye(3))
+        assert G.num_edges() == 9
+        return G
+
+    order = ["s", "s", 0, "s", "s", 1, "s", "s", 2, "s", "s", 3]          # batch order: the noisy graphs between the small members
+
+    def build(gps):
+        return [small(k) if m == "s" else GraphSLAM.from_problem(gps[m]) for k, m in enumerate(order)]
+
+    run1 = _endgame_run(gps, build, 24, monkeypatch, compact=True)
+    run0 = _endgame_run(gps, build, 24, monkeypatch, compact=False)
+    assert run1[2] >= 1 and run0[2] == 0
+    _assert_runs_bitwise_equal(run1, run0)
+    graphs, stats, _ = run1
+    untouched = build(gps)
+    for k, m in enumerate(order):
+        if m == "s":
+            assert stats[k].status == -5 and stats[k].iterations == 0
+            assert np.array_equal(graphs[k].estimates(), untouched[k].estimates())
+    ref = {}
+    for k, m in enumerate(order):                        # every figure is printed before anything is asserted
+        if m == "s":
+            continue
+        gp = gps[m].copy()
+        ref[k] = (gp, gp.optimize(24))
+        st = ref[k][1]
+        chi_rel = abs(stats[k].chi2_after - st.chi2_after) / st.chi2_after
+        est_rel = np.abs(graphs[k].estimates() - gp.est).max() / np.abs(gp.est).max()
+        print(f"noisy graph {m}: HIP iterations {stats[k].iterations} trials {stats[k].trials}, oracle {st.iterations} {st.trials}; chi2 rel {chi_rel:.3e} estimates rel {est_rel:.3e}")
+    for k, (gp, st) in ref.items():
+        assert stats[k].iterations == st.iterations and stats[k].trials == st.trials
+        assert stats[k].chi2_after == pytest.approx(st.chi2_after, rel=1e-9)
+        assert np.abs(graphs[k].estimates() - gp.est).max() <= 1e-6 * np.abs(gp.est).max()
+
+
+def test_lm_endgame_compaction_at_natural_termination(gpu_lib, monkeypatch):
+    """Sixteen graphs run to termination.  Eight (noise_scale 1) stop after at most 29 trials in the oracle, under 1e-13 perturbations of
+    their measurements as well (the count at the noise floor is decided by last bits); eight (noise_scale 50 / 100) need at least 59.  For
+    a batch of >= 8 graphs one step is one trial, so the look after 32 or 40 steps finds the early half done with trials to spare and the
+    late half active: the rest of the run goes off index lists.  compact_rounds >= 1 is the condition on these inputs."""
+    from semantic_slam_amd import GraphSLAM
+    early = [(30, 6, 700, False), (36, 8, 702, True), (42, 6, 704, False), (48, 8, 706, True), (54, 6, 708, False), (60, 8, 710, True),
+             (72, 8, 714, True), (84, 8, 718, True)]
+    late = [(85, 13, 765, 50.0, False), (90, 14, 766, 50.0, True), (95, 15, 767, 50.0, True), (100, 12, 768, 50.0, False),
+            (90, 14, 766, 100.0, True), (95, 15, 767, 100.0, True), (100, 12, 768, 100.0, False), (105, 13, 769, 100.0, False)]
+    gps = []
+    for e, l in zip(early, late):                                            # early and late alternate in batch order
+        gps.append(GraphProblem.from_synth(make_graph(e[0], e[1], seed=e[2]), interleave=e[3]))
+        gps.append(GraphProblem.from_synth(make_graph(l[0], l[1], seed=l[2], noise_scale=l[3]), interleave=l[4]))
+
+    def build(gps):
+        return [GraphSLAM.from_problem(gp) for gp in gps]
+
+    run1 = _endgame_run(gps, build, 1024, monkeypatch, compact=True)
+    run0 = _endgame_run(gps, build, 1024, monkeypatch, compact=False)
+    print("trials:", [s.trials for s in run1[1]], "compact rounds", run1[2])
+    assert run1[2] >= 1 and run0[2] == 0
+    _assert_runs_bitwise_equal(run1, run0)
+    graphs, stats, _ = run1
+    assert all(s.status == 1 for s in stats)
+    for k, gp0 in enumerate(gps):
+        gp = gp0.copy()
+        st = gp.optimize(1024)
+        assert st.status == 1
+        chi_rel = abs(stats[k].chi2_after - st.chi2_after) / st.chi2_after
+        est_rel = np.abs(graphs[k].estimates() - gp.est).max() / np.abs(gp.est).max()
+        print(f"graph {k}: HIP trials {stats[k].trials}, oracle {st.trials}; chi2 rel {chi_rel:.3e} estimates rel {est_rel:.3e}")
+        assert stats[k].chi2_after == pytest.approx(st.chi2_after, rel=1e-9)
+        assert est_rel <= 1e-6
+
+
 def test_edge_shards_sum_to_the_full_system(gpu_lib):
     """SURVEY 8e mode E on one device: the partial normal equations of the edge shards of 3 ranks (graph-local edge ranges
     identical to distributed.shard_range) add up to the full [H || b]; with world = 1 the mode is off again."""
