@@ -178,6 +178,19 @@ class GraphSLAM {
     return &priors_xyz_.back();
   }
 
+  /** Loop-closure gate (sslam_graph_gate): the squared Mahalanobis distance e^T S^-1 e of a candidate edge that is NOT in the graph, with
+   *  S = J Sigma J^T + information^-1 at the current estimates; the arguments of add_se3_edge / add_se3_point_xyz_edge.
+   *  information_matrix == nullptr: the distance in J Sigma J^T alone.  NaN when S is singular. */
+  double gate_se3_edge(const sslam::VertexSE3* v1, const sslam::VertexSE3* v2, const sslam::Isometry& relative_pose, const double* information_matrix) {
+    double tq[7]; sslam::isometry_to_tq(relative_pose, tq);
+    return gate(SSLAM_GATE_SE3, v1->id(), v2->id(), tq, information_matrix, 36);
+  }
+  double gate_se3_point_xyz_edge(const sslam::VertexSE3* v_se3, const sslam::VertexPointXYZ* v_xyz, const std::array<double, 3>& xyz,
+                                 const double* information_matrix) {
+    const double z[7] = {xyz[0], xyz[1], xyz[2], 0, 0, 0, 0};
+    return gate(SSLAM_GATE_SE3_POINT, v_se3->id(), v_xyz->id(), z, information_matrix, 9);
+  }
+
   /** The robust kernel graph_slam.cpp:155,161 means to install on the landmark edges (g2o::RobustKernelDCS; the reference passes an
    *  uninitialised pointer, so the default here is "none").  phi > 0 switches it on for every landmark edge, 0 off. */
   void setRobustKernelDCS(double phi = 1.0) { check(sslam_graph_set_option(graph.get(), "robust_kernel_dcs", phi)); }
@@ -259,6 +272,14 @@ class GraphSLAM {
     double W[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) W[r * 3 + c] = info(r, c);
     return add_se3_point_xyz_edge(v, p, std::array<double, 3>{xyz[0], xyz[1], xyz[2]}, W);
   }
+  double gate_se3_edge(const sslam::VertexSE3* v1, const sslam::VertexSE3* v2, const Eigen::Isometry3d& rel, const Eigen::MatrixXd& info) {
+    double W[36]; for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) W[r * 6 + c] = info(r, c);
+    return gate_se3_edge(v1, v2, from_eigen(rel), W);
+  }
+  double gate_se3_point_xyz_edge(const sslam::VertexSE3* v, const sslam::VertexPointXYZ* p, const Eigen::Vector3d& xyz, const Eigen::MatrixXd& info) {
+    double W[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) W[r * 3 + c] = info(r, c);
+    return gate_se3_point_xyz_edge(v, p, std::array<double, 3>{xyz[0], xyz[1], xyz[2]}, W);
+  }
   sslam::EdgeSE3PriorXY* add_se3_prior_xy_edge(const sslam::VertexSE3* v, const Eigen::Vector2d& xy, const Eigen::MatrixXd& info) {
     double W[4]; for (int r = 0; r < 2; ++r) for (int c = 0; c < 2; ++c) W[r * 2 + c] = info(r, c);
     return add_se3_prior_xy_edge(v, std::array<double, 2>{xy[0], xy[1]}, W);
@@ -282,6 +303,13 @@ class GraphSLAM {
   static int check(int rc) {
     if (rc < 0) throw std::runtime_error(std::string("sslam: ") + sslam_last_error());
     return rc;
+  }
+  double gate(int kind, int v_from, int v_to, const double z[7], const double* information_matrix, int n_info) {
+    const int32_t cand[3] = {kind, v_from, v_to};
+    double W[36] = {0}, d2 = 0;
+    if (information_matrix) for (int k = 0; k < n_info; ++k) W[k] = information_matrix[k];
+    check(sslam_graph_gate(graph.get(), cand, z, information_matrix ? W : nullptr, 1, &d2, nullptr, nullptr));
+    return d2;
   }
   void set_robust_kernel(int edge_id, const std::string& kernel_type, double kernel_size) {
     static const char* const names[8] = {"NONE", "Huber", "PseudoHuber", "Cauchy", "Welsch", "Fair", "Saturated", "DCS"};

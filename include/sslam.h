@@ -265,6 +265,38 @@ int sslam_batch_optimize(sslam_batch* b, int max_iters, sslam_opt_stats* out /* 
  * bitwise the same result; SSLAM_MARGINAL_LDS_BYTES in the environment (read per call, default and ceiling 61440) lowers the LDS budget.
  * The call leaves the batch as it found it: sslam_batch_optimize / sslam_batch_download after it give, bitwise, what they give without it. */
 int sslam_batch_marginals(sslam_batch* b, const int32_t* req, int n, double* out_blocks);
+/* Loop-closure gate: the Mahalanobis distance of candidate edges that are NOT in the graph (their measurement is independent of the
+ * estimate), at the estimates the batch holds on the device and with H the undamped system there -- the conventions of
+ * sslam_batch_marginals.  For a candidate between the vertices u = v_from and v = v_to:
+ *   e   the edge's error, as the linearisation computes it (what sslam_graph_edge_chi2 would work from, were the edge added);
+ *   Ju, Jv   its analytic Jacobians;  Zab   the blocks of H^-1 (zero for a fixed or edge-less vertex and across connected components);
+ *   S = Ju Zuu Ju^T + Ju Zuv Jv^T + Jv Zvu Ju^T + Jv Zvv Jv^T + Omega^-1,   d2 = e^T S^-1 e.
+ * info == NULL leaves Omega^-1 out: S is the covariance of the predicted relative measurement alone.
+ * cand = 4n ints: (graph index in the batch, kind, v_from, v_to).  z = 7n doubles, info = 36n doubles or NULL:
+ *   SSLAM_GATE_SE3        VertexSE3 -> VertexSE3, z = t, q(x,y,z,w), info 6x6 row-major, d = 6;
+ *   SSLAM_GATE_SE3_POINT  VertexSE3 -> VertexPointXYZ, z = the first 3 of the 7, info = the leading 9 of the 36 as 3x3, d = 3.
+ * z and -z (the quaternion negated) are one measurement and give the same d2.  Only the lower triangle of info is read.
+ * d2_out [n].  e_out [6n] or NULL: the leading d entries per candidate.  cov_out [36n] or NULL: S as the leading d * d entries, row-major
+ * d x d.  The remainder of both is zero.
+ * When the Cholesky of Omega or of S breaks down (a pivot <= 0 or not finite) that candidate's d2 is NaN and the call still returns 0;
+ * e_out and cov_out hold what was computed (S without Omega^-1 when it was Omega that broke down).  Both ends fixed and info == NULL
+ * give S = 0, which is such a case; both ends fixed with info give d2 = e^T Omega e.
+ * n == 0 returns 0.  SSLAM_ERR_INVALID, with the outputs unwritten: a NULL handle (checked first), NULL cand, z or d2_out with n > 0, a
+ * graph index, kind or vertex id out of range, a vertex of the wrong type for the kind, v_from == v_to, a z or info that is not finite, a
+ * quaternion of zero norm, a structure change since creation.  SSLAM_ERR_UNSUPPORTED: solver 0 or 2, a batch in edge-sharded mode.
+ * SSLAM_ERR_NUMERIC: an undamped H that is not positive definite (the rule of sslam_batch_marginals).  A stream group works as it does
+ * there: every candidate goes to the part that holds its graph, the parts run one after the other from the calling thread.
+ * One linearisation and one flat factorisation of the whole batch, then ONE WAVE PER CANDIDATE (k_chol_gate_pairs): the forward
+ * substitutions along path(u) and path(v), each once, the three blocks of H^-1 out of them, e, the Jacobians, S and d2 -- 43 doubles per
+ * candidate cross PCIe.  Paths of any length, a path of length 0 (a fixed end) included; LDS or device scratch with bitwise the same
+ * result, SSLAM_MARGINAL_LDS_BYTES as for the marginals (the budget of the whole workgroup, the kernel's fixed 2368 bytes included).
+ * The call leaves the batch as it found it: optimize, download and marginals after it give, bitwise, what they give without it. */
+#define SSLAM_GATE_SE3 0
+#define SSLAM_GATE_SE3_POINT 1
+int sslam_batch_gate(sslam_batch* b, const int32_t* cand, const double* z, const double* info, int n, double* d2_out, double* e_out, double* cov_out);
+/* the same for a single graph handle, at the graph's current estimates: cand = 3n ints (kind, v_from, v_to).  The batch-of-one route:
+ * bitwise what sslam_batch_gate gives for a batch of this one graph. */
+int sslam_graph_gate(sslam_graph* g, const int32_t* cand, const double* z, const double* info, int n, double* d2_out, double* e_out, double* cov_out);
 /* Parity hook.  (H_g + lambda[g] I) x_g = b_g for every graph of the batch at the estimates the device holds, through the launches the
  * LM loop takes.
  * lambda[g] >= 0: graph g takes part.  lambda[g] < 0: it sits out exactly as a terminated graph does in the LM endgame (in_trial = active

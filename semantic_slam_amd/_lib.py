@@ -92,6 +92,8 @@ def load_library():
         "sslam_batch_download": (ci, [vp]),
         "sslam_batch_optimize": (ci, [vp, ci, C.POINTER(OptStats)]),
         "sslam_batch_marginals": (ci, [vp, C.POINTER(C.c_int32), ci, dp]),
+        "sslam_batch_gate": (ci, [vp, C.POINTER(C.c_int32), dp, dp, ci, dp, dp, dp]),
+        "sslam_graph_gate": (ci, [vp, C.POINTER(C.c_int32), dp, dp, ci, dp, dp, dp]),
         "sslam_batch_solve": (i64, [vp, dp, dp, i64, C.POINTER(i64)]),
         "sslam_comm_unique_id": (ci, [C.c_char_p]),
         "sslam_batch_comm_init": (ci, [vp, C.c_char_p, ci, ci]),

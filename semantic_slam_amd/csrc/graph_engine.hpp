@@ -255,6 +255,8 @@ int chol_factor_flat_flow(Batch& b);        // flat factor (marginals) through t
 int chol_flow_check(Batch& b);              // error flag of that launch (synchronises the stream)
 struct MarginalReq { int xoff_u, dim_u, xoff_v, dim_v; };   // first unknown (internal row order) and dimension of the row / column vertex; xoff_v == xoff_u: a diagonal block
 int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double* out36);   // blocks Z(u, v) of H^-1 for pairs of vertices of a batch, paths of any length
+struct GateReq { int xoff_u, dim_u, xoff_v, dim_v, kind, idx_u, idx_v, has_info; };   // as MarginalReq, xoff < 0: fixed or edge-less; SSLAM_GATE_* kind; index of u in V.pose, of v in V.pose / V.lmk
+int chol_gate_pairs(Batch& b, const std::vector<GateReq>& reqs, const double* in44, double* out44);   // Mahalanobis gate of candidate edges: in {z 7, pad, Omega 36}, out {d2, e 6, pad, S 36} per candidate
 
 
 }  // namespace sslam

@@ -8,6 +8,7 @@
 //   k_chol_tail<NT>        one workgroup per graph walks the top pieces of its tree in elimination order
 //   k_chol_back_pieces / k_chol_back_tail   the same pieces top-down for x = L^-T y
 //   k_chol_marginal_pairs<SCRATCH>   blocks of H^-1 along elimination-tree paths of the flat factor (marginals)
+//   k_chol_gate_pairs<SCRATCH>       Mahalanobis distance of candidate edges from the same paths (loop-closure gate)
 // Everything is gather-form: every L entry is written by exactly one thread, sums run in a fixed order -> bitwise
 // repeatable.  Forward substitution is fused into the factorisation (b rides along as an extra row of the diagonal block).
 //   k_front_pieces / k_front_tail (front_kernels.hpp, round 6)   the same pieces through the front tables of front_plan.hpp: the default of batches >= 32
@@ -116,6 +117,8 @@ struct CholPlan {
   size_t mpath_cap = 0, mout_cap = 0;
   char* d_mscratch = nullptr;   // k_chol_marginal_pairs: the Y slices of the requests whose paths LDS does not hold
   size_t mscratch_cap = 0;      // bytes
+  double* d_gin = nullptr;      // k_chol_gate_pairs: measurement and information matrix of every candidate
+  size_t gin_cap = 0;           // bytes
 };
 
 void chol_plan_free(CholPlan* p) {
@@ -145,6 +148,7 @@ void chol_plan_free(CholPlan* p) {
   if (p->d_mpath && !p->arena) (void)hipFree(p->d_mpath);
   if (p->d_mout && !p->arena) (void)hipFree(p->d_mout);
   if (p->d_mscratch && !p->arena) (void)hipFree(p->d_mscratch);
+  if (p->d_gin && !p->arena) (void)hipFree(p->d_gin);
   delete p;
 }
 
@@ -1175,6 +1179,201 @@ __global__ __launch_bounds__(64) void k_chol_marginal_pairs(CholView C, const in
 }
 
 // ------------------------------------------------------------------------------------------------
+// Mahalanobis gate of candidate edges (sslam_batch_gate): d2 = e^T S^-1 e with S = Ju Zuu Ju^T + Ju Zuv Jv^T + Jv Zvu Ju^T + Jv Zvv Jv^T
+// + Omega^-1, for an EdgeSE3 (u, v poses) or an EdgeSE3PointXYZ (u pose, v point) that is NOT in the graph.  One wave per candidate:
+// marginal_path_forward along path(u) and along path(v), each ONCE; the three blocks Zuu, Zvv (whole paths) and Zuv (common suffix) out of
+// the two Ys; e and the analytic Jacobians of sslam_math.hpp at the estimates the device holds; Omega^-1 and S^-1 e through 6 x 6 / 3 x 3
+// Choleskys.  Only d2, e and S cross PCIe.
+// A fixed or edge-less end has no column: its path has length 0, nothing of Y / prec / pyoff is touched for it and its blocks are zero.
+// Placement as in k_chol_marginal_pairs, with a fixed LDS area after the diagonal block in both placements:
+//   [diagonal block 36 | Zuu 36 | Zuv 36 | Zvv 36 | Ju 36 | Jv 36 | S 36 | Omega / its factor 36 | e 6, flags 2 | Y ... ]
+// (the 6 x 6 areas hold rows of stride 6, S and Omega rows of stride d).  Same body, same order of operations: the placements agree bitwise.
+// req: kGateReq ints per candidate {the 8 of k_chol_marginal_pairs (length 0: no column), kind, index of u in pose, index of v in pose /
+// lmk, Omega given}.  in: [candidates][kGateIO] = z 7, pad, Omega 36.  out: [candidates][kGateIO] = d2, e 6, pad, S 36.
+// ------------------------------------------------------------------------------------------------
+constexpr int kGateReq = 12, kGateIO = 44;
+constexpr int kGateZuu = 36, kGateZuv = 72, kGateZvv = 108, kGateJu = 144, kGateJv = 180, kGateS = 216, kGateW = 252, kGateE = 288;
+constexpr int kGateFixed = 296;   // doubles of the fixed LDS area, the diagonal block included
+
+// in-place Cholesky of the d x d matrix A (rows of stride d, lower triangle read and written) by ONE lane; false: a pivot <= 0 or not finite
+__device__ __forceinline__ bool gate_chol_small(double* A, int d) {
+  for (int j = 0; j < d; ++j) {
+    double p = A[j * d + j];
+    for (int m = 0; m < j; ++m) p -= A[j * d + m] * A[j * d + m];
+    if (!(p > 0.0) || !isfinite(p)) return false;
+    p = sqrt(p);
+    A[j * d + j] = p;
+    for (int i = j + 1; i < d; ++i) {
+      double a = A[i * d + j];
+      for (int m = 0; m < j; ++m) a -= A[i * d + m] * A[j * d + m];
+      A[i * d + j] = a / p;
+    }
+  }
+  return true;
+}
+
+template <bool SCRATCH>
+__global__ __launch_bounds__(64) void k_chol_gate_pairs(CholView C, const int* __restrict__ req, const int* __restrict__ path_cols,
+                                                        const double* __restrict__ in, const double* __restrict__ pose,
+                                                        const double* __restrict__ lmk, double* __restrict__ out, int ylen, char* scratch) {
+  extern __shared__ double sm[];
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int* __restrict__ q = req + (size_t)r * kGateReq;
+  const int Pu = q[1], Pv = q[3], Du = q[4], Dv = q[5], nc = q[6];
+  const bool se3 = q[8] == SSLAM_GATE_SE3, has_info = q[11] != 0;
+  const int d = se3 ? 6 : 3;
+  const double* __restrict__ zin = in + (size_t)r * kGateIO;
+  double* o = out + (size_t)r * kGateIO;
+  double* sD = sm;
+  double* Y;
+  int4* prec;
+  int* pyoff;
+  if (SCRATCH) {
+    const int yl = Pu + Pv;
+    Y = reinterpret_cast<double*>(scratch + (size_t)q[7] * 16);
+    prec = reinterpret_cast<int4*>(Y + (size_t)yl * 36);
+    pyoff = reinterpret_cast<int*>(prec + yl);
+  } else {
+    Y = sm + kGateFixed;
+    prec = reinterpret_cast<int4*>(Y + (size_t)ylen * 36);
+    pyoff = reinterpret_cast<int*>(prec + ylen);
+  }
+  for (int k = 36 + lane; k < kGateFixed; k += 64) sm[k] = 0.0;
+  // 1. the two paths, each once; a side without a column is skipped whole
+  if (Pu > 0) marginal_path_forward(C, path_cols + q[0], Pu, Du, Y, sD, prec, pyoff);
+  if (Pv > 0) marginal_path_forward(C, path_cols + q[2], Pv, Dv, Y + (size_t)Pu * 36, sD, prec + Pu, pyoff + Pu);
+  __syncthreads();
+  // 2. Zuu, Zvv over the whole paths, Zuv over the common suffix (nc == 0: different components, or a side without a column)
+  if (lane < 36) {
+    const int a = lane / 6, c = lane - a * 6;
+    const double* Yu = Y;
+    const double* Yv = Y + (size_t)Pu * 36;
+    double zuu = 0, zvv = 0, zuv = 0;
+    if (a < Du && c < Du)
+      for (int t = 0; t < Pu; ++t)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) zuu += Yu[t * 36 + i * 6 + a] * Yu[t * 36 + i * 6 + c];
+    if (a < Dv && c < Dv)
+      for (int t = 0; t < Pv; ++t)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) zvv += Yv[t * 36 + i * 6 + a] * Yv[t * 36 + i * 6 + c];
+    if (a < Du && c < Dv) {
+      const double* Yus = Yu + (size_t)(Pu - nc) * 36;
+      const double* Yvs = Yv + (size_t)(Pv - nc) * 36;
+      for (int t = 0; t < nc; ++t)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) zuv += Yus[t * 36 + i * 6 + a] * Yvs[t * 36 + i * 6 + c];
+    }
+    sm[kGateZuu + lane] = zuu; sm[kGateZvv + lane] = zvv; sm[kGateZuv + lane] = zuv;
+  }
+  // 3. e and the Jacobians at the estimates the device holds
+  const Pose Xu = load_pose(pose, q[9]);
+  if (se3) {
+    const Pose Xv = load_pose(pose, q[10]);
+    const Pose Z{{zin[0], zin[1], zin[2]}, {zin[3], zin[4], zin[5], zin[6]}};
+    Se3Lin L;
+    se3_error(Xu, Xv, Z, L);
+    L.Re = qmat(L.qe);
+    if (lane < 12) {   // one lane per Jacobian column
+      double col[6];
+      if (lane < 6) se3_Ji_col(L, lane, col);
+      else se3_Jj_col(L, lane - 6, col);
+      double* J = sm + (lane < 6 ? kGateJu + lane : kGateJv + lane - 6);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) J[i * 6] = col[i];
+    } else if (lane == 12) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) sm[kGateE + i] = L.e[i];
+    }
+  } else {
+    const double* lp = lmk + (size_t)q[10] * 4;
+    PointLin L;
+    point_error(Xu, Vec3{lp[0], lp[1], lp[2]}, Vec3{zin[0], zin[1], zin[2]}, L);
+    if (lane == 0) {
+      double Ji[18], Jl[9];
+      point_jacobians(L, Ji, Jl);
+#pragma unroll
+      for (int k = 0; k < 18; ++k) sm[kGateJu + k] = Ji[k];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) sm[kGateJv + (k / 3) * 6 + k % 3] = Jl[k];
+    } else if (lane == 12) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) sm[kGateE + i] = L.e[i];
+    }
+  }
+  // 4. Omega^-1: Cholesky by one lane, then one lane per column of the inverse -> sD (free after the paths)
+  if (has_info && lane < d * d) sm[kGateW + lane] = zin[8 + lane];
+  __syncthreads();
+  if (has_info && lane == 0) sm[kGateE + 6] = gate_chol_small(sm + kGateW, d) ? 1.0 : 0.0;
+  __syncthreads();
+  const bool w_ok = !has_info || sm[kGateE + 6] != 0.0;
+  if (has_info && w_ok && lane < d) {
+    const double* W = sm + kGateW;
+    double x[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {   // L y = unit vector `lane`
+      if (i < d) {
+        double a = i == lane ? 1.0 : 0.0;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) if (m < i) a -= W[i * d + m] * x[m];
+        x[i] = a / W[i * d + i];
+      }
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {   // L^T x = y
+      if (i < d) {
+        double a = x[i];
+#pragma unroll
+        for (int m = 5; m >= 0; --m) if (m > i && m < d) a -= W[m * d + i] * x[m];
+        x[i] = a / W[i * d + i];
+        sD[i * d + lane] = x[i];
+      }
+    }
+  }
+  __syncthreads();
+  // S by lanes < d * d; entry (r, c) and entry (c, r) run the same sums: S is symmetric to the bit
+  if (lane < 36) {
+    double s = 0;
+    if (lane < d * d) {
+      const int r0 = lane / d, c0 = lane - r0 * d;
+      const int hi = r0 > c0 ? r0 : c0, lo = r0 > c0 ? c0 : r0;
+      const double *Ju = sm + kGateJu, *Jv = sm + kGateJv;
+      for (int a = 0; a < Du; ++a)
+        for (int c = 0; c < Du; ++c) s += Ju[hi * 6 + a] * sm[kGateZuu + a * 6 + c] * Ju[lo * 6 + c];
+      for (int a = 0; a < Du; ++a)
+        for (int c = 0; c < Dv; ++c) s += Ju[hi * 6 + a] * sm[kGateZuv + a * 6 + c] * Jv[lo * 6 + c];
+      for (int a = 0; a < Dv; ++a)
+        for (int c = 0; c < Du; ++c) s += Jv[hi * 6 + a] * sm[kGateZuv + c * 6 + a] * Ju[lo * 6 + c];
+      for (int a = 0; a < Dv; ++a)
+        for (int c = 0; c < Dv; ++c) s += Jv[hi * 6 + a] * sm[kGateZvv + a * 6 + c] * Jv[lo * 6 + c];
+      if (has_info && w_ok) s += sD[hi * d + lo];
+      sm[kGateS + lane] = s;
+    }
+    o[8 + lane] = s;
+  }
+  __syncthreads();
+  // 5. Cholesky of S, forward substitution, d2 = |L^-1 e|^2
+  if (lane == 0) {
+    double* S = sm + kGateS;
+    double* y = sm + kGateW;
+    double d2 = __longlong_as_double(0x7ff8000000000000ll);   // NaN: Omega or S broke down
+    if (w_ok && gate_chol_small(S, d)) {
+      d2 = 0;
+      for (int i = 0; i < d; ++i) {
+        double a = sm[kGateE + i];
+        for (int m = 0; m < i; ++m) a -= S[i * d + m] * y[m];
+        y[i] = a / S[i * d + i];
+        d2 += y[i] * y[i];
+      }
+    }
+    o[0] = d2;
+    o[7] = 0.0;
+  } else if (lane <= 6) {
+    o[lane] = lane - 1 < d ? sm[kGateE + lane - 1] : 0.0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // One LM iteration of a SMALL graph after its linearisation, in ONE launch (the orchestrator's tick re-optimises a
 // graph of a few hundred vertices 25-40 trials per tick, and ~65 launches per trial made the MI355X slower than one host core).
 // One workgroup per graph whose whole elimination tree is walked by the tail kernels (plans with no per-depth launches):
@@ -2165,6 +2364,16 @@ int chol_backward(Batch& b) {
   return 0;
 }
 
+// Device scratch of the path kernels (marginals, gate): out of the graph handle's arena when there is one (a plan is rebuilt every tick of
+// the orchestrator: no hipMalloc / hipFree pair per tick), else the plan's own allocations
+static int plan_grow(CholPlan& P, void** p, size_t& cap, size_t bytes) {
+  if (cap >= bytes) return 0;
+  bytes += bytes / 4 + 4096;
+  if (P.arena) { *p = P.arena->take(bytes, true); cap = *p ? bytes : 0; if (!*p) return set_error(SSLAM_ERR_HIP, "device allocation of %zu bytes failed", bytes); }
+  else { if (*p) (void)hipFree(*p); *p = nullptr; cap = 0; SSLAM_HIP_TRY(hipMalloc(p, bytes)); cap = bytes; }
+  return 0;
+}
+
 // Z(u, v) of (L L^T)^-1 for pairs of vertices of the graphs of a batch (k_chol_marginal_pairs), from the last FLAT factorisation; out:
 // [n][36], the leading dim_u x dim_v entries row-major.  Any path length: a request whose Y fits the LDS budget (SSLAM_MARGINAL_LDS_BYTES,
 // read per call; default and ceiling 60 KB) runs out of LDS, every other one out of its slice of a device scratch buffer -- one upload, at
@@ -2181,15 +2390,7 @@ int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double*
   auto col_of = [&](int xo) { return (xo >= 0 && xo < (int)P.h_xoff_col.size()) ? P.h_xoff_col[xo] : -1; };
   for (const MarginalReq& rq : reqs)
     if (col_of(rq.xoff_u) < 0 || col_of(rq.xoff_v) < 0) return set_error(SSLAM_ERR_INVALID, "marginal of an unknown that is not the start of a block row");
-  // device scratch: out of the graph handle's arena when there is one (a plan is rebuilt every tick of the orchestrator: no hipMalloc /
-  // hipFree pair per tick), else the plan's own allocations
-  auto grow = [&](void** p, size_t& cap, size_t bytes) -> int {
-    if (cap >= bytes) return 0;
-    bytes += bytes / 4 + 4096;
-    if (P.arena) { *p = P.arena->take(bytes, true); cap = *p ? bytes : 0; if (!*p) return set_error(SSLAM_ERR_HIP, "device allocation of %zu bytes failed", bytes); }
-    else { if (*p) (void)hipFree(*p); *p = nullptr; cap = 0; SSLAM_HIP_TRY(hipMalloc(p, bytes)); cap = bytes; }
-    return 0;
-  };
+  auto grow = [&](void** p, size_t& cap, size_t bytes) { return plan_grow(P, p, cap, bytes); };
   constexpr size_t kPathCap = (size_t)16 << 20, kScratchCap = (size_t)1 << 30;   // ints of path lists, bytes of Y slices per round
   constexpr size_t kEntry = 36 * sizeof(double) + sizeof(int4) + sizeof(int);      // Y block, path record, y offset of one path entry
   struct Rec { int v[8]; size_t src; bool scratch; };
@@ -2254,6 +2455,94 @@ int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double*
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "pair marginals launch: %s", hipGetErrorString(e));
     for (int i = 0; i < m; ++i) std::copy(res + (size_t)i * 36, res + (size_t)i * 36 + 36, out + recs[i].src * 36);
+    k0 = k;
+  }
+  return 0;
+}
+
+// The gate of candidate edges (k_chol_gate_pairs) from the last FLAT factorisation.  in / out: [n][44], see the kernel.  The rounds, the
+// placement rule and the staging are those of chol_marginal_blocks; the LDS of a candidate counts the kernel's fixed area, and a side with
+// xoff < 0 (fixed or edge-less) has a path of length 0.
+int chol_gate_pairs(Batch& b, const std::vector<GateReq>& reqs, const double* in, double* out) {
+  CholPlan& P = *b.chol;
+  const CholView& C = P.C;
+  const size_t n = reqs.size();
+  if (n == 0) return 0;
+  if (!C.flat_L) return set_error(SSLAM_ERR_INVALID, "chol_gate_pairs needs the flat factor (chol_factor_and_forward(b, true))");
+  size_t budget = 60 * 1024;
+  if (const char* e = getenv("SSLAM_MARGINAL_LDS_BYTES")) budget = (size_t)std::min<long long>(std::max<long long>(atoll(e), 0), 60 * 1024);
+  auto col_of = [&](int xo) { return (xo >= 0 && xo < (int)P.h_xoff_col.size()) ? P.h_xoff_col[xo] : -1; };
+  for (const GateReq& rq : reqs)
+    if ((rq.xoff_u >= 0 && col_of(rq.xoff_u) < 0) || (rq.xoff_v >= 0 && col_of(rq.xoff_v) < 0))
+      return set_error(SSLAM_ERR_INVALID, "gate of an unknown that is not the start of a block row");
+  constexpr size_t kPathCap = (size_t)16 << 20, kScratchCap = (size_t)1 << 30;
+  constexpr size_t kEntry = 36 * sizeof(double) + sizeof(int4) + sizeof(int);
+  constexpr size_t kFixed = kGateFixed * sizeof(double);
+  struct Rec { int v[kGateReq]; size_t src; bool scratch; };
+  std::vector<Rec> recs;
+  std::vector<int> cols, up;
+  for (size_t k0 = 0; k0 < n;) {
+    recs.clear(); cols.clear();
+    size_t scr_bytes = 0, k = k0;
+    int ylen_lds = 0, n_lds = 0;
+    for (; k < n && (k == k0 || (cols.size() < kPathCap && scr_bytes < kScratchCap)); ++k) {
+      const GateReq& rq = reqs[k];
+      Rec q{};
+      q.src = k;
+      q.v[0] = (int)cols.size();
+      for (int j = col_of(rq.xoff_u); j >= 0; j = P.h_cparent[j]) cols.push_back(j);
+      q.v[1] = (int)cols.size() - q.v[0];
+      q.v[2] = (int)cols.size();
+      for (int j = col_of(rq.xoff_v); j >= 0; j = P.h_cparent[j]) cols.push_back(j);
+      q.v[3] = (int)cols.size() - q.v[2];
+      q.v[4] = rq.dim_u; q.v[5] = rq.dim_v;
+      int nc = 0;   // common suffix of the two paths (none when a side has no column)
+      while (nc < q.v[1] && nc < q.v[3] && cols[q.v[0] + q.v[1] - 1 - nc] == cols[q.v[2] + q.v[3] - 1 - nc]) ++nc;
+      q.v[6] = nc;
+      q.v[8] = rq.kind; q.v[9] = rq.idx_u; q.v[10] = rq.idx_v; q.v[11] = rq.has_info;
+      const int ylen = q.v[1] + q.v[3];
+      q.scratch = kFixed + (size_t)ylen * kEntry + 16 > budget;
+      if (q.scratch) { q.v[7] = (int)(scr_bytes / 16); scr_bytes += ((size_t)ylen * kEntry + 15) & ~(size_t)15; }
+      else { ylen_lds = std::max(ylen_lds, ylen); ++n_lds; }
+      recs.push_back(q);
+    }
+    const int m = (int)recs.size(), n_scr = m - n_lds;
+    std::stable_partition(recs.begin(), recs.end(), [](const Rec& r) { return !r.scratch; });   // [LDS candidates | scratch candidates]
+    up.resize((size_t)m * kGateReq + cols.size());
+    for (int i = 0; i < m; ++i) std::copy(recs[i].v, recs[i].v + kGateReq, up.begin() + (size_t)i * kGateReq);
+    std::copy(cols.begin(), cols.end(), up.begin() + (size_t)m * kGateReq);
+    int rc;
+    const size_t io_bytes = (size_t)m * kGateIO * sizeof(double);
+    size_t mpath_bytes = P.mpath_cap * sizeof(int), mout_bytes = P.mout_cap * sizeof(double);
+    if ((rc = plan_grow(P, (void**)&P.d_mpath, mpath_bytes, up.size() * sizeof(int)))) return rc;
+    P.mpath_cap = mpath_bytes / sizeof(int);
+    if ((rc = plan_grow(P, (void**)&P.d_mout, mout_bytes, io_bytes))) return rc;
+    P.mout_cap = mout_bytes / sizeof(double);
+    if ((rc = plan_grow(P, (void**)&P.d_gin, P.gin_cap, io_bytes))) return rc;
+    if (n_scr > 0 && (rc = plan_grow(P, (void**)&P.d_mscratch, P.mscratch_cap, scr_bytes))) return rc;
+    const size_t rec_bytes = (up.size() * sizeof(int) + 7) & ~(size_t)7;
+    char* stage = b.pin->get(rec_bytes + 2 * io_bytes);
+    std::vector<char> fallback;
+    if (!stage) { fallback.resize(rec_bytes + 2 * io_bytes); stage = fallback.data(); }
+    memcpy(stage, up.data(), up.size() * sizeof(int));
+    double* zin = reinterpret_cast<double*>(stage + rec_bytes);
+    double* res = zin + (size_t)m * kGateIO;
+    for (int i = 0; i < m; ++i) std::copy(in + recs[i].src * kGateIO, in + (recs[i].src + 1) * kGateIO, zin + (size_t)i * kGateIO);
+    SSLAM_HIP_TRY(hipMemcpyAsync(P.d_mpath, stage, up.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
+    SSLAM_HIP_TRY(hipMemcpyAsync(P.d_gin, zin, io_bytes, hipMemcpyHostToDevice, b.stream));
+    const int* d_cols = P.d_mpath + (size_t)m * kGateReq;
+    if (n_lds > 0)
+      hipLaunchKernelGGL(k_chol_gate_pairs<false>, dim3(n_lds), dim3(64), kFixed + (size_t)ylen_lds * kEntry + 16, b.stream, C, (const int*)P.d_mpath,
+                         d_cols, (const double*)P.d_gin, (const double*)b.V.pose, (const double*)b.V.lmk, P.d_mout, ylen_lds, (char*)nullptr);
+    if (n_scr > 0)
+      hipLaunchKernelGGL(k_chol_gate_pairs<true>, dim3(n_scr), dim3(64), kFixed, b.stream, C, (const int*)(P.d_mpath + (size_t)n_lds * kGateReq), d_cols,
+                         (const double*)(P.d_gin + (size_t)n_lds * kGateIO), (const double*)b.V.pose, (const double*)b.V.lmk,
+                         P.d_mout + (size_t)n_lds * kGateIO, 0, P.d_mscratch);
+    SSLAM_HIP_TRY(hipMemcpyAsync(res, P.d_mout, io_bytes, hipMemcpyDeviceToHost, b.stream));
+    SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // up and the staging are reused by the next round
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "gate launch: %s", hipGetErrorString(e));
+    for (int i = 0; i < m; ++i) std::copy(res + (size_t)i * kGateIO, res + (size_t)(i + 1) * kGateIO, out + recs[i].src * kGateIO);
     k0 = k;
   }
   return 0;

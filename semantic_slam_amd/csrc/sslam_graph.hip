@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -2531,28 +2532,17 @@ int sslam_batch_optimize(sslam_batch* h, int max_iters, sslam_opt_stats* out) {
   return batch_optimize(h->b, max_iters, out);
 }
 // ---- covariance blocks of the graphs of a batch -------------------------------------------------------------------------------
-// Blocks of H^-1 for (graph, row vertex, column vertex) requests of ONE batch (a part of a stream group): linearise once at the estimates the
-// device holds, factor the undamped H flat (factor_undamped_flat, shared with the single-graph marginal_blocks), then one
-// wave per request along the elimination-tree paths (chol_marginal_blocks).  The per-graph LM states are borrowed -- the linearisation wants
-// every graph at the start of an iteration, the factorisation every graph in a trial at lambda 0 -- and put back; H, b, y and the factor
-// are rebuilt by the first step of whatever runs next, the estimates are only read.  out: [n][36].
-static int batch_marginals(Batch& b, const std::vector<std::array<int, 3>>& req, double* out) {
-  if (req.empty()) return 0;
+// What the path kernels (marginals, gate) cannot serve: the iterative solvers have no factor to walk, an edge shard only a partial H.
+static int batch_direct_only(const Batch& b, const char* what) {
   const int solver = b.graphs[0]->opt.solver;
-  if (solver == 0 || solver == 2) return set_error(SSLAM_ERR_UNSUPPORTED, "sslam_batch_marginals: direct solvers only (solver %d)", solver);
-  if (b.sharded) return set_error(SSLAM_ERR_UNSUPPORTED, "sslam_batch_marginals is not available in the edge-sharded mode");
+  if (solver == 0 || solver == 2) return set_error(SSLAM_ERR_UNSUPPORTED, "sslam_batch_%s: direct solvers only (solver %d)", what, solver);
+  if (b.sharded) return set_error(SSLAM_ERR_UNSUPPORTED, "sslam_batch_%s is not available in the edge-sharded mode", what);
+  return 0;
+}
+// The shared first half of batch_marginals and batch_gate: the flat factor of the undamped H of every graph at the estimates the device
+// holds, then body() while the LM states are still borrowed.  `what` names the caller in the messages.
+static int batch_with_flat_factor(Batch& b, const char* what, const std::function<int()>& body) {
   SSLAM_HIP_TRY(hipSetDevice(b.device));
-  std::vector<MarginalReq> mr;
-  std::vector<int> slot(req.size(), -1);
-  for (size_t k = 0; k < req.size(); ++k) {
-    const int g = req[k][0], vr = req[k][1], vc = req[k][2];
-    const int xr = vertex_xoff(b, g, vr), xc = vertex_xoff(b, g, vc);
-    if (xr < 0 || xc < 0) continue;
-    slot[k] = (int)mr.size();
-    mr.push_back({xr, vertex_dim(b.graphs[g]->vtype[vr]), xc, vertex_dim(b.graphs[g]->vtype[vc])});
-  }
-  std::fill(out, out + req.size() * 36, 0.0);
-  if (mr.empty()) return 0;
   int rc;
   if (!b.uploaded && (rc = batch_upload_estimates(b))) return rc;
   if ((rc = chol_set_active(b, nullptr))) return rc;   // a stale compaction (an optimise that failed half way) must not leave graphs out
@@ -2568,12 +2558,36 @@ static int batch_marginals(Batch& b, const std::vector<std::array<int, 3>>& req,
   if ((rc = batch_linearize(b))) return rc;   // undamped H at the current estimates
   int bad;
   if ((rc = factor_undamped_flat(b, &bad))) return rc;
-  if (bad >= 0) return set_error(SSLAM_ERR_NUMERIC, "H of graph %d of the batch is not positive definite: no marginals", bad);
-  std::vector<double> Z(mr.size() * 36);
-  if ((rc = chol_marginal_blocks(b, mr, Z.data()))) return rc;
-  for (size_t k = 0; k < req.size(); ++k)
-    if (slot[k] >= 0) std::copy(Z.begin() + (size_t)slot[k] * 36, Z.begin() + (size_t)slot[k] * 36 + 36, out + k * 36);
-  return 0;
+  if (bad >= 0) return set_error(SSLAM_ERR_NUMERIC, "H of graph %d of the batch is not positive definite: no %s", bad, what);
+  return body();
+}
+
+// Blocks of H^-1 for (graph, row vertex, column vertex) requests of ONE batch (a part of a stream group): linearise once at the estimates the
+// device holds, factor the undamped H flat (factor_undamped_flat, shared with the single-graph marginal_blocks), then one
+// wave per request along the elimination-tree paths (chol_marginal_blocks).  The per-graph LM states are borrowed -- the linearisation wants
+// every graph at the start of an iteration, the factorisation every graph in a trial at lambda 0 -- and put back; H, b, y and the factor
+// are rebuilt by the first step of whatever runs next, the estimates are only read.  out: [n][36].
+static int batch_marginals(Batch& b, const std::vector<std::array<int, 3>>& req, double* out) {
+  if (req.empty()) return 0;
+  if (const int rc = batch_direct_only(b, "marginals")) return rc;
+  std::vector<MarginalReq> mr;
+  std::vector<int> slot(req.size(), -1);
+  for (size_t k = 0; k < req.size(); ++k) {
+    const int g = req[k][0], vr = req[k][1], vc = req[k][2];
+    const int xr = vertex_xoff(b, g, vr), xc = vertex_xoff(b, g, vc);
+    if (xr < 0 || xc < 0) continue;
+    slot[k] = (int)mr.size();
+    mr.push_back({xr, vertex_dim(b.graphs[g]->vtype[vr]), xc, vertex_dim(b.graphs[g]->vtype[vc])});
+  }
+  std::fill(out, out + req.size() * 36, 0.0);
+  if (mr.empty()) return 0;
+  return batch_with_flat_factor(b, "marginals", [&]() -> int {
+    std::vector<double> Z(mr.size() * 36);
+    if (const int rc = chol_marginal_blocks(b, mr, Z.data())) return rc;
+    for (size_t k = 0; k < req.size(); ++k)
+      if (slot[k] >= 0) std::copy(Z.begin() + (size_t)slot[k] * 36, Z.begin() + (size_t)slot[k] * 36 + 36, out + k * 36);
+    return 0;
+  });
 }
 
 int sslam_batch_marginals(sslam_batch* h, const int32_t* req, int n, double* out) {
@@ -2614,6 +2628,97 @@ int sslam_batch_marginals(sslam_batch* h, const int32_t* req, int n, double* out
       const int k = psrc[p][i];
       std::copy(pz[p].begin() + i * 36, pz[p].begin() + i * 36 + (size_t)dr[k] * dc[k], out + off[k]);
     }
+  return 0;
+}
+// ---- loop-closure gate: Mahalanobis distance of candidate edges ---------------------------------------------------------------------
+// One candidate against its host graph, before anything runs.  k: its number in the call (messages).
+static int gate_check(const HostGraph& G, int k, int kind, int vu, int vv, const double* z, const double* info) {
+  if (kind != SSLAM_GATE_SE3 && kind != SSLAM_GATE_SE3_POINT) return set_error(SSLAM_ERR_INVALID, "candidate %d: unknown kind %d", k, kind);
+  if (vu < 0 || vu >= G.nv() || vv < 0 || vv >= G.nv() || vu == vv) return set_error(SSLAM_ERR_INVALID, "candidate %d: vertex ids (%d, %d) invalid", k, vu, vv);
+  if (G.vtype[vu] != VT_SE3 || G.vtype[vv] != (kind == SSLAM_GATE_SE3 ? VT_SE3 : VT_POINT))
+    return set_error(SSLAM_ERR_INVALID, "candidate %d: a vertex of (%d, %d) has the wrong type for this kind of edge", k, vu, vv);
+  const int nz = kind == SSLAM_GATE_SE3 ? 7 : 3, d = kind == SSLAM_GATE_SE3 ? 6 : 3;
+  for (int i = 0; i < nz; ++i) if (!std::isfinite(z[i])) return set_error(SSLAM_ERR_INVALID, "candidate %d: the measurement has a non-finite entry", k);
+  if (kind == SSLAM_GATE_SE3 && !(z[3] * z[3] + z[4] * z[4] + z[5] * z[5] + z[6] * z[6] > 0)) return set_error(SSLAM_ERR_INVALID, "candidate %d: quaternion of zero norm", k);
+  if (info) for (int i = 0; i < d * d; ++i) if (!std::isfinite(info[i])) return set_error(SSLAM_ERR_INVALID, "candidate %d: the information matrix has a non-finite entry", k);
+  return 0;
+}
+// the candidate's record for chol_gate_pairs, and its measurement in the kernel's layout (io: 44 doubles)
+static GateReq gate_request(const Batch& b, int g, int kind, int vu, int vv, const double* z, const double* info, double* io) {
+  const bool se3 = kind == SSLAM_GATE_SE3;
+  std::fill(io, io + 44, 0.0);
+  std::copy(z, z + (se3 ? 7 : 3), io);
+  if (info) std::copy(info, info + (se3 ? 36 : 9), io + 8);
+  return {vertex_xoff(b, g, vu), 6, vertex_xoff(b, g, vv), se3 ? 6 : 3, kind, b.v2pose[g][vu], se3 ? b.v2pose[g][vv] : b.v2lm[g][vv], info ? 1 : 0};
+}
+// d2, e and S of candidate k out of the kernel's record
+static void gate_result(const double* io, int k, double* d2_out, double* e_out, double* cov_out) {
+  d2_out[k] = io[0];
+  if (e_out) std::copy(io + 1, io + 7, e_out + (size_t)k * 6);
+  if (cov_out) std::copy(io + 8, io + 44, cov_out + (size_t)k * 36);
+}
+// The candidates of ONE batch (a part of a stream group): the flat factor as batch_marginals takes it, then one wave per candidate.
+static int batch_gate(Batch& b, const std::vector<GateReq>& req, const double* in, double* out) {
+  if (req.empty()) return 0;
+  if (const int rc = batch_direct_only(b, "gate")) return rc;
+  return batch_with_flat_factor(b, "gate", [&]() -> int { return chol_gate_pairs(b, req, in, out); });
+}
+
+int sslam_batch_gate(sslam_batch* h, const int32_t* cand, const double* z, const double* info, int n, double* d2_out, double* e_out, double* cov_out) {
+  if (!h || n < 0 || (n > 0 && (!cand || !z || !d2_out))) return set_error(SSLAM_ERR_INVALID, "null argument");
+  int rc = batch_check(h);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  const bool group = !h->parts.empty();
+  const int K = group ? (int)h->parts.size() : 1;
+  const int ng = group ? h->part0.back() : (int)h->b.graphs.size();
+  auto part_batch = [&](int k) -> Batch& { return group ? h->parts[k]->b : h->b; };
+  // every candidate is checked before anything runs: a bad one leaves the outputs unwritten
+  std::vector<std::vector<GateReq>> preq(K);
+  std::vector<std::vector<double>> pin(K), pout(K);
+  std::vector<std::vector<int>> psrc(K);
+  for (int k = 0; k < n; ++k) {
+    const int g = cand[4 * k], kind = cand[4 * k + 1], vu = cand[4 * k + 2], vv = cand[4 * k + 3];
+    if (g < 0 || g >= ng) return set_error(SSLAM_ERR_INVALID, "candidate %d: graph index %d out of range (the batch holds %d graphs)", k, g, ng);
+    int p = 0;
+    if (group) p = (int)(std::upper_bound(h->part0.begin(), h->part0.end(), g) - h->part0.begin()) - 1;
+    const int gl = group ? g - h->part0[p] : g;
+    const Batch& pb = part_batch(p);
+    const double *zk = z + (size_t)k * 7, *wk = info ? info + (size_t)k * 36 : nullptr;
+    if ((rc = gate_check(*pb.graphs[gl], k, kind, vu, vv, zk, wk))) return rc;
+    pin[p].resize(pin[p].size() + 44);
+    preq[p].push_back(gate_request(pb, gl, kind, vu, vv, zk, wk, pin[p].data() + pin[p].size() - 44));
+    psrc[p].push_back(k);
+  }
+  // the parts of a stream group one after the other, from the calling thread
+  auto run = [&](int p) { pout[p].resize(pin[p].size() + 1); return batch_gate(part_batch(p), preq[p], pin[p].data(), pout[p].data()); };
+  if (group) rc = for_each_part(h, false, [&](sslam_batch*, int p) { return run(p); });
+  else rc = run(0);
+  if (rc) return rc;
+  for (int p = 0; p < K; ++p)
+    for (size_t i = 0; i < psrc[p].size(); ++i) gate_result(pout[p].data() + i * 44, psrc[p][i], d2_out, e_out, cov_out);
+  return 0;
+}
+
+// The single-graph handle: its batch of one, linearised at the host estimates as marginal_blocks does, then the same factor and kernel.
+int sslam_graph_gate(sslam_graph* h, const int32_t* cand, const double* z, const double* info, int n, double* d2_out, double* e_out, double* cov_out) {
+  if (!h || n < 0 || (n > 0 && (!cand || !z || !d2_out))) return set_error(SSLAM_ERR_INVALID, "null argument");
+  if (n == 0) return 0;
+  int rc;
+  for (int k = 0; k < n; ++k)
+    if ((rc = gate_check(h->g, k, cand[3 * k], cand[3 * k + 1], cand[3 * k + 2], z + (size_t)k * 7, info ? info + (size_t)k * 36 : nullptr))) return rc;
+  if (h->g.opt.solver == 0 || h->g.opt.solver == 2) return set_error(SSLAM_ERR_UNSUPPORTED, "sslam_graph_gate: direct solvers only (solver %d)", h->g.opt.solver);
+  if ((rc = do_linearize(h))) return rc;  // undamped H at the current estimates
+  Batch& b = *h->batch;
+  int bad;
+  if ((rc = factor_undamped_flat(b, &bad))) return rc;
+  if (bad >= 0) return set_error(SSLAM_ERR_NUMERIC, "H is not positive definite: no gate");
+  std::vector<GateReq> req;
+  std::vector<double> in((size_t)n * 44), out((size_t)n * 44);
+  for (int k = 0; k < n; ++k)
+    req.push_back(gate_request(b, 0, cand[3 * k], cand[3 * k + 1], cand[3 * k + 2], z + (size_t)k * 7, info ? info + (size_t)k * 36 : nullptr, in.data() + (size_t)k * 44));
+  if ((rc = chol_gate_pairs(b, req, in.data(), out.data()))) return rc;
+  for (int k = 0; k < n; ++k) gate_result(out.data() + (size_t)k * 44, k, d2_out, e_out, cov_out);
   return 0;
 }
 // ---- one linear solve of every graph of a batch (parity hook) --------------------------------------------------------------------

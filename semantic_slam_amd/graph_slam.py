@@ -50,6 +50,10 @@ def _pose7(pose) -> np.ndarray:
 ROBUST_KERNELS = {"NONE": 0, "Huber": 1, "PseudoHuber": 2, "Cauchy": 3, "Welsch": 4, "Fair": 5, "Saturated": 6, "DCS": 7}
 
 
+# candidate kinds of the loop-closure gate -> SSLAM_GATE_*
+GATE_KINDS = {"se3": 0, "point": 1}
+
+
 class GraphSLAM:
     """``ps_graph_slam::GraphSLAM`` on one MI355X (graph_slam.cpp:40-97)."""
 
@@ -215,6 +219,29 @@ class GraphSLAM:
             res[(int(r), int(c))] = out[o:o + a * b].reshape(a, b).copy()
             o += a * b
         return res
+
+    # -- loop-closure gate -------------------------------------------------------------------
+    def _gate(self, kind: int, v_from: int, v_to: int, z7: np.ndarray, information, d: int) -> float:
+        cand = np.array([kind, int(v_from), int(v_to)], np.int32)
+        w = None
+        if information is not None:
+            w = np.zeros(36)
+            w[:d * d] = np.ascontiguousarray(information, np.float64).reshape(d * d)
+        d2 = np.zeros(1)
+        _check(self._lib, self._lib.sslam_graph_gate(self._h, cand.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(z7),
+                                                     _dptr(w) if w is not None else None, 1, _dptr(d2), None, None))
+        return float(d2[0])
+
+    def gate_se3(self, v1: int, v2: int, relative_pose, information=None) -> float:
+        """sslam_graph_gate: squared Mahalanobis distance of a candidate EdgeSE3 (arguments of add_se3_edge) that is not in the graph, in
+        S = J Sigma J^T + information^-1 at the current estimates; information None: in J Sigma J^T alone.  NaN when S is singular."""
+        return self._gate(GATE_KINDS["se3"], v1, v2, _pose7(relative_pose), information, 6)
+
+    def gate_point(self, v_se3: int, v_xyz: int, xyz, information=None) -> float:
+        """the same for a candidate EdgeSE3PointXYZ (arguments of add_se3_point_xyz_edge)"""
+        z = np.zeros(7)
+        z[:3] = np.ascontiguousarray(xyz, np.float64).reshape(3)
+        return self._gate(GATE_KINDS["point"], v_se3, v_xyz, z, information, 3)
 
     def save(self, filename: str) -> None:
         """graph_slam.cpp:236-239 (g2o text format)"""
@@ -383,6 +410,66 @@ class GraphBatch:
             blocks.append(out[o:o + a * b].reshape(a, b).copy())
             o += a * b
         return blocks
+
+    # -- loop-closure gate -----------------------------------------------------------------------
+    def _candidate_arrays(self, candidates):
+        """(graph, "se3" | "point", v_from, v_to, z, info or None) tuples -> cand [n, 4] int32, z [n, 7], info (36 or None per candidate) and the
+        dimensions, checked before any C call"""
+        cand, zs, ws, dims = [], [], [], []
+        for k, c in enumerate(candidates):
+            try:
+                g, kind, vu, vv, z, info = c
+            except (TypeError, ValueError):
+                raise ValueError(f"candidate {k}: expected (graph, kind, v_from, v_to, z, info), got {c!r}") from None
+            for x in (g, vu, vv):
+                if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                    raise TypeError(f"candidate {k}: graph index and vertex ids are integers, got {(g, vu, vv)!r}")
+            if not 0 <= g < len(self.graphs):
+                raise IndexError(f"candidate {k}: graph index {g} out of range (the batch holds {len(self.graphs)} graphs)")
+            if not isinstance(kind, str) or kind not in GATE_KINDS:
+                raise ValueError(f"candidate {k}: unknown kind {kind!r} (known: {', '.join(GATE_KINDS)})")
+            d, nz = (6, 7) if kind == "se3" else (3, 3)
+            z = np.asarray(z, np.float64)
+            if z.shape != (nz,):
+                raise ValueError(f"candidate {k}: the measurement of a '{kind}' candidate has {nz} numbers, got shape {z.shape}")
+            z7 = np.zeros(7)
+            z7[:nz] = z
+            w = None
+            if info is not None:
+                info = np.asarray(info, np.float64)
+                if info.shape != (d, d):
+                    raise ValueError(f"candidate {k}: the information matrix of a '{kind}' candidate is {d}x{d}, got shape {info.shape}")
+                w = np.zeros(36)
+                w[:d * d] = info.reshape(-1)
+            cand.append((int(g), GATE_KINDS[kind], int(vu), int(vv)))
+            zs.append(z7)
+            ws.append(w)
+            dims.append(d)
+        return np.array(cand, np.int32).reshape(-1, 4), np.array(zs, np.float64).reshape(-1, 7), ws, dims
+
+    def gate(self, candidates, return_cov: bool = False):
+        """sslam_batch_gate: squared Mahalanobis distances of candidate edges that are not in their graphs, at the estimates the batch
+        holds on the device.  A candidate is (graph, "se3" | "point", v_from, v_to, z, info or None) with z = [t, q(xyzw)] / xyz and info
+        6x6 / 3x3 (None: the distance in J Sigma J^T alone; the candidates with and those without an information matrix go in a C call
+        each).  Returns d2 (float64, NaN where S is singular); with ``return_cov`` also the lists of the errors e and of the d x d matrices S."""
+        cand, z, ws, dims = self._candidate_arrays(candidates)
+        n = len(cand)
+        d2, e, S = np.zeros(n), np.zeros((n, 6)), np.zeros((n, 36))
+        for with_info in (True, False):
+            idx = [k for k in range(n) if (ws[k] is not None) == with_info]
+            if not idx:
+                continue
+            c, zz = np.ascontiguousarray(cand[idx]), np.ascontiguousarray(z[idx])
+            w = np.ascontiguousarray([ws[k] for k in idx], np.float64) if with_info else None
+            m = len(idx)
+            pd2, pe, pS = np.zeros(m), np.zeros((m, 6)), np.zeros((m, 36))
+            _check(self._lib, self._lib.sslam_batch_gate(self._h, c.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(zz),
+                                                         _dptr(w) if with_info else None, m, _dptr(pd2),
+                                                         _dptr(pe) if return_cov else None, _dptr(pS) if return_cov else None))
+            d2[idx], e[idx], S[idx] = pd2, pe, pS
+        if not return_cov:
+            return d2
+        return d2, [e[k, :d].copy() for k, d in enumerate(dims)], [S[k, :d * d].reshape(d, d).copy() for k, d in enumerate(dims)]
 
     def landmark_marginals(self, ids_per_graph):
         """diagonal blocks of H^-1 for the listed vertices of every graph: ``ids_per_graph[g]`` -> list of blocks, one list per graph"""
