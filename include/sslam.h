@@ -5,6 +5,7 @@
  * reference interface it replaces (paths relative to the reference repository root).
  * The C++ shims that give these the reference's own method names live in
  *   include/ps_graph_slam_amd/graph_slam.hpp              (ps_graph_slam::GraphSLAM)
+ *   include/ps_graph_slam_amd/information_matrix_calculator.hpp (ps_graph_slam::InformationMatrixCalculator)
  *   include/planar_segmentation_amd/point_cloud_segmentation.hpp (point_cloud_segmentation)
  * and INTEGRATION.md shows the binding a maintainer of the reference would add.
  *
@@ -523,6 +524,52 @@ int sslam_seg_statistical_outlier_removal(sslam_seg* s, const float* xyz, int n,
  * labels_out[n], centers_out[k * dim]; returns k. */
 int sslam_seg_kmeans(sslam_seg* s, const float* pts, int n, int dim, int k, uint64_t seed, int32_t* labels_out, float* centers_out, double* compactness_out);
 
+/* ---- fitness score of cloud pairs and the information matrix it gives (hdl_graph_slam's InformationMatrixCalculator [UPSTREAM]; the
+ * reference keeps its weight() at information_matrix_calculator.hpp:20-24 and has the score stubbed to 0.9 at
+ * information_matrix_calculator.cpp:37, `//calc_fitness_score(cloud1, cloud2, relpose)`) ----------------------------------------------
+ * sslam_seg_fitness_scores: for every pair, every point of the source cloud moved by T looks up its NEAREST point of the target cloud
+ * (exact search, k_nn_pairs); the score is the mean of the squared distances that do not exceed max_range.
+ * xyz: the clouds one after the other, 3 floats per point; cloud c holds the points cloud_start[c] .. cloud_start[c + 1] - 1
+ * (cloud_start[0] >= 0, non-decreasing, n_clouds + 1 entries).  A cloud may serve any number of pairs, as target and as source.
+ * All pairs go through ONE launch.  Arithmetic, in float32 without fused multiply-add (a NumPy restatement matches bit for bit):
+ *   R, t = T cast from double to float once;   x' = ((r00 x + r01 y) + r02 z) + tx  (y', z' alike);
+ *   d2 = (dx dx + dy dy) + dz dz  with dx = x' - x_target   (flann::L2_Simple<float>);
+ *   the nearest target is the one of smallest d2, ties go to the LOWEST target index.
+ * A non-finite point of either cloud takes no part: as a source point it gets index -1 and d2 = -1 and is not counted, as a target it
+ * is never chosen.  A source point with no target at a finite float distance (an empty or all-non-finite target cloud, a d2 that
+ * overflows) is reported the same way.
+ * used = the number of source points with (double)d2 <= max_range -- max_range bounds the SQUARED distance, as in hdl_graph_slam,
+ * which compares nn_dists[0]; DBL_MAX = no bound.  score = the sum of those (double)d2 / used, DBL_MAX when used == 0.  The sum runs
+ * in double in an order fixed by the point index alone (a fixed tree inside every run of 256 consecutive source points, the runs in
+ * ascending order): it does not depend on the launch geometry, and repeating a call repeats its bits.
+ * A pair with few source points and many targets has its targets split over several workgroups (`chunk` targets each, combined by a
+ * 64-bit atomic minimum over (bits of d2, index): exact, order independent, the same bits as unsplit).  chunk comes from a heuristic on
+ * the size of the launch; SSLAM_FITNESS_OPTS="chunk=N" in the environment (read at each call) overrides it.
+ * nn_index_out / nn_dist2_out (optional, either may be NULL): pair after pair, one entry per source point; the index counts inside
+ * the target cloud.  kernel_ms (optional): hipEvent time of the pass (copies excluded).
+ * A pair whose source or target cloud is empty is valid: used = 0, score = DBL_MAX.  Returns n_pairs.  SSLAM_ERR_INVALID: a NULL handle,
+ * cloud_start, pairs / score_out / used_out with n_pairs > 0 or xyz with points; n_pairs < 0 or n_clouds < 0; a cloud_start that
+ * decreases or starts below 0; a cloud index out of range; a batch in flight (sslam_seg_submit_batch).  SSLAM_ERR_NO_DEVICE without a GPU. */
+typedef struct sslam_fitness_pair {
+  int32_t target, source;   /* cloud indices */
+  double T[12];             /* R row-major, then t: source -> target frame */
+  double max_range;         /* bound on the SQUARED distance; DBL_MAX = none */
+} sslam_fitness_pair;
+int sslam_seg_fitness_scores(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_fitness_pair* pairs, int n_pairs,
+                             double* score_out, int32_t* used_out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms);
+/* InformationMatrixCalculator::calc_information_matrix, the branch without ~use_const_inf_matrix (information_matrix_calculator.cpp:39-50):
+ *   weight(a, max_x, min_y, max_y, x) = min_y + (max_y - min_y) * (1 - exp(-a x)) / (1 - exp(-a max_x))     (hpp:20-24; no clamp: a score
+ *   above fitness_score_thresh gives more than max_y, DBL_MAX a finite matrix);
+ *   w_x = (float) weight(var_gain_a, fitness_score_thresh, min_stddev_x^2, max_stddev_x^2, fitness), w_q alike with the _q pair;
+ *   info = diag(1 / w_x, 1 / w_x, 1 / w_x, 1 / w_q, 1 / w_q, 1 / w_q), row-major 6 x 6.
+ * Host only: needs no device.  sslam_inf_default_params: 20, 0.1, 5.0, 0.05, 0.2, 0.5 -- hdl_graph_slam's defaults [UPSTREAM, unverified
+ * here]: quoted from memory, hdl_graph_slam is not part of the reference tree, whose members of these names are never initialised. */
+typedef struct sslam_inf_params {
+  double var_gain_a, min_stddev_x, max_stddev_x, min_stddev_q, max_stddev_q, fitness_score_thresh;
+} sslam_inf_params;
+void sslam_inf_default_params(sslam_inf_params* p);
+int sslam_information_from_fitness(const sslam_inf_params* p, double fitness, double info[36]);
+
 /* parity hooks: per-box products of the last sslam_seg_segment call.
  * normals: w*h*4 floats (nx,ny,nz,curvature), labels: w*h int32 (-1 = no plane; otherwise the
  * region index in output order of pcl::OrganizedMultiPlaneSegmentation::segmentAndRefine). */
@@ -588,6 +635,24 @@ void sslam_slam_default_params(sslam_slam_params* p);
  * boxes (NULL when every keyframe brings pre-segmented objects); it is borrowed, not owned. */
 sslam_slam* sslam_slam_create(const sslam_slam_params* p, sslam_seg* seg);
 void sslam_slam_destroy(sslam_slam* s);
+/* Information of the odometry edges from the fitness score of the two keyframes' clouds (what `use_const_inf_matrix = false` means
+ * upstream; sslam_slam_create still refuses that flag, whose branch reads uninitialised members in the reference, and this setter is
+ * the defined-behaviour route to the same capability).  p = NULL: back to the constant matrix.  voxel_leaf: 0 -> 0.1; max_range (a
+ * bound on the SQUARED distance, as in sslam_seg_fitness_scores): <= 0 -> DBL_MAX.
+ * With the model set, a tick collects its consecutive keyframe pairs (prev, kf) first.  Where both carry a cloud (a keyframe takes the
+ * cloud of sslam_slam_set_point_cloud with its detection boxes, as before, and under this model also a cloud that arrived since the last
+ * keyframe without boxes), the finite points of either cloud are voxel-grid downsampled (sslam_seg_voxel_grid, voxel_leaf) and the
+ * score of rel = prev.odom^-1 * kf.odom is computed with prev's cloud as the target, kf's as the source and T = rel: all pairs of the
+ * tick in ONE sslam_seg_fitness_scores pass on the frontend handle given to sslam_slam_create (SSLAM_ERR_INVALID from sslam_slam_run
+ * when that handle is NULL and a pair needs it).  Each such edge gets sslam_information_from_fitness of its score; a pair where either
+ * keyframe has no cloud gets the constant matrix.  The downsampled cloud of the last keyframe of a tick is kept as the target of the
+ * first pair of the next tick.  Without the model a tick does what it did before this call existed, edge for edge.
+ * Returns 0; SSLAM_ERR_INVALID for a NULL handle, a negative or non-finite voxel_leaf, a non-finite max_range. */
+int sslam_slam_set_fitness_information(sslam_slam* s, const sslam_inf_params* p, float voxel_leaf, double max_range);
+/* the odometry edges the last sslam_slam_run added, in order: the fitness score and the number of points it averages over; -1 and -1
+ * for an edge that took the constant matrix.  Returns the number of edges (copies min(n, max); either output may be NULL); 0 when
+ * the model was not set during that run. */
+int sslam_slam_last_fitness(const sslam_slam* s, double* score, int32_t* used, int max);
 /* setPointCloudData (semantic_graph_slam.cpp:341-345): the cloud is copied */
 int sslam_slam_set_point_cloud(sslam_slam* s, const uint8_t* cloud, int width, int height, int point_step, int row_step,
                                int off_x, int off_y, int off_z);

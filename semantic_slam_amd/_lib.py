@@ -105,6 +105,11 @@ def load_library():
         "sslam_batch_info": (ci, [vp, C.c_char_p, dp]),
         "sslam_batch_set_profiling": (ci, [vp, ci]),
         "sslam_batch_kernel_time": (ci, [vp, C.c_char_p, dp, C.POINTER(i64)]),
+        "sslam_seg_fitness_scores": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, dp]),
+        "sslam_inf_default_params": (None, [vp]),
+        "sslam_information_from_fitness": (ci, [vp, cd, dp]),
+        "sslam_slam_set_fitness_information": (ci, [vp, vp, C.c_float, cd]),
+        "sslam_slam_last_fitness": (ci, [vp, vp, vp, ci]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design

@@ -1974,6 +1974,121 @@ __global__ __launch_bounds__(128) void k_sor_mean_distance(const float* __restri
   mean_dist[i] = (float)(sum / (double)k);
 }
 
+// ---- fitness score of cloud pairs (hdl_graph_slam's InformationMatrixCalculator::calc_fitness_score; stubbed in the reference,
+// information_matrix_calculator.cpp:37): exact nearest neighbour of every transformed source point among the target points ----------
+// One workgroup per item = (pair, block of kNnQ source points, chunk of target points); all pairs of a call in one launch.  A thread
+// keeps kNnQpt transformed queries in registers; the targets of the chunk stream through LDS kNnTile at a time as padded 16-byte
+// points, and every lane reads the SAME tile address (one ds_read_b128 per target, an LDS broadcast) for kNnQpt distance evaluations
+// of ~11 VALU operations each: the loop is VALU bound.  The queries of a thread are held two to a register pair, so that the three
+// differences, three products and two sums of TWO queries go through packed instructions (v_pk_add_f32 / v_pk_mul_f32, the target
+// coordinate broadcast to both halves): 7.4 instructions per evaluation instead of 9.5, the same IEEE operations in the same order.
+// The next tile's global load is issued before the current tile is consumed.
+// Ascending scan with a strict `<`: the lowest index among equal distances; a non-finite target is staged as NaN and fails every
+// compare, a non-finite (or out-of-range) query is NaN and never finds anything.  The chunks of a pair meet in a 64-bit atomicMin on
+// (bits of d2 << 32 | target index): non-negative floats order like their bit patterns, so the minimum is exact, independent of the
+// arrival order, and keeps the lowest-index rule -- bitwise what the unsplit scan gives.  `best` starts as all ones (no neighbour).
+constexpr int kNnThreads = 256, kNnQpt = 4, kNnQ = kNnThreads * kNnQpt, kNnTile = 256, kNnSeg = 256;
+static_assert(kNnTile == kNnThreads, "a thread stages one target point per tile");
+static_assert(kNnQpt % 2 == 0, "queries are held in pairs");
+typedef float NnF2 __attribute__((ext_vector_type(2)));
+static_assert(kNnSeg == 256, "k_nn_finish adds the four waves of a run in order");
+struct NnPair { int t0, nt, s0, ns; long long qoff; float R[9], t[3]; double max_range; };   // point ranges in xyz; qoff: first entry of the pair in best / nn_*
+struct NnItem { int pair, qblock, c0, c1; };   // targets [c0, c1) of the pair's target cloud
+struct NnSeg { int pair, seg; };               // source points [seg * kNnSeg, +kNnSeg) of the pair
+__global__ __launch_bounds__(kNnThreads) void k_nn_pairs(const float* __restrict__ xyz, const NnPair* __restrict__ pairs, const NnItem* __restrict__ items,
+                                                         unsigned long long* __restrict__ best) {
+  __shared__ float4 tile[kNnTile];
+  const NnItem it = items[blockIdx.x];
+  const NnPair P = pairs[it.pair];
+  const int tid = threadIdx.x, ns = P.ns, nt_c = it.c1 - it.c0;
+  const float nanf_ = __int_as_float(0x7fc00000);
+  NnF2 qx[kNnQpt / 2], qy[kNnQpt / 2], qz[kNnQpt / 2], bd[kNnQpt / 2];   // query k = component k % 2 of pair k / 2
+  int bi[kNnQpt];
+#pragma unroll
+  for (int k = 0; k < kNnQpt; ++k) {
+    const int i = it.qblock * kNnQ + k * kNnThreads + tid;
+    float tx = nanf_, ty = nanf_, tz = nanf_;
+    bi[k] = -1;
+    if (i < ns) {
+      const float* p = xyz + 3 * (size_t)(P.s0 + i);
+      const float x = p[0], y = p[1], z = p[2];
+      if (isfinite(x) && isfinite(y) && isfinite(z)) {
+        tx = ((P.R[0] * x + P.R[1] * y) + P.R[2] * z) + P.t[0];
+        ty = ((P.R[3] * x + P.R[4] * y) + P.R[5] * z) + P.t[1];
+        tz = ((P.R[6] * x + P.R[7] * y) + P.R[8] * z) + P.t[2];
+      }
+    }
+    qx[k / 2][k % 2] = tx; qy[k / 2][k % 2] = ty; qz[k / 2][k % 2] = tz;
+    bd[k / 2][k % 2] = __int_as_float(0x7f800000);
+  }
+  auto stage = [&](int j) {   // target j of the chunk as a padded point; NaN when it is past the chunk or not finite
+    float4 c = make_float4(nanf_, nanf_, nanf_, 0.0f);
+    if (j < nt_c) {
+      const float* p = xyz + 3 * (size_t)(P.t0 + it.c0 + j);
+      const float x = p[0], y = p[1], z = p[2];
+      if (isfinite(x) && isfinite(y) && isfinite(z)) { c.x = x; c.y = y; c.z = z; }
+    }
+    return c;
+  };
+  float4 nxt = stage(tid);
+  for (int b = 0; b < nt_c; b += kNnTile) {
+    __syncthreads();          // the previous tile has been consumed
+    tile[tid] = nxt;
+    __syncthreads();
+    nxt = stage(b + kNnTile + tid);
+    const int m = min(kNnTile, nt_c - b), base = it.c0 + b;
+#pragma unroll 4
+    for (int j = 0; j < m; ++j) {
+      const float4 c = tile[j];
+#pragma unroll
+      for (int h = 0; h < kNnQpt / 2; ++h) {
+        const NnF2 dx = qx[h] - c.x, dy = qy[h] - c.y, dz = qz[h] - c.z;
+        const NnF2 d = (dx * dx + dy * dy) + dz * dz;       // flann::L2_Simple<float>, two queries at a time
+        if (d.x < bd[h].x) { bd[h].x = d.x; bi[2 * h] = base + j; }
+        if (d.y < bd[h].y) { bd[h].y = d.y; bi[2 * h + 1] = base + j; }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kNnQpt; ++k) {
+    const int i = it.qblock * kNnQ + k * kNnThreads + tid;
+    if (i < ns && bi[k] >= 0)
+      atomicMin(&best[P.qoff + i], ((unsigned long long)__float_as_uint(bd[k / 2][k % 2]) << 32) | (unsigned long long)(unsigned)bi[k]);
+  }
+}
+// best -> (index, d2) per source point, and per run of kNnSeg consecutive source points of a pair the sum of the accepted (double)d2 and
+// their number.  The sum's order is fixed by the point index alone: the shuffle tree of a wave over its 64 consecutive points, the four
+// waves of the run in order; the host adds the runs of a pair in ascending order.
+__global__ __launch_bounds__(kNnSeg) void k_nn_finish(const NnPair* __restrict__ pairs, const NnSeg* __restrict__ segs, const unsigned long long* __restrict__ best,
+                                                     int* __restrict__ nn_index, float* __restrict__ nn_d2, double* __restrict__ part_sum, int* __restrict__ part_used) {
+  __shared__ double red_v[kNnSeg / 64];
+  __shared__ int red_u[kNnSeg / 64];
+  const NnSeg sg = segs[blockIdx.x];
+  const NnPair P = pairs[sg.pair];
+  const int i = sg.seg * kNnSeg + threadIdx.x;
+  double v = 0.0;
+  int u = 0;
+  if (i < P.ns) {
+    const unsigned long long key = best[P.qoff + i];
+    int idx = -1;
+    float d = -1.0f;
+    if (key != ~0ull) {
+      idx = (int)(unsigned)(key & 0xffffffffull);
+      d = __uint_as_float((unsigned)(key >> 32));
+      if ((double)d <= P.max_range) { v = (double)d; u = 1; }
+    }
+    nn_index[P.qoff + i] = idx;
+    nn_d2[P.qoff + i] = d;
+  }
+  for (int off = 32; off > 0; off >>= 1) { v += __shfl_down(v, off, 64); u += __shfl_down(u, off, 64); }
+  if ((threadIdx.x & 63) == 0) { red_v[threadIdx.x >> 6] = v; red_u[threadIdx.x >> 6] = u; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part_sum[blockIdx.x] = ((red_v[0] + red_v[1]) + red_v[2]) + red_v[3];
+    part_used[blockIdx.x] = ((red_u[0] + red_u[1]) + red_u[2]) + red_u[3];
+  }
+}
+
 // ---- k-means of the legacy path (plane_segmentation::computeKmeans -> cv::kmeans, plane_segmentation.cpp:524-535) -----------------
 // assignment step: nearest centre in float32 (squared distance accumulated coordinate by coordinate; ties -> lowest centre), and for
 // the next centre update the coordinate sums / counts per cluster and the compactness, all in 2^-20 fixed point (integer atomics)
@@ -2054,6 +2169,8 @@ struct sslam_seg {
   std::vector<char> h_icp;            // host image of the tables + state (one H2D copy per call)
   size_t cap_rflag = 0, cap_rbox = 0;
   int r_nbox = -1;                    // boxes the flags belong to (-1: no RANSAC has run on the resident batch)
+  hipEvent_t f_e0 = nullptr, f_e1 = nullptr;   // sslam_seg_fitness_scores: around the kernels of the pass
+  int n_cu = 0;                       // compute units of the device (sizes the target split of k_nn_pairs)
   sslam_seg* twin = nullptr;
   int fifo[2] = {0, 0};            // which pipeline (0 = this, 1 = twin) holds the oldest / the newer submitted batch
   int n_inflight = 0;
@@ -2068,6 +2185,8 @@ struct sslam_seg {
     if (d_icp) (void)hipFree(d_icp);
     if (q_e0) (void)hipEventDestroy(q_e0);
     if (q_e1) (void)hipEventDestroy(q_e1);
+    if (f_e0) (void)hipEventDestroy(f_e0);
+    if (f_e1) (void)hipEventDestroy(f_e1);
     if (stream) (void)hipStreamDestroy(stream);
   }
   void free_all() {
@@ -3060,6 +3179,150 @@ int sslam_seg_kmeans(sslam_seg* s, const float* pts, int n, int dim, int k, uint
   for (int i = 0; i < n; ++i) labels_out[i] = lab[i];
   if (compactness_out) *compactness_out = best;
   return k;
+}
+
+
+// ---- fitness scores (k_nn_pairs, k_nn_finish) and the information matrix of a score -----------------------------------------------
+
+// SSLAM_FITNESS_OPTS="chunk=N": targets per workgroup of k_nn_pairs (0: the heuristic).  Read at each call: tests toggle it.
+static int fitness_chunk_from_env() {
+  const char* e = getenv("SSLAM_FITNESS_OPTS");
+  if (!e) return 0;
+  const char* c = strstr(e, "chunk=");
+  if (!c) return 0;
+  const long v = strtol(c + 6, nullptr, 10);
+  return v > 0 && v < (1l << 30) ? (int)v : 0;
+}
+
+int sslam_seg_fitness_scores(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_fitness_pair* pairs, int n_pairs,
+                             double* score_out, int32_t* used_out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
+  if (!s || !cloud_start || n_clouds < 0 || n_pairs < 0 || (n_pairs > 0 && (!pairs || !score_out || !used_out)))
+    return set_error(SSLAM_ERR_INVALID, "bad argument");
+  if (cloud_start[0] < 0) return set_error(SSLAM_ERR_INVALID, "cloud_start[0] is negative");
+  for (int c = 0; c < n_clouds; ++c)
+    if (cloud_start[c + 1] < cloud_start[c]) return set_error(SSLAM_ERR_INVALID, "cloud_start decreases at cloud %d", c);
+  const int n_points = cloud_start[n_clouds];
+  if (n_points > 0 && !xyz) return set_error(SSLAM_ERR_INVALID, "null xyz");
+  for (int p = 0; p < n_pairs; ++p)
+    if (pairs[p].target < 0 || pairs[p].target >= n_clouds || pairs[p].source < 0 || pairs[p].source >= n_clouds)
+      return set_error(SSLAM_ERR_INVALID, "pair %d names cloud %d / %d of %d", p, pairs[p].target, pairs[p].source, n_clouds);
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  int rc = seg_device(s);
+  if (rc) return rc;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (n_pairs == 0) return 0;
+  if (!s->n_cu) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, s->P.device) != hipSuccess || v <= 0) v = 256;
+    s->n_cu = v;
+  }
+  // the pairs as the kernels read them, the source blocks (items before the target split) and the runs of the reduction
+  std::vector<NnPair> hp(n_pairs);
+  long long total_q = 0, blocks = 0, n_seg = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    NnPair& P = hp[p];
+    P.t0 = cloud_start[pairs[p].target]; P.nt = cloud_start[pairs[p].target + 1] - P.t0;
+    P.s0 = cloud_start[pairs[p].source]; P.ns = cloud_start[pairs[p].source + 1] - P.s0;
+    P.qoff = total_q;
+    for (int k = 0; k < 9; ++k) P.R[k] = (float)pairs[p].T[k];
+    for (int k = 0; k < 3; ++k) P.t[k] = (float)pairs[p].T[9 + k];
+    P.max_range = pairs[p].max_range;
+    total_q += P.ns;
+    if (P.nt > 0) blocks += (P.ns + kNnQ - 1) / kNnQ;
+    n_seg += (P.ns + kNnSeg - 1) / kNnSeg;
+  }
+  // Target split.  Without it the launch has `blocks` workgroups; below four per compute unit the targets of every pair are cut into
+  // as many chunks as bring it there, never shorter than two tiles (a workgroup should scan long enough to pay for its query loads
+  // and atomics).  Chunk boundaries do not change any result.
+  int chunk = fitness_chunk_from_env();
+  long long split = 1;
+  if (!chunk && blocks > 0 && blocks < 4ll * s->n_cu) split = (4ll * s->n_cu + blocks - 1) / blocks;
+  std::vector<NnItem> items;
+  std::vector<NnSeg> segs;
+  segs.reserve((size_t)n_seg);
+  for (int p = 0; p < n_pairs; ++p) {
+    const NnPair& P = hp[p];
+    for (int g = 0; g < (P.ns + kNnSeg - 1) / kNnSeg; ++g) segs.push_back(NnSeg{p, g});
+    if (P.nt <= 0 || P.ns <= 0) continue;
+    long long ch = chunk;
+    if (!ch) {
+      ch = (P.nt + split - 1) / split;
+      ch = std::max<long long>((ch + kNnTile - 1) / kNnTile * kNnTile, 2 * kNnTile);
+    }
+    const long long nch = (P.nt + ch - 1) / ch, nqb = (P.ns + kNnQ - 1) / kNnQ;
+    if ((long long)items.size() + nch * nqb > (1ll << 24))
+      return set_error(SSLAM_ERR_UNSUPPORTED, "fitness pass of more than 2^24 workgroups (chunk = %lld targets is too small for these clouds)", ch);
+    for (long long qb = 0; qb < nqb; ++qb)
+      for (long long c = 0; c < nch; ++c)
+        items.push_back(NnItem{p, (int)qb, (int)(c * ch), (int)std::min<long long>((c + 1) * ch, P.nt)});
+  }
+  DevGuard g;
+  float *d_xyz = nullptr, *d_d2 = nullptr;
+  NnPair* d_pairs = nullptr; NnItem* d_items = nullptr; NnSeg* d_segs = nullptr;
+  unsigned long long* d_best = nullptr;
+  int *d_idx = nullptr, *d_used = nullptr;
+  double* d_sum = nullptr;
+  if ((rc = g.alloc(&d_xyz, (size_t)n_points * 3)) || (rc = g.alloc(&d_pairs, n_pairs)) || (rc = g.alloc(&d_items, items.size())) ||
+      (rc = g.alloc(&d_segs, segs.size())) || (rc = g.alloc(&d_best, (size_t)total_q)) || (rc = g.alloc(&d_idx, (size_t)total_q)) ||
+      (rc = g.alloc(&d_d2, (size_t)total_q)) || (rc = g.alloc(&d_sum, segs.size())) || (rc = g.alloc(&d_used, segs.size()))) return rc;
+  if (!s->f_e0) { SSLAM_HIP_TRY(hipEventCreate(&s->f_e0)); SSLAM_HIP_TRY(hipEventCreate(&s->f_e1)); }
+  if (n_points > 0) SSLAM_HIP_TRY(hipMemcpyAsync(d_xyz, xyz, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_pairs, hp.data(), hp.size() * sizeof(NnPair), hipMemcpyHostToDevice, s->stream));
+  if (!items.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(NnItem), hipMemcpyHostToDevice, s->stream));
+  if (!segs.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(NnSeg), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->f_e0, s->stream));
+  if (total_q > 0) SSLAM_HIP_TRY(hipMemsetAsync(d_best, 0xff, (size_t)total_q * sizeof(unsigned long long), s->stream));
+  if (!items.empty()) hipLaunchKernelGGL(k_nn_pairs, dim3((unsigned)items.size()), dim3(kNnThreads), 0, s->stream, d_xyz, d_pairs, d_items, d_best);
+  if (!segs.empty()) hipLaunchKernelGGL(k_nn_finish, dim3((unsigned)segs.size()), dim3(kNnSeg), 0, s->stream, d_pairs, d_segs, d_best, d_idx, d_d2, d_sum, d_used);
+  SSLAM_HIP_TRY(hipGetLastError());
+  SSLAM_HIP_TRY(hipEventRecord(s->f_e1, s->stream));
+  std::vector<double> h_sum(segs.size());
+  std::vector<int> h_used(segs.size());
+  if (!segs.empty()) {
+    SSLAM_HIP_TRY(hipMemcpyAsync(h_sum.data(), d_sum, segs.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    SSLAM_HIP_TRY(hipMemcpyAsync(h_used.data(), d_used, segs.size() * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  }
+  if (total_q > 0 && nn_index_out) SSLAM_HIP_TRY(hipMemcpyAsync(nn_index_out, d_idx, (size_t)total_q * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  if (total_q > 0 && nn_dist2_out) SSLAM_HIP_TRY(hipMemcpyAsync(nn_dist2_out, d_d2, (size_t)total_q * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if (kernel_ms) {
+    float ms = 0.0f;
+    SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->f_e0, s->f_e1));
+    *kernel_ms = (double)ms;
+  }
+  size_t at = 0;
+  for (int p = 0; p < n_pairs; ++p) {   // the runs of a pair in ascending order
+    double sum = 0.0;
+    long long used = 0;
+    for (int k = 0; k < (hp[p].ns + kNnSeg - 1) / kNnSeg; ++k, ++at) { sum += h_sum[at]; used += h_used[at]; }
+    used_out[p] = (int32_t)used;
+    score_out[p] = used > 0 ? sum / (double)used : 1.7976931348623157e308;
+  }
+  return n_pairs;
+}
+
+void sslam_inf_default_params(sslam_inf_params* p) {
+  if (!p) return;
+  // hdl_graph_slam's InformationMatrixCalculator defaults [UPSTREAM, unverified here]
+  p->var_gain_a = 20.0; p->min_stddev_x = 0.1; p->max_stddev_x = 5.0; p->min_stddev_q = 0.05; p->max_stddev_q = 0.2; p->fitness_score_thresh = 0.5;
+}
+
+// InformationMatrixCalculator::weight (information_matrix_calculator.hpp:20-24)
+static double fitness_weight(double a, double max_x, double min_y, double max_y, double x) {
+  const double y = (1.0 - std::exp(-a * x)) / (1.0 - std::exp(-a * max_x));
+  return min_y + (max_y - min_y) * y;
+}
+
+int sslam_information_from_fitness(const sslam_inf_params* p, double fitness, double info[36]) {
+  if (!p || !info) return set_error(SSLAM_ERR_INVALID, "null argument");
+  // information_matrix_calculator.cpp:39-50; the variances are the squares of the standard deviations
+  const double min_var_x = p->min_stddev_x * p->min_stddev_x, max_var_x = p->max_stddev_x * p->max_stddev_x;
+  const double min_var_q = p->min_stddev_q * p->min_stddev_q, max_var_q = p->max_stddev_q * p->max_stddev_q;
+  const float w_x = (float)fitness_weight(p->var_gain_a, p->fitness_score_thresh, min_var_x, max_var_x, fitness);
+  const float w_q = (float)fitness_weight(p->var_gain_a, p->fitness_score_thresh, min_var_q, max_var_q, fitness);
+  std::memset(info, 0, 36 * sizeof(double));
+  for (int k = 0; k < 3; ++k) { info[k * 7] = 1.0 / (double)w_x; info[(k + 3) * 7] = 1.0 / (double)w_q; }
+  return 0;
 }
 
 }  // extern "C"

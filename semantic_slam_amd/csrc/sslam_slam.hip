@@ -20,8 +20,10 @@
 //   * distance_min is reset per detection unless reference_quirks bit 0 is set; neareast_landmarks_id
 //     (uninitialised in the reference when no candidate beat distance_min) maps to "new landmark".
 //   * InformationMatrixCalculator without ~use_const_inf_matrix reads members that are never initialised
-//     (information_matrix_calculator.hpp:31-36); only the constant matrix is supported.
+//     (information_matrix_calculator.hpp:31-36) and has its score stubbed (information_matrix_calculator.cpp:37): the flag is refused;
+//     sslam_slam_set_fitness_information installs the model with defined parameters and the real score (sslam_seg_fitness_scores).
 #include <hip/hip_runtime.h>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -325,6 +327,15 @@ struct sslam_slam {
   DevBuf<sslam_landmark> d_out;
   sslam::PinnedScratch pin;               // page-locked staging of the table / detection / result copies
   bool table_dirty = true;                // host landmarks changed outside the kernel -> re-upload before the next association
+  // sslam_slam_set_fitness_information: odometry information from the fitness score of the keyframes' clouds
+  bool fit_on = false;
+  sslam_inf_params fit_P{};
+  float fit_leaf = 0.1f;
+  double fit_range = DBL_MAX;
+  bool fit_prev_has = false;              // fit_prev: the downsampled cloud of the last processed keyframe (target of the next tick's first pair)
+  std::vector<float> fit_prev;
+  std::vector<double> fit_score;          // odometry edges of the last run(), in order; -1 / -1: constant matrix
+  std::vector<int32_t> fit_used;
   ~sslam_slam() {
     if (graph) sslam_graph_destroy(graph);
     if (stream) { (void)hipSetDevice(P.device); (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
@@ -449,12 +460,101 @@ void odometry_information(const sslam_slam* s, double info[36]) {
   for (int k = 0; k < 3; ++k) { info[k * 7] = 1.0 / sx; info[(k + 3) * 7] = 1.0 / sq; }
 }
 
+// the finite points of a keyframe's cloud, voxel-grid downsampled on the device -> out (xyz)
+int downsampled_cloud(sslam_slam* s, const KeyFrame& kf, std::vector<float>& out) {
+  std::vector<float> pts;
+  pts.reserve((size_t)kf.width * kf.height * 3);
+  for (int r = 0; r < kf.height; ++r)
+    for (int c = 0; c < kf.width; ++c) {
+      const uint8_t* p = kf.cloud.data() + (size_t)r * kf.row_step + (size_t)c * kf.point_step;
+      float v[3];
+      for (int k = 0; k < 3; ++k) std::memcpy(&v[k], p + kf.off[k], sizeof(float));
+      if (std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2])) pts.insert(pts.end(), v, v + 3);
+    }
+  const int n = (int)(pts.size() / 3);
+  out.assign(pts.size(), 0.0f);
+  if (n == 0) return 0;
+  const int m = sslam_seg_voxel_grid(s->seg, pts.data(), n, s->fit_leaf, out.data(), nullptr, n);
+  if (m < 0) return m;
+  out.resize((size_t)m * 3);
+  return 0;
+}
+
+// With the fitness model: the score of every consecutive pair (prev, kf) of the tick whose keyframes both carry a cloud -- all of them in
+// ONE pass on the frontend handle -- before anything is added to the graph.  score / used [n]: -1 where the edge takes the constant matrix.
+int fitness_of_tick(sslam_slam* s, int n, std::vector<double>& score, std::vector<int32_t>& used, std::vector<float>& last_cloud, bool& last_has) {
+  score.assign(n, -1.0); used.assign(n, -1);
+  last_has = false;
+  auto has_cloud = [&](int i) { return i < 0 ? s->fit_prev_has : !s->keyframe_queue[i]->cloud.empty(); };   // -1: the last keyframe of the tick before
+  std::vector<int> edge;                  // keyframes i whose edge (i - 1, i) is scored
+  for (int i = 0; i < n; ++i) {
+    if (i == 0 && s->keyframes.empty()) continue;   // the first keyframe of all has no odometry edge
+    if (has_cloud(i - 1) && has_cloud(i)) edge.push_back(i);
+  }
+  const bool keep_last = n > 0 && has_cloud(n - 1);
+  if (edge.empty() && !keep_last) return 0;
+  if (!s->seg) return set_error(SSLAM_ERR_INVALID, "the fitness model needs the frontend handle: none was given to sslam_slam_create");
+  // the clouds the pairs name, each downsampled once: slot 0 = the cloud kept from the last tick, slot i + 1 = keyframe i of this one
+  std::vector<int> cloud_of(n + 1, -1);
+  std::vector<float> xyz;
+  std::vector<int32_t> start{0};
+  auto need = [&](int i) -> int {
+    if (cloud_of[i + 1] >= 0) return 0;
+    std::vector<float> ds;
+    if (i < 0) ds = s->fit_prev;
+    else { const int rc = downsampled_cloud(s, *s->keyframe_queue[i], ds); if (rc < 0) return rc; }
+    cloud_of[i + 1] = (int)start.size() - 1;
+    xyz.insert(xyz.end(), ds.begin(), ds.end());
+    start.push_back((int32_t)(xyz.size() / 3));
+    return 0;
+  };
+  int rc;
+  std::vector<sslam_fitness_pair> pairs;
+  for (int i : edge) {
+    if ((rc = need(i - 1)) < 0 || (rc = need(i)) < 0) return rc;
+    const Pose& po = i == 0 ? s->keyframes.back()->odom : s->keyframe_queue[i - 1]->odom;
+    const Pose rel = compose(inverse(po), s->keyframe_queue[i]->odom);
+    sslam_fitness_pair P;
+    P.target = cloud_of[i]; P.source = cloud_of[i + 1];
+    const Mat3 R = qmat(rel.q);            // of the quaternion the edge's measurement carries
+    for (int k = 0; k < 9; ++k) P.T[k] = R.m[k];
+    P.T[9] = rel.t.x; P.T[10] = rel.t.y; P.T[11] = rel.t.z;
+    P.max_range = s->fit_range;
+    pairs.push_back(P);
+  }
+  if (keep_last && (rc = need(n - 1)) < 0) return rc;
+  if (!pairs.empty()) {
+    std::vector<double> sc(pairs.size());
+    std::vector<int32_t> us(pairs.size());
+    rc = sslam_seg_fitness_scores(s->seg, xyz.data(), start.data(), (int)start.size() - 1, pairs.data(), (int)pairs.size(), sc.data(), us.data(),
+                                  nullptr, nullptr, nullptr);
+    if (rc < 0) return rc;
+    for (size_t k = 0; k < edge.size(); ++k) { score[edge[k]] = sc[k]; used[edge[k]] = us[k]; }
+  }
+  if (keep_last) {
+    const int c = cloud_of[n];
+    last_cloud.assign(xyz.begin() + 3 * (size_t)start[c], xyz.begin() + 3 * (size_t)start[c + 1]);
+    last_has = true;
+  }
+  return 0;
+}
+
 // empty_keyframe_queue (semantic_graph_slam.cpp:104-150)
 int empty_keyframe_queue(sslam_slam* s) {
+  s->fit_score.clear(); s->fit_used.clear();
   if (s->keyframe_queue.empty()) return 0;
   const int n = std::min<int>((int)s->keyframe_queue.size(), s->P.max_keyframes_per_update);
-  double info[36];
-  odometry_information(s, info);
+  double info[36], const_info[36];
+  odometry_information(s, const_info);
+  std::memcpy(info, const_info, sizeof info);
+  std::vector<double> score;
+  std::vector<int32_t> nused;
+  std::vector<float> last_cloud;
+  bool last_has = false;
+  if (s->fit_on) {
+    const int rc = fitness_of_tick(s, n, score, nused, last_cloud, last_has);
+    if (rc < 0) return rc;               // nothing has been touched: the queue keeps its keyframes
+  }
   int err = 0, used = 0;
   for (int i = 0; i < n && !err; ++i) {
     const std::shared_ptr<KeyFrame>& kf = s->keyframe_queue[i];
@@ -469,8 +569,17 @@ int empty_keyframe_queue(sslam_slam* s) {
     const Pose rel = compose(inverse(prev->odom), kf->odom);
     double z[7];
     to_tq(rel, z);
+    if (s->fit_on) {
+      if (nused[i] >= 0) { const int rc = sslam_information_from_fitness(&s->fit_P, score[i], info); if (rc < 0) { err = rc; break; } }
+      else std::memcpy(info, const_info, sizeof info);
+    }
     const int rc = sslam_graph_add_edge_se3(s->graph, prev->node, kf->node, z, info);
-    if (rc < 0) err = rc;
+    if (rc < 0) { err = rc; break; }
+    if (s->fit_on) { s->fit_score.push_back(score[i]); s->fit_used.push_back(nused[i]); }
+  }
+  if (s->fit_on) {   // the target of the next tick's first pair; after an error the chain of clouds is broken
+    s->fit_prev_has = !err && last_has;
+    if (s->fit_prev_has) s->fit_prev.swap(last_cloud); else { s->fit_prev.clear(); s->fit_prev.shrink_to_fit(); }
   }
   // whatever was touched leaves the queue, also on an error: a second call must not add the same keyframes again
   s->keyframe_queue.erase(s->keyframe_queue.begin(), s->keyframe_queue.begin() + (err ? used : n));
@@ -689,6 +798,7 @@ int sslam_slam_vio(sslam_slam* s, int32_t sec, int32_t nsec, const double odom_t
   auto kf = std::make_shared<KeyFrame>();
   kf->sec = sec; kf->nsec = nsec; kf->odom = odom; kf->robot_pose = s->robot_pose; kf->accum_distance = s->accum_distance;
   // getPointCloudData / getDetectedObjectInfo (semantic_graph_slam.cpp:264-272): the latest cloud always, the boxes when a detection is pending
+  const bool fresh_cloud = s->point_cloud_available;
   s->point_cloud_available = false;
   if (s->object_detection_available) {
     s->object_detection_available = false;
@@ -699,6 +809,11 @@ int sslam_slam_vio(sslam_slam* s, int32_t sec, int32_t nsec, const double odom_t
       kf->width = s->latest.width; kf->height = s->latest.height; kf->point_step = s->latest.point_step; kf->row_step = s->latest.row_step;
       for (int k = 0; k < 3; ++k) kf->off[k] = s->latest.off[k];
     }
+  }
+  if (s->fit_on && fresh_cloud && kf->cloud.empty() && !s->latest.cloud.empty()) {   // the fitness model reads the cloud of a keyframe without boxes too
+    kf->cloud = s->latest.cloud;
+    kf->width = s->latest.width; kf->height = s->latest.height; kf->point_step = s->latest.point_step; kf->row_step = s->latest.row_step;
+    for (int k = 0; k < 3; ++k) kf->off[k] = s->latest.off[k];
   }
   s->keyframe_queue.push_back(kf);
   s->vio_pose = odom; s->prev_odom = odom;
@@ -737,7 +852,10 @@ int sslam_slam_run(sslam_slam* s, sslam_tick_stats* st) {
     kf.cloud.clear(); kf.cloud.shrink_to_fit();
   }
   st->seconds_association = now_s() - t0;
-  for (auto& kf : s->new_keyframes) s->keyframes.push_back(kf);
+  for (auto& kf : s->new_keyframes) {
+    if (s->fit_on) { kf->cloud.clear(); kf->cloud.shrink_to_fit(); }   // only the downsampled cloud of the last keyframe is kept
+    s->keyframes.push_back(kf);
+  }
   s->new_keyframes.clear();
   t0 = now_s();
   rc = sslam_graph_optimize(s->graph, s->P.max_iterations, &st->opt);
@@ -787,6 +905,26 @@ int sslam_slam_keyframes(const sslam_slam* s, int32_t* ids, double* est, int max
   return n;
 }
 sslam_graph* sslam_slam_graph(sslam_slam* s) { return s ? s->graph : nullptr; }
+
+int sslam_slam_set_fitness_information(sslam_slam* s, const sslam_inf_params* p, float voxel_leaf, double max_range) {
+  if (!s || !std::isfinite(voxel_leaf) || voxel_leaf < 0 || !std::isfinite(max_range)) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  s->fit_on = p != nullptr;
+  if (p) s->fit_P = *p;
+  s->fit_leaf = voxel_leaf == 0 ? 0.1f : voxel_leaf;
+  s->fit_range = max_range <= 0 ? DBL_MAX : max_range;
+  if (!s->fit_on) { s->fit_prev_has = false; s->fit_prev.clear(); s->fit_prev.shrink_to_fit(); }
+  return 0;
+}
+
+int sslam_slam_last_fitness(const sslam_slam* s, double* score, int32_t* used, int max) {
+  if (!s) return set_error(SSLAM_ERR_INVALID, "null handle");
+  const int n = (int)s->fit_score.size();
+  for (int i = 0; i < n && i < max; ++i) {
+    if (score) score[i] = s->fit_score[i];
+    if (used) used[i] = s->fit_used[i];
+  }
+  return n;
+}
 
 int sslam_slam_find_matches(sslam_slam* s, const sslam_plane* objects, int n, const float robot_pose[6], sslam_landmark* out) {
   if (!s || n < 0 || (n > 0 && (!objects || !out)) || !robot_pose) return set_error(SSLAM_ERR_INVALID, "null argument");

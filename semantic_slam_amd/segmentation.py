@@ -74,6 +74,23 @@ class IcpResult(C.Structure):
     _fields_ = [("T", C.c_double * 12), ("rms", C.c_double), ("used", C.c_int32), ("status", C.c_int32)]
 
 
+class FitnessPair(C.Structure):
+    """``sslam_fitness_pair`` (include/sslam.h)"""
+    _fields_ = [("target", C.c_int32), ("source", C.c_int32), ("T", C.c_double * 12), ("max_range", C.c_double)]
+
+
+class InfParams(C.Structure):
+    """``sslam_inf_params`` (include/sslam.h)"""
+    _fields_ = [("var_gain_a", C.c_double), ("min_stddev_x", C.c_double), ("max_stddev_x", C.c_double), ("min_stddev_q", C.c_double),
+                ("max_stddev_q", C.c_double), ("fitness_score_thresh", C.c_double)]
+
+
+# geometry of k_nn_pairs (csrc/sslam_seg.hip kNnTile, kNnQ): target points per LDS tile, source points per workgroup
+NN_TILE = 256
+NN_Q = 1024
+DBL_MAX = float(np.finfo(np.float64).max)
+
+
 def _bind(lib):
     global _BOUND
     if _BOUND:
@@ -112,7 +129,29 @@ def _bind(lib):
     lib.sslam_seg_icp_boxes.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, ci, C.POINTER(C.c_double)]
     lib.sslam_seg_icp_point_to_plane.restype = ci
     lib.sslam_seg_icp_point_to_plane.argtypes = [vp, vp, vp, ci, vp, ci, ci, vp, vp, C.POINTER(C.c_double)]
+    # sslam_seg_fitness_scores, sslam_inf_default_params, sslam_information_from_fitness: declared in _lib.load_library
     _BOUND = True
+
+
+def default_inf_params() -> InfParams:
+    """``sslam_inf_default_params``: var_gain_a 20, stddev_x 0.1 .. 5.0, stddev_q 0.05 .. 0.2, fitness_score_thresh 0.5"""
+    lib = load_library(); _bind(lib)
+    p = InfParams()
+    lib.sslam_inf_default_params(C.byref(p))
+    return p
+
+
+def information_from_fitness(fitness: float, params: InfParams | None = None) -> np.ndarray:
+    """InformationMatrixCalculator::calc_information_matrix, the branch that reads a fitness score (``sslam_information_from_fitness``):
+    the 6 x 6 information matrix of an edge whose clouds match with this score.  Host only, needs no GPU."""
+    lib = load_library(); _bind(lib)
+    p = params if params is not None else default_inf_params()
+    out = np.zeros(36)
+    rc = lib.sslam_information_from_fitness(C.byref(p), C.c_double(fitness), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc < 0:
+        from .graph_slam import SslamError
+        raise SslamError(rc, lib.sslam_last_error().decode())
+    return out.reshape(6, 6)
 
 
 def default_params(device: int = 0) -> SegParams:
@@ -405,6 +444,43 @@ class PointCloudSegmentation:
                                                                int(iterations), None if t0 is None else t0.ctypes.data, out.ctypes.data,
                                                                C.byref(rms)))
         return out, rms.value, n
+
+    def fitness_scores(self, clouds, pairs, return_nn: bool = False):
+        """``sslam_seg_fitness_scores``: InformationMatrixCalculator::calc_fitness_score of several cloud pairs in one pass.
+        ``clouds``: a sequence of [n, 3] float arrays.  ``pairs``: (target, source, T, max_range) with cloud indices, T = 12 doubles (R
+        row-major, then t) or a 4x4 / 3x4 matrix taking the source into the target's frame, max_range a bound on the SQUARED distance
+        (None: none).  Returns (scores, used), with ``return_nn`` also per pair (nearest target index, squared distance) of every source
+        point.  The hipEvent time of the pass is left in ``last_fitness_ms``."""
+        cl = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in clouds]
+        start = np.zeros(len(cl) + 1, np.int32)
+        start[1:] = np.cumsum([len(c) for c in cl])
+        xyz = np.ascontiguousarray(np.concatenate(cl, 0)) if cl else np.zeros((0, 3), np.float32)
+        rec = (FitnessPair * max(len(pairs), 1))()
+        n_src = []
+        for k, (tgt, src, T, max_range) in enumerate(pairs):
+            T = np.asarray(T, np.float64)
+            if T.shape in ((4, 4), (3, 4)):
+                T = np.concatenate([T[:3, :3].reshape(-1), T[:3, 3]])
+            T = T.reshape(12)
+            rec[k].target, rec[k].source = int(tgt), int(src)
+            for q in range(12):
+                rec[k].T[q] = T[q]
+            rec[k].max_range = DBL_MAX if max_range is None else float(max_range)
+            n_src.append(len(cl[int(src)]) if 0 <= int(src) < len(cl) else 0)
+        score = np.zeros(max(len(pairs), 1)); used = np.zeros(max(len(pairs), 1), np.int32)
+        total = max(int(sum(n_src)), 1)
+        idx = np.zeros(total, np.int32) if return_nn else None
+        d2 = np.zeros(total, np.float32) if return_nn else None
+        ms = C.c_double(0)
+        self._check(self._lib.sslam_seg_fitness_scores(self._h, xyz.ctypes.data, start.ctypes.data, len(cl), C.cast(rec, C.c_void_p), len(pairs),
+                                                       score.ctypes.data, used.ctypes.data, idx.ctypes.data if return_nn else None,
+                                                       d2.ctypes.data if return_nn else None, C.byref(ms)))
+        self.last_fitness_ms = ms.value
+        score, used = score[:len(pairs)], used[:len(pairs)]
+        if not return_nn:
+            return score, used
+        cuts = np.cumsum(n_src)[:-1] if n_src else []
+        return score, used, list(zip(np.split(idx[:sum(n_src)], cuts), np.split(d2[:sum(n_src)], cuts)))
 
     def compute2DConvexHull(self, xyz, seed: int = 0):
         """plane_segmentation::compute2DConvexHull (plane_segmentation.cpp:631-665): RANSAC plane (threshold 0.01, refined

@@ -12,7 +12,7 @@ import numpy as np
 
 from ._lib import load_library, OptStats
 from .graph_slam import SslamError, _pose7
-from .segmentation import Plane, PointCloudSegmentation
+from .segmentation import DBL_MAX, InfParams, Plane, PointCloudSegmentation, default_inf_params
 
 
 class SlamParams(C.Structure):   # sslam_slam_params
@@ -60,6 +60,7 @@ def _bind(lib):
     lib.sslam_slam_keyframes.restype = ci; lib.sslam_slam_keyframes.argtypes = [vp, vp, vp, ci]
     lib.sslam_slam_graph.restype = vp; lib.sslam_slam_graph.argtypes = [vp]
     lib.sslam_slam_find_matches.restype = ci; lib.sslam_slam_find_matches.argtypes = [vp, vp, ci, vp, vp]
+    # sslam_slam_set_fitness_information, sslam_slam_last_fitness: declared in _lib.load_library
     _BOUND = True
 
 
@@ -126,6 +127,22 @@ class SemanticGraphSLAM:
         rc = self._check(self._lib.sslam_slam_run(self._h, C.byref(st)))
         self.last_stats = st
         return bool(rc)
+
+    def set_fitness_information(self, params: InfParams | None = "default", voxel_leaf: float = 0.1, max_range: float | None = None) -> None:
+        """``sslam_slam_set_fitness_information``: the odometry edges of the following ticks take the information matrix of the fitness
+        score of their keyframes' clouds (InformationMatrixCalculator without ~use_const_inf_matrix).  ``params``: an ``InfParams``, the
+        defaults, or None to go back to the constant matrix.  ``max_range`` bounds the SQUARED nearest-neighbour distance (None: no bound)."""
+        if isinstance(params, str):
+            params = default_inf_params()
+        self._check(self._lib.sslam_slam_set_fitness_information(self._h, None if params is None else C.byref(params), C.c_float(voxel_leaf),
+                                                                 C.c_double(DBL_MAX if max_range is None else max_range)))
+
+    def last_fitness(self):
+        """(scores, used) of the odometry edges the last ``run`` added, in order; -1 / -1 for an edge that took the constant matrix"""
+        n = self._check(self._lib.sslam_slam_last_fitness(self._h, None, None, 0))
+        score = np.zeros(max(n, 1)); used = np.zeros(max(n, 1), np.int32)
+        self._check(self._lib.sslam_slam_last_fitness(self._h, score.ctypes.data, used.ctypes.data, n))
+        return score[:n], used[:n]
 
     # -- getters --------------------------------------------------------------------------------------------------------------
     def getRobotPose(self) -> np.ndarray:
