@@ -237,7 +237,9 @@ typedef struct sslam_batch sslam_batch;
 sslam_batch* sslam_batch_create(sslam_graph* const* graphs, int n);
 /* Stream group: the n graphs split into n_streams contiguous parts, each a batch of its own on its own HIP stream; sslam_batch_optimize
  * drives every part from its own host thread.  Results are those of sslam_batch_create (every graph runs its own LM; the parts only
- * change what overlaps on the chip: one part's tree tops and LM endgame run under another part's leaves).  Measured on 512 distinct L
+ * change what overlaps on the chip: one part's tree tops and LM endgame run under another part's leaves) -- bit for bit where every
+ * part is planned like the whole batch; a part is planned by its own size, so parts of fewer than 8 graphs of a larger batch take the
+ * single-launch factorisation and give the bits of a batch of that part (same accuracy, another summation order).  Measured on 512 distinct L
  * graphs: 4 streams = +16 % iterations/s.  upload / download / optimize / info / profiling / time_* work on a group; the edge-sharded
  * mode and sslam_batch_linearize_hb return SSLAM_ERR_UNSUPPORTED.  sslam_batch_create reads the number of streams from the environment
  * (SSLAM_BATCH_STREAMS, default 1). */
@@ -399,7 +401,10 @@ void sslam_seg_destroy(sslam_seg* s);
 
 /* segmentallPointCloudData(robot_pose, cam_angle, object_info, point_cloud)
  * cloud = sensor_msgs::PointCloud2::data of an organised width x height cloud; off_* = field
- * offsets of x,y,z (plane_segmentation.cpp:48-61).  Returns the number of planes written. */
+ * offsets of x,y,z (plane_segmentation.cpp:48-61).  Returns the number of planes written.
+ * The layout is checked before the device is looked at, here and in sslam_seg_segment_batch / sslam_seg_submit_batch: width > 0,
+ * height > 0, point_step >= 4, 0 <= off_* <= point_step - 4, row_step >= width * point_step, n_frames > 0, n_boxes >= 0 -- anything
+ * else is SSLAM_ERR_INVALID (a pixel of the image would be read outside the row_step * height bytes of the cloud). */
 int sslam_seg_segment(sslam_seg* s, const uint8_t* cloud, int width, int height, int point_step, int row_step,
                       int off_x, int off_y, int off_z, const sslam_box* boxes, int n_boxes,
                       const float robot_pose[6], float cam_angle, sslam_plane* out, int max_out);

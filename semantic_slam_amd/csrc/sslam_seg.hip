@@ -2311,10 +2311,21 @@ static int seg_lds_opt_in(int device) {
 }
 static int seg_enqueue(sslam_seg* s, const sslam_frame* frames, int n_frames, int width, int height, int point_step, int row_step, int ox, int oy, int oz,
                        sslam_seg* peer = nullptr) {
-  if (!s || !frames || n_frames <= 0) return set_error(SSLAM_ERR_INVALID, "null argument");
+  if (!s || !frames) return set_error(SSLAM_ERR_INVALID, "null argument");
+  if (n_frames <= 0) return set_error(SSLAM_ERR_INVALID, "n_frames %d", n_frames);
   if (s->q_busy) return set_error(SSLAM_ERR_INVALID, "the previous batch of this pipeline has not been collected");
-  for (int f = 0; f < n_frames; ++f)
+  // the cloud layout feeds k_crop's address arithmetic (row * row_step + col * point_step + offset) unchecked from here on: every
+  // read of a pixel inside the image must stay inside the row_step * height bytes that are copied to the device
+  if (width <= 0 || height <= 0) return set_error(SSLAM_ERR_INVALID, "cloud of %d x %d points", width, height);
+  if (point_step < 4) return set_error(SSLAM_ERR_INVALID, "point_step %d holds no float", point_step);
+  if (ox < 0 || oy < 0 || oz < 0 || ox > point_step - 4 || oy > point_step - 4 || oz > point_step - 4)
+    return set_error(SSLAM_ERR_INVALID, "field offsets (%d, %d, %d) outside a point of %d bytes", ox, oy, oz, point_step);
+  if ((long long)row_step < (long long)width * point_step)
+    return set_error(SSLAM_ERR_INVALID, "row_step %d below width * point_step = %lld", row_step, (long long)width * point_step);
+  for (int f = 0; f < n_frames; ++f) {
+    if (frames[f].n_boxes < 0) return set_error(SSLAM_ERR_INVALID, "frame %d: n_boxes %d", f, frames[f].n_boxes);
     if (!frames[f].cloud || (!frames[f].boxes && frames[f].n_boxes > 0)) return set_error(SSLAM_ERR_INVALID, "frame %d: null cloud or boxes", f);
+  }
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return set_error(SSLAM_ERR_NO_DEVICE, "no HIP device visible; the product has no CPU fallback");
   SSLAM_HIP_TRY(hipSetDevice(s->P.device));
@@ -2533,7 +2544,7 @@ static int seg_finish(sslam_seg* s, sslam_plane* out, int max_out, int32_t* out_
 }
 static int seg_run(sslam_seg* s, const sslam_frame* frames, int n_frames, int width, int height, int point_step, int row_step, int ox, int oy, int oz,
                    sslam_plane* out, int max_out, int32_t* out_frame) {
-  if (!s || !frames || n_frames <= 0 || (!out && max_out > 0)) return set_error(SSLAM_ERR_INVALID, "null argument");
+  if (!s || !frames || (!out && max_out > 0)) return set_error(SSLAM_ERR_INVALID, "null argument");
   if (s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "%d submitted batch(es) must be collected first", s->n_inflight);
   const int rc = seg_enqueue(s, frames, n_frames, width, height, point_step, row_step, ox, oy, oz);
   if (rc) { s->q_busy = false; return rc; }
