@@ -435,7 +435,12 @@ int sslam_seg_submit_batch(sslam_seg* s, const sslam_frame* frames, int n_frames
                            int off_x, int off_y, int off_z);
 int sslam_seg_collect_batch(sslam_seg* s, sslam_plane* out, int max_out, int32_t* out_frame);
 /* Truncation of the last segment call: planes not returned because max_out was reached, boxes with more than 64 connected
- * components above num_point_seg, boxes with more than 64 accepted planes.  Returns the sum (0 = nothing was truncated). */
+ * components above num_point_seg, boxes with more than 64 accepted planes.  Returns the sum (0 = nothing was truncated).
+ * A box with a full candidate table keeps the 64 components with the LOWEST root pixel index (the order in which the reference
+ * numbers its labels), whatever the order the kernel met them in: its planes repeat from call to call.  They equal the reference's
+ * only if none of the components left out would have been accepted: the reference fits every component and caps the ACCEPTED planes
+ * at 64 in the same order, so a candidate beyond the 64th can still enter its table when an earlier one fails the curvature test.
+ * The third counter cannot become non-zero while the candidate and the region table both hold 64 entries. */
 int sslam_seg_last_overflow(const sslam_seg* s, int* dropped_planes, int* boxes_with_full_candidate_table, int* boxes_with_full_region_table);
 
 /* RANSAC plane fit: pcl::SACSegmentation(SACMODEL_PLANE, SAC_RANSAC, optimise coefficients)

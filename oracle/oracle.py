@@ -283,3 +283,33 @@ def segment_frame(frame, params, want_products: bool = False):
                      nrm.ctypes.data_as(C.c_void_p) if want_products else None,
                      lab.ctypes.data_as(C.c_void_p) if want_products else None)
     return [out[k] for k in range(n)], nrm, lab
+
+
+class SegRegion(C.Structure):
+    """os_region of oracle_seg.c"""
+    _fields_ = [("centroid", C.c_float * 3), ("model", C.c_float * 4), ("inliers", C.c_int), ("last_inlier", C.c_int),
+                ("first_inlier", C.c_int), ("label", C.c_int)]
+
+
+def box_normals(pts, w: int, h: int, max_depth_change_factor: float, normal_smoothing_size: float):
+    """os_normals on the w x h crop of one box: (normals [w*h, 4] with the curvature in column 3, distance map [w*h])"""
+    pts = np.ascontiguousarray(pts, np.float32).reshape(w * h, 3)
+    nrm = np.zeros((w * h, 4), np.float32); dist = np.zeros(w * h, np.float32)
+    lib().os_normals(pts.ctypes.data_as(C.c_void_p), w, h, C.c_float(max_depth_change_factor), C.c_float(normal_smoothing_size),
+                     nrm.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p))
+    return nrm, dist
+
+
+def box_multi_plane(pts, nrm, w: int, h: int, min_inliers: int, angular_threshold: float, distance_threshold: float,
+                    maximum_curvature: float, max_regions: int = 64):
+    """os_multi_plane on one box: (regions, refined label image [w*h], connected-component labels before refinement [w*h])"""
+    pts = np.ascontiguousarray(pts, np.float32).reshape(w * h, 3)
+    nrm = np.ascontiguousarray(nrm, np.float32).reshape(w * h, 4)
+    regs = (SegRegion * max_regions)()
+    lab = np.zeros(w * h, np.int32); cc = np.zeros(w * h, np.int32)
+    cont = np.zeros(4 * w * h + 16, np.int32); cptr = np.zeros(max_regions + 1, np.int32)
+    n = lib().os_multi_plane(pts.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p), w, h, C.c_uint(min_inliers),
+                             C.c_float(angular_threshold), C.c_float(distance_threshold), C.c_float(maximum_curvature), regs, max_regions,
+                             lab.ctypes.data_as(C.c_void_p), cc.ctypes.data_as(C.c_void_p), cont.ctypes.data_as(C.c_void_p),
+                             cptr.ctypes.data_as(C.c_void_p), len(cont))
+    return [regs[k] for k in range(n)], lab, cc

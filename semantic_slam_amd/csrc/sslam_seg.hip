@@ -526,6 +526,23 @@ __global__ __launch_bounds__(NT) void k_regions(View V) {
   for (int i = threadIdx.x; i < n; i += NT)
     if (L[i] == i && (unsigned)cnt[i] > V.min_inliers) { const int k = atomicAdd(&ncand, 1); if (k < kMaxCand) cand[k] = i; }
   __syncthreads();
+  if (ncand > kMaxCand) {
+    // Full table: which 64 roots the atomic counter let in depends on the arrival order of the threads.  Keep the 64 LOWEST roots
+    // instead -- PCL hands its labels out in root order and stops accepting after 64 regions, so this is the set the reference fits
+    // first.  One wave walks the pixels in ascending chunks of 64 and ranks the roots of a chunk by ballot; taken only on overflow.
+    if (threadIdx.x < 64) {
+      int taken = 0;
+      for (int i0 = 0; i0 < n && taken < kMaxCand; i0 += 64) {
+        const int i = i0 + (int)threadIdx.x;
+        const bool m = i < n && L[i] == i && (unsigned)cnt[i] > V.min_inliers;
+        const unsigned long long mask = __ballot(m);
+        const int rank = taken + __popcll(mask & ((1ull << threadIdx.x) - 1ull));
+        if (m && rank < kMaxCand) cand[rank] = i;
+        taken += __popcll(mask);
+      }
+    }
+    __syncthreads();
+  }
   const int nc = min(ncand, kMaxCand);
   if (threadIdx.x == 0) {  // order by root pixel index = PCL's label order (insertion sort, short list)
     for (int a = 1; a < nc; ++a) { const int v = cand[a]; int q = a - 1; while (q >= 0 && cand[q] > v) { cand[q + 1] = cand[q]; --q; } cand[q + 1] = v; }
@@ -630,7 +647,7 @@ __global__ __launch_bounds__(NT) void k_regions(View V) {
     for (int q = 0; q < nc; ++q) tot += accepted[q];
     V.nreg[blockIdx.x] = min(tot, kMaxRegions);
     if (ncand > kMaxCand) atomicAdd(&V.overflow[0], 1);
-    if (tot > kMaxRegions) atomicAdd(&V.overflow[1], 1);
+    if (tot > kMaxRegions) atomicAdd(&V.overflow[1], 1);   // cannot fire while kMaxRegions == kMaxCand (tot <= nc); kept for the ABI's third counter
   }
 }
 
