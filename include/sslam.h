@@ -674,7 +674,9 @@ int sslam_slam_set_segmented_objects(sslam_slam* s, const sslam_plane* objects, 
 /* VIOCallback (semantic_graph_slam.cpp:234-287): keyframe gate, dead-reckoned robot pose, queue.  Returns 1 when the odometry sample
  * became a keyframe, 0 when the gate rejected it. */
 int sslam_slam_vio(sslam_slam* s, int32_t stamp_sec, int32_t stamp_nsec, const double odom_tq[7]);
-/* run (semantic_graph_slam.cpp:58-102): returns 1 when keyframes were processed, 0 when the queue was empty */
+/* run (semantic_graph_slam.cpp:58-102): returns 1 when keyframes were processed, 0 when the queue was empty.  On an error after the
+ * queue was touched, the keyframes that reached the graph stay in it (once: sslam_slam_keyframes lists them), their objects are lost,
+ * nothing is optimised in that call, and the next call associates against the landmark table uploaded again. */
 int sslam_slam_run(sslam_slam* s, sslam_tick_stats* stats);
 /* getRobotPose / getMap2OdomTrans / getVIOPose (semantic_graph_slam.cpp:375-381,333-339) */
 int sslam_slam_robot_pose(const sslam_slam* s, double tq[7]);
@@ -687,7 +689,9 @@ int sslam_slam_keyframes(const sslam_slam* s, int32_t* vertex_ids, double* estim
 sslam_graph* sslam_slam_graph(sslam_slam* s);
 /* data_association::find_matches (data_association.h:75-95) on its own: associates n segmented objects seen from robot_pose
  * (x,y,z,roll,pitch,yaw) against the mapped landmarks ON THE DEVICE and appends the new ones to the landmark list (without adding
- * graph vertices: parity hook for the association kernel).  out = n records. */
+ * graph vertices: parity hook for the association kernel).  out = n records.
+ * A sslam_slam_run after the hook still optimises, but finds no marginal for the vertex-less landmarks: marginals_ok == 0, every
+ * covariance keeps its value, no error is returned. */
 int sslam_slam_find_matches(sslam_slam* s, const sslam_plane* objects, int n, const float robot_pose[6], sslam_landmark* out);
 
 #ifdef __cplusplus

@@ -8,8 +8,9 @@ tests or golden vectors for this path, and it cannot be built here (ROS / g2o / 
                                               :152-179  empty_landmark_queue
                                               :181-205  getAndSetLandmarkCov
                                               :234-287  VIOCallback
+                                              :289-329  addFirstPoseAndLandmark
     include/ps_graph_slam/keyframe_updater.hpp:41-65    KeyframeUpdater::update
-    include/ps_graph_slam/data_association.h:75-389     find_matches, associate_lanmarks, map_a_new_lan, inserst_a_mapped_lan, ...
+    include/ps_graph_slam/data_association.h:70-389     addFirstLandmark, find_matches, associate_lanmarks, map_a_new_lan, inserst_a_mapped_lan, ...
     src/ps_graph_slam/information_matrix_calculator.cpp:28-35
     include/ps_graph_slam/ros_utils.hpp:90-106          matrix2vector
     include/tools.h:18-135                              transformNormalsToWorld, transformPoseFromCameraToRobot
@@ -30,6 +31,7 @@ from . import oracle as O
 
 F = np.float32
 FLT_MAX = F(3.402823466e+38)
+CLASS_BUCKET = 6                   # SSLAM_CLASS_BUCKET of include/sslam.h: "bucket" in the reference's class list
 
 
 # ---- rigid transforms -----------------------------------------------------------------------------------------------------------
@@ -64,9 +66,30 @@ def mat_to_quat(R):
     return q
 
 
+def _norm(v):
+    """sqrt of the sum of squares, added up in order (np.linalg.norm goes through a BLAS dot whose order is its own)"""
+    s = 0.0
+    for x in v:
+        s += float(x) * float(x)
+    return math.sqrt(s)
+
+
+def _mm4(A, B):
+    """4x4 double product with the plain left-to-right accumulation of oracle_slam.c's mm4: the two CPU drivers then hand the same
+    bits to the optimiser, and LM, whose last steps hang on the last bits of its input, ends at the same point in both"""
+    C = np.zeros((4, 4))
+    for r in range(4):
+        for c in range(4):
+            s = 0.0
+            for k in range(4):
+                s += float(A[r, k]) * float(B[k, c])
+            C[r, c] = s
+    return C
+
+
 def tq_to_iso(tq):
     q = np.asarray(tq[3:7], float)
-    q = q / np.linalg.norm(q)
+    q = q / _norm(q)
     T = np.eye(4)
     T[:3, :3] = quat_to_mat(q)
     T[:3, 3] = tq[:3]
@@ -75,7 +98,7 @@ def tq_to_iso(tq):
 
 def iso_to_tq(T):
     q = mat_to_quat(T[:3, :3])
-    q = q / np.linalg.norm(q)
+    q = q / _norm(q)
     return np.concatenate([T[:3, 3], q])
 
 
@@ -83,7 +106,11 @@ def iso_inv(T):
     R = T[:3, :3].T
     o = np.eye(4)
     o[:3, :3] = R
-    o[:3, 3] = -R @ T[:3, 3]
+    for r in range(3):
+        s = 0.0
+        for k in range(3):
+            s += float(R[r, k]) * float(T[k, 3])
+        o[r, 3] = -s
     return o
 
 
@@ -196,11 +223,19 @@ def _inverse_lu3(A):
     return inv
 
 
+_INVERSES = {}      # (S + qI) bytes -> its inverse: a map of a thousand landmarks is scanned once per detection
+
+
 def mahalanobis(sigma, q, z):
     Q = sigma.astype(F).copy()
     for k in range(3):
         Q[k, k] = F(Q[k, k] + F(q))
-    inv = _inverse_lu3(Q)
+    key = Q.tobytes()
+    inv = _INVERSES.get(key)
+    if inv is None:
+        if len(_INVERSES) > 65536:
+            _INVERSES.clear()
+        inv = _INVERSES[key] = _inverse_lu3(Q)
     rv = [F(F(F(z[0] * inv[0, c]) + F(z[1] * inv[1, c])) + F(z[2] * inv[2, c])) for c in range(3)]
     return F(F(F(rv[0] * z[0]) + F(rv[1] * z[1])) + F(rv[2] * z[2]))
 
@@ -304,7 +339,7 @@ def _inverse3f(m):
 class SemanticGraphSlam:
     def __init__(self, keyframe_delta_trans=0.5, keyframe_delta_angle=0.5, keyframe_delta_time=1.0, max_keyframes_per_update=10,
                  update_keyframes_using_detections=False, camera_angle_deg=0.0, const_stddev_x=0.0, const_stddev_q=0.0,
-                 max_iterations=1024, seg_params=None, **da):
+                 max_iterations=1024, seg_params=None, add_first_lan=False, first_lan=(1.8, 0.0, 0.3), **da):
         self.dt, self.da_, self.dtime = keyframe_delta_trans, keyframe_delta_angle, keyframe_delta_time
         self.max_kf = max_keyframes_per_update
         self.using_det = update_keyframes_using_detections
@@ -325,6 +360,26 @@ class SemanticGraphSlam:
         self.vtype, self.vfixed, self.est = [], [], []
         self.etype, self.evi, self.evj, self.meas, self.info = [], [], [], [], []
         self.last_stats = None
+        if add_first_lan:
+            self._add_first_pose_and_landmark(first_lan)
+
+    def _add_first_pose_and_landmark(self, first_lan):
+        """addFirstPoseAndLandmark (semantic_graph_slam.cpp:289-329) with addFirstLandmark (data_association.h:70-73): a vertical bucket
+        plane at first_lan, known before anything is seen, hangs by one edge on a keyframe at the identity.  The keyframe gate and
+        first_key_added are not touched: the first odometry sample still becomes a keyframe and gets an odometry edge to this one."""
+        p = np.array(first_lan, F)
+        cov = np.zeros((3, 3), F)
+        cov[0, 0] = cov[1, 1] = cov[2, 2] = F(0.1)
+        l = dict(id=0, vertex=-1, class_id=CLASS_BUCKET, plane_type=1, pose=p.copy(), local_pose=p.copy(), covariance=cov,
+                 normal=np.array([-0.4, 0.86, 0, 0], F), is_new=True, distance=-1.0)
+        self.assoc.first_object = False
+        self.assoc.landmarks.append(dict(l, covariance=cov.copy()))
+        self.queue.append(dict(odom=np.eye(4), robot_pose=self.robot_pose.copy(), node=-1, objects=[], boxes=None, cloud=None))
+        if self._empty_keyframe_queue():
+            for kf in self.new_keyframes:
+                self._landmark_edges([l], kf, None)
+            self.keyframes += self.new_keyframes
+            self.new_keyframes = []
 
     # -- callbacks
     def set_segmented_objects(self, objs):
@@ -356,9 +411,9 @@ class SemanticGraphSlam:
         if self.is_first:
             self.is_first = False; self.prev_stamp = stamp; self.prev_keypose = odom
             return True
-        delta = iso_inv(self.prev_keypose) @ odom
-        dx = float(np.linalg.norm(delta[:3, 3]))
-        da = math.acos(min(1.0, mat_to_quat(delta[:3, :3])[3] / np.linalg.norm(mat_to_quat(delta[:3, :3]))))
+        delta = _mm4(iso_inv(self.prev_keypose), odom)
+        dx = _norm(delta[:3, 3])
+        da = math.acos(min(1.0, mat_to_quat(delta[:3, :3])[3] / _norm(mat_to_quat(delta[:3, :3]))))
         dsec, dnsec = stamp[0] - self.prev_stamp[0], stamp[1] - self.prev_stamp[1]
         if dnsec < 0:
             dsec -= 1
@@ -373,7 +428,7 @@ class SemanticGraphSlam:
         reject = (not accept and not self.object_detection_available) if self.using_det else (not accept)
         if reject:
             if self.first_key_added:
-                self.robot_pose = self.robot_pose @ (iso_inv(self.prev_odom) @ odom)
+                self.robot_pose = _mm4(self.robot_pose, _mm4(iso_inv(self.prev_odom), odom))
             self.vio_pose = odom; self.prev_odom = odom
             return False
         kf = dict(odom=odom, robot_pose=self.robot_pose.copy(), node=-1, objects=[], boxes=None, cloud=None)
@@ -414,7 +469,7 @@ class SemanticGraphSlam:
             if i == 0 and not self.keyframes:
                 continue
             prev = self.keyframes[-1] if i == 0 else self.queue[i - 1]
-            rel = iso_inv(prev["odom"]) @ kf["odom"]
+            rel = _mm4(iso_inv(prev["odom"]), kf["odom"])
             self._add_edge(O.ET_SE3, prev["node"], kf["node"], iso_to_tq(rel), info)
         del self.queue[:n]
         return True
@@ -426,6 +481,23 @@ class SemanticGraphSlam:
 
     def problem(self):
         return O.GraphProblem(self.vtype, self.vfixed, np.array(self.est), self.etype, self.evi, self.evj, np.array(self.meas), np.array(self.info))
+
+    def _landmark_edges(self, cur, kf, stats):
+        """empty_landmark_queue (semantic_graph_slam.cpp:152-179)"""
+        count = stats if stats is not None else dict(landmarks_added=0, landmarks_matched=0, landmark_edges_added=0)
+        for l in cur:
+            if l["is_new"]:
+                l["vertex"] = self._add_vertex(O.VT_POINT, l["pose"].astype(float))
+                l["is_new"] = False
+                self.assoc.landmarks[l["id"]]["vertex"] = l["vertex"]
+                count["landmarks_added"] += 1
+            else:
+                if l["vertex"] < 0:      # matched a landmark an earlier detection of the same frame created: it has its vertex by now
+                    l["vertex"] = self.assoc.landmarks[l["id"]]["vertex"]
+                count["landmarks_matched"] += 1
+            inf = _inverse3f(l["covariance"]).astype(float)
+            self._add_edge(O.ET_SE3_POINT, kf["node"], l["vertex"], l["local_pose"].astype(float), inf)
+            count["landmark_edges_added"] += 1
 
     def run(self):
         if not self._empty_keyframe_queue():
@@ -441,19 +513,7 @@ class SemanticGraphSlam:
             rp = matrix2vector(kf["robot_pose"])
             cur = self.assoc.find_matches(kf["objects"], rp, F(self.cam_angle), self._estimate_of)
             stats["records"].append(cur)
-            for l in cur:
-                if l["is_new"]:
-                    l["vertex"] = self._add_vertex(O.VT_POINT, l["pose"].astype(float))
-                    l["is_new"] = False
-                    self.assoc.landmarks[l["id"]]["vertex"] = l["vertex"]
-                    stats["landmarks_added"] += 1
-                else:
-                    if l["vertex"] < 0:      # matched a landmark an earlier detection of the same frame created: it has its vertex by now
-                        l["vertex"] = self.assoc.landmarks[l["id"]]["vertex"]
-                    stats["landmarks_matched"] += 1
-                inf = _inverse3f(l["covariance"]).astype(float)
-                self._add_edge(O.ET_SE3_POINT, kf["node"], l["vertex"], l["local_pose"].astype(float), inf)
-                stats["landmark_edges_added"] += 1
+            self._landmark_edges(cur, kf, stats)
         self.keyframes += self.new_keyframes
         self.new_keyframes = []
         if len(self.etype) >= 10:                      # GraphSLAM::optimize (graph_slam.cpp:184-186)
@@ -475,7 +535,7 @@ class SemanticGraphSlam:
                 stats["marginals_ok"] = True
             last = self.keyframes[-1]
             self.robot_pose = tq_to_iso(self.est[last["node"]])
-            self.map2odom = self.robot_pose @ iso_inv(last["odom"])
+            self.map2odom = _mm4(self.robot_pose, iso_inv(last["odom"]))
         self.first_key_added = True
         self.last_stats = stats
         return True

@@ -185,7 +185,8 @@ class OslamParams(C.Structure):
                 ("max_keyframes_per_update", C.c_int), ("update_keyframes_using_detections", C.c_int),
                 ("camera_angle_rad", C.c_double), ("const_stddev_x", C.c_double), ("const_stddev_q", C.c_double),
                 ("max_iterations", C.c_int), ("maha_dist_thres", C.c_double), ("eq_dist_thres", C.c_double), ("land_noise_low", C.c_float),
-                ("use_maha_dist", C.c_int), ("use_eq_dist", C.c_int), ("use_rtab_map_odom", C.c_int), ("keep_distance_min", C.c_int), ("quirks", C.c_int)]
+                ("use_maha_dist", C.c_int), ("use_eq_dist", C.c_int), ("use_rtab_map_odom", C.c_int), ("keep_distance_min", C.c_int), ("quirks", C.c_int),
+                ("add_first_lan", C.c_int), ("first_lan", C.c_double * 3)]
 
 
 class OslamTickStats(C.Structure):
@@ -202,14 +203,14 @@ class SlamTickC:
     def __init__(self, keyframe_delta_trans=0.5, keyframe_delta_angle=0.5, keyframe_delta_time=1.0, max_keyframes_per_update=10,
                  update_keyframes_using_detections=False, camera_angle_deg=0.0, const_stddev_x=0.0, const_stddev_q=0.0, max_iterations=1024,
                  maha_dist_thres=0.5, eq_dist_thres=1.21, land_noise_low=0.5, use_maha_dist=True, use_eq_dist=False,
-                 use_rtab_map_odom=False, keep_distance_min=False, quirks=True):
+                 use_rtab_map_odom=False, keep_distance_min=False, quirks=True, add_first_lan=False, first_lan=(1.8, 0.0, 0.3)):
         import math
         L = lib()
         L.oslam_create.restype = C.c_void_p
         p = OslamParams(keyframe_delta_trans, keyframe_delta_angle, keyframe_delta_time, max_keyframes_per_update,
                         int(update_keyframes_using_detections), camera_angle_deg * (math.pi / 180), const_stddev_x, const_stddev_q, max_iterations,
                         maha_dist_thres, eq_dist_thres, land_noise_low, int(use_maha_dist), int(use_eq_dist), int(use_rtab_map_odom),
-                        int(keep_distance_min), int(quirks))
+                        int(keep_distance_min), int(quirks), int(add_first_lan), (C.c_double * 3)(*[float(v) for v in first_lan]))
         self._L = L
         self._h = C.c_void_p(L.oslam_create(C.byref(p)))
         self.last_stats = None

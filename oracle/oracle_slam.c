@@ -8,8 +8,9 @@
  *                                               :152-179  empty_landmark_queue
  *                                               :181-205  getAndSetLandmarkCov
  *                                               :234-287  VIOCallback
+ *                                               :289-329  addFirstPoseAndLandmark
  *     include/ps_graph_slam/keyframe_updater.hpp:41-65    KeyframeUpdater::update
- *     include/ps_graph_slam/data_association.h:75-389     find_matches and what it calls
+ *     include/ps_graph_slam/data_association.h:70-389     addFirstLandmark, find_matches and what it calls
  *     src/ps_graph_slam/information_matrix_calculator.cpp:28-35
  *     include/ps_graph_slam/ros_utils.hpp:90-106          matrix2vector
  *     include/tools.h:18-135                              transformNormalsToWorld, transformPoseFromCameraToRobot
@@ -44,6 +45,8 @@ typedef struct {
   double maha_dist_thres, eq_dist_thres;
   float land_noise_low;
   int use_maha_dist, use_eq_dist, use_rtab_map_odom, keep_distance_min, quirks;
+  int add_first_lan;
+  double first_lan[3];
 } oslam_params;
 typedef struct {
   int keyframes_added, landmarks_added, landmarks_matched, landmark_edges_added, optimized, marginals_ok;
@@ -277,6 +280,7 @@ static void add_edge(oslam *S, int etype, int i, int j, const double *meas, int 
 }
 
 /* ---- public interface ---- */
+static void push_lmk(oslam *S, const lmk_t *l);
 oslam *oslam_create(const oslam_params *p) {
   oslam *S = calloc(1, sizeof(oslam));
   S->p = *p;
@@ -285,6 +289,27 @@ oslam *oslam_create(const oslam_params *p) {
   S->first_object = 1; S->is_first = 1;
   eye4(S->robot_pose); eye4(S->prev_odom); eye4(S->prev_keypose); eye4(S->last_odom);
   S->last_node = -1;
+  if (S->p.add_first_lan) {   /* addFirstPoseAndLandmark (semantic_graph_slam.cpp:289-329), addFirstLandmark (data_association.h:70-73) */
+    lmk_t l;
+    memset(&l, 0, sizeof l);
+    l.class_id = 6 /* bucket */; l.plane_type = 1; l.id = 0; l.is_new = 1; l.distance = -1.0;
+    for (int k = 0; k < 3; ++k) l.pose[k] = l.local_pose[k] = (F)S->p.first_lan[k];
+    l.normal[0] = -0.4f; l.normal[1] = 0.86f;
+    l.cov[0] = l.cov[4] = l.cov[8] = 0.1f;
+    S->first_object = 0;
+    /* the keyframe at the identity, alone in the queue: no odometry edge; the gate and first_key_added stay as they were */
+    const double tq[7] = {0, 0, 0, 0, 0, 0, 1};
+    S->last_node = add_vertex(S, VT_SE3, tq, 7);
+    S->nkeyframes = 1;
+    const double e[3] = {l.pose[0], l.pose[1], l.pose[2]};
+    l.vertex = add_vertex(S, VT_POINT, e, 3);
+    push_lmk(S, &l);
+    F inff[9];
+    inverse3f(l.cov, inff);
+    double inf[9];
+    for (int q = 0; q < 9; ++q) inf[q] = inff[q];
+    add_edge(S, ET_SE3_POINT, S->last_node, l.vertex, e, 3, inf, 9);
+  }
   return S;
 }
 void oslam_destroy(oslam *S) {

@@ -37,9 +37,11 @@ def _compare_state(P, Or, tol_est=1e-6):
     assert np.abs(mp[:3] - mo[:3]).max() <= 10 * tol_est
 
 
-def _run_both(events):
-    """the product and the oracle through the same events, compared tick by tick; returns (product, oracle, ticks)"""
-    P, Or = product_instance(), oracle_instance()
+def _run_both(events, on_tick=None, **kw):
+    """the product and the oracle (both built with the parameters `kw`) through the same events, compared tick by tick
+    (on_tick(product, oracle) after each tick that ran); returns (product, oracle, ticks)"""
+    P, Or = product_instance(**kw), oracle_instance(**kw)
+    max_kf = kw.get("max_keyframes_per_update", 10)
     ticks = 0
     for ev in events:
         kp, rp = feed(P, ev, True)
@@ -51,10 +53,12 @@ def _run_both(events):
         st, so = P.last_stats, Or.last_stats
         assert (st.keyframes_added, st.landmarks_added, st.landmarks_matched, st.landmark_edges_added, bool(st.optimized), bool(st.marginals_ok)) == \
                (so["keyframes_added"], so["landmarks_added"], so["landmarks_matched"], so["landmark_edges_added"], so["optimized"], so["marginals_ok"])
-        assert st.keyframes_added <= 10
+        assert st.keyframes_added <= max_kf
         if so["optimized"]:
             assert abs(st.opt.chi2_after - so["opt"].chi2_after) <= 1e-6 * max(1.0, so["opt"].chi2_after)
         _compare_state(P, Or)
+        if on_tick:
+            on_tick(P, Or)
     return P, Or, ticks
 
 
