@@ -8,6 +8,7 @@
 #include <map>
 #include <string>
 #include <vector>
+#include "batch_tables.hpp"
 #include "graph_host.hpp"
 #include "graph_kernels.hpp"
 #include "sslam_common.hpp"
@@ -76,7 +77,6 @@ struct DevArena {
     flushed = small_used;
     return 0;
   }
-  void note_direct(void*, size_t) {}   // large-region arrays are written by their own memset / copy; nothing of the mirror overlaps them
   void reset() {   // the caller guarantees that no kernel still uses the memory (the owning batch has been released)
     for (void* p : spill) (void)hipFree(p);
     spill.clear();
@@ -114,17 +114,7 @@ struct Batch {
   double plan_build_ms = 0;    // host time of chol_plan_build since the last sslam_graph_optimize read it (sslam_opt_stats::host_plan_us)
   PinnedScratch own_pin;       // staging of the small copies ...
   PinnedScratch* pin = &own_pin;   // ... or the graph handle's (kept across the per-tick rebuilds of its batch of one)
-  // host-side metadata
-  std::vector<GraphSeg> seg;
-  std::vector<std::vector<int>> v2pose, v2lm;     // per graph: vertex id -> pose / landmark index (global), -1
-  std::vector<int> pose_row, lm_row;              // global
-  std::vector<int> prow_pose, lrow_lm;
-  std::vector<std::pair<int, int>> ppoff;         // unique pose-pose blocks (row a < row b)
-  std::vector<std::pair<int, int>> plblk;         // unique pose-landmark blocks (pose row, lm row)
-  std::vector<std::pair<int, int>> llblk;         // unique landmark-landmark blocks (lm row a < lm row b): point-point edges
-  int64_t hll_off_base = 0;
-  std::vector<int> pose_vertex, lm_vertex;        // global pose/lm index -> vertex id in its graph
-  int64_t hpp_off_base = 0, hpl_base = 0, hll_base = 0;
+  BatchMaps T;   // host side of the device tables (batch_tables.hpp): index maps, unique blocks, the layout of H
   double* d_part_e = nullptr;  // [B*maxEdgeChunks]
   double* d_part_m = nullptr;  // [B*maxRowChunks] (max diag)
   bool profiling = false;
@@ -134,10 +124,6 @@ struct Batch {
   std::vector<hipEvent_t> event_pool;
   bool uploaded = false;
   LmState* d_lm_save = nullptr;   // [B] sslam_batch_marginals / sslam_batch_solve: the per-graph LM states while the call borrows them (allocated at its first use)
-  bool has_duplicate_blocks = false;
-  bool has_planes = false;
-  std::vector<int> dup_eo, dup_el;
-  int max_row_slots = 0;
   CholPlan* chol = nullptr;    // piece plan (chol_plan.hpp) of the direct solvers: the LM loop and the flat factor of the marginals
   // edge-sharded mode
   bool sharded = false;        // linearize only the edges of this rank's range
@@ -147,9 +133,8 @@ struct Batch {
   int64_t allreduce_calls = 0; // ncclAllReduce calls issued so far (tests: the collective really ran)
   int shard_rank = 0, shard_world = 1;
   int64_t compact_rounds = 0;  // chol_set_active calls so far that left the launches sized by index lists (tests: the compacted forms really ran)
-  // per-edge robust kernels: (graph, graph-local edge id) of every edge of the four storage classes (SE3, landmark, point-point, prior) as
-  // batch_build ordered them, the device arrays (allocated when a kernel is first seen) and the sum of the graphs' robust_version they hold
-  std::vector<int> cls_src[4], cls_g[4];
+  // per-edge robust kernels: kind / delta of every edge of the four storage classes in device order, allocated when a kernel is first
+  // seen, and the sum of the graphs' robust_version they hold
   unsigned char* d_rk[4] = {nullptr, nullptr, nullptr, nullptr};
   double* d_rd[4] = {nullptr, nullptr, nullptr, nullptr};
   bool robust_synced = false, has_robust = false;
@@ -205,7 +190,6 @@ inline int dev_upload(Batch& b, const std::vector<T>& h, T** out, size_t min_ele
       *out = (T*)p;
       return 0;
     }
-    b.arena->note_direct(p, n * sizeof(T));
   } else { SSLAM_HIP_TRY(hipMalloc(&p, n * sizeof(T))); b.allocs.push_back(p); }
   if (!h.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, b.stream));
   *out = (T*)p;
@@ -223,7 +207,6 @@ inline int dev_alloc(Batch& b, size_t n, T** out, bool zero = true) {
       *out = (T*)p;
       return 0;
     }
-    b.arena->note_direct(p, n * sizeof(T));
   } else { SSLAM_HIP_TRY(hipMalloc(&p, n * sizeof(T))); b.allocs.push_back(p); }
   if (zero) SSLAM_HIP_TRY(hipMemsetAsync(p, 0, n * sizeof(T), b.stream));
   *out = (T*)p;
@@ -233,7 +216,7 @@ inline int dev_alloc(Batch& b, size_t n, T** out, bool zero = true) {
 
 // sparse block Cholesky (sslam_chol.hip; symbolic phase in chol_plan.hpp)
 struct SymIn;
-void chol_sym_input(const Batch& b, SymIn& in);
+void chol_sym_input(const BatchMaps& T, SymIn& in);
 int chol_plan_build(Batch& b);
 int chol_plan_launches(const Batch& b);
 int chol_factor_and_forward(Batch& b, bool flat = false);   // (H + lambda I) = L L^T for in_trial graphs, y = L^-1 b

@@ -11,24 +11,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "graph_host.hpp"   // GraphSeg, kEdgeChunk, kRowChunk
 #include "sslam_math.hpp"
 
 namespace sslam {
-
-constexpr int kEdgeChunk = 256;  // threads per workgroup in edge-parallel kernels
-constexpr int kRowChunk = 192;
-constexpr int kTileSlots = 96;   // max (row, edge) slots per Jacobian-build tile (LDS budget)   // threads per workgroup in scalar-row kernels (multiple of 6 and 64)
-
-struct GraphSeg {
-  int prow0, nprow;  // active pose rows  [prow0, prow0+nprow)
-  int lrow0, nlrow;  // active landmark rows
-  int eo0, neo;      // SE3 edges
-  int el0, nel;      // landmark edges
-  int pose0, npose;  // all SE3 vertices (incl. fixed)
-  int lm0, nlm;      // all landmark vertices
-  int ell0, nell;    // point-point edges (g2o::EdgePointXYZ)
-  int ep0, nep;      // position priors (EdgeSE3PriorXY / EdgeSE3PriorXYZ)
-};
 
 struct LmState {
   double lambda, nu, cur_chi, tmp_chi, rho, scale, chi_before, max_diag;
@@ -75,12 +61,9 @@ struct BatchView {
   int64_t h_total;  // doubles in the H allocation
   // row adjacency for SpMV (rows = pose rows then landmark rows)
   const int* adj_ptr; const int* adj_blk; const int* adj_x; const unsigned char* adj_fmt;
-  // gather-form Jacobian build: (row, incident edge) slots, pose rows tiled by slot count
-  int nTiles;
-  const int* tile_row0; const int* tile_row1;       // [nTiles] pose-row range of a tile (one graph each)
+  // gather-form Jacobian build: (row, incident edge) slots
   const int* pslot_ptr;                             // [nPr+1]
-  const int4* pslot_rec;                            // [slots] {edge, kind, pose i | pose, pose j | landmark}
-  const int* pslot_edge; const unsigned char* pslot_kind;  // kind 0: SE3 edge, self = i; 1: SE3, self = j; 2: landmark edge
+  const int4* pslot_rec;                            // [slots] {edge, kind, pose i | pose, pose j | landmark}; kind 0: SE3 edge, self = i; 1: SE3, self = j; 2: landmark edge
   const int* lslot_ptr; const int* lslot_edge;      // [nLr+1], landmark-side slots (edge index into el_*)
   int nDupEo, nDupEl; const int* dup_eo; const int* dup_el;  // non-owner edges of shared off-diagonal blocks
   // edge-sharded mode (one graph's edges split across ranks, SURVEY 8e mode E): a rank builds the partial normal equations of the

@@ -1799,7 +1799,6 @@ int up_to_dev(CholPlan& P, hipStream_t s, const std::vector<T>& h, const T** out
       *out = (const T*)p;
       return 0;
     }
-    P.arena->note_direct(p, n * sizeof(T));
   } else { SSLAM_HIP_TRY(hipMalloc(&p, n * sizeof(T))); P.allocs.push_back(p); }
   SSLAM_HIP_TRY(hipMemsetAsync(p, 0, n * sizeof(T), s));
   if (!h.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
@@ -1808,12 +1807,12 @@ int up_to_dev(CholPlan& P, hipStream_t s, const std::vector<T>& h, const T** out
 }
 }  // namespace
 
-void chol_sym_input(const Batch& b, SymIn& in) {
-  in.B = b.V.B; in.nPr = b.V.nPr; in.nLr = b.V.nLr;
-  in.seg.resize(b.seg.size());
-  for (size_t g = 0; g < b.seg.size(); ++g) in.seg[g] = SymGraph{b.seg[g].prow0, b.seg[g].nprow, b.seg[g].lrow0, b.seg[g].nlrow};
-  in.ppoff = b.ppoff; in.plblk = b.plblk; in.llblk = b.llblk;
-  in.hll_base = b.hll_base; in.hpp_off_base = b.hpp_off_base; in.hpl_base = b.hpl_base; in.hll_off_base = b.hll_off_base;
+void chol_sym_input(const BatchMaps& T, SymIn& in) {
+  in.B = (int)T.seg.size(); in.nPr = T.nPr(); in.nLr = T.nLr();
+  in.seg.resize(T.seg.size());
+  for (size_t g = 0; g < T.seg.size(); ++g) in.seg[g] = SymGraph{T.seg[g].prow0, T.seg[g].nprow, T.seg[g].lrow0, T.seg[g].nlrow};
+  in.ppoff = T.ppoff; in.plblk = T.plblk; in.llblk = T.llblk;
+  in.hll_base = T.hll_base; in.hpp_off_base = T.hpp_off_base; in.hpl_base = T.hpl_base; in.hll_off_base = T.hll_off_base;
 }
 
 // speculative damping trials of a single small graph: the graph's option, or SSLAM_LM_SPEC = 0 / 1 / 2 for every graph of the process
@@ -1827,7 +1826,7 @@ int chol_plan_build(Batch& b) {
   if (b.chol) { chol_plan_free(b.chol); b.chol = nullptr; }
   SSLAM_HIP_TRY(hipSetDevice(b.device));
   SymIn in;
-  chol_sym_input(b, in);
+  chol_sym_input(b.T, in);
   CholOpts opt;
   opt.from_env();
   // small batches (latency-bound: the orchestrator's graph, a single large graph): the dependency-driven single launch (k_chol_flow) runs
@@ -1908,8 +1907,7 @@ int chol_plan_build(Batch& b) {
   void* p = nullptr;
   auto plan_alloc = [&](void** q, size_t bytes) -> int {
     if (P->arena) {
-      *q = P->arena->take(bytes, true);
-      if (*q) P->arena->note_direct(*q, bytes);   // zero-filled below with its own memset: the arena's flush must leave it alone
+      *q = P->arena->take(bytes, true);   // direct: zero-filled below with its own memset, the arena's flush leaves it alone
       return *q ? 0 : set_error(SSLAM_ERR_HIP, "device allocation of %zu bytes failed", bytes);
     }
     SSLAM_HIP_TRY(hipMalloc(q, bytes)); P->allocs.push_back(*q);

@@ -1128,337 +1128,85 @@ std::string& last_error_ref() {
   return e;
 }
 
-static inline uint64_t pair_key(int a, int b) { return ((uint64_t)(uint32_t)a << 32) | (uint32_t)b; }
+// A host table -> the device array behind a BatchView field (out of the handle's arena, where it travels with the one flush below, or an
+// allocation and copy of its own).  T and U differ in name only (std::array<int, 4> on the host, int4 on the device).
+template <class T, class U>
+static int upload_table(Batch& b, const std::vector<T>& h, const U*& field) {
+  static_assert(sizeof(T) == sizeof(U), "host and device records must have one layout");
+  T* p = nullptr;
+  const int rc = dev_upload(b, h, &p);
+  field = reinterpret_cast<const U*>(p);
+  return rc;
+}
 
-// Compile host graphs into the device-resident batch layout (g2o initializeOptimization +
-// BlockSolver::buildStructure analogue; symbolic work only).
-static int batch_build(Batch& b, bool host_only = false) {
-  if (!host_only) {
-    SSLAM_HIP_TRY(hipSetDevice(b.device));
-    if (!b.stream) SSLAM_HIP_TRY(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
-  }
-  const int B = (int)b.graphs.size();
-  b.seg.assign(B, GraphSeg{});
-  b.v2pose.assign(B, {}); b.v2lm.assign(B, {});
-  b.pose_row.clear(); b.lm_row.clear(); b.prow_pose.clear(); b.lrow_lm.clear();
-  b.ppoff.clear(); b.plblk.clear(); b.llblk.clear(); b.pose_vertex.clear(); b.lm_vertex.clear();
-  std::vector<int> prow_graph, lrow_graph;
-  std::vector<unsigned char> lm_kind;
-  std::vector<int> eo_i, eo_j, eo_blk, el_p, el_l, el_blk;
-  std::vector<int> eo_src, el_src;  // (graph-local edge id) for SoA fill
-  std::vector<int> eo_g, el_g;
-  std::vector<int> ell_a, ell_b, ell_src, ell_g, ell_blk;   // point-point edges (g2o::EdgePointXYZ)
-  std::vector<int> ep_pose, ep_dim, ep_src, ep_g;          // position priors (EdgeSE3PriorXY / XYZ)
-  std::vector<int> shard_lo(b.graphs.size(), 0), shard_hi(b.graphs.size(), 0x7fffffff);
-  int maxRow = 1, maxEdge = 1;
-  for (int g = 0; g < B; ++g) {
-    const HostGraph& G = *b.graphs[g];
-    std::vector<int> hidx;
-    hessian_indices(G, hidx);
-    GraphSeg& sg = b.seg[g];
-    sg.pose0 = (int)b.pose_row.size(); sg.lm0 = (int)b.lm_row.size();
-    sg.prow0 = (int)b.prow_pose.size(); sg.lrow0 = (int)b.lrow_lm.size();
-    sg.eo0 = (int)eo_i.size(); sg.el0 = (int)el_p.size(); sg.ell0 = (int)ell_a.size(); sg.ep0 = (int)ep_pose.size();
-    auto& vp = b.v2pose[g]; auto& vl = b.v2lm[g];
-    vp.assign(G.nv(), -1); vl.assign(G.nv(), -1);
-    for (int v = 0; v < G.nv(); ++v) {
-      if (G.vtype[v] == VT_SE3) {
-        vp[v] = (int)b.pose_row.size();
-        b.pose_vertex.push_back(v);
-        if (hidx[v] >= 0) { b.pose_row.push_back((int)b.prow_pose.size()); b.prow_pose.push_back(vp[v]); prow_graph.push_back(g); }
-        else b.pose_row.push_back(-1);
-      } else {
-        vl[v] = (int)b.lm_row.size();
-        b.lm_vertex.push_back(v);
-        lm_kind.push_back((unsigned char)G.vtype[v]);
-        if (hidx[v] >= 0) { b.lm_row.push_back((int)b.lrow_lm.size()); b.lrow_lm.push_back(vl[v]); lrow_graph.push_back(g); }
-        else b.lm_row.push_back(-1);
-      }
-    }
-    sg.npose = (int)b.pose_row.size() - sg.pose0; sg.nlm = (int)b.lm_row.size() - sg.lm0;
-    sg.nprow = (int)b.prow_pose.size() - sg.prow0; sg.nlrow = (int)b.lrow_lm.size() - sg.lrow0;
-    for (int k = 0; k < G.ne(); ++k) {
-      if (G.etype[k] == ET_SE3) { eo_i.push_back(vp[G.evi[k]]); eo_j.push_back(vp[G.evj[k]]); eo_src.push_back(k); eo_g.push_back(g); }
-      else if (G.etype[k] == ET_POINT_POINT) { ell_a.push_back(vl[G.evi[k]]); ell_b.push_back(vl[G.evj[k]]); ell_src.push_back(k); ell_g.push_back(g); }
-      else if (is_prior_edge(G.etype[k])) { ep_pose.push_back(vp[G.evi[k]]); ep_dim.push_back(G.etype[k] == ET_SE3_PRIOR_XYZ ? 3 : 2); ep_src.push_back(k); ep_g.push_back(g); }
-      else { el_p.push_back(vp[G.evi[k]]); el_l.push_back(vl[G.evj[k]]); el_src.push_back(k); el_g.push_back(g); }
-    }
-    sg.neo = (int)eo_i.size() - sg.eo0; sg.nel = (int)el_p.size() - sg.el0; sg.nell = (int)ell_a.size() - sg.ell0; sg.nep = (int)ep_pose.size() - sg.ep0;
-    maxRow = std::max(maxRow, (sg.nprow * 6 + sg.nlrow * 3 + kRowChunk - 1) / kRowChunk);
-    maxEdge = std::max(maxEdge, (sg.neo + sg.nel + sg.nell + sg.nep + kEdgeChunk - 1) / kEdgeChunk);
-  }
-  const int nPr = (int)b.prow_pose.size(), nLr = (int)b.lrow_lm.size();
-  const int nEo = (int)eo_i.size(), nEl = (int)el_p.size(), nEll = (int)ell_a.size(), nEp = (int)ep_pose.size();
-  // unique off-diagonal blocks
-  std::unordered_map<uint64_t, int> ppmap, plmap, llmap;
-  std::vector<std::vector<int>> llblk_edges;                 // per landmark-landmark block: its edges
-  std::vector<std::vector<std::pair<int, int>>> llslots(nLr);   // per landmark row: {edge, side}
-  ell_blk.assign(nEll, -1);
-  for (int k = 0; k < nEll; ++k) {
-    const int ra = b.lm_row[ell_a[k]], rb = b.lm_row[ell_b[k]];
-    if (ra >= 0) llslots[ra].push_back({k, 0});
-    if (rb >= 0) llslots[rb].push_back({k, 1});
-    if (ra < 0 || rb < 0 || ra == rb) continue;
-    const int a = std::min(ra, rb), c = std::max(ra, rb);
-    auto it = llmap.find(pair_key(a, c));
-    int idx;
-    if (it == llmap.end()) { idx = (int)b.llblk.size(); llmap.emplace(pair_key(a, c), idx); b.llblk.push_back({a, c}); llblk_edges.push_back({}); }
-    else idx = it->second;
-    llblk_edges[idx].push_back(k);
-    ell_blk[k] = idx;
-  }
-  eo_blk.assign(nEo, -1); el_blk.assign(nEl, -1);
-  for (int k = 0; k < nEo; ++k) {
-    const int ri = b.pose_row[eo_i[k]], rj = b.pose_row[eo_j[k]];
-    if (ri < 0 || rj < 0 || ri == rj) continue;
-    const int a = std::min(ri, rj), c = std::max(ri, rj);
-    auto it = ppmap.find(pair_key(a, c));
-    int idx;
-    if (it == ppmap.end()) { idx = (int)b.ppoff.size(); ppmap.emplace(pair_key(a, c), idx); b.ppoff.push_back({a, c}); }
-    else idx = it->second;
-    eo_blk[k] = idx * 2 + (ri > rj ? 1 : 0);
-  }
-  for (int k = 0; k < nEl; ++k) {
-    const int rp = b.pose_row[el_p[k]], rl = b.lm_row[el_l[k]];
-    if (rp < 0 || rl < 0) continue;
-    auto it = plmap.find(pair_key(rp, rl));
-    int idx;
-    if (it == plmap.end()) { idx = (int)b.plblk.size(); plmap.emplace(pair_key(rp, rl), idx); b.plblk.push_back({rp, rl}); }
-    else idx = it->second;
-    el_blk[k] = idx;
-  }
-  // (row, incident edge) slots for the gather-form Jacobian build; duplicates of an off-diagonal
-  // block (two edges on the same vertex pair) force the atomic variant
-  std::vector<std::vector<std::pair<int, unsigned char>>> pslots(nPr);
-  std::vector<std::vector<int>> lslots(nLr);
-  {
-    std::vector<char> seen_pp(b.ppoff.size(), 0), seen_pl(b.plblk.size(), 0);
-    b.has_duplicate_blocks = false;
-    b.dup_eo.clear(); b.dup_el.clear();
-    b.has_planes = false;
-    for (unsigned char k : lm_kind) if (k == VT_PLANE) b.has_planes = true;
-    for (int k = 0; k < nEo; ++k) {
-      const int ri = b.pose_row[eo_i[k]], rj = b.pose_row[eo_j[k]];
-      if (ri >= 0) pslots[ri].push_back({k, 0});
-      if (rj >= 0) pslots[rj].push_back({k, 1});
-      if (eo_blk[k] >= 0) {   // a later edge on an already-owned block: not the owner (code <= -2)
-        if (seen_pp[eo_blk[k] >> 1]) { b.has_duplicate_blocks = true; b.dup_eo.push_back(k); eo_blk[k] = -2 - eo_blk[k]; }
-        else seen_pp[eo_blk[k] >> 1] = 1;
-      }
-    }
-    for (int k = 0; k < nEl; ++k) {
-      const int rp = b.pose_row[el_p[k]], rl = b.lm_row[el_l[k]];
-      if (rp >= 0) pslots[rp].push_back({k, 2});
-      if (rl >= 0) lslots[rl].push_back(k);
-      if (el_blk[k] >= 0) {
-        if (seen_pl[el_blk[k]]) { b.has_duplicate_blocks = true; b.dup_el.push_back(k); el_blk[k] = -2 - el_blk[k]; }
-        else seen_pl[el_blk[k]] = 1;
-      }
-    }
-  }
-  std::stable_sort(b.dup_eo.begin(), b.dup_eo.end(), [&](int x, int y) { return ((-2 - eo_blk[x]) >> 1) < ((-2 - eo_blk[y]) >> 1); });
-  std::stable_sort(b.dup_el.begin(), b.dup_el.end(), [&](int x, int y) { return (-2 - el_blk[x]) < (-2 - el_blk[y]); });
-  std::vector<int> pslot_ptr(nPr + 1, 0), pslot_edge, lslot_ptr(nLr + 1, 0), lslot_edge, tile_row0, tile_row1;
-  std::vector<unsigned char> pslot_kind;
-  b.max_row_slots = 0;
-  // record = {edge, kind (0: EdgeSE3 seen from its i side, 1: from its j side, 2: landmark edge), vertex i | pose, vertex j | landmark}
-  std::vector<int4> pslot_rec;
-  for (int r = 0; r < nPr; ++r) {
-    for (auto& s : pslots[r]) {
-      pslot_edge.push_back(s.first); pslot_kind.push_back(s.second);
-      if (s.second < 2) pslot_rec.push_back(make_int4(s.first, s.second, eo_i[s.first], eo_j[s.first]));
-      else pslot_rec.push_back(make_int4(s.first, 2, el_p[s.first], el_l[s.first]));
-    }
-    pslot_ptr[r + 1] = (int)pslot_edge.size();
-    b.max_row_slots = std::max(b.max_row_slots, (int)pslots[r].size());
-  }
-  // thread -> row of the pose-row kernel: within a graph, rows with the same numbers of EdgeSE3 and landmark slots next to each other.  The
-  // lanes of a wave walk their rows' slots in step; a chain pose has two EdgeSE3 slots, the ~200 endpoints of the loop closures of an L
-  // graph three or four, and spread over the graph's 78 waves they made nearly every wave run the EdgeSE3 arithmetic a third and fourth
-  // time for one or two lanes.  Sorted, those rows fill three waves of their own (2.07 -> 2.02 ms per 512-graph build).
-  std::vector<int> prow_perm(nPr);
-  for (int r = 0; r < nPr; ++r) prow_perm[r] = r;
-  {
-    std::vector<int> nse3(nPr, 0);
-    for (int r = 0; r < nPr; ++r) for (auto& sl : pslots[r]) nse3[r] += sl.second < 2 ? 1 : 0;
-    for (int g = 0; g < B; ++g) {
-      const GraphSeg& sg = b.seg[g];
-      std::stable_sort(prow_perm.begin() + sg.prow0, prow_perm.begin() + sg.prow0 + sg.nprow, [&](int x, int y) {
-        if (nse3[x] != nse3[y]) return nse3[x] < nse3[y];
-        return pslots[x].size() < pslots[y].size();
-      });
-    }
-  }
-  for (int r = 0; r < nLr; ++r) {
-    for (int k : lslots[r]) lslot_edge.push_back(k);
-    lslot_ptr[r + 1] = (int)lslot_edge.size();
-  }
-  for (int g = 0; g < B; ++g) {   // tiles never span graphs
-    const GraphSeg& sg = b.seg[g];
-    int r = sg.prow0;
-    const int rend = sg.prow0 + sg.nprow;
-    while (r < rend) {
-      int r1 = r, ns = 0;
-      while (r1 < rend && r1 - r < 32 && ns + (pslot_ptr[r1 + 1] - pslot_ptr[r1]) <= kTileSlots) { ns += pslot_ptr[r1 + 1] - pslot_ptr[r1]; ++r1; }
-      if (r1 == r) ++r1;  // a single row with more than kTileSlots slots: atomic variant is used instead
-      tile_row0.push_back(r); tile_row1.push_back(r1);
-      r = r1;
-    }
-  }
-  const int nPP = (int)b.ppoff.size(), nPL = (int)b.plblk.size(), nLL = (int)b.llblk.size();
-  b.hll_base = (int64_t)nPr * 36;
-  b.hpp_off_base = b.hll_base + (((int64_t)nLr * 9 + 1) & ~(int64_t)1);   // even: the 6-wide blocks behind it stay 16-byte aligned
-  b.hpl_base = b.hpp_off_base + (int64_t)nPP * 36;
-  b.hll_off_base = b.hpl_base + (int64_t)nPL * 18;
-  const int64_t h_total = b.hll_off_base + (int64_t)nLL * 9;
-  if (h_total >= (int64_t)1 << 31) return set_error(SSLAM_ERR_INVALID, "batch too large: H has %lld doubles (int32 block offsets)", (long long)h_total);
-  if (host_only) {   // symbolic structure only (plan introspection on a box without a GPU)
-    memset(&b.V, 0, sizeof b.V);
-    b.V.B = B; b.V.nPr = nPr; b.V.nLr = nLr; b.V.h_total = h_total;
-    return 0;
-  }
-  // adjacency (rows: pose rows then landmark rows)
-  std::vector<std::vector<std::array<int, 3>>> adj(nPr + nLr);
-  for (int i = 0; i < nPP; ++i) {
-    const int a = b.ppoff[i].first, c = b.ppoff[i].second;
-    const int off = (int)(b.hpp_off_base + (int64_t)i * 36);
-    adj[a].push_back({off, 6 * c, 0});
-    adj[c].push_back({off, 6 * a, 1});
-  }
-  for (int i = 0; i < nPL; ++i) {
-    const int rp = b.plblk[i].first, rl = b.plblk[i].second;
-    const int off = (int)(b.hpl_base + (int64_t)i * 18);
-    adj[rp].push_back({off, 6 * nPr + 3 * rl, 2});
-    adj[nPr + rl].push_back({off, 6 * rp, 3});
-  }
-  for (int i = 0; i < nLL; ++i) {
-    const int a = b.llblk[i].first, c = b.llblk[i].second;
-    const int off = (int)(b.hll_off_base + (int64_t)i * 9);
-    adj[nPr + a].push_back({off, 6 * nPr + 3 * c, 4});
-    adj[nPr + c].push_back({off, 6 * nPr + 3 * a, 5});
-  }
-  std::vector<int> adj_ptr(nPr + nLr + 1, 0), adj_blk, adj_x;
-  std::vector<unsigned char> adj_fmt;
-  for (int r = 0; r < nPr + nLr; ++r) {
-    std::sort(adj[r].begin(), adj[r].end(), [](const std::array<int, 3>& x, const std::array<int, 3>& y) { return x[1] < y[1]; });
-    for (auto& a : adj[r]) { adj_blk.push_back(a[0]); adj_x.push_back(a[1]); adj_fmt.push_back((unsigned char)a[2]); }
-    adj_ptr[r + 1] = (int)adj_blk.size();
-  }
-  // edge SoA payloads
-  std::vector<double> eo_z((size_t)7 * nEo), eo_w((size_t)21 * nEo), el_z((size_t)4 * nEl), el_w((size_t)6 * nEl);
-  for (int k = 0; k < nEo; ++k) {
-    const HostGraph& G = *b.graphs[eo_g[k]];
-    const int s = eo_src[k];
-    for (int c = 0; c < 7; ++c) eo_z[(size_t)c * nEo + k] = G.meas[(size_t)s * 7 + c];
-    int q = 0;
-    for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) eo_w[(size_t)(q++) * nEo + k] = G.info[(size_t)s * 36 + r * 6 + c];
-  }
-  for (int k = 0; k < nEl; ++k) {
-    const HostGraph& G = *b.graphs[el_g[k]];
-    const int s = el_src[k];
-    for (int c = 0; c < 4; ++c) el_z[(size_t)c * nEl + k] = G.meas[(size_t)s * 7 + c];
-    int q = 0;
-    for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) el_w[(size_t)(q++) * nEl + k] = G.info[(size_t)s * 36 + r * 3 + c];
-  }
-  std::vector<double> ell_z((size_t)3 * nEll), ell_w((size_t)6 * nEll);
-  for (int k = 0; k < nEll; ++k) {
-    const HostGraph& G = *b.graphs[ell_g[k]];
-    const int s = ell_src[k];
-    for (int c = 0; c < 3; ++c) ell_z[(size_t)c * nEll + k] = G.meas[(size_t)s * 7 + c];
-    int q = 0;
-    for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) ell_w[(size_t)(q++) * nEll + k] = G.info[(size_t)s * 36 + r * 3 + c];
-  }
-  std::vector<int> llslot_ptr(nLr + 1, 0), llblk_ptr(nLL + 1, 0), llblk_edge;
-  std::vector<int2> llslot_rec;
-  for (int r = 0; r < nLr; ++r) { for (auto& q : llslots[r]) llslot_rec.push_back(make_int2(q.first, q.second)); llslot_ptr[r + 1] = (int)llslot_rec.size(); }
-  for (int i = 0; i < nLL; ++i) { for (int k : llblk_edges[i]) llblk_edge.push_back(k); llblk_ptr[i + 1] = (int)llblk_edge.size(); }
-  // position priors: SoA payload, and the pose rows that carry them (a prior on a fixed pose adds to chi2 only)
-  std::vector<double> ep_z((size_t)3 * nEp), ep_w((size_t)6 * nEp);
-  for (int k = 0; k < nEp; ++k) {
-    const HostGraph& G = *b.graphs[ep_g[k]];
-    const int s = ep_src[k], d = ep_dim[k];
-    for (int c = 0; c < 3; ++c) ep_z[(size_t)c * nEp + k] = c < d ? G.meas[(size_t)s * 7 + c] : 0.0;
-    int q = 0;
-    for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) ep_w[(size_t)(q++) * nEp + k] = (r < d && c < d) ? G.info[(size_t)s * 36 + r * d + c] : 0.0;
-  }
-  std::vector<int> ep_row, ep_ptr(1, 0), ep_edge;
-  {
-    std::vector<std::vector<int>> per_row(nPr);
-    for (int k = 0; k < nEp; ++k) { const int r = b.pose_row[ep_pose[k]]; if (r >= 0) per_row[r].push_back(k); }
-    for (int r = 0; r < nPr; ++r) {
-      if (per_row[r].empty()) continue;
-      ep_row.push_back(r);
-      for (int k : per_row[r]) ep_edge.push_back(k);
-      ep_ptr.push_back((int)ep_edge.size());
-    }
-  }
-  // ---- device allocation
+// The tables of batch_compile -> device, the work arrays of the solvers next to them, BatchView filled in; one flush.
+static int batch_upload(Batch& b, BatchTables&& T) {
+  SSLAM_HIP_TRY(hipSetDevice(b.device));
+  if (!b.stream) SSLAM_HIP_TRY(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+  const EdgeClassTab &EO = T.cls[EC_SE3], &EL = T.cls[EC_LANDMARK], &ELL = T.cls[EC_POINT_POINT], &EP = T.cls[EC_PRIOR];
+  const int B = (int)b.graphs.size(), nPr = T.nPr(), nLr = T.nLr(), maxRow = T.max_row_chunks, maxEdge = T.max_edge_chunks;
   BatchView& V = b.V;
   memset(&V, 0, sizeof V);
-  V.B = B; V.nPr = nPr; V.nLr = nLr; V.nPose = (int)b.pose_row.size(); V.nLm = (int)b.lm_row.size();
-  V.nEo = nEo; V.nEl = nEl; V.nEll = nEll; V.nLL = nLL; V.maxRowChunks = maxRow; V.maxEdgeChunks = maxEdge;
-  V.h_total = h_total;
+  V.B = B; V.nPr = nPr; V.nLr = nLr; V.nPose = (int)T.pose_row.size(); V.nLm = (int)T.lm_row.size();
+  V.nEo = EO.n(); V.nEl = EL.n(); V.nEll = ELL.n(); V.nLL = (int)T.llblk.size(); V.nEp = EP.n(); V.nEpRows = (int)T.ep_row.size();
+  V.nDupEo = (int)T.dup_eo.size(); V.nDupEl = (int)T.dup_el.size();
+  V.maxRowChunks = maxRow; V.maxEdgeChunks = maxEdge;
+  V.h_total = T.h_total;
   V.dcs_phi = b.graphs[0]->opt.dcs_phi;
-  int rc;
-#define UP(vec, field) if ((rc = dev_upload(b, vec, (std::remove_const<std::remove_pointer<decltype(V.field)>::type>::type**)&V.field)) != 0) return rc
-  UP(b.seg, seg); UP(b.pose_row, pose_row); UP(b.lm_row, lm_row); UP(b.prow_pose, prow_pose); UP(b.lrow_lm, lrow_lm);
-  UP(prow_graph, prow_graph); UP(lrow_graph, lrow_graph); UP(lm_kind, lm_kind); UP(prow_perm, prow_perm);
-  UP(eo_i, eo_i); UP(eo_j, eo_j); UP(eo_z, eo_z); UP(eo_w, eo_w); UP(eo_blk, eo_blk);
-  UP(el_p, el_p); UP(el_l, el_l); UP(el_z, el_z); UP(el_w, el_w); UP(el_blk, el_blk);
-  UP(adj_ptr, adj_ptr); UP(adj_blk, adj_blk); UP(adj_x, adj_x); UP(adj_fmt, adj_fmt);
-  UP(tile_row0, tile_row0); UP(tile_row1, tile_row1); UP(pslot_ptr, pslot_ptr); UP(pslot_edge, pslot_edge); UP(pslot_kind, pslot_kind);
-  UP(lslot_ptr, lslot_ptr); UP(lslot_edge, lslot_edge);
-  UP(b.dup_eo, dup_eo); UP(b.dup_el, dup_el); UP(pslot_rec, pslot_rec);
-  UP(eo_src, eo_id); UP(el_src, el_id); UP(shard_lo, shard_lo); UP(shard_hi, shard_hi);
-  UP(ell_a, ell_a); UP(ell_b, ell_b); UP(ell_z, ell_z); UP(ell_w, ell_w); UP(ell_src, ell_id);
-  UP(llslot_ptr, llslot_ptr); UP(llslot_rec, llslot_rec); UP(llblk_ptr, llblk_ptr); UP(llblk_edge, llblk_edge);
-  V.nEp = nEp; V.nEpRows = (int)ep_row.size();
-  if (nEp > 0) {   // a batch without priors uploads nothing more than before
-    UP(ep_pose, ep_pose); UP(ep_dim, ep_dim); UP(ep_z, ep_z); UP(ep_w, ep_w); UP(ep_src, ep_id);
-    UP(ep_row, ep_row); UP(ep_ptr, ep_ptr); UP(ep_edge, ep_edge);
+  int rc = 0;
+  auto up = [&](const auto& vec, auto& field) { if (!rc) rc = upload_table(b, vec, field); };
+  up(T.seg, V.seg); up(T.pose_row, V.pose_row); up(T.lm_row, V.lm_row); up(T.prow_pose, V.prow_pose); up(T.lrow_lm, V.lrow_lm);
+  up(T.prow_graph, V.prow_graph); up(T.lrow_graph, V.lrow_graph); up(T.lm_kind, V.lm_kind); up(T.prow_perm, V.prow_perm);
+  up(EO.a, V.eo_i); up(EO.b, V.eo_j); up(EO.z, V.eo_z); up(EO.w, V.eo_w); up(EO.blk, V.eo_blk); up(EO.id, V.eo_id);
+  up(EL.a, V.el_p); up(EL.b, V.el_l); up(EL.z, V.el_z); up(EL.w, V.el_w); up(EL.blk, V.el_blk); up(EL.id, V.el_id);
+  up(ELL.a, V.ell_a); up(ELL.b, V.ell_b); up(ELL.z, V.ell_z); up(ELL.w, V.ell_w); up(ELL.id, V.ell_id);
+  up(T.adj_ptr, V.adj_ptr); up(T.adj_blk, V.adj_blk); up(T.adj_x, V.adj_x); up(T.adj_fmt, V.adj_fmt);
+  up(T.pslot_ptr, V.pslot_ptr); up(T.pslot_rec, V.pslot_rec); up(T.lslot_ptr, V.lslot_ptr); up(T.lslot_edge, V.lslot_edge);
+  up(T.llslot_ptr, V.llslot_ptr); up(T.llslot_rec, V.llslot_rec); up(T.llblk_ptr, V.llblk_ptr); up(T.llblk_edge, V.llblk_edge);
+  up(T.dup_eo, V.dup_eo); up(T.dup_el, V.dup_el); up(T.shard_lo, V.shard_lo); up(T.shard_hi, V.shard_hi);
+  if (EP.n() > 0) {   // a batch without priors uploads nothing for them
+    up(EP.a, V.ep_pose); up(EP.dim, V.ep_dim); up(EP.z, V.ep_z); up(EP.w, V.ep_w); up(EP.id, V.ep_id);
+    up(T.ep_row, V.ep_row); up(T.ep_ptr, V.ep_ptr); up(T.ep_edge, V.ep_edge);
   }
-  V.nDupEo = (int)b.dup_eo.size(); V.nDupEl = (int)b.dup_el.size();
-  V.nTiles = (int)tile_row0.size();
-#undef UP
+  if (rc) return rc;
+  // the system and the work vectors of the solvers (zero-filled)
+  auto alloc = [&](size_t n, auto& p) { if (!rc) rc = dev_alloc(b, n, &p); };
   double* H = nullptr;
   const size_t dim = (size_t)6 * nPr + (size_t)3 * nLr;
-  const size_t h_even = ((size_t)h_total + 1) & ~(size_t)1;   // b right behind H (16-byte aligned): [H || b] is one all-reduce buffer
-  if ((rc = dev_alloc(b, h_even + dim, &H))) return rc;
-  V.Hpp_diag = H; V.Hll_diag = H + b.hll_base; V.Hpp_off = H + b.hpp_off_base; V.Hpl = H + b.hpl_base; V.Hll_off = H + b.hll_off_base;
+  const size_t h_even = ((size_t)T.h_total + 1) & ~(size_t)1;   // b right behind H (16-byte aligned): [H || b] is one all-reduce buffer
+  alloc(h_even + dim, H);
+  if (T.has_planes) alloc((size_t)std::max(V.nEl, 1) * kPjDoubles, V.pj);
+  alloc((size_t)V.nPose * 8, V.pose); alloc((size_t)V.nPose * 8, V.pose_trial); alloc((size_t)V.nLm * 4, V.lmk); alloc((size_t)V.nLm * 4, V.lmk_trial);
+  alloc(dim, V.x); alloc(dim, V.r); alloc(dim, V.z); alloc(dim, V.p); alloc(dim, V.q);
+  alloc((size_t)nPr * 36 + (size_t)nLr * 9, V.Minv);
+  alloc((size_t)B * maxRow, V.part_a); alloc((size_t)B * maxRow, V.part_b); alloc((size_t)B * maxRow, V.part_c);
+  alloc((size_t)B * maxRow, b.d_part_m); alloc((size_t)B * maxEdge, b.d_part_e);
+  alloc((size_t)2 * B, V.rz); alloc((size_t)B, V.bb); alloc((size_t)2 * B, V.pcg_done); alloc((size_t)B, V.pcg_fail); alloc((size_t)4, V.flags);
+  alloc((size_t)B, V.lm);
+  if (rc) return rc;
+  V.Hpp_diag = H; V.Hll_diag = H + T.hll_base; V.Hpp_off = H + T.hpp_off_base; V.Hpl = H + T.hpl_base; V.Hll_off = H + T.hll_off_base;
   V.bvec = H + h_even;
   b.hb_doubles = (int64_t)(h_even + dim);
-  V.pj = nullptr;
-  if (b.has_planes && (rc = dev_alloc(b, (size_t)std::max(nEl, 1) * kPjDoubles, &V.pj))) return rc;
-  if ((rc = dev_alloc(b, (size_t)V.nPose * 8, &V.pose))) return rc;
-  if ((rc = dev_alloc(b, (size_t)V.nPose * 8, &V.pose_trial))) return rc;
-  if ((rc = dev_alloc(b, (size_t)V.nLm * 4, &V.lmk))) return rc;
-  if ((rc = dev_alloc(b, (size_t)V.nLm * 4, &V.lmk_trial))) return rc;
-  if ((rc = dev_alloc(b, dim, &V.x))) return rc;
-  if ((rc = dev_alloc(b, dim, &V.r))) return rc;
-  if ((rc = dev_alloc(b, dim, &V.z))) return rc;
-  if ((rc = dev_alloc(b, dim, &V.p))) return rc;
-  if ((rc = dev_alloc(b, dim, &V.q))) return rc;
-  if ((rc = dev_alloc(b, (size_t)nPr * 36 + (size_t)nLr * 9, &V.Minv))) return rc;
-  if ((rc = dev_alloc(b, (size_t)B * maxRow, &V.part_a))) return rc;
-  if ((rc = dev_alloc(b, (size_t)B * maxRow, &V.part_b))) return rc;
-  if ((rc = dev_alloc(b, (size_t)B * maxRow, &V.part_c))) return rc;
-  if ((rc = dev_alloc(b, (size_t)B * maxRow, &b.d_part_m))) return rc;
-  if ((rc = dev_alloc(b, (size_t)B * maxEdge, &b.d_part_e))) return rc;
-  if ((rc = dev_alloc(b, (size_t)2 * B, &V.rz))) return rc;
-  if ((rc = dev_alloc(b, (size_t)B, &V.bb))) return rc;
-  if ((rc = dev_alloc(b, (size_t)2 * B, &V.pcg_done))) return rc;
-  if ((rc = dev_alloc(b, (size_t)B, &V.pcg_fail))) return rc;
-  if ((rc = dev_alloc(b, (size_t)4, &V.flags))) return rc;
-  if ((rc = dev_alloc(b, (size_t)B, &V.lm))) return rc;
   if (b.arena && b.arena->flush(b.stream)) return set_error(SSLAM_ERR_HIP, "upload of the batch tables failed");
   SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));
+  b.T = std::move(static_cast<BatchMaps&>(T));   // the batch keeps the host's part; the rest is on the device now
   b.versions.resize(B);
   for (int g = 0; g < B; ++g) b.versions[g] = b.graphs[g]->structure_version;
   b.uploaded = false;
-  b.cls_src[0] = std::move(eo_src); b.cls_g[0] = std::move(eo_g); b.cls_src[1] = std::move(el_src); b.cls_g[1] = std::move(el_g);
-  b.cls_src[2] = std::move(ell_src); b.cls_g[2] = std::move(ell_g); b.cls_src[3] = std::move(ep_src); b.cls_g[3] = std::move(ep_g);
   b.robust_synced = false; b.has_robust = false;
   return 0;
+}
+
+// batch_compile, and the one thing it cannot express: H is addressed with int32 block offsets
+static int batch_compile_checked(const std::vector<HostGraph*>& graphs, BatchTables& T) {
+  T = batch_compile(graphs);
+  if (T.h_total >= (int64_t)1 << 31) return set_error(SSLAM_ERR_INVALID, "batch too large: H has %lld doubles (int32 block offsets)", (long long)T.h_total);
+  return 0;
+}
+static int batch_build(Batch& b) {
+  BatchTables T;
+  if (const int rc = batch_compile_checked(b.graphs, T)) return rc;
+  return batch_upload(b, std::move(T));
 }
 
 // Per-edge robust kernels are edge data: when a graph's kernels changed since this batch last looked (robust_version), the kind / delta arrays
@@ -1472,25 +1220,24 @@ static int batch_sync_robust(Batch& b) {
   if (b.robust_synced && ver == b.robust_ver) return 0;
   BatchView& V = b.V;
   if (any) {
-    for (int c = 0; c < 4; ++c) {
-      const size_t n = b.cls_src[c].size();
-      std::vector<unsigned char> kind(std::max<size_t>(n, 1), 0);
-      std::vector<double> delta(std::max<size_t>(n, 1), 0.0);
-      for (size_t k = 0; k < n; ++k) {
-        const HostGraph& G = *b.graphs[b.cls_g[c][k]];
-        kind[k] = G.rk_kind[b.cls_src[c][k]]; delta[k] = G.rk_delta[b.cls_src[c][k]];
-      }
+    // device order is class order: by graph, then by edge id (batch_tables.hpp)
+    std::vector<unsigned char> kind[kEdgeClasses];
+    std::vector<double> delta[kEdgeClasses];
+    for (const HostGraph* G : b.graphs)
+      for (int k = 0; k < G->ne(); ++k) { const int c = kEdgeType[G->etype[k]].cls; kind[c].push_back(G->rk_kind[k]); delta[c].push_back(G->rk_delta[k]); }
+    for (int c = 0; c < kEdgeClasses; ++c) {
+      if (kind[c].empty()) { kind[c].push_back(0); delta[c].push_back(0.0); }
       if (!b.d_rk[c]) {
         void* p = nullptr;
-        SSLAM_HIP_TRY(hipMalloc(&p, kind.size())); b.allocs.push_back(p); b.d_rk[c] = (unsigned char*)p;
-        SSLAM_HIP_TRY(hipMalloc(&p, delta.size() * sizeof(double))); b.allocs.push_back(p); b.d_rd[c] = (double*)p;
+        SSLAM_HIP_TRY(hipMalloc(&p, kind[c].size())); b.allocs.push_back(p); b.d_rk[c] = (unsigned char*)p;
+        SSLAM_HIP_TRY(hipMalloc(&p, delta[c].size() * sizeof(double))); b.allocs.push_back(p); b.d_rd[c] = (double*)p;
       }
-      SSLAM_HIP_TRY(hipMemcpyAsync(b.d_rk[c], kind.data(), kind.size(), hipMemcpyHostToDevice, b.stream));
-      SSLAM_HIP_TRY(hipMemcpyAsync(b.d_rd[c], delta.data(), delta.size() * sizeof(double), hipMemcpyHostToDevice, b.stream));
-      SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // (the host vectors go out of scope)
+      SSLAM_HIP_TRY(hipMemcpyAsync(b.d_rk[c], kind[c].data(), kind[c].size(), hipMemcpyHostToDevice, b.stream));
+      SSLAM_HIP_TRY(hipMemcpyAsync(b.d_rd[c], delta[c].data(), delta[c].size() * sizeof(double), hipMemcpyHostToDevice, b.stream));
     }
-    V.eo_rk = b.d_rk[0]; V.el_rk = b.d_rk[1]; V.ell_rk = b.d_rk[2]; V.ep_rk = b.d_rk[3];
-    V.eo_rd = b.d_rd[0]; V.el_rd = b.d_rd[1]; V.ell_rd = b.d_rd[2]; V.ep_rd = b.d_rd[3];
+    SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // (the host vectors go out of scope)
+    V.eo_rk = b.d_rk[EC_SE3]; V.el_rk = b.d_rk[EC_LANDMARK]; V.ell_rk = b.d_rk[EC_POINT_POINT]; V.ep_rk = b.d_rk[EC_PRIOR];
+    V.eo_rd = b.d_rd[EC_SE3]; V.el_rd = b.d_rd[EC_LANDMARK]; V.ell_rd = b.d_rd[EC_POINT_POINT]; V.ep_rd = b.d_rd[EC_PRIOR];
   } else {
     V.eo_rk = V.el_rk = V.ell_rk = V.ep_rk = nullptr;
     V.eo_rd = V.el_rd = V.ell_rd = V.ep_rd = nullptr;
@@ -1513,8 +1260,8 @@ static int batch_upload_estimates(Batch& b) {
     const HostGraph& G = *b.graphs[g];
     for (int v = 0; v < G.nv(); ++v) {
       const double* e = &G.est[(size_t)v * 7];
-      if (G.vtype[v] == VT_SE3) { double* o = &pose[(size_t)b.v2pose[g][v] * 8]; for (int k = 0; k < 7; ++k) o[k] = e[k]; }
-      else { double* o = &lmk[(size_t)b.v2lm[g][v] * 4]; for (int k = 0; k < (G.vtype[v] == VT_POINT ? 3 : 4); ++k) o[k] = e[k]; }
+      if (G.vtype[v] == VT_SE3) { double* o = &pose[(size_t)b.T.v2pose[g][v] * 8]; for (int k = 0; k < 7; ++k) o[k] = e[k]; }
+      else { double* o = &lmk[(size_t)b.T.v2lm[g][v] * 4]; for (int k = 0; k < (G.vtype[v] == VT_POINT ? 3 : 4); ++k) o[k] = e[k]; }
     }
   }
   if (np) {
@@ -1544,8 +1291,8 @@ static int batch_download_estimates(Batch& b) {
     HostGraph& G = *b.graphs[g];
     for (int v = 0; v < G.nv(); ++v) {
       double* e = &G.est[(size_t)v * 7];
-      if (G.vtype[v] == VT_SE3) { const double* o = &pose[(size_t)b.v2pose[g][v] * 8]; for (int k = 0; k < 7; ++k) e[k] = o[k]; }
-      else { const double* o = &lmk[(size_t)b.v2lm[g][v] * 4]; for (int k = 0; k < (G.vtype[v] == VT_POINT ? 3 : 4); ++k) e[k] = o[k]; }
+      if (G.vtype[v] == VT_SE3) { const double* o = &pose[(size_t)b.T.v2pose[g][v] * 8]; for (int k = 0; k < 7; ++k) e[k] = o[k]; }
+      else { const double* o = &lmk[(size_t)b.T.v2lm[g][v] * 4]; for (int k = 0; k < (G.vtype[v] == VT_POINT ? 3 : 4); ++k) e[k] = o[k]; }
     }
   }
   return 0;
@@ -1598,11 +1345,11 @@ static int batch_linearize(Batch& b) {
     // ranks is again the system it already had: the all-reduce is idempotent for it.  (Summing in place would multiply the H of such a
     // graph by `world` on every step: the damping of a retried trial would fall instead of rising -- round-2 ADVICE.)
     BatchView Vp = V;
-    Vp.Hpp_diag = b.d_hb_part; Vp.Hll_diag = b.d_hb_part + b.hll_base; Vp.Hpp_off = b.d_hb_part + b.hpp_off_base;
-    Vp.Hpl = b.d_hb_part + b.hpl_base; Vp.Hll_off = b.d_hb_part + b.hll_off_base; Vp.bvec = b.d_hb_part + (V.bvec - V.Hpp_diag);
+    Vp.Hpp_diag = b.d_hb_part; Vp.Hll_diag = b.d_hb_part + b.T.hll_base; Vp.Hpp_off = b.d_hb_part + b.T.hpp_off_base;
+    Vp.Hpl = b.d_hb_part + b.T.hpl_base; Vp.Hll_off = b.d_hb_part + b.T.hll_off_base; Vp.bvec = b.d_hb_part + (V.bvec - V.Hpp_diag);
     {
       const BatchView& V = Vp;
-      if (b.has_planes) SSLAM_LAUNCH_LIN_RK(true, true) else SSLAM_LAUNCH_LIN_RK(false, true)
+      if (b.T.has_planes) SSLAM_LAUNCH_LIN_RK(true, true) else SSLAM_LAUNCH_LIN_RK(false, true)
     }
     if (b.comm) {
       // the partial [H || b] arrays of all ranks -> their sum on every rank: ONE all-reduce over xGMI (RCCL), in stream order;
@@ -1614,7 +1361,7 @@ static int batch_linearize(Batch& b) {
       SSLAM_HIP_TRY(hipMemcpyAsync(V.Hpp_diag, b.d_hb_part, (size_t)b.hb_doubles * sizeof(double), hipMemcpyDeviceToDevice, b.stream));
     }
   } else {
-    if (b.has_planes) SSLAM_LAUNCH_LIN_RK(true, false) else SSLAM_LAUNCH_LIN_RK(false, false)
+    if (b.T.has_planes) SSLAM_LAUNCH_LIN_RK(true, false) else SSLAM_LAUNCH_LIN_RK(false, false)
   }
 #undef SSLAM_LAUNCH_LIN_RK
 #undef SSLAM_LAUNCH_LIN
@@ -1685,6 +1432,15 @@ static int batch_chi2(Batch& b, const double* pose, const double* lmk, int mask_
 
 constexpr int kStepChunk = 8;   // LM steps enqueued between two looks at the per-graph state
 // the per-graph LM states -> host, through the page-locked staging buffer (synchronises the stream)
+// The system at the current estimates: the estimates go up if the device's are stale, every graph gets its chi2 and a fresh LM state, and
+// (lin) the undamped H and b are built.
+static int batch_system_at_estimates(Batch& b, bool lin = true) {
+  int rc;
+  if (!b.uploaded && (rc = batch_upload_estimates(b))) return rc;
+  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
+  hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
+  return lin ? batch_linearize(b) : 0;
+}
 static int read_lm_state(Batch& b, std::vector<LmState>& st) { return read_device(b, st.data(), b.V.lm, sizeof(LmState) * (size_t)b.V.B); }
 
 static int batch_optimize(Batch& b, int max_iters, sslam_opt_stats* out) {
@@ -1918,19 +1674,17 @@ int sslam_graph_add_vertex_plane(sslam_graph* h, const double n_d[4]) {
   return add_vertex(h, VT_PLANE, p, 4, 0);
 }
 
-// j = -1 for a unary edge (position prior)
-static int add_edge(sslam_graph* h, int type, int i, int j, const double* z, int nz, const double* info, int d) {
+// j = -1 for a unary edge (position prior); measurement length, information dimension and vertex types are the type's (kEdgeType)
+static int add_edge(sslam_graph* h, int type, int i, int j, const double* z, const double* info) {
   if (!h || !z || !info) return set_error(SSLAM_ERR_INVALID, "null argument");
   HostGraph& G = h->g;
-  if (is_prior_edge(type)) {
+  const EdgeType& et = kEdgeType[type];
+  const int nz = et.nz, d = et.d;
+  if (et.vt_j < 0) {
     if (i < 0 || i >= G.nv() || j != -1) return set_error(SSLAM_ERR_INVALID, "prior vertex id %d invalid", i);
-    if (G.vtype[i] != VT_SE3) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", i);
-  } else {
-    if (i < 0 || j < 0 || i >= G.nv() || j >= G.nv() || i == j) return set_error(SSLAM_ERR_INVALID, "edge vertex ids (%d,%d) invalid", i, j);
-    if (G.vtype[i] != (type == ET_POINT_POINT ? VT_POINT : VT_SE3)) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", i);
-    const int want = type == ET_SE3 ? VT_SE3 : ((type == ET_SE3_POINT || type == ET_POINT_POINT) ? VT_POINT : VT_PLANE);
-    if (G.vtype[j] != want) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", j);
-  }
+  } else if (i < 0 || j < 0 || i >= G.nv() || j >= G.nv() || i == j) return set_error(SSLAM_ERR_INVALID, "edge vertex ids (%d,%d) invalid", i, j);
+  if (G.vtype[i] != et.vt_i) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", i);
+  if (et.vt_j >= 0 && G.vtype[j] != et.vt_j) return set_error(SSLAM_ERR_INVALID, "vertex %d has the wrong type for this edge", j);
   // only the upper triangle of the information matrix travels to the device: an asymmetric one would be symmetrised silently
   double amax = 0;
   for (int k = 0; k < d * d; ++k) { if (!std::isfinite(info[k])) return set_error(SSLAM_ERR_INVALID, "information matrix has a non-finite entry"); amax = std::max(amax, std::fabs(info[k])); }
@@ -1947,28 +1701,28 @@ static int add_edge(sslam_graph* h, int type, int i, int j, const double* z, int
   return id;
 }
 int sslam_graph_add_edge_se3(sslam_graph* h, int i, int j, const double z[7], const double info[36]) {
-  return add_edge(h, ET_SE3, i, j, z, 7, info, 6);
+  return add_edge(h, ET_SE3, i, j, z, info);
 }
 int sslam_graph_add_edge_se3_point(sslam_graph* h, int i, int l, const double z[3], const double info[9]) {
-  return add_edge(h, ET_SE3_POINT, i, l, z, 3, info, 3);
+  return add_edge(h, ET_SE3_POINT, i, l, z, info);
 }
 int sslam_graph_add_edge_se3_plane(sslam_graph* h, int i, int l, const double z[4], const double info[9]) {
   if (!z) return set_error(SSLAM_ERR_INVALID, "null argument");
   const double nn = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
   if (!(nn > 0)) return set_error(SSLAM_ERR_INVALID, "plane normal has zero length");
   const double p[4] = {z[0] / nn, z[1] / nn, z[2] / nn, z[3] / nn};
-  return add_edge(h, ET_SE3_PLANE, i, l, p, 4, info, 3);
+  return add_edge(h, ET_SE3_PLANE, i, l, p, info);
 }
 
 int sslam_graph_add_edge_point_point(sslam_graph* h, int l1, int l2, const double z[3], const double info[9]) {
-  return add_edge(h, ET_POINT_POINT, l1, l2, z, 3, info, 3);
+  return add_edge(h, ET_POINT_POINT, l1, l2, z, info);
 }
 
 int sslam_graph_add_edge_se3_prior_xyz(sslam_graph* h, int v, const double z[3], const double info[9]) {
-  return add_edge(h, ET_SE3_PRIOR_XYZ, v, -1, z, 3, info, 3);
+  return add_edge(h, ET_SE3_PRIOR_XYZ, v, -1, z, info);
 }
 int sslam_graph_add_edge_se3_prior_xy(sslam_graph* h, int v, const double z[2], const double info[4]) {
-  return add_edge(h, ET_SE3_PRIOR_XY, v, -1, z, 2, info, 2);
+  return add_edge(h, ET_SE3_PRIOR_XY, v, -1, z, info);
 }
 
 int sslam_graph_num_vertices(const sslam_graph* h) { return h ? h->g.nv() : SSLAM_ERR_INVALID; }
@@ -2039,10 +1793,10 @@ int sslam_graph_edge_chi2(sslam_graph* h, const int* edge_ids, int n, double* e2
   if (n == 0) return 0;
   // edge id -> graph-local index in the order of edge_chi2: SE3 edges, landmark edges, point-point edges, priors, each in id order
   std::vector<int> pos(G.ne());
-  int cnt[4] = {0, 0, 0, 0};
-  auto cls = [&](int k) { return G.etype[k] == ET_SE3 ? 0 : (G.etype[k] == ET_POINT_POINT ? 2 : (is_prior_edge(G.etype[k]) ? 3 : 1)); };
+  int cnt[kEdgeClasses] = {}, off[kEdgeClasses] = {};
+  auto cls = [&](int k) { return kEdgeType[G.etype[k]].cls; };
   for (int k = 0; k < G.ne(); ++k) pos[k] = cnt[cls(k)]++;
-  const int off[4] = {0, cnt[0], cnt[0] + cnt[1], cnt[0] + cnt[1] + cnt[2]};
+  for (int c = 1; c < kEdgeClasses; ++c) off[c] = off[c - 1] + cnt[c - 1];
   std::vector<int> loc(n);
   for (int t = 0; t < n; ++t) {
     const int k = edge_ids ? edge_ids[t] : t;
@@ -2112,9 +1866,8 @@ int sslam_graph_chi2(sslam_graph* h, double* chi2) {
   int rc = ensure_batch(h);
   if (rc) return rc;
   Batch& b = *h->batch;
-  if ((rc = batch_upload_estimates(b))) return rc;
-  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
-  hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
+  b.uploaded = false;   // a graph handle's host estimates are the truth: they always go up
+  if ((rc = batch_system_at_estimates(b, false))) return rc;
   LmState s;
   if ((rc = read_device(b, &s, b.V.lm, sizeof s))) return rc;
   *chi2 = s.cur_chi;
@@ -2125,10 +1878,8 @@ static int do_linearize(sslam_graph* h) {
   int rc = ensure_batch(h);
   if (rc) return rc;
   Batch& b = *h->batch;
-  if ((rc = batch_upload_estimates(b))) return rc;
-  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
-  hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
-  if ((rc = batch_linearize(b))) return rc;
+  b.uploaded = false;   // as in sslam_graph_chi2
+  if ((rc = batch_system_at_estimates(b))) return rc;
   SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));
   b.harvest();
   h->linearized = true;
@@ -2144,15 +1895,15 @@ int sslam_graph_linearize(sslam_graph* h, int* dim, int64_t* nnz_upper, int32_t*
   const int n = hessian_indices(h->g, hidx);
   *dim = n;
   const int nPr = b.V.nPr, nLr = b.V.nLr;
-  const int64_t nnz = (int64_t)nPr * 21 + (int64_t)nLr * 6 + (int64_t)b.ppoff.size() * 36 + (int64_t)b.plblk.size() * 18 + (int64_t)b.llblk.size() * 9;
+  const int64_t nnz = (int64_t)nPr * 21 + (int64_t)nLr * 6 + (int64_t)b.T.ppoff.size() * 36 + (int64_t)b.T.plblk.size() * 18 + (int64_t)b.T.llblk.size() * 9;
   *nnz_upper = nnz;
   if (!rows || !cols || !vals || !bout) return 0;
   if ((rc = do_linearize(h))) return rc;
   std::vector<double> H((size_t)b.V.h_total), bv((size_t)6 * nPr + (size_t)3 * nLr);
   SSLAM_HIP_TRY(hipMemcpy(H.data(), b.V.Hpp_diag, H.size() * 8, hipMemcpyDeviceToHost));
   SSLAM_HIP_TRY(hipMemcpy(bv.data(), b.V.bvec, bv.size() * 8, hipMemcpyDeviceToHost));
-  auto prow_off = [&](int r) { return hidx[b.pose_vertex[b.prow_pose[r]]]; };
-  auto lrow_off = [&](int r) { return hidx[b.lm_vertex[b.lrow_lm[r]]]; };
+  auto prow_off = [&](int r) { return hidx[b.T.pose_vertex[b.T.prow_pose[r]]]; };
+  auto lrow_off = [&](int r) { return hidx[b.T.lm_vertex[b.T.lrow_lm[r]]]; };
   int64_t q = 0;
   auto emit = [&](int R, int C, double v) { if (R > C) std::swap(R, C); rows[q] = R; cols[q] = C; vals[q] = v; ++q; };
   for (int r = 0; r < nPr; ++r) {
@@ -2161,20 +1912,20 @@ int sslam_graph_linearize(sslam_graph* h, int* dim, int64_t* nnz_upper, int32_t*
   }
   for (int r = 0; r < nLr; ++r) {
     const int o = lrow_off(r);
-    for (int a = 0; a < 3; ++a) { for (int c = a; c < 3; ++c) emit(o + a, o + c, H[(size_t)b.hll_base + (size_t)r * 9 + a * 3 + c]); bout[o + a] = bv[(size_t)6 * nPr + (size_t)3 * r + a]; }
+    for (int a = 0; a < 3; ++a) { for (int c = a; c < 3; ++c) emit(o + a, o + c, H[(size_t)b.T.hll_base + (size_t)r * 9 + a * 3 + c]); bout[o + a] = bv[(size_t)6 * nPr + (size_t)3 * r + a]; }
   }
-  for (size_t i = 0; i < b.ppoff.size(); ++i) {
-    const int oa = prow_off(b.ppoff[i].first), oc = prow_off(b.ppoff[i].second);
-    for (int a = 0; a < 6; ++a) for (int c = 0; c < 6; ++c) emit(oa + a, oc + c, H[(size_t)b.hpp_off_base + i * 36 + a * 6 + c]);
+  for (size_t i = 0; i < b.T.ppoff.size(); ++i) {
+    const int oa = prow_off(b.T.ppoff[i].first), oc = prow_off(b.T.ppoff[i].second);
+    for (int a = 0; a < 6; ++a) for (int c = 0; c < 6; ++c) emit(oa + a, oc + c, H[(size_t)b.T.hpp_off_base + i * 36 + a * 6 + c]);
   }
-  for (size_t i = 0; i < b.plblk.size(); ++i) {
-    const int op = prow_off(b.plblk[i].first), ol = lrow_off(b.plblk[i].second);
-    for (int a = 0; a < 6; ++a) for (int c = 0; c < 3; ++c) emit(op + a, ol + c, H[(size_t)b.hpl_base + i * 18 + a * 3 + c]);
+  for (size_t i = 0; i < b.T.plblk.size(); ++i) {
+    const int op = prow_off(b.T.plblk[i].first), ol = lrow_off(b.T.plblk[i].second);
+    for (int a = 0; a < 6; ++a) for (int c = 0; c < 3; ++c) emit(op + a, ol + c, H[(size_t)b.T.hpl_base + i * 18 + a * 3 + c]);
   }
-  for (size_t i = 0; i < b.llblk.size(); ++i) {   // emit() orders (row, column) into the upper triangle; the block is symmetric (-Omega)
-    const int oa = lrow_off(b.llblk[i].first), oc = lrow_off(b.llblk[i].second);
+  for (size_t i = 0; i < b.T.llblk.size(); ++i) {   // emit() orders (row, column) into the upper triangle; the block is symmetric (-Omega)
+    const int oa = lrow_off(b.T.llblk[i].first), oc = lrow_off(b.T.llblk[i].second);
     for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) {
-      const double v = H[(size_t)b.hll_off_base + i * 9 + a * 3 + c];
+      const double v = H[(size_t)b.T.hll_off_base + i * 9 + a * 3 + c];
       if (oa < oc) emit(oa + a, oc + c, v); else emit(oc + c, oa + a, v);
     }
   }
@@ -2186,16 +1937,16 @@ static void to_g2o_order(const sslam_graph* h, const std::vector<double>& xin, d
   const Batch& b = *h->batch;
   std::vector<int> hidx;
   hessian_indices(h->g, hidx);
-  for (int r = 0; r < b.V.nPr; ++r) { const int o = hidx[b.pose_vertex[b.prow_pose[r]]]; for (int a = 0; a < 6; ++a) xout[o + a] = xin[(size_t)6 * r + a]; }
-  for (int r = 0; r < b.V.nLr; ++r) { const int o = hidx[b.lm_vertex[b.lrow_lm[r]]]; for (int a = 0; a < 3; ++a) xout[o + a] = xin[(size_t)6 * b.V.nPr + (size_t)3 * r + a]; }
+  for (int r = 0; r < b.V.nPr; ++r) { const int o = hidx[b.T.pose_vertex[b.T.prow_pose[r]]]; for (int a = 0; a < 6; ++a) xout[o + a] = xin[(size_t)6 * r + a]; }
+  for (int r = 0; r < b.V.nLr; ++r) { const int o = hidx[b.T.lm_vertex[b.T.lrow_lm[r]]]; for (int a = 0; a < 3; ++a) xout[o + a] = xin[(size_t)6 * b.V.nPr + (size_t)3 * r + a]; }
 }
 static void from_g2o_order(const sslam_graph* h, const double* xin, std::vector<double>& xout) {
   const Batch& b = *h->batch;
   std::vector<int> hidx;
   hessian_indices(h->g, hidx);
   xout.assign((size_t)6 * b.V.nPr + (size_t)3 * b.V.nLr, 0.0);
-  for (int r = 0; r < b.V.nPr; ++r) { const int o = hidx[b.pose_vertex[b.prow_pose[r]]]; for (int a = 0; a < 6; ++a) xout[(size_t)6 * r + a] = xin[o + a]; }
-  for (int r = 0; r < b.V.nLr; ++r) { const int o = hidx[b.lm_vertex[b.lrow_lm[r]]]; for (int a = 0; a < 3; ++a) xout[(size_t)6 * b.V.nPr + (size_t)3 * r + a] = xin[o + a]; }
+  for (int r = 0; r < b.V.nPr; ++r) { const int o = hidx[b.T.pose_vertex[b.T.prow_pose[r]]]; for (int a = 0; a < 6; ++a) xout[(size_t)6 * r + a] = xin[o + a]; }
+  for (int r = 0; r < b.V.nLr; ++r) { const int o = hidx[b.T.lm_vertex[b.T.lrow_lm[r]]]; for (int a = 0; a < 3; ++a) xout[(size_t)6 * b.V.nPr + (size_t)3 * r + a] = xin[o + a]; }
 }
 
 int sslam_graph_solve(sslam_graph* h, double lambda, double* x, int64_t* solver_iterations) {
@@ -2239,8 +1990,8 @@ int sslam_graph_oplus(sslam_graph* h, const double* dx) {
 
 // First unknown of vertex v of graph g in the batch's internal row order, -1: fixed or without edges.
 static int vertex_xoff(const Batch& b, int g, int v) {
-  if (b.graphs[g]->vtype[v] == VT_SE3) { const int r = b.pose_row[b.v2pose[g][v]]; return r < 0 ? -1 : 6 * r; }
-  const int r = b.lm_row[b.v2lm[g][v]];
+  if (b.graphs[g]->vtype[v] == VT_SE3) { const int r = b.T.pose_row[b.T.v2pose[g][v]]; return r < 0 ? -1 : 6 * r; }
+  const int r = b.T.lm_row[b.T.v2lm[g][v]];
   return r < 0 ? -1 : 6 * b.V.nPr + 3 * r;
 }
 
@@ -2369,36 +2120,24 @@ int sslam_graph_save_g2o(const sslam_graph* h, const char* path) {
     if (G.vfixed[v]) fprintf(f, "FIX %d\n", v);
   }
   for (int k = 0; k < G.ne(); ++k) {
-    const double* z = &G.meas[(size_t)k * 7];
-    const double* W = &G.info[(size_t)k * 36];
-    if (G.etype[k] == ET_SE3) {
-      fprintf(f, "EDGE_SE3:QUAT %d %d", G.evi[k], G.evj[k]);
-      for (int c = 0; c < 7; ++c) fprintf(f, " %.17g", z[c]);
-      for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) fprintf(f, " %.17g", W[r * 6 + c]);
-    } else if (G.etype[k] == ET_SE3_POINT) {
-      fprintf(f, "EDGE_SE3_TRACKXYZ %d %d 0", G.evi[k], G.evj[k]);
-      for (int c = 0; c < 3; ++c) fprintf(f, " %.17g", z[c]);
-      for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) fprintf(f, " %.17g", W[r * 3 + c]);
-    } else if (G.etype[k] == ET_POINT_POINT) {   // g2o::EdgePointXYZ
-      fprintf(f, "EDGE_POINTXYZ %d %d", G.evi[k], G.evj[k]);
-      for (int c = 0; c < 3; ++c) fprintf(f, " %.17g", z[c]);
-      for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) fprintf(f, " %.17g", W[r * 3 + c]);
-    } else if (is_prior_edge(G.etype[k])) {   // hdl_graph_slam's EdgeSE3PriorXY(Z)::write: vertex, z, upper triangle of Omega
-      const int d = G.etype[k] == ET_SE3_PRIOR_XYZ ? 3 : 2;
-      fprintf(f, d == 3 ? "EDGE_SE3_PRIORXYZ %d" : "EDGE_SE3_PRIORXY %d", G.evi[k]);
-      for (int c = 0; c < d; ++c) fprintf(f, " %.17g", z[c]);
-      for (int r = 0; r < d; ++r) for (int c = r; c < d; ++c) fprintf(f, " %.17g", W[r * d + c]);
-    } else {  // row format of the in-tree EdgeSE3Plane::write (edge_se3_plane.hpp:40-47)
-      fprintf(f, "EDGE_SE3_PLANE %d %d", G.evi[k], G.evj[k]);
-      for (int c = 0; c < 4; ++c) fprintf(f, " %.17g", z[c]);
-      for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) fprintf(f, " %.17g", W[r * 3 + c]);
-    }
+    const EdgeType& et = kEdgeType[G.etype[k]];
+    double u[21];
+    pack_upper(&G.info[(size_t)k * 36], et.d, u);
+    fprintf(f, "%s %d", et.tag, G.evi[k]);
+    if (et.vt_j >= 0) fprintf(f, " %d", G.evj[k]);
+    for (int c = 0; c < et.extra_ints; ++c) fprintf(f, " 0");
+    for (int c = 0; c < et.nz; ++c) fprintf(f, " %.17g", G.meas[(size_t)k * 7 + c]);
+    for (int c = 0; c < upper_len(et.d); ++c) fprintf(f, " %.17g", u[c]);
     fprintf(f, "\n");
   }
   fclose(f);
   return 0;
 }
 
+static const EdgeType* edge_type_of_tag(const std::string& tag) {
+  for (const EdgeType& et : kEdgeType) if (tag == et.tag) return &et;
+  return nullptr;
+}
 int sslam_graph_load_g2o(sslam_graph* h, const char* path) {
   if (!h || !path) return set_error(SSLAM_ERR_INVALID, "null argument");
   if (h->g.nv() != 0) return set_error(SSLAM_ERR_INVALID, "load requires an empty graph");
@@ -2414,32 +2153,15 @@ int sslam_graph_load_g2o(sslam_graph* h, const char* path) {
     else if (t == "VERTEX_TRACKXYZ") { int id; double e[3]; if (fscanf(f, "%d", &id) != 1 || !rd(e, 3)) { rc = -1; break; } idmap[id] = add_vertex(h, VT_POINT, e, 3, 0); }
     else if (t == "VERTEX_PLANE") { int id; double e[4]; if (fscanf(f, "%d", &id) != 1 || !rd(e, 4)) { rc = -1; break; } idmap[id] = add_vertex(h, VT_PLANE, e, 4, 0); }
     else if (t == "FIX") { int id; if (fscanf(f, "%d", &id) != 1 || !idmap.count(id)) { rc = -1; break; } h->g.vfixed[idmap[id]] = 1; }
-    else if (t == "EDGE_SE3:QUAT") {
-      int i, j; double z[7], u[21], W[36];
-      if (fscanf(f, "%d %d", &i, &j) != 2 || !rd(z, 7) || !rd(u, 21) || !idmap.count(i) || !idmap.count(j)) { rc = -1; break; }
-      int q = 0; for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { W[r * 6 + c] = u[q]; W[c * 6 + r] = u[q]; ++q; }
-      if (add_edge(h, ET_SE3, idmap[i], idmap[j], z, 7, W, 6) < 0) { rc = -1; break; }
-    } else if (t == "EDGE_SE3_TRACKXYZ") {
-      int i, j, pid; double z[3], u[6], W[9];
-      if (fscanf(f, "%d %d %d", &i, &j, &pid) != 3 || !rd(z, 3) || !rd(u, 6) || !idmap.count(i) || !idmap.count(j)) { rc = -1; break; }
-      int q = 0; for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) { W[r * 3 + c] = u[q]; W[c * 3 + r] = u[q]; ++q; }
-      if (add_edge(h, ET_SE3_POINT, idmap[i], idmap[j], z, 3, W, 3) < 0) { rc = -1; break; }
-    } else if (t == "EDGE_POINTXYZ") {
-      int i, j; double z[3], u[6], W[9];
-      if (fscanf(f, "%d %d", &i, &j) != 2 || !rd(z, 3) || !rd(u, 6) || !idmap.count(i) || !idmap.count(j)) { rc = -1; break; }
-      int q = 0; for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) { W[r * 3 + c] = u[q]; W[c * 3 + r] = u[q]; ++q; }
-      if (add_edge(h, ET_POINT_POINT, idmap[i], idmap[j], z, 3, W, 3) < 0) { rc = -1; break; }
-    } else if (t == "EDGE_SE3_PLANE") {
-      int i, j; double z[4], u[6], W[9];
-      if (fscanf(f, "%d %d", &i, &j) != 2 || !rd(z, 4) || !rd(u, 6) || !idmap.count(i) || !idmap.count(j)) { rc = -1; break; }
-      int q = 0; for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) { W[r * 3 + c] = u[q]; W[c * 3 + r] = u[q]; ++q; }
-      if (add_edge(h, ET_SE3_PLANE, idmap[i], idmap[j], z, 4, W, 3) < 0) { rc = -1; break; }
-    } else if (t == "EDGE_SE3_PRIORXYZ" || t == "EDGE_SE3_PRIORXY") {
-      const int d = t == "EDGE_SE3_PRIORXYZ" ? 3 : 2;
-      int i; double z[3], u[6], W[9];
-      if (fscanf(f, "%d", &i) != 1 || !rd(z, d) || !rd(u, d * (d + 1) / 2) || !idmap.count(i)) { rc = -1; break; }
-      int q = 0; for (int r = 0; r < d; ++r) for (int c = r; c < d; ++c) { W[r * d + c] = u[q]; W[c * d + r] = u[q]; ++q; }
-      if (add_edge(h, d == 3 ? ET_SE3_PRIOR_XYZ : ET_SE3_PRIOR_XY, idmap[i], -1, z, d, W, d) < 0) { rc = -1; break; }
+    else if (const EdgeType* et = edge_type_of_tag(t)) {
+      int id[2] = {0, -1}, skip;
+      double z[7], u[21], W[36];
+      bool ok = true;
+      for (int c = 0; c < (et->vt_j >= 0 ? 2 : 1); ++c) ok = ok && fscanf(f, "%d", &id[c]) == 1 && idmap.count(id[c]);
+      for (int c = 0; c < et->extra_ints; ++c) ok = ok && fscanf(f, "%d", &skip) == 1;
+      if (!ok || !rd(z, et->nz) || !rd(u, upper_len(et->d))) { rc = -1; break; }
+      unpack_upper(u, et->d, W);
+      if (add_edge(h, (int)(et - kEdgeType), idmap[id[0]], et->vt_j >= 0 ? idmap[id[1]] : -1, z, W) < 0) { rc = -1; break; }
     } else {  // PARAMS_SE3OFFSET and unknown rows: skip to end of line
       int ch; while ((ch = fgetc(f)) != EOF && ch != '\n') {}
     }
@@ -2544,7 +2266,6 @@ static int batch_direct_only(const Batch& b, const char* what) {
 static int batch_with_flat_factor(Batch& b, const char* what, const std::function<int()>& body) {
   SSLAM_HIP_TRY(hipSetDevice(b.device));
   int rc;
-  if (!b.uploaded && (rc = batch_upload_estimates(b))) return rc;
   if ((rc = chol_set_active(b, nullptr))) return rc;   // a stale compaction (an optimise that failed half way) must not leave graphs out
   const size_t lm_bytes = sizeof(LmState) * (size_t)b.V.B;
   if (!b.d_lm_save && (rc = dev_alloc(b, (size_t)b.V.B, &b.d_lm_save, false))) return rc;
@@ -2553,9 +2274,7 @@ static int batch_with_flat_factor(Batch& b, const char* what, const std::functio
     Batch& b; size_t bytes;
     ~Restore() { (void)hipMemcpyAsync(b.V.lm, b.d_lm_save, bytes, hipMemcpyDeviceToDevice, b.stream); (void)hipStreamSynchronize(b.stream); b.harvest(); }
   } restore{b, lm_bytes};
-  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
-  hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
-  if ((rc = batch_linearize(b))) return rc;   // undamped H at the current estimates
+  if ((rc = batch_system_at_estimates(b))) return rc;   // undamped H at the current estimates
   int bad;
   if ((rc = factor_undamped_flat(b, &bad))) return rc;
   if (bad >= 0) return set_error(SSLAM_ERR_NUMERIC, "H of graph %d of the batch is not positive definite: no %s", bad, what);
@@ -2649,7 +2368,7 @@ static GateReq gate_request(const Batch& b, int g, int kind, int vu, int vv, con
   std::fill(io, io + 44, 0.0);
   std::copy(z, z + (se3 ? 7 : 3), io);
   if (info) std::copy(info, info + (se3 ? 36 : 9), io + 8);
-  return {vertex_xoff(b, g, vu), 6, vertex_xoff(b, g, vv), se3 ? 6 : 3, kind, b.v2pose[g][vu], se3 ? b.v2pose[g][vv] : b.v2lm[g][vv], info ? 1 : 0};
+  return {vertex_xoff(b, g, vu), 6, vertex_xoff(b, g, vv), se3 ? 6 : 3, kind, b.T.v2pose[g][vu], se3 ? b.T.v2pose[g][vv] : b.T.v2lm[g][vv], info ? 1 : 0};
 }
 // d2, e and S of candidate k out of the kernel's record
 static void gate_result(const double* io, int k, double* d2_out, double* e_out, double* cov_out) {
@@ -2898,10 +2617,7 @@ int64_t sslam_batch_linearize_hb(sslam_batch* h, double* h_and_b, int64_t capaci
   int rc = batch_check(h);
   if (rc) return rc;
   SSLAM_HIP_TRY(hipSetDevice(b.device));
-  if (!b.uploaded && (rc = batch_upload_estimates(b))) return rc;
-  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
-  hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
-  if ((rc = batch_linearize(b))) return rc;
+  if ((rc = batch_system_at_estimates(b))) return rc;
   SSLAM_HIP_TRY(hipMemcpyAsync(h_and_b, b.V.Hpp_diag, (size_t)b.hb_doubles * sizeof(double), hipMemcpyDeviceToHost, b.stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));
   b.harvest();
@@ -2917,9 +2633,7 @@ int sslam_batch_time_linearize(sslam_batch* h, int repeats, double* ms_per_build
   Batch& b = h->b;
   SSLAM_HIP_TRY(hipSetDevice(b.device));
   int rc;
-  if (!b.uploaded && (rc = batch_upload_estimates(b))) return rc;
-  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
-  hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
+  if ((rc = batch_system_at_estimates(b, false))) return rc;
   const bool prof = b.profiling;
   b.profiling = false;
   if ((rc = batch_linearize(b))) return rc;  // warm-up
@@ -2950,10 +2664,7 @@ int sslam_batch_time_solver(sslam_batch* h, int repeats, double* factor_ms, doub
   SSLAM_HIP_TRY(hipSetDevice(b.device));
   int rc;
   if ((rc = chol_set_active(b, nullptr))) return rc;   // a stale compaction (an optimise that failed half way) must not shrink what is timed
-  if (!b.uploaded && (rc = batch_upload_estimates(b))) return rc;
-  if ((rc = batch_chi2(b, b.V.pose, b.V.lmk, 0))) return rc;
-  hipLaunchKernelGGL(k_lm_init, dim3(b.V.B), dim3(64), 0, b.stream, b.V, b.d_part_e, 0);
-  if ((rc = batch_linearize(b))) return rc;
+  if ((rc = batch_system_at_estimates(b))) return rc;
   hipLaunchKernelGGL(k_set_trial_all, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, 1.0);
   struct Restore {   // events and the profiling switch are put back on every return path
     Batch& b; bool prof; hipEvent_t e[3] = {nullptr, nullptr, nullptr};
@@ -2982,15 +2693,13 @@ int64_t sslam_batch_linearize_bytes(const sslam_batch* h) {
   if (!h) return 0;
   if (!h->parts.empty()) { int64_t t = 0; for (const sslam_batch* p : h->parts) t += sslam_batch_linearize_bytes(p); return t; }
   const Batch& b = h->b;
-  // 344*Eo + 160*El(176 plane) + 288*Np + 72*Nl + 288*Eo + 144*El + 48*Np + 24*Nl
-  // position priors (k_linearize_priors): 80 per prior (z 24, Omega 48, dim 4, slot 4) + 268 per pose row that carries one (pose 64, row
-  // and CSR entries 8 + 4, the 9 + 3 doubles of H and b it adds to read 96 and written 96)
+  // per edge its type's lin_bytes (kEdgeType) + 288*Np + 72*Nl + 48*Np + 24*Nl
+  // position priors (k_linearize_priors): + 268 per pose row that carries one (pose 64, row and CSR entries 8 + 4, the 9 + 3 doubles of
+  // H and b it adds to read 96 and written 96)
   int64_t bytes = 0;
   for (size_t g = 0; g < b.graphs.size(); ++g) {
     const HostGraph& G = *b.graphs[g];
-    for (int k = 0; k < G.ne(); ++k)
-      bytes += G.etype[k] == ET_SE3 ? 344 + 288 : (G.etype[k] == ET_SE3_POINT ? 160 + 144 : (G.etype[k] == ET_SE3_PLANE ? 176 + 144 :
-               (is_prior_edge(G.etype[k]) ? 80 : 8 + 24 + 48 + 48 + 72)));
+    for (int k = 0; k < G.ne(); ++k) bytes += kEdgeType[G.etype[k]].lin_bytes;
   }
   bytes += (int64_t)b.V.nPr * (288 + 48) + (int64_t)b.V.nLr * (72 + 24) + (int64_t)b.V.nEpRows * 268;
   return bytes;
@@ -3052,54 +2761,70 @@ int sslam_batch_kernel_time(sslam_batch* h, const char* name, double* total_ms, 
   return 0;
 }
 
-// ---- plan introspection (host only, no device needed): the symbolic Cholesky plan of a batch as flat int32 arrays ----------
-struct sslam_debug_plan { CholHost H; int64_t h_total = 0; std::vector<int> ppoff, plblk; int sc[16] = {0}; };
+// ---- plan introspection (host only, no device needed): the batch tables (batch_tables.hpp) and the symbolic Cholesky plan of a batch as
+// flat arrays.  The same batch_compile as a device batch runs; only batch_upload is left out.
+struct sslam_debug_plan { CholHost H; BatchTables T; };
 void* sslam_debug_plan_create(sslam_graph* const* graphs, int n) {
   if (!graphs || n <= 0) { set_error(SSLAM_ERR_INVALID, "empty batch"); return nullptr; }
-  Batch b;
-  for (int i = 0; i < n; ++i) { if (!graphs[i]) { set_error(SSLAM_ERR_INVALID, "null graph"); return nullptr; } b.graphs.push_back(&graphs[i]->g); }
+  std::vector<HostGraph*> gs;
+  for (int i = 0; i < n; ++i) { if (!graphs[i]) { set_error(SSLAM_ERR_INVALID, "null graph"); return nullptr; } gs.push_back(&graphs[i]->g); }
   static const bool timing = getenv("SSLAM_TIMING") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
-  if (batch_build(b, true) != 0) return nullptr;
+  std::unique_ptr<sslam_debug_plan> P(new sslam_debug_plan());
+  if (batch_compile_checked(gs, P->T) != 0) return nullptr;
   const auto t1 = std::chrono::steady_clock::now();
   SymIn in;
-  chol_sym_input(b, in);
+  chol_sym_input(P->T, in);
   CholOpts opt;
   opt.from_env();
-  chol_opts_normalise(opt, b.V.B, b.V.nPr + b.V.nLr);   // the plan chol_plan_build would execute, small-batch regime included
-  sslam_debug_plan* P = new sslam_debug_plan();
-  P->h_total = b.V.h_total;
-  for (auto& q : b.ppoff) { P->ppoff.push_back(q.first); P->ppoff.push_back(q.second); }
-  for (auto& q : b.plblk) { P->plblk.push_back(q.first); P->plblk.push_back(q.second); }
-  P->sc[11] = b.V.nPr; P->sc[12] = b.V.nLr; P->sc[13] = (int)b.hll_base; P->sc[14] = (int)b.hpp_off_base; P->sc[15] = (int)b.hpl_base;
-  if (chol_symbolic(in, opt, P->H)) { set_error(SSLAM_ERR_NUMERIC, "Cholesky plan: %s", P->H.error.c_str()); delete P; return nullptr; }
+  chol_opts_normalise(opt, n, P->T.nPr() + P->T.nLr());   // the plan chol_plan_build would execute, small-batch regime included
+  if (chol_symbolic(in, opt, P->H)) { set_error(SSLAM_ERR_NUMERIC, "Cholesky plan: %s", P->H.error.c_str()); return nullptr; }
   if (timing) fprintf(stderr, "[timing] host plan: batch tables %.3f ms, symbolic Cholesky %.3f ms\n", std::chrono::duration<double, std::milli>(t1 - t0).count(),
                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
-  return P;
+  return P.release();
 }
 void sslam_debug_plan_destroy(void* p) { delete (sslam_debug_plan*)p; }
 int64_t sslam_debug_plan_array(void* p, const char* name, void* out, int64_t cap_bytes) {
   if (!p || !name) return set_error(SSLAM_ERR_INVALID, "null argument");
   const CholHost& H = ((sslam_debug_plan*)p)->H;
+  const BatchTables& T = ((sslam_debug_plan*)p)->T;
+  const EdgeClassTab &EO = T.cls[EC_SE3], &EL = T.cls[EC_LANDMARK], &ELL = T.cls[EC_POINT_POINT], &EP = T.cls[EC_PRIOR];
   const std::string k(name);
   const void* src = nullptr; int64_t bytes = 0;
-  const sslam_debug_plan& DP = *(sslam_debug_plan*)p;
-  int scal[17] = {H.ncol, H.nlevels, H.dim, H.B, H.npiece, (int)H.lnz, H.tail_lds_f, H.tail_lds_b, H.nt_leaf, H.nt_tail, (int)DP.h_total,
-                  DP.sc[11], DP.sc[12], DP.sc[13], DP.sc[14], DP.sc[15], (int)H.unz};
+  int scal[17] = {H.ncol, H.nlevels, H.dim, H.B, H.npiece, (int)H.lnz, H.tail_lds_f, H.tail_lds_b, H.nt_leaf, H.nt_tail, (int)T.h_total,
+                  T.nPr(), T.nLr(), (int)T.hll_base, (int)T.hpp_off_base, (int)T.hpl_base, (int)H.unz};
 #define ARR(nm, vec) if (k == nm) { src = (vec).data(); bytes = (int64_t)(vec).size() * sizeof((vec)[0]); }
   ARR("col", H.col) ARR("blk", H.blk) ARR("upd", H.upd) ARR("item", H.item) ARR("mb", H.mb) ARR("ilv", H.ilv) ARR("piece", H.piece)
   ARR("lvl_ptr", H.lvl_ptr) ARR("lvl_cols", H.lvl_cols) ARR("plv_ptr", H.plv_ptr) ARR("plv_pieces", H.plv_pieces)
-  ARR("ppoff", DP.ppoff) ARR("plblk", DP.plblk) ARR("tail_ptr", H.tail_ptr)
+  ARR("ppoff", T.ppoff) ARR("plblk", T.plblk) ARR("tail_ptr", H.tail_ptr)
   ARR("asrc", H.asrc) ARR("usrc", H.usrc) ARR("fwd", H.fwd) ARR("uitem", H.uitem) ARR("umb", H.umb) ARR("tail_pieces", H.tail_pieces) ARR("plv_lds_f", H.plv_lds_f) ARR("plv_lds_b", H.plv_lds_b)
   ARR("rcol", H.rcol) ARR("rupd", H.rupd) ARR("plv_nt", H.plv_nt) ARR("plv_cls", H.plv_cls)
   ARR("fblob", H.fblob) ARR("fgrp", H.fgrp) ARR("plv_lds_ff", H.plv_lds_ff)
+  // the batch tables, under the names of BatchTables; a storage class's arrays are <class>_{a, b, blk, id, z, w} with class eo, el, ell, ep
+  ARR("seg", T.seg) ARR("pose_row", T.pose_row) ARR("lm_row", T.lm_row) ARR("prow_pose", T.prow_pose) ARR("lrow_lm", T.lrow_lm)
+  ARR("prow_graph", T.prow_graph) ARR("lrow_graph", T.lrow_graph) ARR("pose_vertex", T.pose_vertex) ARR("lm_vertex", T.lm_vertex)
+  ARR("lm_kind", T.lm_kind) ARR("prow_perm", T.prow_perm) ARR("llblk", T.llblk)
+  ARR("eo_a", EO.a) ARR("eo_b", EO.b) ARR("eo_blk", EO.blk) ARR("eo_id", EO.id) ARR("eo_z", EO.z) ARR("eo_w", EO.w)
+  ARR("el_a", EL.a) ARR("el_b", EL.b) ARR("el_blk", EL.blk) ARR("el_id", EL.id) ARR("el_z", EL.z) ARR("el_w", EL.w)
+  ARR("ell_a", ELL.a) ARR("ell_b", ELL.b) ARR("ell_blk", ELL.blk) ARR("ell_id", ELL.id) ARR("ell_z", ELL.z) ARR("ell_w", ELL.w)
+  ARR("ep_a", EP.a) ARR("ep_id", EP.id) ARR("ep_z", EP.z) ARR("ep_w", EP.w) ARR("ep_dim", EP.dim)
+  ARR("pslot_ptr", T.pslot_ptr) ARR("pslot_rec", T.pslot_rec) ARR("lslot_ptr", T.lslot_ptr) ARR("lslot_edge", T.lslot_edge)
+  ARR("llslot_ptr", T.llslot_ptr) ARR("llslot_rec", T.llslot_rec) ARR("llblk_ptr", T.llblk_ptr) ARR("llblk_edge", T.llblk_edge)
+  ARR("dup_eo", T.dup_eo) ARR("dup_el", T.dup_el) ARR("ep_row", T.ep_row) ARR("ep_ptr", T.ep_ptr) ARR("ep_edge", T.ep_edge)
+  ARR("adj_ptr", T.adj_ptr) ARR("adj_blk", T.adj_blk) ARR("adj_x", T.adj_x) ARR("adj_fmt", T.adj_fmt)
+  ARR("shard_lo", T.shard_lo) ARR("shard_hi", T.shard_hi)
 #undef ARR
   int fscal[4] = {H.front ? 1 : 0, (int)H.funz, H.tail_lds_ff, 0};   // front tables (front_plan.hpp): present, doubles of update matrices, LDS of the tail
   if (k == "fscalars") { src = fscal; bytes = sizeof fscal; }
   if (k == "scalars") { src = scal; bytes = sizeof scal; }
   static const char* known[] = {"col", "blk", "upd", "item", "mb", "ilv", "piece", "lvl_ptr", "lvl_cols", "plv_ptr", "plv_pieces", "ppoff", "plblk",
                                 "tail_ptr", "tail_pieces", "plv_lds_f", "plv_lds_b", "scalars", "asrc", "usrc", "fwd", "uitem", "umb", "rcol", "rupd", "plv_nt", "plv_cls",
-                                "fblob", "fgrp", "plv_lds_ff", "fscalars"};
+                                "fblob", "fgrp", "plv_lds_ff", "fscalars",
+                                "seg", "pose_row", "lm_row", "prow_pose", "lrow_lm", "prow_graph", "lrow_graph", "pose_vertex", "lm_vertex", "lm_kind", "prow_perm", "llblk",
+                                "eo_a", "eo_b", "eo_blk", "eo_id", "eo_z", "eo_w", "el_a", "el_b", "el_blk", "el_id", "el_z", "el_w",
+                                "ell_a", "ell_b", "ell_blk", "ell_id", "ell_z", "ell_w", "ep_a", "ep_id", "ep_z", "ep_w", "ep_dim",
+                                "pslot_ptr", "pslot_rec", "lslot_ptr", "lslot_edge", "llslot_ptr", "llslot_rec", "llblk_ptr", "llblk_edge",
+                                "dup_eo", "dup_el", "ep_row", "ep_ptr", "ep_edge", "adj_ptr", "adj_blk", "adj_x", "adj_fmt", "shard_lo", "shard_hi"};
   bool ok = false;
   for (const char* q : known) ok |= (k == q);
   if (!ok) return set_error(SSLAM_ERR_INVALID, "unknown plan array '%s'", name);

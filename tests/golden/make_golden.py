@@ -154,8 +154,22 @@ def make_tick():
     print("tick fixture:", len(per_tick), "ticks,", c.counts())
 
 
+def make_batch_tables():
+    """The device tables of the two-graph batch of tests/test_batch_tables_cpu.py, as the library that is built in this tree compiles them.
+    The committed file was recorded from the batch build as it was before it became batch_compile / batch_upload (with only the accessor
+    of sslam_debug_plan_array added to it); it is a reference for refactors of the compile, so regenerate it only when a table is MEANT to
+    change."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_batch_tables_cpu import batch
+    _, tables = batch()
+    np.savez_compressed(os.path.join(HERE, "batch_tables_mixed.npz"), **tables)
+    print("batch tables fixture:", len(tables), "arrays,", sum(a.nbytes for a in tables.values()), "bytes")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "hull":
+    if len(sys.argv) > 1 and sys.argv[1] == "batch_tables":
+        make_batch_tables()
+    elif len(sys.argv) > 1 and sys.argv[1] == "hull":
         make_hull()
     elif len(sys.argv) > 1 and sys.argv[1] == "tick":
         make_tick()
