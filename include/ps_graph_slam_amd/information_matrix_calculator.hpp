@@ -85,6 +85,7 @@ class InformationMatrixCalculator {
   }
 
  private:
+  friend class ScanMatcher;   // scan_matcher.hpp: the same cloud and pose types, the same handle
   struct Handle {
     sslam_seg* s;
     Handle() : s(sslam_seg_create(nullptr)) {}

@@ -580,6 +580,51 @@ typedef struct sslam_inf_params {
 void sslam_inf_default_params(sslam_inf_params* p);
 int sslam_information_from_fitness(const sslam_inf_params* p, double fitness, double info[36]);
 
+/* ---- scan matching: nearest-neighbour ICP of cloud pairs (what hdl_graph_slam's LoopDetector::matching does with
+ * pcl::IterativeClosestPoint [UPSTREAM]; the reference has no scan matcher) ------------------------------------------------------------
+ * sslam_seg_register_pairs: for every pair, the rigid transform T (source -> target frame) that the point-to-point ICP loop reaches from
+ * the initial guess T0, and the fitness score at it.  Clouds are laid out as for sslam_seg_fitness_scores; a cloud may serve several
+ * pairs.  All pairs share one set of launches per iteration, and the whole loop runs on the device: the host only reads, every 8
+ * iterations at most, how many pairs are still unfinished.  One iteration of a pair, from its current T (12 doubles):
+ *   1. correspondences: exactly the fitness pass at T (R, t cast to float once, the float32 arithmetic and the lowest-index tie rule
+ *      stated above).  Source point i is ACCEPTED when it found a neighbour and (double)d2 <= max_corr2.
+ *   2. fewer than 3 accepted: status = SSLAM_ERR_NUMERIC, the pair is finished and T is left as it stood before this pass.
+ *   3. in double, over the accepted points: n, sum p, sum q, sum p q^T with p the ORIGINAL source point and q its target, widened from
+ *      float.  The order of summation is fixed by the point index alone (the tree of the fitness score inside every run of 256
+ *      consecutive source points, the runs in ascending order; no floating-point atomics): it depends neither on the target split nor
+ *      on the other pairs of the call, and repeating a call repeats its bits.
+ *   4. T_new = the rigid transform minimising sum |R p + t - q|^2 over those correspondences, solved for the ABSOLUTE transform (no
+ *      composition of increments, so no composition error accumulates): Horn's closed form, the unit quaternion of R being the dominant
+ *      eigenvector of a symmetric 4 x 4 matrix of the cross-covariance, found by cyclic Jacobi sweeps; t = mean q - R mean p.  This is
+ *      the minimiser pcl::TransformationEstimationSVD computes.  R is a proper rotation (det = +1) for coplanar correspondences too.
+ *      COLLINEAR correspondences leave the rotation about their line undetermined: any of the minimisers may be returned.
+ *   5. iterations += 1 and T = T_new; if no entry of T moved by more than epsilon (max |T_new - T| <= epsilon over the 12 entries) the
+ *      pair is finished with converged = 1.  epsilon = 0 asks for T to repeat bit for bit, which happens once the correspondences
+ *      repeat (equal correspondences give equal sums).
+ * A finished pair is frozen: its T never changes again while the others iterate on, at most max_iterations times.  Then one more
+ * fitness pass at the final T fills score, used and the optional nn_index_out / nn_dist2_out (layout as in sslam_seg_fitness_scores):
+ * bitwise what sslam_seg_fitness_scores returns for out.T with max_range = max_corr2, so sslam_information_from_fitness(out.score) is
+ * the information matrix of the loop edge.  max_iterations = 0 is valid: T = T0 and the call is the fitness pass at T0.
+ * kernel_ms (optional): hipEvent time from the first reset to the end of the final pass (the reads of the counter in between included).
+ * Empty clouds are valid (status SSLAM_ERR_NUMERIC when max_iterations > 0; used = 0, score = DBL_MAX).  Returns n_pairs.
+ * SSLAM_ERR_INVALID: the cases of sslam_seg_fitness_scores (with out in the place of score_out / used_out), max_iterations < 0, a
+ * negative or NaN epsilon.  SSLAM_ERR_NO_DEVICE without a GPU.  SSLAM_FITNESS_OPTS="chunk=N" acts as in the fitness pass. */
+typedef struct sslam_reg_pair {
+  int32_t target, source;      /* cloud indices, as in sslam_fitness_pair */
+  double  T0[12];              /* initial guess, R row-major then t: source -> target frame */
+  double  max_corr2;           /* bound on the SQUARED correspondence distance; DBL_MAX = none */
+} sslam_reg_pair;
+typedef struct sslam_reg_result {
+  double  T[12];               /* the estimate the loop ended at */
+  double  score;               /* fitness score AT T, as sslam_seg_fitness_scores with max_range = max_corr2 */
+  int32_t used;                /* source points behind `score` */
+  int32_t iterations;          /* updates of T that were carried out */
+  int32_t converged;           /* 1: the last update moved no entry of T by more than epsilon */
+  int32_t status;              /* 0, or SSLAM_ERR_NUMERIC: fewer than 3 accepted correspondences in some pass; T as it stood before that pass */
+} sslam_reg_result;
+int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
+                             int max_iterations, double epsilon, sslam_reg_result* out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms);
+
 /* parity hooks: per-box products of the last sslam_seg_segment call.
  * normals: w*h*4 floats (nx,ny,nz,curvature), labels: w*h int32 (-1 = no plane; otherwise the
  * region index in output order of pcl::OrganizedMultiPlaneSegmentation::segmentAndRefine). */

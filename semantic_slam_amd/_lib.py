@@ -106,6 +106,7 @@ def load_library():
         "sslam_batch_set_profiling": (ci, [vp, ci]),
         "sslam_batch_kernel_time": (ci, [vp, C.c_char_p, dp, C.POINTER(i64)]),
         "sslam_seg_fitness_scores": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, dp]),
+        "sslam_seg_register_pairs": (ci, [vp, vp, vp, ci, vp, ci, ci, cd, vp, vp, vp, dp]),
         "sslam_inf_default_params": (None, [vp]),
         "sslam_information_from_fitness": (ci, [vp, cd, dp]),
         "sslam_slam_set_fitness_information": (ci, [vp, vp, C.c_float, cd]),

@@ -230,4 +230,82 @@ SSLAM_HD void plane_jacobians(const Pose& Xi, Plane pw, Plane z, double Ji[18], 
   }
 }
 
+// ---- absolute orientation (the update of sslam_seg_register_pairs) -------------------------------------------------------------------
+// One Jacobi rotation of the symmetric 4 x 4 matrix A in the (P, Q) plane, A <- J^T A J, accumulated into V <- V J.  P and Q are
+// template parameters and every loop is unrolled, so that no array is indexed at run time (A and V stay in registers on the device).
+template <int P, int Q>
+SSLAM_HD void jacobi4_rotate(double (&A)[4][4], double (&V)[4][4]) {
+  const double apq = A[P][Q];
+  if (apq == 0.0) return;
+  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // the smaller root: |angle| <= pi / 4
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double akp = A[k][P], akq = A[k][Q];
+    A[k][P] = c * akp - s * akq; A[k][Q] = s * akp + c * akq;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double apk = A[P][k], aqk = A[Q][k];
+    A[P][k] = c * apk - s * aqk; A[Q][k] = s * apk + c * aqk;
+  }
+  A[P][Q] = 0.0; A[Q][P] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double vkp = V[k][P], vkq = V[k][Q];
+    V[k][P] = c * vkp - s * vkq; V[k][Q] = s * vkp + c * vkq;
+  }
+}
+// The rigid transform (R, t) minimising sum |R p + t - q|^2 over n >= 3 correspondences, from their plain sums n, sum p, sum q and
+// M = sum p q^T (Mab = sum p_a q_b).  T: R row-major, then t.  Horn's closed form (J. Opt. Soc. Am. A 4 (1987) 629): with the
+// cross-covariance S = M - (sum p)(sum q)^T / n, the unit quaternion of R is the eigenvector of the largest eigenvalue of the symmetric
+//   N = | Sxx+Syy+Szz   Syz-Szy        Szx-Sxz        Sxy-Syx      |
+//       | Syz-Szy       Sxx-Syy-Szz    Sxy+Syx        Szx+Sxz      |
+//       | Szx-Sxz       Sxy+Syx       -Sxx+Syy-Szz    Syz+Szy      |
+//       | Sxy-Syx       Szx+Sxz        Syz+Szy       -Sxx-Syy+Szz  |     (order w, x, y, z),
+// found by cyclic Jacobi sweeps; t = mean q - R mean p.  R comes from a unit quaternion, so it is a proper rotation whatever the
+// correspondences are (coplanar ones too, where the SVD form needs its determinant correction): it is the minimiser over rotations,
+// which is what pcl::TransformationEstimationSVD computes.  The eigenvalues of N are s1+s2+s3', s1-s2-s3', -s1+s2-s3', -s1-s2+s3' for
+// the singular values s1 >= s2 >= s3 of S (s3' = s3 times the sign of det S): the largest is simple unless s2 = -s3', i.e. for
+// collinear correspondences (s2 = s3 = 0), where the rotation about the line is undetermined and the column Jacobi happens to end
+// at is returned, one of the minimisers.
+SSLAM_HD void horn_rigid(double n, double px, double py, double pz, double qx, double qy, double qz, double Mxx, double Mxy, double Mxz, double Myx,
+                         double Myy, double Myz, double Mzx, double Mzy, double Mzz, double T[12]) {
+  const double Sxx = Mxx - px * qx / n, Sxy = Mxy - px * qy / n, Sxz = Mxz - px * qz / n;
+  const double Syx = Myx - py * qx / n, Syy = Myy - py * qy / n, Syz = Myz - py * qz / n;
+  const double Szx = Mzx - pz * qx / n, Szy = Mzy - pz * qy / n, Szz = Mzz - pz * qz / n;
+  double A[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                    {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
+                    {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
+                    {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
+  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+  for (int sweep = 0; sweep < 30; ++sweep) {   // quadratic convergence: 6 to 8 sweeps in practice
+    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[0][3] * A[0][3] + A[1][2] * A[1][2] + A[1][3] * A[1][3] + A[2][3] * A[2][3];
+    const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2] + A[3][3] * A[3][3];
+    if (off <= 1e-40 * dia) break;
+    jacobi4_rotate<0, 1>(A, V); jacobi4_rotate<0, 2>(A, V); jacobi4_rotate<0, 3>(A, V);
+    jacobi4_rotate<1, 2>(A, V); jacobi4_rotate<1, 3>(A, V); jacobi4_rotate<2, 3>(A, V);
+  }
+  // the column of the largest eigenvalue (the first among equals), picked with 0 / 1 weights: exact, and unlike a chain of conditional
+  // copies the compiler cannot turn it into a run-time index into V, which would put V into scratch memory
+  double best = A[0][0];
+  int kb = 0;
+  if (A[1][1] > best) { best = A[1][1]; kb = 1; }
+  if (A[2][2] > best) { best = A[2][2]; kb = 2; }
+  if (A[3][3] > best) { best = A[3][3]; kb = 3; }
+  const double m0 = kb == 0 ? 1.0 : 0.0, m1 = kb == 1 ? 1.0 : 0.0, m2 = kb == 2 ? 1.0 : 0.0, m3 = kb == 3 ? 1.0 : 0.0;
+  const double w = (m0 * V[0][0] + m1 * V[0][1]) + (m2 * V[0][2] + m3 * V[0][3]);
+  const double x = (m0 * V[1][0] + m1 * V[1][1]) + (m2 * V[1][2] + m3 * V[1][3]);
+  const double y = (m0 * V[2][0] + m1 * V[2][1]) + (m2 * V[2][2] + m3 * V[2][3]);
+  const double z = (m0 * V[3][0] + m1 * V[3][1]) + (m2 * V[3][2] + m3 * V[3][3]);
+  const double nq = sqrt(w * w + x * x + y * y + z * z);
+  const Mat3 R = qmat(Quat{x / nq, y / nq, z / nq, w / nq});
+  const Vec3 pm = {px / n, py / n, pz / n}, qm = {qx / n, qy / n, qz / n};
+  const Vec3 t = qm - mul(R, pm);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) T[k] = R.m[k];
+  T[9] = t.x; T[10] = t.y; T[11] = t.z;
+}
+
 }  // namespace sslam

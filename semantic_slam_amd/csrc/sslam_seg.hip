@@ -24,6 +24,7 @@
 
 #include "../../include/sslam.h"
 #include "sslam_common.hpp"
+#include "sslam_math.hpp"
 
 namespace sslam {
 namespace seg {
@@ -2106,6 +2107,95 @@ __global__ __launch_bounds__(kNnSeg) void k_nn_finish(const NnPair* __restrict__
   }
 }
 
+// ---- scan matching: nearest-neighbour ICP of cloud pairs (hdl_graph_slam's LoopDetector::matching with pcl::IterativeClosestPoint
+// [UPSTREAM]; the reference has no scan matcher) ----------------------------------------------------------------------------------
+// One iteration of ALL pairs is  reset best -> k_nn_pairs -> k_reg_sums -> k_reg_step  on the handle's stream, no host round trip:
+// k_nn_pairs reads R, t from the device's pair table, and k_reg_step writes the float casts of the new estimate back into it.
+//   k_reg_sums  one workgroup per run of kNnSeg consecutive source points of a pair (the NnSeg table of k_nn_finish): a thread unpacks
+//               `best` for its point and, if the correspondence is accepted ((double)d2 <= max_range), loads the ORIGINAL source point p
+//               (coalesced: the run's 3 * 256 floats are contiguous) and its target q (a gather: 12 bytes wherever the neighbour lies)
+//               and forms, in double, sum p, sum q, sum p q^T and the count.  The products of two widened floats are exact.  Reduced
+//               with the tree of k_nn_finish: the shuffle tree of a wave over its 64 consecutive points, the four waves in order.
+//   k_reg_step  one wave per pair: lanes 0..15 add the run records in ascending run order, lane 0 solves the absolute orientation
+//               problem (horn_rigid, csrc/sslam_math.hpp) and applies the status and convergence rules.
+// The order of every sum is fixed by the point index alone.  A finished pair (converged, or fewer than 3 correspondences) is frozen by
+// its `done` flag: its runs leave k_reg_sums at once and its state and pair-table entry are never written again; it still rides through
+// k_nn_pairs, whose instruction stream is the fitness pass's.
+constexpr int kRegSums = 16;   // sum p (3), sum q (3), sum p q^T (9, row-major: p's coordinate is the row), count
+struct RegState { double T[12]; int iterations, converged, status, done; };
+__global__ __launch_bounds__(kNnSeg) void k_reg_sums(const float* __restrict__ xyz, const NnPair* __restrict__ pairs, const NnSeg* __restrict__ segs,
+                                                    const unsigned long long* __restrict__ best, const RegState* __restrict__ st,
+                                                    double* __restrict__ part) {
+  __shared__ double red[kNnSeg / 64][kRegSums];
+  const NnSeg sg = segs[blockIdx.x];
+  if (st[sg.pair].done) return;          // the same for the whole workgroup
+  const NnPair P = pairs[sg.pair];
+  const int tid = threadIdx.x, i = sg.seg * kNnSeg + tid;
+  double a[kRegSums];
+#pragma unroll
+  for (int k = 0; k < kRegSums; ++k) a[k] = 0.0;
+  if (i < P.ns) {
+    const unsigned long long key = best[P.qoff + i];
+    if (key != ~0ull && (double)__uint_as_float((unsigned)(key >> 32)) <= P.max_range) {
+      const int j = (int)(unsigned)(key & 0xffffffffull);   // < P.nt: k_nn_pairs only ever writes indices of the pair's target cloud
+      const float* ps = xyz + 3 * (size_t)(P.s0 + i);
+      const float* qt = xyz + 3 * (size_t)(P.t0 + j);
+      const double p[3] = {(double)ps[0], (double)ps[1], (double)ps[2]}, q[3] = {(double)qt[0], (double)qt[1], (double)qt[2]};
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        a[r] = p[r]; a[3 + r] = q[r];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a[6 + 3 * r + c] = p[r] * q[c];
+      }
+      a[15] = 1.0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kRegSums; ++k) {
+    double v = a[k];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6][k] = v;
+  }
+  __syncthreads();
+  if (tid < kRegSums) part[(size_t)blockIdx.x * kRegSums + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+__global__ __launch_bounds__(64) void k_reg_step(const int* __restrict__ seg0, const double* __restrict__ part, double epsilon, NnPair* __restrict__ pairs,
+                                                 RegState* __restrict__ st, int* __restrict__ live) {
+  __shared__ double sums[kRegSums];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  if (st[p].done) return;
+  if (tid < kRegSums) {
+    double v = 0.0;
+    for (int r = seg0[p]; r < seg0[p + 1]; ++r) v += part[(size_t)r * kRegSums + tid];   // ascending run order
+    sums[tid] = v;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  if (sums[15] < 3.0) {                  // fewer than 3 correspondences: T stays as it stood before this pass
+    st[p].status = SSLAM_ERR_NUMERIC;
+    st[p].done = 1;
+    atomicSub(live, 1);
+    return;
+  }
+  double Tn[12], moved = 0.0;            // sums of finite floats and their pairwise products cannot overflow a double: Tn is finite
+  horn_rigid(sums[15], sums[0], sums[1], sums[2], sums[3], sums[4], sums[5], sums[6], sums[7], sums[8], sums[9], sums[10], sums[11], sums[12],
+             sums[13], sums[14], Tn);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) moved = fmax(moved, fabs(Tn[k] - st[p].T[k]));
+#pragma unroll
+  for (int k = 0; k < 12; ++k) st[p].T[k] = Tn[k];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) pairs[p].R[k] = (float)Tn[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pairs[p].t[k] = (float)Tn[9 + k];
+  st[p].iterations += 1;
+  if (moved <= epsilon) {
+    st[p].converged = 1;
+    st[p].done = 1;
+    atomicSub(live, 1);
+  }
+}
+
 // ---- k-means of the legacy path (plane_segmentation::computeKmeans -> cv::kmeans, plane_segmentation.cpp:524-535) -----------------
 // assignment step: nearest centre in float32 (squared distance accumulated coordinate by coordinate; ties -> lowest centre), and for
 // the next centre update the coordinate sums / counts per cluster and the compactness, all in 2^-20 fixed point (integer atomics)
@@ -3222,30 +3312,40 @@ static int fitness_chunk_from_env() {
   return v > 0 && v < (1l << 30) ? (int)v : 0;
 }
 
-int sslam_seg_fitness_scores(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_fitness_pair* pairs, int n_pairs,
-                             double* score_out, int32_t* used_out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
-  if (!s || !cloud_start || n_clouds < 0 || n_pairs < 0 || (n_pairs > 0 && (!pairs || !score_out || !used_out)))
-    return set_error(SSLAM_ERR_INVALID, "bad argument");
+// The host side of a nearest-neighbour pass, shared by sslam_seg_fitness_scores and sslam_seg_register_pairs: the checks of the cloud
+// layout, the plan (pairs as the kernels read them, items, runs), the device buffers and the two halves of the pass.
+static int nn_check_clouds(const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_fitness_pair* pairs, int n_pairs) {
   if (cloud_start[0] < 0) return set_error(SSLAM_ERR_INVALID, "cloud_start[0] is negative");
   for (int c = 0; c < n_clouds; ++c)
     if (cloud_start[c + 1] < cloud_start[c]) return set_error(SSLAM_ERR_INVALID, "cloud_start decreases at cloud %d", c);
-  const int n_points = cloud_start[n_clouds];
-  if (n_points > 0 && !xyz) return set_error(SSLAM_ERR_INVALID, "null xyz");
+  if (cloud_start[n_clouds] > 0 && !xyz) return set_error(SSLAM_ERR_INVALID, "null xyz");
   for (int p = 0; p < n_pairs; ++p)
     if (pairs[p].target < 0 || pairs[p].target >= n_clouds || pairs[p].source < 0 || pairs[p].source >= n_clouds)
       return set_error(SSLAM_ERR_INVALID, "pair %d names cloud %d / %d of %d", p, pairs[p].target, pairs[p].source, n_clouds);
-  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
-  int rc = seg_device(s);
-  if (rc) return rc;
-  if (kernel_ms) *kernel_ms = 0.0;
-  if (n_pairs == 0) return 0;
+  return 0;
+}
+struct NnPlan {
+  std::vector<NnPair> hp;
+  std::vector<NnItem> items;
+  std::vector<NnSeg> segs;
+  long long total_q = 0;
+};
+struct NnDev {
+  float *xyz = nullptr, *d2 = nullptr;
+  NnPair* pairs = nullptr; NnItem* items = nullptr; NnSeg* segs = nullptr;
+  unsigned long long* best = nullptr;
+  int *idx = nullptr, *used = nullptr;
+  double* sum = nullptr;
+};
+static int nn_plan(sslam_seg* s, const int32_t* cloud_start, const sslam_fitness_pair* pairs, int n_pairs, NnPlan& pl) {
   if (!s->n_cu) {
     int v = 0;
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, s->P.device) != hipSuccess || v <= 0) v = 256;
     s->n_cu = v;
   }
   // the pairs as the kernels read them, the source blocks (items before the target split) and the runs of the reduction
-  std::vector<NnPair> hp(n_pairs);
+  std::vector<NnPair>& hp = pl.hp;
+  hp.resize(n_pairs);
   long long total_q = 0, blocks = 0, n_seg = 0;
   for (int p = 0; p < n_pairs; ++p) {
     NnPair& P = hp[p];
@@ -3259,14 +3359,15 @@ int sslam_seg_fitness_scores(sslam_seg* s, const float* xyz, const int32_t* clou
     if (P.nt > 0) blocks += (P.ns + kNnQ - 1) / kNnQ;
     n_seg += (P.ns + kNnSeg - 1) / kNnSeg;
   }
+  pl.total_q = total_q;
   // Target split.  Without it the launch has `blocks` workgroups; below four per compute unit the targets of every pair are cut into
   // as many chunks as bring it there, never shorter than two tiles (a workgroup should scan long enough to pay for its query loads
   // and atomics).  Chunk boundaries do not change any result.
   int chunk = fitness_chunk_from_env();
   long long split = 1;
   if (!chunk && blocks > 0 && blocks < 4ll * s->n_cu) split = (4ll * s->n_cu + blocks - 1) / blocks;
-  std::vector<NnItem> items;
-  std::vector<NnSeg> segs;
+  std::vector<NnItem>& items = pl.items;
+  std::vector<NnSeg>& segs = pl.segs;
   segs.reserve((size_t)n_seg);
   for (int p = 0; p < n_pairs; ++p) {
     const NnPair& P = hp[p];
@@ -3284,34 +3385,44 @@ int sslam_seg_fitness_scores(sslam_seg* s, const float* xyz, const int32_t* clou
       for (long long c = 0; c < nch; ++c)
         items.push_back(NnItem{p, (int)qb, (int)(c * ch), (int)std::min<long long>((c + 1) * ch, P.nt)});
   }
-  DevGuard g;
-  float *d_xyz = nullptr, *d_d2 = nullptr;
-  NnPair* d_pairs = nullptr; NnItem* d_items = nullptr; NnSeg* d_segs = nullptr;
-  unsigned long long* d_best = nullptr;
-  int *d_idx = nullptr, *d_used = nullptr;
-  double* d_sum = nullptr;
-  if ((rc = g.alloc(&d_xyz, (size_t)n_points * 3)) || (rc = g.alloc(&d_pairs, n_pairs)) || (rc = g.alloc(&d_items, items.size())) ||
-      (rc = g.alloc(&d_segs, segs.size())) || (rc = g.alloc(&d_best, (size_t)total_q)) || (rc = g.alloc(&d_idx, (size_t)total_q)) ||
-      (rc = g.alloc(&d_d2, (size_t)total_q)) || (rc = g.alloc(&d_sum, segs.size())) || (rc = g.alloc(&d_used, segs.size()))) return rc;
+  return 0;
+}
+// buffers and the copies to the device, all on the handle's stream; f_e0 is NOT recorded here
+static int nn_upload(sslam_seg* s, DevGuard& g, const NnPlan& pl, const float* xyz, int n_points, NnDev& d) {
+  int rc;
+  const size_t total_q = (size_t)pl.total_q;
+  if ((rc = g.alloc(&d.xyz, (size_t)n_points * 3)) || (rc = g.alloc(&d.pairs, pl.hp.size())) || (rc = g.alloc(&d.items, pl.items.size())) ||
+      (rc = g.alloc(&d.segs, pl.segs.size())) || (rc = g.alloc(&d.best, total_q)) || (rc = g.alloc(&d.idx, total_q)) ||
+      (rc = g.alloc(&d.d2, total_q)) || (rc = g.alloc(&d.sum, pl.segs.size())) || (rc = g.alloc(&d.used, pl.segs.size()))) return rc;
   if (!s->f_e0) { SSLAM_HIP_TRY(hipEventCreate(&s->f_e0)); SSLAM_HIP_TRY(hipEventCreate(&s->f_e1)); }
-  if (n_points > 0) SSLAM_HIP_TRY(hipMemcpyAsync(d_xyz, xyz, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  SSLAM_HIP_TRY(hipMemcpyAsync(d_pairs, hp.data(), hp.size() * sizeof(NnPair), hipMemcpyHostToDevice, s->stream));
-  if (!items.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(NnItem), hipMemcpyHostToDevice, s->stream));
-  if (!segs.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(NnSeg), hipMemcpyHostToDevice, s->stream));
-  SSLAM_HIP_TRY(hipEventRecord(s->f_e0, s->stream));
-  if (total_q > 0) SSLAM_HIP_TRY(hipMemsetAsync(d_best, 0xff, (size_t)total_q * sizeof(unsigned long long), s->stream));
-  if (!items.empty()) hipLaunchKernelGGL(k_nn_pairs, dim3((unsigned)items.size()), dim3(kNnThreads), 0, s->stream, d_xyz, d_pairs, d_items, d_best);
-  if (!segs.empty()) hipLaunchKernelGGL(k_nn_finish, dim3((unsigned)segs.size()), dim3(kNnSeg), 0, s->stream, d_pairs, d_segs, d_best, d_idx, d_d2, d_sum, d_used);
+  if (n_points > 0) SSLAM_HIP_TRY(hipMemcpyAsync(d.xyz, xyz, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d.pairs, pl.hp.data(), pl.hp.size() * sizeof(NnPair), hipMemcpyHostToDevice, s->stream));
+  if (!pl.items.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(d.items, pl.items.data(), pl.items.size() * sizeof(NnItem), hipMemcpyHostToDevice, s->stream));
+  if (!pl.segs.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(d.segs, pl.segs.data(), pl.segs.size() * sizeof(NnSeg), hipMemcpyHostToDevice, s->stream));
+  return 0;
+}
+// reset `best` and search: the nearest target of every source point at the R, t the device's pair table holds
+static int nn_search(sslam_seg* s, const NnPlan& pl, const NnDev& d) {
+  if (pl.total_q > 0) SSLAM_HIP_TRY(hipMemsetAsync(d.best, 0xff, (size_t)pl.total_q * sizeof(unsigned long long), s->stream));
+  if (!pl.items.empty()) hipLaunchKernelGGL(k_nn_pairs, dim3((unsigned)pl.items.size()), dim3(kNnThreads), 0, s->stream, d.xyz, d.pairs, d.items, d.best);
+  return 0;
+}
+// k_nn_finish, f_e1, the copies back, the wait, and the score of every pair (the time between f_e0 and f_e1 goes to kernel_ms)
+static int nn_finish(sslam_seg* s, const NnPlan& pl, const NnDev& d, double* score_out, int32_t* used_out, int32_t* nn_index_out, float* nn_dist2_out,
+                     double* kernel_ms) {
+  const std::vector<NnSeg>& segs = pl.segs;
+  const size_t total_q = (size_t)pl.total_q;
+  if (!segs.empty()) hipLaunchKernelGGL(k_nn_finish, dim3((unsigned)segs.size()), dim3(kNnSeg), 0, s->stream, d.pairs, d.segs, d.best, d.idx, d.d2, d.sum, d.used);
   SSLAM_HIP_TRY(hipGetLastError());
   SSLAM_HIP_TRY(hipEventRecord(s->f_e1, s->stream));
   std::vector<double> h_sum(segs.size());
   std::vector<int> h_used(segs.size());
   if (!segs.empty()) {
-    SSLAM_HIP_TRY(hipMemcpyAsync(h_sum.data(), d_sum, segs.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    SSLAM_HIP_TRY(hipMemcpyAsync(h_used.data(), d_used, segs.size() * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    SSLAM_HIP_TRY(hipMemcpyAsync(h_sum.data(), d.sum, segs.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    SSLAM_HIP_TRY(hipMemcpyAsync(h_used.data(), d.used, segs.size() * sizeof(int), hipMemcpyDeviceToHost, s->stream));
   }
-  if (total_q > 0 && nn_index_out) SSLAM_HIP_TRY(hipMemcpyAsync(nn_index_out, d_idx, (size_t)total_q * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  if (total_q > 0 && nn_dist2_out) SSLAM_HIP_TRY(hipMemcpyAsync(nn_dist2_out, d_d2, (size_t)total_q * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  if (total_q > 0 && nn_index_out) SSLAM_HIP_TRY(hipMemcpyAsync(nn_index_out, d.idx, total_q * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  if (total_q > 0 && nn_dist2_out) SSLAM_HIP_TRY(hipMemcpyAsync(nn_dist2_out, d.d2, total_q * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
   if (kernel_ms) {
     float ms = 0.0f;
@@ -3319,12 +3430,100 @@ int sslam_seg_fitness_scores(sslam_seg* s, const float* xyz, const int32_t* clou
     *kernel_ms = (double)ms;
   }
   size_t at = 0;
-  for (int p = 0; p < n_pairs; ++p) {   // the runs of a pair in ascending order
+  for (size_t p = 0; p < pl.hp.size(); ++p) {   // the runs of a pair in ascending order
     double sum = 0.0;
     long long used = 0;
-    for (int k = 0; k < (hp[p].ns + kNnSeg - 1) / kNnSeg; ++k, ++at) { sum += h_sum[at]; used += h_used[at]; }
+    for (int k = 0; k < (pl.hp[p].ns + kNnSeg - 1) / kNnSeg; ++k, ++at) { sum += h_sum[at]; used += h_used[at]; }
     used_out[p] = (int32_t)used;
     score_out[p] = used > 0 ? sum / (double)used : 1.7976931348623157e308;
+  }
+  return 0;
+}
+
+int sslam_seg_fitness_scores(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_fitness_pair* pairs, int n_pairs,
+                             double* score_out, int32_t* used_out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
+  if (!s || !cloud_start || n_clouds < 0 || n_pairs < 0 || (n_pairs > 0 && (!pairs || !score_out || !used_out)))
+    return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = nn_check_clouds(xyz, cloud_start, n_clouds, pairs, n_pairs);
+  if (rc) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  rc = seg_device(s);
+  if (rc) return rc;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (n_pairs == 0) return 0;
+  NnPlan pl;
+  if ((rc = nn_plan(s, cloud_start, pairs, n_pairs, pl))) return rc;
+  DevGuard g;
+  NnDev d;
+  if ((rc = nn_upload(s, g, pl, xyz, cloud_start[n_clouds], d))) return rc;
+  SSLAM_HIP_TRY(hipEventRecord(s->f_e0, s->stream));
+  if ((rc = nn_search(s, pl, d)) || (rc = nn_finish(s, pl, d, score_out, used_out, nn_index_out, nn_dist2_out, kernel_ms))) return rc;
+  return n_pairs;
+}
+
+// ---- scan matching: nearest-neighbour ICP of cloud pairs (k_nn_pairs, k_reg_sums, k_reg_step; k_nn_finish at the end) ----------------
+int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
+                             int max_iterations, double epsilon, sslam_reg_result* out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
+  if (!s || !cloud_start || n_clouds < 0 || n_pairs < 0 || (n_pairs > 0 && (!pairs || !out)) || max_iterations < 0 || !(epsilon >= 0.0))
+    return set_error(SSLAM_ERR_INVALID, "bad argument");
+  std::vector<sslam_fitness_pair> fp(n_pairs);   // the search reads a pair as the fitness pass does: T = the initial guess, max_range = max_corr2
+  for (int p = 0; p < n_pairs; ++p) {
+    fp[p].target = pairs[p].target; fp[p].source = pairs[p].source; fp[p].max_range = pairs[p].max_corr2;
+    for (int k = 0; k < 12; ++k) fp[p].T[k] = pairs[p].T0[k];
+  }
+  int rc = nn_check_clouds(xyz, cloud_start, n_clouds, fp.data(), n_pairs);
+  if (rc) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  rc = seg_device(s);
+  if (rc) return rc;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (n_pairs == 0) return 0;
+  NnPlan pl;
+  if ((rc = nn_plan(s, cloud_start, fp.data(), n_pairs, pl))) return rc;
+  std::vector<RegState> h_st(n_pairs);
+  std::vector<int> seg0(n_pairs + 1, 0);       // first run of every pair in the partial records
+  for (int p = 0; p < n_pairs; ++p) {
+    RegState& S = h_st[p];
+    for (int k = 0; k < 12; ++k) S.T[k] = pairs[p].T0[k];
+    S.iterations = S.converged = S.status = S.done = 0;
+    seg0[p + 1] = seg0[p] + (pl.hp[p].ns + kNnSeg - 1) / kNnSeg;
+  }
+  DevGuard g;
+  NnDev d;
+  RegState* d_st = nullptr;
+  int *d_seg0 = nullptr, *d_live = nullptr;
+  double* d_part = nullptr;
+  if ((rc = nn_upload(s, g, pl, xyz, cloud_start[n_clouds], d)) || (rc = g.alloc(&d_st, (size_t)n_pairs)) || (rc = g.alloc(&d_seg0, seg0.size())) ||
+      (rc = g.alloc(&d_live, 1)) || (rc = g.alloc(&d_part, pl.segs.size() * kRegSums))) return rc;
+  int live = n_pairs;
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_st, h_st.data(), h_st.size() * sizeof(RegState), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_seg0, seg0.data(), seg0.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_live, &live, sizeof(int), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->f_e0, s->stream));
+  // Iterations in chunks of at most 8, no host round trip inside a chunk; between chunks the number of unfinished pairs comes back.
+  // Every unfinished pair has made the same number of updates, so the cap needs no per-pair count.
+  for (int it = 0; it < max_iterations && live > 0;) {
+    const int n = std::min(8, max_iterations - it);
+    for (int k = 0; k < n; ++k) {
+      if ((rc = nn_search(s, pl, d))) return rc;
+      if (!pl.segs.empty()) hipLaunchKernelGGL(k_reg_sums, dim3((unsigned)pl.segs.size()), dim3(kNnSeg), 0, s->stream, d.xyz, d.pairs, d.segs, d.best, d_st, d_part);
+      hipLaunchKernelGGL(k_reg_step, dim3((unsigned)n_pairs), dim3(64), 0, s->stream, d_seg0, d_part, epsilon, d.pairs, d_st, d_live);
+    }
+    SSLAM_HIP_TRY(hipGetLastError());
+    SSLAM_HIP_TRY(hipMemcpyAsync(&live, d_live, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+    it += n;
+  }
+  // the fitness pass at the estimate the loop ended at: the pair table holds its float casts
+  SSLAM_HIP_TRY(hipMemcpyAsync(h_st.data(), d_st, h_st.size() * sizeof(RegState), hipMemcpyDeviceToHost, s->stream));
+  std::vector<double> score(n_pairs);
+  std::vector<int32_t> used(n_pairs);
+  if ((rc = nn_search(s, pl, d)) || (rc = nn_finish(s, pl, d, score.data(), used.data(), nn_index_out, nn_dist2_out, kernel_ms))) return rc;
+  for (int p = 0; p < n_pairs; ++p) {
+    const RegState& S = h_st[p];
+    for (int k = 0; k < 12; ++k) out[p].T[k] = S.T[k];
+    out[p].score = score[p]; out[p].used = used[p];
+    out[p].iterations = S.iterations; out[p].converged = S.converged; out[p].status = S.status;
   }
   return n_pairs;
 }

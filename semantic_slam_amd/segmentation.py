@@ -79,6 +79,28 @@ class FitnessPair(C.Structure):
     _fields_ = [("target", C.c_int32), ("source", C.c_int32), ("T", C.c_double * 12), ("max_range", C.c_double)]
 
 
+class RegPair(C.Structure):
+    """``sslam_reg_pair`` (include/sslam.h)"""
+    _fields_ = [("target", C.c_int32), ("source", C.c_int32), ("T0", C.c_double * 12), ("max_corr2", C.c_double)]
+
+
+class RegResult(C.Structure):
+    """``sslam_reg_result`` (include/sslam.h)"""
+    _fields_ = [("T", C.c_double * 12), ("score", C.c_double), ("used", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32),
+                ("status", C.c_int32)]
+
+
+@dataclasses.dataclass
+class Registration:
+    """one pair's result of ``PointCloudSegmentation.register_pairs``"""
+    T: np.ndarray                    # 12 doubles: R row-major, then t (source -> target frame)
+    score: float
+    used: int
+    iterations: int
+    converged: int
+    status: int                      # 0, or -4 (SSLAM_ERR_NUMERIC): fewer than 3 correspondences in some pass
+
+
 class InfParams(C.Structure):
     """``sslam_inf_params`` (include/sslam.h)"""
     _fields_ = [("var_gain_a", C.c_double), ("min_stddev_x", C.c_double), ("max_stddev_x", C.c_double), ("min_stddev_q", C.c_double),
@@ -481,6 +503,46 @@ class PointCloudSegmentation:
             return score, used
         cuts = np.cumsum(n_src)[:-1] if n_src else []
         return score, used, list(zip(np.split(idx[:sum(n_src)], cuts), np.split(d2[:sum(n_src)], cuts)))
+
+    def register_pairs(self, clouds, pairs, max_iterations: int = 50, epsilon: float = 0.0, return_nn: bool = False):
+        """``sslam_seg_register_pairs``: nearest-neighbour ICP of several cloud pairs, the whole loop on the device (what
+        LoopDetector::matching does with pcl::IterativeClosestPoint).  ``clouds``: a sequence of [n, 3] float arrays.  ``pairs``:
+        (target, source, T0, max_corr2) with cloud indices, T0 = the initial guess as 12 doubles (R row-major, then t), a 4x4 / 3x4
+        matrix or None (identity), taking the source into the target's frame, max_corr2 a bound on the SQUARED correspondence distance
+        (None: none).  ``epsilon``: a pair has converged when an update moves no entry of T by more than it (0: T repeats bit for bit).
+        Returns one ``Registration`` per pair, with ``return_nn`` also per pair (nearest target index, squared distance) of every source
+        point at the final T.  The hipEvent time of the loop is left in ``last_registration_ms``."""
+        cl = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in clouds]
+        start = np.zeros(len(cl) + 1, np.int32)
+        start[1:] = np.cumsum([len(c) for c in cl])
+        xyz = np.ascontiguousarray(np.concatenate(cl, 0)) if cl else np.zeros((0, 3), np.float32)
+        rec = (RegPair * max(len(pairs), 1))()
+        n_src = []
+        for k, (tgt, src, T0, max_corr2) in enumerate(pairs):
+            T = np.concatenate([np.eye(3).reshape(-1), np.zeros(3)]) if T0 is None else np.asarray(T0, np.float64)
+            if T.shape in ((4, 4), (3, 4)):
+                T = np.concatenate([T[:3, :3].reshape(-1), T[:3, 3]])
+            T = T.reshape(12)
+            rec[k].target, rec[k].source = int(tgt), int(src)
+            for q in range(12):
+                rec[k].T0[q] = T[q]
+            rec[k].max_corr2 = DBL_MAX if max_corr2 is None else float(max_corr2)
+            n_src.append(len(cl[int(src)]) if 0 <= int(src) < len(cl) else 0)
+        res = (RegResult * max(len(pairs), 1))()
+        total = max(int(sum(n_src)), 1)
+        idx = np.zeros(total, np.int32) if return_nn else None
+        d2 = np.zeros(total, np.float32) if return_nn else None
+        ms = C.c_double(0)
+        self._check(self._lib.sslam_seg_register_pairs(self._h, xyz.ctypes.data, start.ctypes.data, len(cl), C.cast(rec, C.c_void_p), len(pairs),
+                                                       int(max_iterations), float(epsilon), C.cast(res, C.c_void_p),
+                                                       idx.ctypes.data if return_nn else None, d2.ctypes.data if return_nn else None, C.byref(ms)))
+        self.last_registration_ms = ms.value
+        out = [Registration(np.array(res[k].T[:], np.float64), res[k].score, res[k].used, res[k].iterations, res[k].converged, res[k].status)
+               for k in range(len(pairs))]
+        if not return_nn:
+            return out
+        cuts = np.cumsum(n_src)[:-1] if n_src else []
+        return out, list(zip(np.split(idx[:sum(n_src)], cuts), np.split(d2[:sum(n_src)], cuts)))
 
     def compute2DConvexHull(self, xyz, seed: int = 0):
         """plane_segmentation::compute2DConvexHull (plane_segmentation.cpp:631-665): RANSAC plane (threshold 0.01, refined

@@ -1,0 +1,178 @@
+"""Scan matching (sslam_seg_register_pairs), the parts that need no GPU: the conditions under which tests/test_registration_gpu.py says
+something, shown on the NumPy reference of tests/registration_ref.py alone, and the contract of the new entry point on a machine
+without a device."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from fitness_ref import DBL_MAX, IDENTITY_T
+from registration_ref import (BOUNDED_MAX_CORR2, COPLANAR, ERR_NUMERIC, MAX_ITERATIONS, SCENES, correspondences, fast_pair, icp_ref, kabsch,
+                              pose_error, scene, step_ref, two_correspondences)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NON_DEGENERATE = [n for n in SCENES if n not in COPLANAR]
+
+
+@pytest.fixture(scope="module")
+def runs():
+    """icp_ref from the identity on every scene: computed once"""
+    return {name: icp_ref(*scene(name)[:2], max_iterations=MAX_ITERATIONS) for name in SCENES}
+
+
+def test_reference_reaches_an_exact_fixed_point_nearer_to_the_truth(runs):
+    for name in SCENES:
+        tg, sr, T_true = scene(name)
+        T, iterations, converged, status = runs[name]
+        e0, e1 = pose_error(IDENTITY_T, T_true), pose_error(T, T_true)
+        print(f"{name}: {iterations} iterations, error {e0[0]:.4f} rad {e0[1]:.4f} m -> {e1[0]:.4f} rad {e1[1]:.4f} m")
+        assert status == 0 and converged == 1 and 3 <= iterations < MAX_ITERATIONS, name
+        again, _ = step_ref(tg, sr, T)
+        assert again.tobytes() == T.tobytes(), name                           # epsilon = 0: T repeats bit for bit
+        assert 0.04 < e0[0] < 0.06 and 0.08 < e0[1] < 0.12, name              # about 0.05 rad and 0.1 m
+        assert e1[0] < e0[0] and e1[1] < e0[1], name
+        R = T[:9].reshape(3, 3)
+        assert abs(np.linalg.det(R) - 1) < 1e-12 and np.abs(R.T @ R - np.eye(3)).max() < 1e-12, name
+
+
+def test_cross_covariance_is_well_conditioned_off_the_planes():
+    for name in NON_DEGENERATE:
+        tg, sr, _ = scene(name)
+        p, q, _ = correspondences(tg, sr, IDENTITY_T)
+        _, _, S = kabsch(p, q)
+        print(name, S / S[0])
+        assert S[1] / S[0] >= 0.1 and S[2] > 1e-3 * S[0], name
+
+
+def test_bounded_distance_case_bites(runs):
+    tg, sr, _ = scene("small")
+    _, _, acc = correspondences(tg, sr, IDENTITY_T, BOUNDED_MAX_CORR2)
+    assert 0.5 * len(sr) <= acc.sum() <= 0.95 * len(sr), acc.mean()
+    T, iterations, converged, status = icp_ref(tg, sr, max_corr2=BOUNDED_MAX_CORR2, max_iterations=MAX_ITERATIONS)
+    assert status == 0 and converged == 1
+    assert np.abs(T - runs["small"][0]).max() > 1e-3
+
+
+def test_coplanar_scenes_need_the_determinant_correction():
+    dets = []
+    for name in COPLANAR:
+        tg, sr, _ = scene(name)
+        p, q, _ = correspondences(tg, sr, IDENTITY_T)
+        H = (p - p.mean(0)).T @ (q - q.mean(0))
+        U, S, Vt = np.linalg.svd(H)
+        assert S[2] <= 1e-12 * S[0] and S[1] >= 0.1 * S[0], (name, S)          # rank 2, and not collinear
+        dets.append(np.linalg.det(Vt.T @ U.T))
+        R, _, _ = kabsch(p, q)
+        assert abs(np.linalg.det(R) - 1) < 1e-12, name
+    print(dets)
+    assert any(d < -0.5 for d in dets)
+
+
+def _one_pass_longdouble(p, q):
+    """the same minimiser from the plain sums n, sum p, sum q, sum p q^T in long double, as the device forms them (uncentred, one pass),
+    and Horn's quaternion through the eigenvectors of the symmetric 4 x 4 (numpy.linalg.eigh) -- neither the centring nor the SVD of
+    step_ref"""
+    pl, ql = p.astype(np.longdouble), q.astype(np.longdouble)
+    n = np.longdouble(len(p))
+    sp, sq = pl.sum(0), ql.sum(0)
+    S = (pl.T @ ql - np.outer(sp, sq) / n).astype(np.float64)
+    N = np.array([[S[0, 0] + S[1, 1] + S[2, 2], S[1, 2] - S[2, 1], S[2, 0] - S[0, 2], S[0, 1] - S[1, 0]],
+                  [S[1, 2] - S[2, 1], S[0, 0] - S[1, 1] - S[2, 2], S[0, 1] + S[1, 0], S[2, 0] + S[0, 2]],
+                  [S[2, 0] - S[0, 2], S[0, 1] + S[1, 0], -S[0, 0] + S[1, 1] - S[2, 2], S[1, 2] + S[2, 1]],
+                  [S[0, 1] - S[1, 0], S[2, 0] + S[0, 2], S[1, 2] + S[2, 1], -S[0, 0] - S[1, 1] + S[2, 2]]])
+    w, V = np.linalg.eigh(N)
+    qw, qx, qy, qz = V[:, 3] / np.linalg.norm(V[:, 3])
+    R = np.array([[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy)],
+                  [2 * (qx * qy + qw * qz), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qw * qx)],
+                  [2 * (qx * qz - qw * qy), 2 * (qy * qz + qw * qx), 1 - 2 * (qx * qx + qy * qy)]])
+    t = (sq / n).astype(np.float64) - R @ (sp / n).astype(np.float64)
+    return np.concatenate([R.reshape(-1), t])
+
+
+def test_step_ref_against_an_independent_evaluation(runs):
+    worst = 0.0
+    for name in SCENES:
+        tg, sr, _ = scene(name)
+        for T in (IDENTITY_T, runs[name][0]):
+            p, q, _ = correspondences(tg, sr, T)
+            Tn, n = step_ref(tg, sr, T)
+            assert n == len(p) >= 3
+            err = float(np.abs(Tn - _one_pass_longdouble(p, q)).max())
+            worst = max(worst, err)
+            assert err <= 1e-12, (name, err)
+    print(f"largest difference {worst:.3e}")
+
+
+def test_edge_case_inputs_behave_on_the_reference(runs):
+    tg, sr, mc = two_correspondences()
+    _, _, acc = correspondences(tg, sr, IDENTITY_T, mc)
+    assert acc.sum() == 2
+    T, iterations, converged, status = icp_ref(tg, sr, max_corr2=mc, max_iterations=MAX_ITERATIONS)
+    assert status == ERR_NUMERIC and iterations == 0 and converged == 0 and T.tobytes() == IDENTITY_T.tobytes()
+    ftg, fsr = fast_pair()
+    _, fast_iterations, fast_converged, _ = icp_ref(ftg, fsr, max_iterations=MAX_ITERATIONS)
+    assert fast_converged == 1 and fast_iterations <= 4
+    assert runs["large"][1] >= fast_iterations + 8                              # the slow pair of the freezing test goes on long after
+
+
+def _reg_pairs(n, target=0, source=0):
+    from semantic_slam_amd.segmentation import RegPair
+    rec = (RegPair * max(n, 1))()
+    for k in range(n):
+        rec[k].target, rec[k].source, rec[k].max_corr2 = target, source, DBL_MAX
+        for q, v in enumerate(IDENTITY_T):
+            rec[k].T0[q] = v
+    return rec
+
+
+def _raw(lib, h, xyz, start, n_clouds, pairs, n_pairs, max_iterations, epsilon, out):
+    return lib.sslam_seg_register_pairs(h, None if xyz is None else xyz.ctypes.data, None if start is None else start.ctypes.data, n_clouds,
+                                        None if pairs is None else C.cast(pairs, C.c_void_p), n_pairs, max_iterations, C.c_double(epsilon),
+                                        None if out is None else C.cast(out, C.c_void_p), None, None, None)
+
+
+def test_argument_checks_come_before_the_device(hip_lib):
+    """every SSLAM_ERR_INVALID case is reported whether or not a device is there"""
+    from semantic_slam_amd.segmentation import PointCloudSegmentation, RegResult
+    seg = PointCloudSegmentation()
+    xyz = np.random.default_rng(0).normal(size=(90, 3)).astype(np.float32)
+    start = np.array([0, 40, 90], np.int32)
+    out = (RegResult * 2)()
+    good = _reg_pairs(2, 0, 1)
+    bad = [dict(pairs=_reg_pairs(1, 0, 2), n_pairs=1), dict(pairs=_reg_pairs(1, -1, 0), n_pairs=1),      # a cloud index out of range
+           dict(start=np.array([0, 50, 40], np.int32)), dict(start=np.array([-1, 40, 90], np.int32)),  # cloud_start decreases / starts below 0
+           dict(n_pairs=-1), dict(n_clouds=-1), dict(xyz=None), dict(start=None), dict(pairs=None), dict(out=None), dict(h=None),
+           dict(max_iterations=-1), dict(epsilon=-1e-9), dict(epsilon=float("nan"))]
+    for kw in bad:
+        a = dict(h=seg._h, xyz=xyz, start=start, n_clouds=2, pairs=good, n_pairs=2, max_iterations=5, epsilon=0.0, out=out)
+        a.update(kw)
+        assert _raw(hip_lib, **a) == -1, kw
+    assert all(out[k].iterations == 0 and out[k].used == 0 and out[k].T[0] == 0.0 for k in range(2))     # nothing was written
+    rc = _raw(hip_lib, seg._h, xyz, start, 2, good, 2, 5, 0.0, out)
+    assert rc == (2 if hip_lib.sslam_device_count() > 0 else -2)
+
+
+def test_contract_without_a_device(hip_lib):
+    if hip_lib.sslam_device_count() > 0:
+        pytest.skip("a GPU is visible here; the loud-failure path is for CPU-only boxes")
+    from semantic_slam_amd import SslamError
+    from semantic_slam_amd.segmentation import PointCloudSegmentation
+    seg = PointCloudSegmentation()
+    pts = np.random.default_rng(0).normal(size=(50, 3)).astype(np.float32)
+    with pytest.raises(SslamError) as ei:
+        seg.register_pairs([pts, pts], [(0, 1, None, None)], max_iterations=3)
+    assert ei.value.code == -2 and "no CPU fallback" in str(ei.value)
+    with pytest.raises(SslamError) as ei:                                       # n_pairs = 0 still looks for the device, as the fitness call does
+        seg.register_pairs([pts], [])
+    assert ei.value.code == -2
+
+
+def test_symbol_is_exported_and_declared(hip_lib):
+    from semantic_slam_amd.segmentation import RegPair, RegResult
+    hdr = open(os.path.join(ROOT, "include", "sslam.h")).read()
+    assert re.search(r"\bint sslam_seg_register_pairs\s*\(", hdr) and "typedef struct sslam_reg_pair" in hdr and "typedef struct sslam_reg_result" in hdr
+    fn = hip_lib.sslam_seg_register_pairs                                       # AttributeError if the library does not export it
+    assert fn.restype is C.c_int and len(fn.argtypes) == 12                     # declared by semantic_slam_amd._lib.load_library
+    assert C.sizeof(RegPair) == 8 + 12 * 8 + 8 and C.sizeof(RegResult) == 12 * 8 + 8 + 4 * 4
