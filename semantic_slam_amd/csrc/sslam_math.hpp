@@ -308,4 +308,41 @@ SSLAM_HD void horn_rigid(double n, double px, double py, double pz, double qx, d
   T[9] = t.x; T[10] = t.y; T[11] = t.z;
 }
 
+// ---- point-to-plane ICP (sslam_seg_icp_point_to_plane on the host, k_icp_frame_step on the device) -----------------------------------
+// One Gauss-Newton step from the 29 sums of a pass: J^T J (upper triangle by rows, 21), J^T r (6), r^2, the point count.
+// (J^T J) delta = -J^T r by Cholesky, two triangular solves, then T <- (exp[w]x, u) o T with Rodrigues' formula; T: R row-major, then
+// t.  Returns false and leaves T alone when the system is rank deficient (planes with fewer than three independent normals leave the
+// transform free along some direction).
+SSLAM_HD bool icp_gn_step(const double sums[29], double T[12]) {
+  double A[36], bvec[6], L[36];
+  for (int k = 0; k < 36; ++k) L[k] = 0;
+  int m = 0;
+  for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { A[r * 6 + c] = A[c * 6 + r] = sums[m++]; }
+  for (int r = 0; r < 6; ++r) bvec[r] = -sums[21 + r];
+  for (int j = 0; j < 6; ++j) {
+    double dsum = A[j * 6 + j];
+    for (int k = 0; k < j; ++k) dsum -= L[j * 6 + k] * L[j * 6 + k];
+    if (!(dsum > 1e-12 * A[j * 6 + j]) || !(dsum > 0)) return false;
+    L[j * 6 + j] = sqrt(dsum);
+    for (int i = j + 1; i < 6; ++i) { double v = A[i * 6 + j]; for (int k = 0; k < j; ++k) v -= L[i * 6 + k] * L[j * 6 + k]; L[i * 6 + j] = v / L[j * 6 + j]; }
+  }
+  double y[6], dx[6];
+  for (int i = 0; i < 6; ++i) { double v = bvec[i]; for (int k = 0; k < i; ++k) v -= L[i * 6 + k] * y[k]; y[i] = v / L[i * 6 + i]; }
+  for (int i = 5; i >= 0; --i) { double v = y[i]; for (int k = i + 1; k < 6; ++k) v -= L[k * 6 + i] * dx[k]; dx[i] = v / L[i * 6 + i]; }
+  const double wx = dx[0], wy = dx[1], wz = dx[2], th = sqrt(wx * wx + wy * wy + wz * wz);
+  double E[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (th > 0) {
+    const double sa = sin(th) / th, bq = (1.0 - cos(th)) / (th * th);
+    const double K[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { double kk = 0; for (int q = 0; q < 3; ++q) kk += K[r * 3 + q] * K[q * 3 + c]; E[r * 3 + c] += sa * K[r * 3 + c] + bq * kk; }
+  }
+  double Tn[12];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) Tn[r * 3 + c] = E[r * 3] * T[c] + E[r * 3 + 1] * T[3 + c] + E[r * 3 + 2] * T[6 + c];
+    Tn[9 + r] = E[r * 3] * T[9] + E[r * 3 + 1] * T[10] + E[r * 3 + 2] * T[11] + dx[3 + r];
+  }
+  for (int k = 0; k < 12; ++k) T[k] = Tn[k];
+  return true;
+}
+
 }  // namespace sslam

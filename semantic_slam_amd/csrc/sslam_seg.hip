@@ -1116,33 +1116,58 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
 __device__ __forceinline__ bool plane_inlier(const float* m, const float* p, float thr) {
   return fabsf(m[0] * p[0] + m[1] * p[1] + m[2] * p[2] + m[3]) < thr;
 }
+// One hypothesis: the sample triple of (seed, iter) -- the first attempt whose three indices differ and whose points pass PCL's
+// collinearity test -- and the unit-normal plane through it.  m: the model (zeros if no attempt gave a sample); returns whether a
+// sample was found and its model is finite.
+__device__ __forceinline__ bool ransac_draw(const float* P, int n, unsigned long long seed, int iter, float* m) {
+  float m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+  int good = 0;
+  for (int attempt = 0; attempt < 1000 && !good; ++attempt) {
+    int id[3];
+    for (int j = 0; j < 3; ++j)
+      id[j] = (int)(splitmix64(seed ^ ((unsigned long long)iter << 32) ^ ((unsigned long long)attempt << 8) ^ (unsigned long long)j) % (unsigned long long)n);
+    if (id[0] == id[1] || id[0] == id[2] || id[1] == id[2]) continue;
+    const float* p0 = P + (size_t)id[0] * 3; const float* p1 = P + (size_t)id[1] * 3; const float* p2 = P + (size_t)id[2] * 3;
+    const float a0 = p1[0] - p0[0], a1 = p1[1] - p0[1], a2 = p1[2] - p0[2];
+    const float b0 = p2[0] - p0[0], b1 = p2[1] - p0[1], b2 = p2[2] - p0[2];
+    const float r0 = a0 / b0, r1 = a1 / b1, r2 = a2 / b2;
+    if (!((r0 != r1) || (r2 != r1))) continue;
+    m0 = a1 * b2 - a2 * b1; m1 = a2 * b0 - a0 * b2; m2 = a0 * b1 - a1 * b0;
+    const float nn = sqrtf(m0 * m0 + m1 * m1 + m2 * m2);
+    m0 /= nn; m1 /= nn; m2 /= nn;
+    m3 = -1 * (m0 * p0[0] + m1 * p0[1] + m2 * p0[2]);
+    good = 2;   // a sample was found (whether or not its model is finite)
+  }
+  m[0] = m0; m[1] = m1; m[2] = m2; m[3] = m3;
+  return (good == 2) && isfinite(m0) && isfinite(m3);
+}
+// pcl::RandomSampleConsensus::computeModel's adaptive loop, one hypothesis at a time, over the state (k, iterations, skipped, best):
+// the loop goes on while ransac_loop_open; ransac_loop_take consumes a hypothesis with `count` inliers (< 0: no valid sample) out of
+// 1 / one_over_n points and says whether it is the best so far.  Used by the host replay of sslam_seg_ransac_plane and by k_ransac_hyp.
+SSLAM_HD bool ransac_loop_open(double k, int iterations, int skipped, int max_iterations) {
+  return (double)iterations < k && skipped < max_iterations * 10 && iterations <= max_iterations;
+}
+SSLAM_HD bool ransac_loop_take(int count, double one_over_n, double log_probability, double& k, int& iterations, int& skipped, int& best) {
+  if (count < 0) { ++skipped; return false; }
+  const bool better = count > best;
+  if (better) {
+    best = count;
+    const double w = (double)count * one_over_n, eps = 2.220446049250313e-16;
+    double p_no = 1.0 - pow(w, 3.0);
+    if (p_no < eps) p_no = eps;
+    if (p_no > 1.0 - eps) p_no = 1.0 - eps;
+    k = log_probability / log(p_no);
+  }
+  ++iterations;
+  return better;
+}
 __global__ __launch_bounds__(256) void k_ransac_score(const float* __restrict__ pts, int n, float thr, unsigned long long seed,
                                                      float* __restrict__ models, int* __restrict__ counts) {
   __shared__ float m[4];
   __shared__ int ok;
   __shared__ int wsum[4];
   const int iter = blockIdx.x;
-  if (threadIdx.x == 0) {
-    int good = 0;
-    for (int attempt = 0; attempt < 1000 && !good; ++attempt) {
-      int id[3];
-      for (int j = 0; j < 3; ++j)
-        id[j] = (int)(splitmix64(seed ^ ((unsigned long long)iter << 32) ^ ((unsigned long long)attempt << 8) ^ (unsigned long long)j) % (unsigned long long)n);
-      if (id[0] == id[1] || id[0] == id[2] || id[1] == id[2]) continue;
-      const float* p0 = pts + (size_t)id[0] * 3; const float* p1 = pts + (size_t)id[1] * 3; const float* p2 = pts + (size_t)id[2] * 3;
-      const float a0 = p1[0] - p0[0], a1 = p1[1] - p0[1], a2 = p1[2] - p0[2];
-      const float b0 = p2[0] - p0[0], b1 = p2[1] - p0[1], b2 = p2[2] - p0[2];
-      const float r0 = a0 / b0, r1 = a1 / b1, r2 = a2 / b2;
-      if (!((r0 != r1) || (r2 != r1))) continue;
-      float m0 = a1 * b2 - a2 * b1, m1 = a2 * b0 - a0 * b2, m2 = a0 * b1 - a1 * b0;
-      const float nn = sqrtf(m0 * m0 + m1 * m1 + m2 * m2);
-      m0 /= nn; m1 /= nn; m2 /= nn;
-      m[0] = m0; m[1] = m1; m[2] = m2;
-      m[3] = -1 * (m0 * p0[0] + m1 * p0[1] + m2 * p0[2]);
-      good = 2;   // a sample was found (whether or not its model is finite)
-    }
-    ok = (good == 2) && isfinite(m[0]) && isfinite(m[3]);
-  }
+  if (threadIdx.x == 0) ok = ransac_draw(pts, n, seed, iter, m);
   __syncthreads();
   int cnt = 0;
   if (ok)
@@ -1156,42 +1181,51 @@ __global__ __launch_bounds__(256) void k_ransac_score(const float* __restrict__ 
     models[iter * 4 + 0] = m[0]; models[iter * 4 + 1] = m[1]; models[iter * 4 + 2] = m[2]; models[iter * 4 + 3] = m[3];
   }
 }
-// ordered inlier list of one model: per-block counts -> offsets -> indices (index order = PCL's)
-__global__ __launch_bounds__(256) void k_ransac_mark(const float* __restrict__ pts, int n, float thr, const float* __restrict__ model,
-                                                    int* __restrict__ block_counts) {
+// ---- ordered compaction: the i in [0, n) that a predicate keeps, in ascending order (PCL's index order) ------------------------------
+// k_count_if (kept per block of 256) -> k_exclusive_scan -> k_write_if (every kept i learns its position from the block's offset and
+// wave ballots).  A predicate is a small struct passed by value: keep(i) decides, put(pos, i) emits.  compact_if on the host launches
+// the three.
+template <class Pred>
+__global__ __launch_bounds__(256) void k_count_if(Pred pred, int n, int* __restrict__ block_counts) {
   __shared__ int wsum[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const float m[4] = {model[0], model[1], model[2], model[3]};
-  int c = (i < n && plane_inlier(m, pts + (size_t)i * 3, thr)) ? 1 : 0;
+  int c = (i < n && pred.keep(i)) ? 1 : 0;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
-__global__ void k_ransac_scan(int* block_counts, int nblocks, int* total) {   // exclusive scan by one thread (nblocks is small)
+// exclusive scan by one thread (nblocks is small); off may be counts itself
+__global__ void k_exclusive_scan(const int* counts, int nblocks, int* off, int* total) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   int acc = 0;
-  for (int b = 0; b < nblocks; ++b) { const int c = block_counts[b]; block_counts[b] = acc; acc += c; }
+  for (int b = 0; b < nblocks; ++b) { const int c = counts[b]; off[b] = acc; acc += c; }
   *total = acc;
 }
-__global__ __launch_bounds__(256) void k_ransac_write(const float* __restrict__ pts, int n, float thr, const float* __restrict__ model,
-                                                     const int* __restrict__ block_off, int* __restrict__ inliers, int max_inliers) {
+template <class Pred>
+__global__ __launch_bounds__(256) void k_write_if(Pred pred, int n, const int* __restrict__ block_off) {
   __shared__ int woff[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const float m[4] = {model[0], model[1], model[2], model[3]};
-  const bool in = i < n && plane_inlier(m, pts + (size_t)i * 3, thr);
+  const bool in = i < n && pred.keep(i);
   const unsigned long long mask = __ballot(in);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) woff[wave] = __popcll(mask);
   __syncthreads();
   int base = block_off[blockIdx.x];
   for (int w = 0; w < wave; ++w) base += woff[w];
-  if (in) {
-    const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-    if (pos < max_inliers) inliers[pos] = i;
-  }
+  if (in) pred.put(base + __popcll(mask & ((1ull << lane) - 1ull)), i);
 }
+struct FlagPred {      // set flags -> their indices
+  const unsigned char* flag; int* out; int max_out;
+  __device__ bool keep(int i) const { return flag[i]; }
+  __device__ void put(int pos, int i) const { if (pos < max_out) out[pos] = i; }
+};
+struct InlierPred {    // inliers of one plane model -> their indices
+  const float* pts; const float* model; float thr; int* out; int max_out;
+  __device__ bool keep(int i) const { const float m[4] = {model[0], model[1], model[2], model[3]}; return plane_inlier(m, pts + (size_t)i * 3, thr); }
+  __device__ void put(int pos, int i) const { if (pos < max_out) out[pos] = i; }
+};
 // ---- a15, second half: pcl::ProjectInliers (plane) + 2-D pcl::ConvexHull (plane_segmentation.cpp:648-662) ---------
 // projectPoints: mc = (a, b, c, 0) normalised in float, dist = mc . p + d (d is not rescaled, as in PCL), p' = p - mc dist
 __global__ __launch_bounds__(256) void k_hull_project(const float* __restrict__ pts, const int* __restrict__ inliers, int n_in,
@@ -1302,33 +1336,11 @@ __device__ __forceinline__ bool hull_keep(const double* __restrict__ ext, float 
   }
   return !(inside && edges >= 3);
 }
-__global__ __launch_bounds__(256) void k_hull_mark(const float* __restrict__ px, const float* __restrict__ py, int n_in, const double* __restrict__ ext,
-                                                  int* __restrict__ block_counts) {
-  __shared__ int wsum[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  int c = (i < n_in && hull_keep(ext, px[i], py[i])) ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-__global__ __launch_bounds__(256) void k_hull_write(const float* __restrict__ px, const float* __restrict__ py, int n_in, const double* __restrict__ ext,
-                                                   const int* __restrict__ block_off, float* __restrict__ cx, float* __restrict__ cy, int* __restrict__ ci) {
-  __shared__ int woff[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool in = i < n_in && hull_keep(ext, px[i], py[i]);
-  const unsigned long long mask = __ballot(in);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) woff[wave] = __popcll(mask);
-  __syncthreads();
-  int base = block_off[blockIdx.x];
-  for (int w = 0; w < wave; ++w) base += woff[w];
-  if (in) {
-    const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-    cx[pos] = px[i]; cy[pos] = py[i]; ci[pos] = i;
-  }
-}
+struct HullPred {      // points not strictly inside the octagon -> (x, y, index) candidates
+  const float* px; const float* py; const double* ext; float* cx; float* cy; int* ci;
+  __device__ bool keep(int i) const { return hull_keep(ext, px[i], py[i]); }
+  __device__ void put(int pos, int i) const { cx[pos] = px[i]; cy[pos] = py[i]; ci[pos] = i; }
+};
 // One workgroup per chunk of <= kHullCap candidates: bitonic sort by (x, y, index) in LDS, Andrew's monotone chain by
 // one thread (strict turns, duplicates keep the lowest index).  FINAL: counter-clockwise polygon rotated to start at the
 // vertex of smallest angle about the (double mean -> float) vertex centroid, indices only.  Otherwise the chunk's hull
@@ -1417,14 +1429,24 @@ __global__ __launch_bounds__(256) void k_hull_compact(const float* __restrict__ 
   const int c = blockIdx.x, n = counts[c], o = off[c];
   for (int k = threadIdx.x; k < n; k += 256) { cx[o + k] = ox[c * kHullCap + k]; cy[o + k] = oy[c * kHullCap + k]; ci[o + k] = oi[c * kHullCap + k]; }
 }
-__global__ void k_hull_scan(const int* __restrict__ counts, int nchunks, int* __restrict__ off, int* __restrict__ total) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  int acc = 0;
-  for (int c = 0; c < nchunks; ++c) { off[c] = acc; acc += counts[c]; }
-  *total = acc;
-}
 
-// optimizeModelCoefficients: float mean / covariance of the inliers in index order + eigen33 (one wave)
+// optimizeModelCoefficients' last step: the inliers' sums of xx, xy, xz, yy, yz, zz, x, y, z (float, added in index order) -> means,
+// covariance, the eigenvector of its smallest eigenvalue as the normal, d = -n . mean
+__device__ __forceinline__ void plane_from_moments(const float* sum, int count, float* model) {
+  float a[9];
+  const float cf = (float)count;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) a[q] = sum[q] / cf;
+  float cov[9];
+  cov[0] = a[0] - a[6] * a[6]; cov[1] = a[1] - a[6] * a[7]; cov[2] = a[2] - a[6] * a[8];
+  cov[4] = a[3] - a[7] * a[7]; cov[5] = a[4] - a[7] * a[8]; cov[8] = a[5] - a[8] * a[8];
+  cov[3] = cov[1]; cov[6] = cov[2]; cov[7] = cov[5];
+  float ev, v[3];
+  eigen33(cov, ev, v);
+  model[0] = v[0]; model[1] = v[1]; model[2] = v[2];
+  model[3] = -1 * (v[0] * a[6] + v[1] * a[7] + v[2] * a[8]);
+}
+// optimizeModelCoefficients: float sums over the inliers in index order + plane_from_moments (one wave)
 __global__ __launch_bounds__(64) void k_ransac_refit(const float* __restrict__ pts, const int* __restrict__ inliers, const int* __restrict__ total,
                                                     float* __restrict__ model) {
   __shared__ float prod[64][9];
@@ -1447,19 +1469,7 @@ __global__ __launch_bounds__(64) void k_ransac_refit(const float* __restrict__ p
   float a[9];
 #pragma unroll
   for (int q = 0; q < 9; ++q) a[q] = __shfl(acc, q, 64);
-  if (lane == 0) {
-    const float cf = (float)cntN;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) a[q] = a[q] / cf;
-    float cov[9];
-    cov[0] = a[0] - a[6] * a[6]; cov[1] = a[1] - a[6] * a[7]; cov[2] = a[2] - a[6] * a[8];
-    cov[4] = a[3] - a[7] * a[7]; cov[5] = a[4] - a[7] * a[8]; cov[8] = a[5] - a[8] * a[8];
-    cov[3] = cov[1]; cov[6] = cov[2]; cov[7] = cov[5];
-    float ev, v[3];
-    eigen33(cov, ev, v);
-    model[0] = v[0]; model[1] = v[1]; model[2] = v[2];
-    model[3] = -1 * (v[0] * a[6] + v[1] * a[7] + v[2] * a[8]);
-  }
+  if (lane == 0) plane_from_moments(a, cntN, model);
 }
 
 // final label image for the parity hook: region index or -1
@@ -1476,10 +1486,43 @@ __global__ __launch_bounds__(256) void k_label_image(View V, int box, int* out) 
 // reference tree) -------------------------------------------------------------------------------------------------------------------
 // One Gauss-Newton round: every labelled point q = R p + t contributes, for its plane (n, d),
 //   r = n . q + d,   J = [ (q x n)^T  n^T ]      (update  T <- (exp[w]x, u) o T,  d r / d w = q x n,  d r / d u = n)
-// to  J^T J (21 values), J^T r (6), r^2 and the point count: 29 double sums, reduced per workgroup in a fixed order (wave shuffles,
-// then the waves in order) -> partial[block][29]; the host adds the blocks in order and solves the 6 x 6 system.
-struct IcpPose { double R[9]; double t[3]; };
+// to  J^T J (21 values), J^T r (6), r^2 and the point count (icp_add_point): 29 double sums, reduced per workgroup in a fixed order
+// (block_sum4) -> partial[block][29]; the host adds the blocks in order and takes the step (icp_gn_step, csrc/sslam_math.hpp).
+struct IcpPose { double T[12]; };   // R row-major, then t
 constexpr int kIcpSums = 29;
+// the contribution of point p (skipped unless finite) measured against plane (n, d) under the transform (R, t)
+__device__ __forceinline__ void icp_add_point(const double* R, const double* t, const float* p, double nx, double ny, double nz, double d,
+                                              double (&a)[kIcpSums]) {
+  const double px = p[0], py = p[1], pz = p[2];
+  if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return;
+  const double qx = R[0] * px + R[1] * py + R[2] * pz + t[0];
+  const double qy = R[3] * px + R[4] * py + R[5] * pz + t[1];
+  const double qz = R[6] * px + R[7] * py + R[8] * pz + t[2];
+  const double r = nx * qx + ny * qy + nz * qz + d;
+  const double J[6] = {qy * nz - qz * ny, qz * nx - qx * nz, qx * ny - qy * nx, nx, ny, nz};
+  int m = 0;
+#pragma unroll
+  for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+    for (int cc = rr; cc < 6; ++cc) a[m++] += J[rr] * J[cc];
+#pragma unroll
+  for (int rr = 0; rr < 6; ++rr) a[21 + rr] += J[rr] * r;
+  a[27] += r * r;
+  a[28] += 1.0;
+}
+// a[K] summed over a 256-thread workgroup in a fixed order -- the shuffle tree of each wave, then the four waves in order -- into out[K]
+template <int K>
+__device__ __forceinline__ void block_sum4(const double (&a)[K], double (&red)[4][K], double* __restrict__ out) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    double v = a[k];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6][k] = v;
+  }
+  __syncthreads();
+  if (tid < K) out[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
 __global__ __launch_bounds__(256) void k_icp_accumulate(const float* __restrict__ xyz, const int* __restrict__ lab, int n,
                                                         const float* __restrict__ planes, int n_planes, IcpPose T, double* __restrict__ partial) {
   __shared__ double red[4][kIcpSums];
@@ -1489,33 +1532,9 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const float* __restrict_
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const int k = lab[i];
     if (k < 0 || k >= n_planes) continue;
-    const double px = xyz[3 * (size_t)i], py = xyz[3 * (size_t)i + 1], pz = xyz[3 * (size_t)i + 2];
-    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) continue;
-    const double qx = T.R[0] * px + T.R[1] * py + T.R[2] * pz + T.t[0];
-    const double qy = T.R[3] * px + T.R[4] * py + T.R[5] * pz + T.t[1];
-    const double qz = T.R[6] * px + T.R[7] * py + T.R[8] * pz + T.t[2];
-    const double nx = planes[4 * k], ny = planes[4 * k + 1], nz = planes[4 * k + 2], d = planes[4 * k + 3];
-    const double r = nx * qx + ny * qy + nz * qz + d;
-    const double J[6] = {qy * nz - qz * ny, qz * nx - qx * nz, qx * ny - qy * nx, nx, ny, nz};
-    int m = 0;
-#pragma unroll
-    for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-      for (int cc = rr; cc < 6; ++cc) a[m++] += J[rr] * J[cc];
-#pragma unroll
-    for (int rr = 0; rr < 6; ++rr) a[21 + rr] += J[rr] * r;
-    a[27] += r * r;
-    a[28] += 1.0;
+    icp_add_point(T.T, T.T + 9, xyz + 3 * (size_t)i, planes[4 * k], planes[4 * k + 1], planes[4 * k + 2], planes[4 * k + 3], a);
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kIcpSums; ++k) {
-    double v = a[k];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kIcpSums) partial[(size_t)blockIdx.x * kIcpSums + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+  block_sum4(a, red, partial + (size_t)blockIdx.x * kIcpSums);
 }
 
 
@@ -1524,22 +1543,23 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(const float* __restrict_
 // the only RANSAC hook upstream is compute2DConvexHull, plane_segmentation.cpp:631-665) -------------------------------------------------
 // One workgroup per box.  The box's cropped cloud (w x h points in crop order, invalid points included: they are never inliers and a
 // sample that hits one is a bad sample) is staged in LDS once -- 12 bytes per point read from HBM once -- and every hypothesis is scored
-// out of LDS: sixteen hypotheses at a time, one wave each (lane 0 draws the sample with the counter hash of the single-cloud entry
-// point, the wave counts inliers with a point per lane), then one thread replays pcl::RandomSampleConsensus' adaptive loop over the
-// sixteen counts in order and stops the box as soon as the sequential algorithm would have stopped.  optimizeModelCoefficients needs
-// float sums over the inliers IN INDEX ORDER: the points are walked 1024 at a time, every inlier gets its rank from wave ballots and
-// parks its nine products in LDS, nine lanes add them in rank order -- the arithmetic of oracle_seg.c's serial loop, bit for bit.
+// out of LDS: sixteen hypotheses at a time, one wave each (lane 0 draws the sample with ransac_draw, as the single-cloud entry
+// point does, the wave counts inliers with a point per lane), then one thread runs pcl::RandomSampleConsensus' adaptive loop
+// (ransac_loop_open / ransac_loop_take) over the sixteen counts in order and stops the box as soon as the sequential algorithm would
+// have stopped.  optimizeModelCoefficients needs float sums over the inliers IN INDEX ORDER: the points are walked 1024 at a time,
+// every inlier gets its rank from wave ballots and parks its nine products in LDS, nine lanes add them in rank order -- the arithmetic
+// of oracle_seg.c's serial loop, bit for bit.
 struct RansacBox { float coeff[4]; int inliers, best_count, best_iter, hyps; };
 // Round 6: two kernels.  (PMC, profiles/r6_pmc_frontend.json: the one-kernel form spent 85 % of its wave cycles parked -- nine lanes added
 // the inliers' products one LDS round trip at a time while fifteen waves and a 147 KB crop waited, one box per CU.)
 //   k_ransac_hyp      one 1024-thread workgroup per box, the crop staged in LDS once.  A round draws up to sixteen samples (one wave each, lane
-//                     0, the counter hash of the single-cloud entry point), then ONE pass over the points scores all of them: a thread keeps the
+//                     0, ransac_draw), then ONE pass over the points scores all of them: a thread keeps the
 //                     round's models in registers and tests each of its points against every model -- three LDS reads per point instead of
 //                     three per point and hypothesis.  Thread 0 replays pcl::RandomSampleConsensus' adaptive loop over the counts in order and
 //                     stops where the sequential algorithm stops (rounds after the first draw eight samples: the scene's boxes stop at 17).
 //   k_ransac_refine   one 256-thread workgroup per box, eight per CU: optimizeModelCoefficients' float sums over the inliers IN INDEX ORDER
 //                     (ranks from wave ballots, nine products parked in LDS, nine lanes add them in rank order, sixteen loads in flight ahead of
-//                     the dependent adds) -- the arithmetic of oracle_seg.c's serial loop, bit for bit --, eigen33, then the inlier flags of the
+//                     the dependent adds) -- the arithmetic of oracle_seg.c's serial loop, bit for bit --, plane_from_moments, then the inlier flags of the
 //                     refined model.  The chains of eight boxes overlap on a CU; the points come through L2.
 constexpr int kRsProd = 256;   // inlier products parked per round of the ordered sums
 constexpr int kRsHyp = 16;     // hypotheses of the first round of a box (later rounds: kRsHyp / 2)
@@ -1573,32 +1593,11 @@ __global__ __launch_bounds__(1024) void k_ransac_hyp(View V, float thr, int max_
   // the adaptive loop's state lives in thread 0
   double k = 1.0;
   int iterations = 0, skipped = 0;
-  const int max_skip = max_iterations * 10;
-  const double log_probability = log(1.0 - probability), one_over = 1.0 / (double)n, eps = 2.220446049250313e-16;
+  const double log_probability = log(1.0 - probability), one_over = 1.0 / (double)n;
   int nh = kRsHyp;
   while (!s_stop) {
     if (wave < nh && lane == 0) {
-      const int iter = s_it + wave;
-      float m0 = 0, m1 = 0, m2 = 0, m3 = 0;
-      int good = 0;
-      for (int attempt = 0; attempt < 1000 && !good; ++attempt) {
-        int id[3];
-        for (int j = 0; j < 3; ++j)
-          id[j] = (int)(splitmix64(seed ^ ((unsigned long long)iter << 32) ^ ((unsigned long long)attempt << 8) ^ (unsigned long long)j) % (unsigned long long)n);
-        if (id[0] == id[1] || id[0] == id[2] || id[1] == id[2]) continue;
-        const float* p0 = P + (size_t)id[0] * 3; const float* p1 = P + (size_t)id[1] * 3; const float* p2 = P + (size_t)id[2] * 3;
-        const float a0 = p1[0] - p0[0], a1 = p1[1] - p0[1], a2 = p1[2] - p0[2];
-        const float b0 = p2[0] - p0[0], b1 = p2[1] - p0[1], b2 = p2[2] - p0[2];
-        const float r0 = a0 / b0, r1 = a1 / b1, r2 = a2 / b2;
-        if (!((r0 != r1) || (r2 != r1))) continue;
-        m0 = a1 * b2 - a2 * b1; m1 = a2 * b0 - a0 * b2; m2 = a0 * b1 - a1 * b0;
-        const float nn = sqrtf(m0 * m0 + m1 * m1 + m2 * m2);
-        m0 /= nn; m1 /= nn; m2 /= nn;
-        m3 = -1 * (m0 * p0[0] + m1 * p0[1] + m2 * p0[2]);
-        good = 2;
-      }
-      s_ok[wave] = (good == 2) && isfinite(m0) && isfinite(m3);
-      s_models[wave][0] = m0; s_models[wave][1] = m1; s_models[wave][2] = m2; s_models[wave][3] = m3;
+      s_ok[wave] = ransac_draw(P, n, seed, s_it + wave, s_models[wave]);
       s_cnt[wave] = 0;
     }
     __syncthreads();
@@ -1638,23 +1637,14 @@ __global__ __launch_bounds__(1024) void k_ransac_hyp(View V, float thr, int max_
     if (tid == 0) {   // pcl::RandomSampleConsensus::computeModel over these hypotheses, in order
       int stop = 0;
       for (int j = 0; j < nh; ++j) {
-        if (!((double)iterations < k && skipped < max_skip)) { stop = 1; break; }
-        const int c = s_ok[j] ? s_cnt[j] : -1;
-        ++s_it;
-        if (c < 0) { ++skipped; continue; }
-        if (c > s_best_n) {
-          s_best_n = c; s_best_it = s_it - 1;
+        if (!ransac_loop_open(k, iterations, skipped, max_iterations)) { stop = 1; break; }
+        if (ransac_loop_take(s_ok[j] ? s_cnt[j] : -1, one_over, log_probability, k, iterations, skipped, s_best_n)) {
+          s_best_it = s_it;
           s_best[0] = s_models[j][0]; s_best[1] = s_models[j][1]; s_best[2] = s_models[j][2]; s_best[3] = s_models[j][3];
-          const double w = (double)c * one_over;
-          double p_no = 1.0 - pow(w, 3.0);
-          if (p_no < eps) p_no = eps;
-          if (p_no > 1.0 - eps) p_no = 1.0 - eps;
-          k = log_probability / log(p_no);
         }
-        ++iterations;
-        if (iterations > max_iterations) { stop = 1; break; }
+        ++s_it;
       }
-      s_stop = stop;
+      s_stop = stop || iterations > max_iterations;
     }
     nh = kRsHyp / 2;
     __syncthreads();
@@ -1715,20 +1705,7 @@ __global__ __launch_bounds__(256) void k_ransac_refine(View V, float thr, Ransac
     }
     if (tid < 9) s_acc[tid] = acc;
     __syncthreads();
-    if (tid == 0) {
-      float a[9];
-      const float cf = (float)total;
-#pragma unroll
-      for (int q = 0; q < 9; ++q) a[q] = s_acc[q] / cf;
-      float cov[9];
-      cov[0] = a[0] - a[6] * a[6]; cov[1] = a[1] - a[6] * a[7]; cov[2] = a[2] - a[6] * a[8];
-      cov[4] = a[3] - a[7] * a[7]; cov[5] = a[4] - a[7] * a[8]; cov[8] = a[5] - a[8] * a[8];
-      cov[3] = cov[1]; cov[6] = cov[2]; cov[7] = cov[5];
-      float ev, v[3];
-      eigen33(cov, ev, v);
-      s_best[0] = v[0]; s_best[1] = v[1]; s_best[2] = v[2];
-      s_best[3] = -1 * (v[0] * a[6] + v[1] * a[7] + v[2] * a[8]);
-    }
+    if (tid == 0) plane_from_moments(s_acc, total, s_best);
     __syncthreads();
     model[0] = s_best[0]; model[1] = s_best[1]; model[2] = s_best[2]; model[3] = s_best[3];
   }
@@ -1755,15 +1732,16 @@ __global__ __launch_bounds__(256) void k_ransac_refine(View V, float thr, Ransac
 //                     a thread's points in index order, wave shuffles, the waves in order) -> part[box][29]
 //   k_icp_frame_step  one wave per FRAME: the boxes' partial sums in slot order, the 6 x 6 Cholesky solve and T <- (exp[w]x, u) o T by
 //                     lane 0; a frame that is finished (last pass, < 6 points, rank-deficient plane set) is frozen by its flag
-// -- 2 (iterations + 1) launches of a few microseconds for ALL frames, still no host round trip per iteration.  Same arithmetic per point
-// as k_icp_accumulate + the host solve of sslam_seg_icp_point_to_plane; only the order of the sums differs.
+// -- 2 (iterations + 1) launches of a few microseconds for ALL frames, still no host round trip per iteration.  The point's row is
+// icp_add_point and the step is icp_gn_step (csrc/sslam_math.hpp), the ones of k_icp_accumulate and sslam_seg_icp_point_to_plane; only
+// the order of the sums differs.
 struct IcpFrame { double T[12]; double rms; int used, status; };
 struct IcpState { double T[12]; int status, done, pad0, pad1; };
 __global__ __launch_bounds__(256) void k_icp_box_sums(View V, const unsigned char* __restrict__ flag, const int* __restrict__ box_frame,
                                                       const int* __restrict__ box_plane, const float* __restrict__ planes, int n_planes,
                                                       const IcpState* __restrict__ st, double* __restrict__ part) {
   __shared__ double red[4][kIcpSums];
-  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q = blockIdx.x, tid = threadIdx.x;
   const int f = box_frame[q], kpl = box_plane[q];
   double a[kIcpSums];
 #pragma unroll
@@ -1779,33 +1757,10 @@ __global__ __launch_bounds__(256) void k_icp_box_sums(View V, const unsigned cha
     const int n = b.w * b.h;
     for (int i = tid; i < n; i += 256) {
       if (!flag[(size_t)b.pix0 + i]) continue;
-      const float* p = V.pts + ((size_t)b.pix0 + i) * 3;
-      const double px = p[0], py = p[1], pz = p[2];
-      if (!(isfinite(px) && isfinite(py) && isfinite(pz))) continue;
-      const double qx = R[0] * px + R[1] * py + R[2] * pz + t[0];
-      const double qy = R[3] * px + R[4] * py + R[5] * pz + t[1];
-      const double qz = R[6] * px + R[7] * py + R[8] * pz + t[2];
-      const double r = nx * qx + ny * qy + nz * qz + d;
-      const double J[6] = {qy * nz - qz * ny, qz * nx - qx * nz, qx * ny - qy * nx, nx, ny, nz};
-      int m = 0;
-#pragma unroll
-      for (int rr = 0; rr < 6; ++rr)
-#pragma unroll
-        for (int cc = rr; cc < 6; ++cc) a[m++] += J[rr] * J[cc];
-#pragma unroll
-      for (int rr = 0; rr < 6; ++rr) a[21 + rr] += J[rr] * r;
-      a[27] += r * r;
-      a[28] += 1.0;
+      icp_add_point(R, t, V.pts + ((size_t)b.pix0 + i) * 3, nx, ny, nz, d, a);
     }
   }
-#pragma unroll
-  for (int k = 0; k < kIcpSums; ++k) {
-    double v = a[k];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < kIcpSums) part[(size_t)q * kIcpSums + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  block_sum4(a, red, part + (size_t)q * kIcpSums);
 }
 __global__ __launch_bounds__(64) void k_icp_frame_step(const int* __restrict__ frame_box0, const double* __restrict__ part, int it, int iterations,
                                                        IcpState* __restrict__ st, IcpFrame* __restrict__ out) {
@@ -1829,65 +1784,12 @@ __global__ __launch_bounds__(64) void k_icp_frame_step(const int* __restrict__ f
     st[f].done = 1;
     return;
   }
-  double A[36], bvec[6], L[36];
-  for (int k = 0; k < 36; ++k) L[k] = 0;
-  int m = 0;
-  for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { A[r * 6 + c] = A[c * 6 + r] = sums[m++]; }
-  for (int r = 0; r < 6; ++r) bvec[r] = -sums[21 + r];
-  bool okc = true;
-  for (int j = 0; j < 6 && okc; ++j) {
-    double dsum = A[j * 6 + j];
-    for (int k = 0; k < j; ++k) dsum -= L[j * 6 + k] * L[j * 6 + k];
-    if (!(dsum > 1e-12 * A[j * 6 + j]) || !(dsum > 0)) { okc = false; break; }
-    L[j * 6 + j] = sqrt(dsum);
-    for (int i = j + 1; i < 6; ++i) { double v = A[i * 6 + j]; for (int k = 0; k < j; ++k) v -= L[i * 6 + k] * L[j * 6 + k]; L[i * 6 + j] = v / L[j * 6 + j]; }
-  }
-  if (!okc) { st[f].status = SSLAM_ERR_NUMERIC; return; }   // the planes leave a degree of freedom unconstrained: the next pass reports it
-  double y[6], dx[6];
-  for (int i = 0; i < 6; ++i) { double v = bvec[i]; for (int k = 0; k < i; ++k) v -= L[i * 6 + k] * y[k]; y[i] = v / L[i * 6 + i]; }
-  for (int i = 5; i >= 0; --i) { double v = y[i]; for (int k = i + 1; k < 6; ++k) v -= L[k * 6 + i] * dx[k]; dx[i] = v / L[i * 6 + i]; }
-  const double wx = dx[0], wy = dx[1], wz = dx[2], th = sqrt(wx * wx + wy * wy + wz * wz);
-  double E[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  if (th > 0) {
-    const double sa = sin(th) / th, bq = (1.0 - cos(th)) / (th * th);
-    const double K[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { double kk = 0; for (int q = 0; q < 3; ++q) kk += K[r * 3 + q] * K[q * 3 + c]; E[r * 3 + c] += sa * K[r * 3 + c] + bq * kk; }
-  }
-  double Tn[12];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) Tn[r * 3 + c] = E[r * 3] * S.T[c] + E[r * 3 + 1] * S.T[3 + c] + E[r * 3 + 2] * S.T[6 + c];
-    Tn[9 + r] = E[r * 3] * S.T[9] + E[r * 3 + 1] * S.T[10] + E[r * 3 + 2] * S.T[11] + dx[3 + r];
-  }
-  for (int k = 0; k < 12; ++k) st[f].T[k] = Tn[k];
+  if (!icp_gn_step(sums, S.T)) { st[f].status = SSLAM_ERR_NUMERIC; return; }   // the planes leave a degree of freedom unconstrained: the next pass reports it
+  for (int k = 0; k < 12; ++k) st[f].T[k] = S.T[k];
 }
 
 // ---- cloud filters of the legacy path (plane_segmentation.cpp:557-629) ---------------------------------------------
-// ordered compaction of a flag array (ascending indices): per-block counts -> k_ransac_scan -> write
-__global__ __launch_bounds__(256) void k_flag_count(const unsigned char* __restrict__ flag, int n, int* __restrict__ block_counts) {
-  __shared__ int wsum[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  int c = (i < n && flag[i]) ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-__global__ __launch_bounds__(256) void k_flag_write(const unsigned char* __restrict__ flag, int n, const int* __restrict__ block_off, int* __restrict__ out, int max_out) {
-  __shared__ int woff[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool in = i < n && flag[i];
-  const unsigned long long mask = __ballot(in);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) woff[wave] = __popcll(mask);
-  __syncthreads();
-  int base = block_off[blockIdx.x];
-  for (int w = 0; w < wave; ++w) base += woff[w];
-  if (in) {
-    const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-    if (pos < max_out) out[pos] = i;
-  }
-}
+// (their index lists come from the ordered compaction above with FlagPred)
 // distance_filter (plane_segmentation.cpp:607-629): keep p with 0.3 < |p| < 3 (float norm, compared as double)
 __global__ __launch_bounds__(256) void k_range_flag(const float* __restrict__ pts, int n, double dmin, double dmax, unsigned char* __restrict__ flag) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -2115,7 +2017,7 @@ __global__ __launch_bounds__(kNnSeg) void k_nn_finish(const NnPair* __restrict__
 //               `best` for its point and, if the correspondence is accepted ((double)d2 <= max_range), loads the ORIGINAL source point p
 //               (coalesced: the run's 3 * 256 floats are contiguous) and its target q (a gather: 12 bytes wherever the neighbour lies)
 //               and forms, in double, sum p, sum q, sum p q^T and the count.  The products of two widened floats are exact.  Reduced
-//               with the tree of k_nn_finish: the shuffle tree of a wave over its 64 consecutive points, the four waves in order.
+//               by block_sum4, the tree of k_nn_finish: the shuffle tree of a wave over its 64 consecutive points, the four waves in order.
 //   k_reg_step  one wave per pair: lanes 0..15 add the run records in ascending run order, lane 0 solves the absolute orientation
 //               problem (horn_rigid, csrc/sslam_math.hpp) and applies the status and convergence rules.
 // The order of every sum is fixed by the point index alone.  A finished pair (converged, or fewer than 3 correspondences) is frozen by
@@ -2150,14 +2052,7 @@ __global__ __launch_bounds__(kNnSeg) void k_reg_sums(const float* __restrict__ x
       a[15] = 1.0;
     }
   }
-#pragma unroll
-  for (int k = 0; k < kRegSums; ++k) {
-    double v = a[k];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((tid & 63) == 0) red[tid >> 6][k] = v;
-  }
-  __syncthreads();
-  if (tid < kRegSums) part[(size_t)blockIdx.x * kRegSums + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  block_sum4(a, red, part + (size_t)blockIdx.x * kRegSums);
 }
 __global__ __launch_bounds__(64) void k_reg_step(const int* __restrict__ seg0, const double* __restrict__ part, double epsilon, NnPair* __restrict__ pairs,
                                                  RegState* __restrict__ st, int* __restrict__ live) {
@@ -2322,7 +2217,7 @@ static int seg_alloc(sslam_seg* s, size_t n, T** out) {
   return 0;
 }
 
-// helpers of the cloud filters (row f4)
+// helpers of the single-cloud entry points (RANSAC plane, hull, ICP, cloud filters, fitness, registration)
 namespace {
 struct DevGuard {
   std::vector<void*> ptrs;
@@ -2334,26 +2229,38 @@ struct DevGuard {
     return 0;
   }
 };
-int seg_device(sslam_seg* s) {
+int seg_have_device() {
   int nd = 0;
   if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return set_error(SSLAM_ERR_NO_DEVICE, "no HIP device visible; the product has no CPU fallback");
+  return 0;
+}
+int seg_device(sslam_seg* s) {
+  int rc = seg_have_device();
+  if (rc) return rc;
   SSLAM_HIP_TRY(hipSetDevice(s->P.device));
   if (!s->stream) SSLAM_HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   return 0;
 }
-// ascending indices of the set flags -> out (host); returns their number
-int compact_flags(sslam_seg* s, DevGuard& g, const unsigned char* d_flag, int n, int* d_out, int max_out, int* total_out) {
+// ordered compaction of [0, n) under `pred` on the handle's stream (k_count_if -> k_exclusive_scan -> k_write_if).  d_blk: one int per
+// block of 256, d_total: one int, which keeps the number kept; with total_out the call waits and returns that number on the host too.
+template <class Pred>
+int compact_if(sslam_seg* s, Pred pred, int n, int* d_blk, int* d_total, int* total_out) {
   const int nblk = (n + 255) / 256;
-  int *d_blk = nullptr, *d_total = nullptr;
-  int rc;
-  if ((rc = g.alloc(&d_blk, nblk)) || (rc = g.alloc(&d_total, 1))) return rc;
-  hipLaunchKernelGGL(k_flag_count, dim3(nblk), dim3(256), 0, s->stream, d_flag, n, d_blk);
-  hipLaunchKernelGGL(k_ransac_scan, dim3(1), dim3(64), 0, s->stream, d_blk, nblk, d_total);
-  hipLaunchKernelGGL(k_flag_write, dim3(nblk), dim3(256), 0, s->stream, d_flag, n, d_blk, d_out, max_out);
+  hipLaunchKernelGGL(k_count_if<Pred>, dim3(nblk), dim3(256), 0, s->stream, pred, n, d_blk);
+  hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(64), 0, s->stream, d_blk, nblk, d_blk, d_total);
+  hipLaunchKernelGGL(k_write_if<Pred>, dim3(nblk), dim3(256), 0, s->stream, pred, n, d_blk);
   SSLAM_HIP_TRY(hipGetLastError());
+  if (!total_out) return 0;
   SSLAM_HIP_TRY(hipMemcpyAsync(total_out, d_total, sizeof(int), hipMemcpyDeviceToHost, s->stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
   return 0;
+}
+// ascending indices of the set flags -> d_out; their number -> *total_out (host)
+int compact_flags(sslam_seg* s, DevGuard& g, const unsigned char* d_flag, int n, int* d_out, int max_out, int* total_out) {
+  int *d_blk = nullptr, *d_total = nullptr;
+  int rc;
+  if ((rc = g.alloc(&d_blk, (n + 255) / 256)) || (rc = g.alloc(&d_total, 1))) return rc;
+  return compact_if(s, FlagPred{d_flag, d_out, max_out}, n, d_blk, d_total, total_out);
 }
 }  // namespace
 
@@ -2433,10 +2340,7 @@ static int seg_enqueue(sslam_seg* s, const sslam_frame* frames, int n_frames, in
     if (frames[f].n_boxes < 0) return set_error(SSLAM_ERR_INVALID, "frame %d: n_boxes %d", f, frames[f].n_boxes);
     if (!frames[f].cloud || (!frames[f].boxes && frames[f].n_boxes > 0)) return set_error(SSLAM_ERR_INVALID, "frame %d: null cloud or boxes", f);
   }
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return set_error(SSLAM_ERR_NO_DEVICE, "no HIP device visible; the product has no CPU fallback");
-  SSLAM_HIP_TRY(hipSetDevice(s->P.device));
-  if (!s->stream) SSLAM_HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  { const int rc_dev = seg_device(s); if (rc_dev) return rc_dev; }
   s->q_t0 = std::chrono::steady_clock::now();
   const sslam_seg_params& P = s->P;
   // ---- host-side box filter: class whitelist (point_cloud_segmentation.h:126-130), crop bounds
@@ -2717,80 +2621,48 @@ int sslam_seg_ransac_plane(sslam_seg* s, const float* xyz, int n, float threshol
                            uint64_t seed, float coeff_out[4], int32_t* inliers_out, int max_inliers) {
   if (!s || !xyz || !coeff_out || (!inliers_out && max_inliers > 0) || n < 0 || max_iterations < 1)
     return set_error(SSLAM_ERR_INVALID, "bad argument");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return set_error(SSLAM_ERR_NO_DEVICE, "no HIP device visible; the product has no CPU fallback");
+  int rc = seg_device(s);
+  if (rc) return rc;
   coeff_out[0] = coeff_out[1] = coeff_out[2] = coeff_out[3] = 0;
   if (n < 3) return 0;
-  SSLAM_HIP_TRY(hipSetDevice(s->P.device));
-  if (!s->stream) SSLAM_HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  const int max_skip = max_iterations * 10;
-  const int H = max_iterations + 1 + max_skip;       // every hypothesis index the sequential loop can reach
-  const int nblk = (n + 255) / 256;
+  const int H = max_iterations + 1 + max_iterations * 10;   // every hypothesis index the sequential loop can reach (10 skips per iteration)
   float *d_pts = nullptr, *d_models = nullptr;
   int *d_counts = nullptr, *d_blk = nullptr, *d_inl = nullptr, *d_total = nullptr;
-  struct Guard {   // frees whatever was allocated on every exit path (an early SSLAM_HIP_TRY return included)
-    std::vector<void**> ptrs;
-    ~Guard() { for (void** p : ptrs) if (*p) (void)hipFree(*p); }
-  } guard;
-  guard.ptrs = {(void**)&d_pts, (void**)&d_models, (void**)&d_counts, (void**)&d_blk, (void**)&d_inl, (void**)&d_total};
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_pts, (size_t)n * 3 * sizeof(float)));
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_models, (size_t)(H + 1) * 4 * sizeof(float)));
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_counts, (size_t)H * sizeof(int)));
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_blk, (size_t)nblk * sizeof(int)));
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_inl, (size_t)std::max(n, 1) * sizeof(int)));
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_total, sizeof(int)));
-  auto cleanup = [&]() {};   // the guard frees
+  DevGuard g;
+  if ((rc = g.alloc(&d_pts, (size_t)n * 3)) || (rc = g.alloc(&d_models, (size_t)(H + 1) * 4)) || (rc = g.alloc(&d_counts, H)) ||
+      (rc = g.alloc(&d_blk, (n + 255) / 256)) || (rc = g.alloc(&d_inl, n)) || (rc = g.alloc(&d_total, 1))) return rc;
   SSLAM_HIP_TRY(hipMemcpyAsync(d_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
   hipLaunchKernelGGL(k_ransac_score, dim3(H), dim3(256), 0, s->stream, d_pts, n, threshold, (unsigned long long)seed, d_models, d_counts);
   std::vector<int> counts(H);
-  std::vector<float> models((size_t)H * 4);
   SSLAM_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  SSLAM_HIP_TRY(hipMemcpyAsync(models.data(), d_models, (size_t)H * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
   // replay of pcl::RandomSampleConsensus::computeModel over the precomputed counts
-  int best = -1, best_it = -1, iterations = 0, skipped = 0, it = 0;
+  int best = -1, best_it = -1, iterations = 0, skipped = 0;
   double k = 1.0;
-  const double log_probability = std::log(1.0 - probability), one_over = 1.0 / (double)n, eps = 2.220446049250313e-16;
-  while ((double)iterations < k && skipped < max_skip && it < H) {
-    const int cnt = counts[it];
-    ++it;
-    if (cnt < 0) { ++skipped; continue; }
-    if (cnt > best) {
-      best = cnt; best_it = it - 1;
-      const double w = (double)best * one_over;
-      double p_no = 1.0 - std::pow(w, 3.0);
-      p_no = std::max(eps, p_no); p_no = std::min(1.0 - eps, p_no);
-      k = log_probability / std::log(p_no);
-    }
-    ++iterations;
-    if (iterations > max_iterations) break;
-  }
-  if (best <= 0) { cleanup(); return 0; }
+  const double log_probability = std::log(1.0 - probability), one_over = 1.0 / (double)n;
+  for (int it = 0; it < H && ransac_loop_open(k, iterations, skipped, max_iterations); ++it)
+    if (ransac_loop_take(counts[it], one_over, log_probability, k, iterations, skipped, best)) best_it = it;
+  if (best <= 0) return 0;
   float* d_model = d_models + (size_t)H * 4;   // working copy of the winning model
   SSLAM_HIP_TRY(hipMemcpyAsync(d_model, d_models + (size_t)best_it * 4, 4 * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-  for (int pass = 0; pass < 2; ++pass) {   // inliers of the sampled model -> refit -> inliers of the refined model
-    hipLaunchKernelGGL(k_ransac_mark, dim3(nblk), dim3(256), 0, s->stream, d_pts, n, threshold, d_model, d_blk);
-    hipLaunchKernelGGL(k_ransac_scan, dim3(1), dim3(64), 0, s->stream, d_blk, nblk, d_total);
-    hipLaunchKernelGGL(k_ransac_write, dim3(nblk), dim3(256), 0, s->stream, d_pts, n, threshold, d_model, d_blk, d_inl, n);
-    if (pass == 0) hipLaunchKernelGGL(k_ransac_refit, dim3(1), dim3(64), 0, s->stream, d_pts, d_inl, d_total, d_model);
-  }
+  // inliers of the sampled model -> refit -> inliers of the refined model
+  const InlierPred inliers{d_pts, d_model, threshold, d_inl, n};
   int total = 0;
-  SSLAM_HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  SSLAM_HIP_TRY(hipMemcpyAsync(coeff_out, d_model, 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if ((rc = compact_if(s, inliers, n, d_blk, d_total, nullptr))) return rc;
+  hipLaunchKernelGGL(k_ransac_refit, dim3(1), dim3(64), 0, s->stream, d_pts, d_inl, d_total, d_model);
+  if ((rc = compact_if(s, inliers, n, d_blk, d_total, &total))) return rc;
+  SSLAM_HIP_TRY(hipMemcpy(coeff_out, d_model, 4 * sizeof(float), hipMemcpyDeviceToHost));
   if (total > 0 && max_inliers > 0)
     SSLAM_HIP_TRY(hipMemcpy(inliers_out, d_inl, (size_t)std::min(total, max_inliers) * sizeof(int), hipMemcpyDeviceToHost));
-  hipError_t le = hipGetLastError();
-  cleanup();
-  if (le != hipSuccess) return set_error(SSLAM_ERR_HIP, "ransac kernels: %s", hipGetErrorString(le));
+  SSLAM_HIP_TRY(hipGetLastError());
   return total;
 }
 
 // ---- RANSAC + ICP over the boxes of the resident batch (configs[3]) ------------------------------------------------------------------
 static int seg_resident_check(sslam_seg* s) {
   if (!s) return set_error(SSLAM_ERR_INVALID, "null handle");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return set_error(SSLAM_ERR_NO_DEVICE, "no HIP device visible; the product has no CPU fallback");
+  const int rc = seg_have_device();
+  if (rc) return rc;
   if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
   if (!s->stream || s->V.nbox != (int)s->boxes.size()) return set_error(SSLAM_ERR_INVALID, "no resident batch: call sslam_seg_segment / sslam_seg_segment_batch first");
   return 0;
@@ -2940,72 +2812,56 @@ int sslam_seg_convex_hull_2d(sslam_seg* s, const float* xyz, int n, const int32_
                              float* projected_out, int32_t* hull_out, int max_hull, int* axes_out) {
   if (!s || !xyz || !inliers || !coeff || (!hull_out && max_hull > 0) || n < 0 || n_inliers < 0)
     return set_error(SSLAM_ERR_INVALID, "bad argument");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return set_error(SSLAM_ERR_NO_DEVICE, "no HIP device visible; the product has no CPU fallback");
+  int rc = seg_device(s);
+  if (rc) return rc;
   if (axes_out) *axes_out = -1;
   if (n_inliers < 3) return set_error(SSLAM_ERR_INVALID, "a 2-D hull needs at least 3 inliers");
   for (int k = 0; k < n_inliers; ++k) if (inliers[k] < 0 || inliers[k] >= n) return set_error(SSLAM_ERR_INVALID, "inlier index out of range");
-  SSLAM_HIP_TRY(hipSetDevice(s->P.device));
-  if (!s->stream) SSLAM_HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   const int m0 = n_inliers, nblk = (m0 + 255) / 256;
-  std::vector<void*> bufs;
-  auto alloc = [&](size_t bytes) -> void* { void* p = nullptr; if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr; bufs.push_back(p); return p; };
-  auto cleanup = [&]() { for (void* p : bufs) (void)hipFree(p); };
-  float* d_pts = (float*)alloc((size_t)n * 3 * sizeof(float));
-  int* d_inl = (int*)alloc((size_t)m0 * sizeof(int));
-  float* d_proj = (float*)alloc((size_t)m0 * 3 * sizeof(float));
-  float* d_px = (float*)alloc((size_t)m0 * sizeof(float)); float* d_py = (float*)alloc((size_t)m0 * sizeof(float));
-  float* d_cx = (float*)alloc((size_t)m0 * sizeof(float)); float* d_cy = (float*)alloc((size_t)m0 * sizeof(float)); int* d_ci = (int*)alloc((size_t)m0 * sizeof(int));
-  const int max_chunks = (m0 + kHullCap - 1) / kHullCap;
-  float* d_ox = (float*)alloc((size_t)max_chunks * kHullCap * sizeof(float)); float* d_oy = (float*)alloc((size_t)max_chunks * kHullCap * sizeof(float));
-  int* d_oi = (int*)alloc((size_t)max_chunks * kHullCap * sizeof(int));
-  int* d_meta = (int*)alloc(4 * sizeof(int));
-  double* d_bkey = (double*)alloc((size_t)nblk * 8 * sizeof(double)); int* d_bidx = (int*)alloc((size_t)nblk * 8 * sizeof(int));
-  double* d_ext = (double*)alloc(17 * sizeof(double)); int* d_eidx = (int*)alloc(8 * sizeof(int));
-  int* d_blk = (int*)alloc((size_t)nblk * sizeof(int)); int* d_total = (int*)alloc(sizeof(int));
-  int* d_counts = (int*)alloc((size_t)max_chunks * sizeof(int)); int* d_off = (int*)alloc((size_t)max_chunks * sizeof(int));
-  if (!d_pts || !d_inl || !d_proj || !d_px || !d_py || !d_cx || !d_cy || !d_ci || !d_ox || !d_oy || !d_oi || !d_meta || !d_bkey || !d_bidx || !d_ext ||
-      !d_eidx || !d_blk || !d_total || !d_counts || !d_off) { cleanup(); return set_error(SSLAM_ERR_HIP, "hipMalloc failed (convex hull)"); }
-#define SSLAM_HULL_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return set_error(SSLAM_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-  SSLAM_HULL_TRY(hipMemcpyAsync(d_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  SSLAM_HULL_TRY(hipMemcpyAsync(d_inl, inliers, (size_t)m0 * sizeof(int), hipMemcpyHostToDevice, s->stream));
+  const size_t max_chunks = (m0 + kHullCap - 1) / kHullCap;
+  float *d_pts = nullptr, *d_proj = nullptr, *d_px = nullptr, *d_py = nullptr, *d_cx = nullptr, *d_cy = nullptr, *d_ox = nullptr, *d_oy = nullptr;
+  int *d_inl = nullptr, *d_ci = nullptr, *d_oi = nullptr, *d_meta = nullptr, *d_bidx = nullptr, *d_eidx = nullptr, *d_blk = nullptr, *d_total = nullptr,
+      *d_counts = nullptr, *d_off = nullptr;
+  double *d_bkey = nullptr, *d_ext = nullptr;
+  DevGuard g;
+  if ((rc = g.alloc(&d_pts, (size_t)n * 3)) || (rc = g.alloc(&d_inl, m0)) || (rc = g.alloc(&d_proj, (size_t)m0 * 3)) || (rc = g.alloc(&d_px, m0)) ||
+      (rc = g.alloc(&d_py, m0)) || (rc = g.alloc(&d_cx, m0)) || (rc = g.alloc(&d_cy, m0)) || (rc = g.alloc(&d_ci, m0)) ||
+      (rc = g.alloc(&d_ox, max_chunks * kHullCap)) || (rc = g.alloc(&d_oy, max_chunks * kHullCap)) || (rc = g.alloc(&d_oi, max_chunks * kHullCap)) ||
+      (rc = g.alloc(&d_meta, 4)) || (rc = g.alloc(&d_bkey, (size_t)nblk * 8)) || (rc = g.alloc(&d_bidx, (size_t)nblk * 8)) || (rc = g.alloc(&d_ext, 17)) ||
+      (rc = g.alloc(&d_eidx, 8)) || (rc = g.alloc(&d_blk, nblk)) || (rc = g.alloc(&d_total, 1)) || (rc = g.alloc(&d_counts, max_chunks)) ||
+      (rc = g.alloc(&d_off, max_chunks))) return rc;
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_inl, inliers, (size_t)m0 * sizeof(int), hipMemcpyHostToDevice, s->stream));
   hipLaunchKernelGGL(k_hull_project, dim3(nblk), dim3(256), 0, s->stream, d_pts, d_inl, m0, coeff[0], coeff[1], coeff[2], coeff[3], d_proj);
   hipLaunchKernelGGL(k_hull_axes, dim3(1), dim3(1), 0, s->stream, d_proj, m0, cosf(0.174532925f), d_meta);
   int axes = -1;
-  SSLAM_HULL_TRY(hipMemcpyAsync(&axes, d_meta, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  if (projected_out) SSLAM_HULL_TRY(hipMemcpyAsync(projected_out, d_proj, (size_t)m0 * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  SSLAM_HULL_TRY(hipStreamSynchronize(s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(&axes, d_meta, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  if (projected_out) SSLAM_HIP_TRY(hipMemcpyAsync(projected_out, d_proj, (size_t)m0 * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
   if (axes_out) *axes_out = axes;
-  if (axes < 0) { cleanup(); return set_error(SSLAM_ERR_NUMERIC, "convex hull: the projected inliers are collinear"); }
+  if (axes < 0) return set_error(SSLAM_ERR_NUMERIC, "convex hull: the projected inliers are collinear");
   hipLaunchKernelGGL(k_hull_coords, dim3(nblk), dim3(256), 0, s->stream, d_proj, m0, d_meta, d_px, d_py);
   hipLaunchKernelGGL(k_hull_extreme_partial, dim3(nblk), dim3(256), 0, s->stream, d_px, d_py, m0, d_bkey, d_bidx);
   hipLaunchKernelGGL(k_hull_extreme_final, dim3(1), dim3(64), 0, s->stream, d_bkey, d_bidx, nblk, d_px, d_py, d_ext, d_eidx);
-  hipLaunchKernelGGL(k_hull_mark, dim3(nblk), dim3(256), 0, s->stream, d_px, d_py, m0, d_ext, d_blk);
-  hipLaunchKernelGGL(k_ransac_scan, dim3(1), dim3(64), 0, s->stream, d_blk, nblk, d_total);
-  hipLaunchKernelGGL(k_hull_write, dim3(nblk), dim3(256), 0, s->stream, d_px, d_py, m0, d_ext, d_blk, d_cx, d_cy, d_ci);
   int m = 0;
-  SSLAM_HULL_TRY(hipMemcpyAsync(&m, d_total, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  SSLAM_HULL_TRY(hipStreamSynchronize(s->stream));
+  if ((rc = compact_if(s, HullPred{d_px, d_py, d_ext, d_cx, d_cy, d_ci}, m0, d_blk, d_total, &m))) return rc;
   while (m > kHullCap) {   // hull of hulls until one workgroup holds every candidate
     const int nchunks = (m + kHullCap - 1) / kHullCap;
     hipLaunchKernelGGL(k_hull_core<false>, dim3(nchunks), dim3(1024), 0, s->stream, d_cx, d_cy, d_ci, m, d_ox, d_oy, d_oi, d_counts);
-    hipLaunchKernelGGL(k_hull_scan, dim3(1), dim3(64), 0, s->stream, d_counts, nchunks, d_off, d_total);
+    hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(64), 0, s->stream, d_counts, nchunks, d_off, d_total);
     hipLaunchKernelGGL(k_hull_compact, dim3(nchunks), dim3(256), 0, s->stream, d_ox, d_oy, d_oi, d_counts, d_off, d_cx, d_cy, d_ci);
     int m2 = 0;
-    SSLAM_HULL_TRY(hipMemcpyAsync(&m2, d_total, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    SSLAM_HULL_TRY(hipStreamSynchronize(s->stream));
-    if (m2 >= m) { cleanup(); return set_error(SSLAM_ERR_UNSUPPORTED, "convex hull with more than %d vertices", kHullCap); }
+    SSLAM_HIP_TRY(hipMemcpyAsync(&m2, d_total, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+    if (m2 >= m) return set_error(SSLAM_ERR_UNSUPPORTED, "convex hull with more than %d vertices", kHullCap);
     m = m2;
   }
   hipLaunchKernelGGL(k_hull_core<true>, dim3(1), dim3(1024), 0, s->stream, d_cx, d_cy, d_ci, m, d_ox, d_oy, d_oi, d_counts);
   int h = 0;
-  SSLAM_HULL_TRY(hipMemcpyAsync(&h, d_counts, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  SSLAM_HULL_TRY(hipStreamSynchronize(s->stream));
-  if (h > 0 && max_hull > 0) SSLAM_HULL_TRY(hipMemcpy(hull_out, d_oi, (size_t)std::min(h, max_hull) * sizeof(int), hipMemcpyDeviceToHost));
-  hipError_t le = hipGetLastError();
-  cleanup();
-#undef SSLAM_HULL_TRY
-  if (le != hipSuccess) return set_error(SSLAM_ERR_HIP, "convex hull kernels: %s", hipGetErrorString(le));
+  SSLAM_HIP_TRY(hipMemcpyAsync(&h, d_counts, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if (h > 0 && max_hull > 0) SSLAM_HIP_TRY(hipMemcpy(hull_out, d_oi, (size_t)std::min(h, max_hull) * sizeof(int), hipMemcpyDeviceToHost));
+  SSLAM_HIP_TRY(hipGetLastError());
   return h;
 }
 
@@ -3047,26 +2903,17 @@ int sslam_seg_last_timing(const sslam_seg* s, double* kernel_ms, double* total_m
 int sslam_seg_icp_point_to_plane(sslam_seg* s, const float* xyz, const int32_t* labels, int n, const float* planes, int n_planes,
                                  int iterations, const double T0[12], double T_out[12], double* rms_out) {
   if (!s || !xyz || !labels || !planes || !T_out || n < 0 || n_planes <= 0 || iterations < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return set_error(SSLAM_ERR_NO_DEVICE, "no HIP device visible; the product has no CPU fallback");
-  SSLAM_HIP_TRY(hipSetDevice(s->P.device));
-  if (!s->stream) SSLAM_HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  int rc = seg_device(s);
+  if (rc) return rc;
   IcpPose T;
-  if (T0) { for (int k = 0; k < 9; ++k) T.R[k] = T0[k]; for (int k = 0; k < 3; ++k) T.t[k] = T0[9 + k]; }
-  else { for (int k = 0; k < 9; ++k) T.R[k] = (k % 4 == 0) ? 1.0 : 0.0; T.t[0] = T.t[1] = T.t[2] = 0.0; }
+  for (int k = 0; k < 12; ++k) T.T[k] = T0 ? T0[k] : ((k < 9 && k % 4 == 0) ? 1.0 : 0.0);
   const int nblk = std::max(1, std::min(256, (n + 255) / 256));
   float *d_pts = nullptr, *d_planes = nullptr;
   int* d_lab = nullptr;
   double* d_part = nullptr;
-  struct Guard {
-    std::vector<void**> ptrs;
-    ~Guard() { for (void** p : ptrs) if (*p) (void)hipFree(*p); }
-  } guard;
-  guard.ptrs = {(void**)&d_pts, (void**)&d_planes, (void**)&d_lab, (void**)&d_part};
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_pts, (size_t)std::max(n, 1) * 3 * sizeof(float)));
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_lab, (size_t)std::max(n, 1) * sizeof(int)));
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_planes, (size_t)n_planes * 4 * sizeof(float)));
-  SSLAM_HIP_TRY(hipMalloc((void**)&d_part, (size_t)nblk * kIcpSums * sizeof(double)));
+  DevGuard g;
+  if ((rc = g.alloc(&d_pts, (size_t)n * 3)) || (rc = g.alloc(&d_lab, n)) || (rc = g.alloc(&d_planes, (size_t)n_planes * 4)) ||
+      (rc = g.alloc(&d_part, (size_t)nblk * kIcpSums))) return rc;
   if (n > 0) {
     SSLAM_HIP_TRY(hipMemcpyAsync(d_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
     SSLAM_HIP_TRY(hipMemcpyAsync(d_lab, labels, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s->stream));
@@ -3082,44 +2929,14 @@ int sslam_seg_icp_point_to_plane(sslam_seg* s, const float* xyz, const int32_t* 
     for (int k = 0; k < kIcpSums; ++k) { double v = 0; for (int b = 0; b < nblk; ++b) v += part[(size_t)b * kIcpSums + k]; sums[k] = v; }
     return 0;
   };
-  int rc;
   for (int it = 0; it < iterations; ++it) {
     if ((rc = accumulate())) return rc;
     if (sums[28] < 6) break;
-    // (J^T J) delta = -J^T r by Cholesky; a rank-deficient plane set (fewer than three independent normals) leaves the transform
-    // free along some direction: SSLAM_ERR_NUMERIC
-    double A[36], bvec[6], L[36] = {0};
-    int m = 0;
-    for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { A[r * 6 + c] = A[c * 6 + r] = sums[m++]; }
-    for (int r = 0; r < 6; ++r) bvec[r] = -sums[21 + r];
-    for (int j = 0; j < 6; ++j) {
-      double dsum = A[j * 6 + j];
-      for (int k = 0; k < j; ++k) dsum -= L[j * 6 + k] * L[j * 6 + k];
-      if (!(dsum > 1e-12 * A[j * 6 + j]) || !(dsum > 0)) return set_error(SSLAM_ERR_NUMERIC, "point-to-plane system is rank deficient (the planes do not constrain all six degrees of freedom)");
-      L[j * 6 + j] = std::sqrt(dsum);
-      for (int i = j + 1; i < 6; ++i) { double v = A[i * 6 + j]; for (int k = 0; k < j; ++k) v -= L[i * 6 + k] * L[j * 6 + k]; L[i * 6 + j] = v / L[j * 6 + j]; }
-    }
-    double y[6], dx[6];
-    for (int i = 0; i < 6; ++i) { double v = bvec[i]; for (int k = 0; k < i; ++k) v -= L[i * 6 + k] * y[k]; y[i] = v / L[i * 6 + i]; }
-    for (int i = 5; i >= 0; --i) { double v = y[i]; for (int k = i + 1; k < 6; ++k) v -= L[k * 6 + i] * dx[k]; dx[i] = v / L[i * 6 + i]; }
-    // T <- (exp[w]x, u) o T   (Rodrigues)
-    const double wx = dx[0], wy = dx[1], wz = dx[2], th = std::sqrt(wx * wx + wy * wy + wz * wz);
-    double E[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (th > 0) {
-      const double a = std::sin(th) / th, bq = (1.0 - std::cos(th)) / (th * th);
-      const double K[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-      for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { double kk = 0; for (int q = 0; q < 3; ++q) kk += K[r * 3 + q] * K[q * 3 + c]; E[r * 3 + c] += a * K[r * 3 + c] + bq * kk; }
-    }
-    IcpPose Tn;
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) Tn.R[r * 3 + c] = E[r * 3] * T.R[c] + E[r * 3 + 1] * T.R[3 + c] + E[r * 3 + 2] * T.R[6 + c];
-      Tn.t[r] = E[r * 3] * T.t[0] + E[r * 3 + 1] * T.t[1] + E[r * 3 + 2] * T.t[2] + dx[3 + r];
-    }
-    T = Tn;
+    if (!icp_gn_step(sums, T.T))
+      return set_error(SSLAM_ERR_NUMERIC, "point-to-plane system is rank deficient (the planes do not constrain all six degrees of freedom)");
   }
   if ((rc = accumulate())) return rc;   // residual at the returned transform
-  for (int k = 0; k < 9; ++k) T_out[k] = T.R[k];
-  for (int k = 0; k < 3; ++k) T_out[9 + k] = T.t[k];
+  for (int k = 0; k < 12; ++k) T_out[k] = T.T[k];
   if (rms_out) *rms_out = sums[28] > 0 ? std::sqrt(sums[27] / sums[28]) : 0.0;
   return (int)sums[28];
 }

@@ -421,6 +421,73 @@ def test_icp_point_to_plane_matches_oracle(gpu_lib):
     assert ei.value.code == -4
 
 
+def test_icp_point_to_plane_block_edge_and_too_few_points(gpu_lib):
+    """the ends of the shared reduction and step: a cloud whose second workgroup holds one point, fewer than six labelled points
+    (no step: the start transform comes back untouched, the residual is measured at it), and no points at all"""
+    from oracle.np_icp import icp_point_to_plane
+    from tests.icp_scene import make_icp_scene, small_motion
+    from semantic_slam_amd.segmentation import PointCloudSegmentation
+    seg = PointCloudSegmentation()
+    obs, lab, planes, _ = make_icp_scene(seed=3)
+    obs, lab = obs[::62][:257], lab[::62][:257]                       # 257 points over all four planes, NaNs and unlabelled ones included
+    assert len(obs) == 257 and set(lab) == {-1, 0, 1, 2, 3}
+    T, rms, n = seg.icp_point_to_plane(obs, lab, planes, 1)
+    To, rmso, no = icp_point_to_plane(obs, lab, planes, 1)
+    assert n == no and 200 < n < 257
+    assert np.abs(T - To).max() <= 1e-9 and abs(rms - rmso) <= 1e-9
+    R0, t0 = small_motion(3)
+    T0 = np.concatenate([R0.reshape(9), t0])
+    valid = np.flatnonzero((lab >= 0) & np.isfinite(obs).all(1))
+    five = np.full_like(lab, -1)
+    five[valid[::50][:5]] = lab[valid[::50][:5]]
+    T, rms, n = seg.icp_point_to_plane(obs, five, planes, 4, T0=T0)
+    To, rmso, no = icp_point_to_plane(obs, five, planes, 4, T0=T0)
+    assert n == no == 5
+    assert np.array_equal(T, T0) and abs(rms - rmso) <= 1e-9 and rmso > 1e-3
+    T, rms, n = seg.icp_point_to_plane(np.zeros((0, 3), np.float32), np.zeros(0, np.int32), planes, 4, T0=T0)
+    assert n == 0 and rms == 0.0 and np.array_equal(T, T0)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1025])
+def test_distance_filter_block_edges(gpu_lib, n):
+    """ordered compaction at the edges of a wave and of a 256-point block: the last point is always kept"""
+    from oracle import np_filters as NF
+    from semantic_slam_amd.segmentation import PointCloudSegmentation
+    seg = PointCloudSegmentation()
+    rng = np.random.default_rng(n)
+    d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    mixed = (d * rng.uniform(0.05, 5.0, (n, 1))).astype(np.float32)          # about half inside 0.3 < |p| < 3
+    mixed[n - 1] = (1.0, 0.0, 0.0)
+    clouds = [(mixed, None)]
+    if n == 257:
+        clouds += [(d.astype(np.float32), n), ((5.0 * d).astype(np.float32), 0)]   # all kept, none kept
+    for xyz, kept in clouds:
+        ref = NF.distance_filter(xyz)
+        assert ref[-1] == n - 1 if kept is None else len(ref) == kept
+        assert np.array_equal(seg.distance_filter(xyz), ref)
+
+
+@pytest.mark.parametrize("n", [4, 65, 257, 1025])
+def test_ransac_plane_and_hull_block_edges(gpu_lib, n):
+    """the single-cloud RANSAC (draw, adaptive loop, two compactions, refit) and the hull's compaction on clouds that end inside a
+    wave or one point into a block, the last point an inlier: index set, coefficients and hull bit-equal to the oracle"""
+    from semantic_slam_amd.segmentation import PointCloudSegmentation
+    rng = np.random.default_rng(n)
+    pts = np.zeros((n, 3), np.float32)
+    pts[:, :2] = rng.uniform(-1, 1, (n, 2))
+    pts[:, 2] = 0.3 * pts[:, 0] - 0.2 * pts[:, 1] + 1.5 + rng.normal(0, 0.003, n)
+    out = rng.choice(n - 1, n // 3, replace=False)
+    pts[out] += rng.uniform(-0.5, 0.5, (len(out), 3)).astype(np.float32)
+    rc, ri = _oracle_ransac(pts, 0.01, 50, 0.99, n)
+    assert ri[-1] == n - 1 and (len(ri) == 3 if n == 4 else len(ri) > n // 2)    # the refit runs for more than 3 inliers
+    seg = PointCloudSegmentation()
+    coeff, inl = seg.ransac_plane(pts, 0.01, 50, 0.99, n)
+    assert np.array_equal(inl, ri) and np.array_equal(coeff, rc)
+    proj, hull, axes = seg.convex_hull_2d(pts, inl, coeff)
+    rproj, rhull, raxes = _oracle_hull(pts, ri, rc)
+    assert axes == raxes and np.array_equal(proj, rproj) and np.array_equal(hull, rhull) and len(rhull) >= 3
+
+
 def test_cloud_filters_match_oracle(gpu_lib):
     """row f4: range filter, voxel grid and statistical outlier removal on the xyz of a synthetic frame (NaN drop-outs included):
     index sets and voxel counts bit-exact, centroids and mean neighbour distances bit-exact (fixed-point sums / exact kNN in float32)."""
