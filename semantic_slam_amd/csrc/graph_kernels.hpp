@@ -146,17 +146,41 @@ __device__ __forceinline__ double se3_e2(const double* __restrict__ w, int n, in
     for (int c = r; c < 6; ++c) { e2 += (r == c ? 1.0 : 2.0) * w[(size_t)q * n + k] * (ev[r] * ev[c]); ++q; }
   return e2;
 }
-// rho1 of an edge that may carry a kernel of its own (kind 0: none)
-__device__ __forceinline__ double robust_rho1(int kind, double d, double e2) {
-  double r0, r1;
-  robust_rho(kind, d, e2, r0, r1);
-  return r1;
-}
 __device__ __forceinline__ double quad3(const double W[9], const double e[3]) {
   double c = 0;
 #pragma unroll
   for (int r = 0; r < 3; ++r) c += e[r] * (W[r * 3 + 0] * e[0] + W[r * 3 + 1] * e[1] + W[r * 3 + 2] * e[2]);
   return c;
+}
+// The robust kernel an edge is under (kind 0: none; callers test it first, so an edge under none forms no e2).  rho0(e2) is the edge's chi2
+// term and rho1(e2) the factor on its Omega in H and b, e2 = e^T Omega e of the UNMASKED Omega (se3_e2 / quad3): every rank of a sharded
+// batch, both endpoint rows, a duplicate's block and the chi2 term see one value.  <RK = false>: only the DCS fallback exists, no sqrt / log / exp.
+template <bool RK>
+struct EdgeKernel {
+  int kind;
+  double delta;
+  __device__ __forceinline__ void rho(double e2, double& rho0, double& rho1) const {
+    if constexpr (RK) robust_rho(kind, delta, e2, rho0, rho1);
+    else { rho1 = dcs_rho1(delta, e2); rho0 = e2 * rho1; }
+  }
+  __device__ __forceinline__ double rho0(double e2) const { double r0, r1; rho(e2, r0, r1); return r0; }
+  __device__ __forceinline__ double rho1(double e2) const { double r0, r1; rho(e2, r0, r1); return r1; }
+};
+// The information-scaling rule, its ONE copy: edge k of a class (rk_of / rd_of: its kind and width arrays) is under its own kernel if it has one,
+// else under DCS(dcs_phi) when dcs_phi > 0, else under none.  A pose-landmark edge passes V.dcs_phi; every other class passes 0.
+template <bool RK>
+__device__ __forceinline__ EdgeKernel<RK> info_scale(const unsigned char* __restrict__ rk_of, const double* __restrict__ rd_of, int k, double dcs_phi) {
+  if constexpr (RK) {
+    const int rk = rk_of[k];
+    if (rk) return {rk, rd_of[k]};
+  }
+  return {dcs_phi > 0 ? RK_DCS : RK_NONE, dcs_phi};
+}
+// edge-sharded mode: this rank builds the edges of graph g whose id (id_of[k]) lies in [shard_lo[g], shard_hi[g]); the others count with Omega = 0
+template <bool SHARD>
+__device__ __forceinline__ bool in_shard(const BatchView& V, int g, const int* __restrict__ id_of, int k) {
+  if constexpr (!SHARD) return true;
+  else { const int id = id_of[k]; return V.shard_lo[g] <= id && id < V.shard_hi[g]; }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -215,6 +239,50 @@ __device__ __forceinline__ void load_sym3(const double* w, int n, int e, double 
   int k = 0;
   for (int r = 0; r < 3; ++r)
     for (int c = r; c < 3; ++c) { const double v = w[(size_t)k * n + e]; W[r * 3 + c] = v; W[c * 3 + r] = v; ++k; }
+}
+
+// ---- edge errors: every edge class evaluates its error HERE, and takes its weight from info_scale above --------------------------------
+// measurement of EdgeSE3 k (SoA z[7][n]: t, q)
+__device__ __forceinline__ Pose load_meas_pose(const double* z, int n, int k) {
+  return Pose{{z[0 * (size_t)n + k], z[1 * (size_t)n + k], z[2 * (size_t)n + k]},
+              {z[3 * (size_t)n + k], z[4 * (size_t)n + k], z[5 * (size_t)n + k], z[6 * (size_t)n + k]}};
+}
+// the 4-double landmark record li of lmk (the current or the trial estimates): a point xyz, pad | a plane n, d
+__device__ __forceinline__ Vec3 load_point(const double* lmk, int li) {
+  const double* p = lmk + (size_t)li * 4;
+  return Vec3{p[0], p[1], p[2]};
+}
+__device__ __forceinline__ Plane load_plane(const double* lmk, int li) {
+  const double* p = lmk + (size_t)li * 4;
+  return Plane{{p[0], p[1], p[2]}, p[3]};
+}
+// measurement of pose-landmark edge k (SoA el_z[4][nEl])
+__device__ __forceinline__ Vec3 el_meas_point(const BatchView& V, int k) {
+  const size_t n = (size_t)V.nEl;
+  return Vec3{V.el_z[0 * n + k], V.el_z[1 * n + k], V.el_z[2 * n + k]};
+}
+__device__ __forceinline__ Plane el_meas_plane(const BatchView& V, int k) {
+  const size_t n = (size_t)V.nEl;
+  return Plane{{V.el_z[0 * n + k], V.el_z[1 * n + k], V.el_z[2 * n + k]}, V.el_z[3 * n + k]};
+}
+// error of pose-landmark edge k seen from pose Xi, a point or a plane by the kind of its landmark
+__device__ __forceinline__ void lm_edge_error(const BatchView& V, int k, const Pose& Xi, const double* lmk, double err[3]) {
+  const int li = V.el_l[k];
+  if (V.lm_kind[li] == VT_POINT) {
+    PointLin L;
+    point_error(Xi, load_point(lmk, li), el_meas_point(V, k), L);
+    err[0] = L.e[0]; err[1] = L.e[1]; err[2] = L.e[2];
+  } else {
+    plane_error(Xi, load_plane(lmk, li), el_meas_plane(V, k), err);
+  }
+}
+// error of point-point edge k (g2o::EdgePointXYZ): e = (p_b - p_a) - z
+__device__ __forceinline__ void ll_edge_error(const BatchView& V, const double* lmk, int k, double err[3]) {
+  const size_t n = (size_t)V.nEll;
+  const double* pa = lmk + (size_t)V.ell_a[k] * 4;
+  const double* pb = lmk + (size_t)V.ell_b[k] * 4;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) err[r] = (pb[r] - pa[r]) - V.ell_z[r * n + k];
 }
 
 // ---- scalar-row helpers -------------------------------------------------------------------------
@@ -333,9 +401,8 @@ __device__ __forceinline__ double prior_chi2(const BatchView& V, int k, const do
 }
 
 // chi2 term of the graph-local edge e of graph segment sg (SE3 edges, then landmark edges, then point-point edges, then position priors;
-// 0 beyond the last):
-// g2o computeActiveErrors + the robust kernel's rho[0].  RK: the batch carries per-edge kernels (an edge with one uses it; a
-// landmark edge without one still follows dcs_phi); RK = false is the code as it was without them.  RAW: e^T Omega e, no kernel at all.
+// 0 beyond the last): g2o computeActiveErrors + the robust kernel's rho[0].  RK: the batch carries per-edge kernels.
+// RAW: e^T Omega e, no kernel at all.
 template <bool RK = false, bool RAW = false>
 __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& sg, int e, const double* __restrict__ pose, const double* __restrict__ lmk) {
   double c = 0;
@@ -343,13 +410,11 @@ __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& 
     const int k = sg.eo0 + e;
     const Pose Xi = load_pose(pose, V.eo_i[k]), Xj = load_pose(pose, V.eo_j[k]);
     const int n = V.nEo;
-    const Pose Z{{V.eo_z[0 * (size_t)n + k], V.eo_z[1 * (size_t)n + k], V.eo_z[2 * (size_t)n + k]},
-                 {V.eo_z[3 * (size_t)n + k], V.eo_z[4 * (size_t)n + k], V.eo_z[5 * (size_t)n + k], V.eo_z[6 * (size_t)n + k]}};
     Se3Lin L;
-    se3_error(Xi, Xj, Z, L);
+    se3_error(Xi, Xj, load_meas_pose(V.eo_z, n, k), L);
     if constexpr (RK || RAW) {   // the e2 the robust linearisation forms (se3_e2), then the edge's own kernel
       c = se3_e2(V.eo_w, n, k, L.e);
-      if constexpr (!RAW) { const int rk = V.eo_rk[k]; if (rk) { double r1; const double e2 = c; robust_rho(rk, V.eo_rd[k], e2, c, r1); } }
+      if constexpr (!RAW) { const auto K = info_scale<RK>(V.eo_rk, V.eo_rd, k, 0.0); if (K.kind) c = K.rho0(c); }
       return c;
     }
     double W[36];
@@ -361,62 +426,38 @@ __device__ __forceinline__ double edge_chi2(const BatchView& V, const GraphSeg& 
     }
   } else if (e < sg.neo + sg.nel) {
     const int k = sg.el0 + (e - sg.neo);
-    const int n = V.nEl;
-    const int li = V.el_l[k];
-    const Pose Xi = load_pose(pose, V.el_p[k]);
-    const double* lp = lmk + (size_t)li * 4;
     double err[3];
-    if (V.lm_kind[li] == VT_POINT) {
-      PointLin L;
-      point_error(Xi, Vec3{lp[0], lp[1], lp[2]},
-                  Vec3{V.el_z[0 * (size_t)n + k], V.el_z[1 * (size_t)n + k], V.el_z[2 * (size_t)n + k]}, L);
-      err[0] = L.e[0]; err[1] = L.e[1]; err[2] = L.e[2];
-    } else {
-      plane_error(Xi, Plane{{lp[0], lp[1], lp[2]}, lp[3]},
-                  Plane{{V.el_z[0 * (size_t)n + k], V.el_z[1 * (size_t)n + k], V.el_z[2 * (size_t)n + k]}, V.el_z[3 * (size_t)n + k]}, err);
-    }
+    lm_edge_error(V, k, load_pose(pose, V.el_p[k]), lmk, err);
     double W[9];
-    load_sym3(V.el_w, n, k, W);
+    load_sym3(V.el_w, V.nEl, k, W);
     for (int r = 0; r < 3; ++r) {
       double a = 0;
       for (int s = 0; s < 3; ++s) a += W[r * 3 + s] * err[s];
       c += err[r] * a;
     }
-    if constexpr (RAW) return c;
-    if constexpr (RK) {
-      const int rk = V.el_rk[k];
-      if (rk) { double r1; const double e2 = c; robust_rho(rk, V.el_rd[k], e2, c, r1); return c; }
-    }
-    if (V.dcs_phi > 0) c *= dcs_rho1(V.dcs_phi, c);
-  } else if (e < sg.neo + sg.nel + sg.nell) {   // g2o::EdgePointXYZ: e = (p_b - p_a) - z
+    if constexpr (!RAW) { const auto K = info_scale<RK>(V.el_rk, V.el_rd, k, V.dcs_phi); if (K.kind) c = K.rho0(c); }
+  } else if (e < sg.neo + sg.nel + sg.nell) {
     const int k = sg.ell0 + (e - sg.neo - sg.nel);
-    const size_t n = V.nEll;
-    const double* pa = lmk + (size_t)V.ell_a[k] * 4;
-    const double* pb = lmk + (size_t)V.ell_b[k] * 4;
     double err[3], W[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) err[r] = (pb[r] - pa[r]) - V.ell_z[r * n + k];
-    load_sym3(V.ell_w, (int)n, k, W);
+    ll_edge_error(V, lmk, k, err);
+    load_sym3(V.ell_w, V.nEll, k, W);
     c = quad3(W, err);
-    if constexpr (RK && !RAW) { const int rk = V.ell_rk[k]; if (rk) { double r1; const double e2 = c; robust_rho(rk, V.ell_rd[k], e2, c, r1); } }
+    if constexpr (!RAW) { const auto K = info_scale<RK>(V.ell_rk, V.ell_rd, k, 0.0); if (K.kind) c = K.rho0(c); }
   } else if (e < edge_count(sg)) {
     const int k = sg.ep0 + (e - sg.neo - sg.nel - sg.nell);
     c = prior_chi2(V, k, pose);
-    if constexpr (RK && !RAW) { const int rk = V.ep_rk[k]; if (rk) { double r1; const double e2 = c; robust_rho(rk, V.ep_rd[k], e2, c, r1); } }
+    if constexpr (!RAW) { const auto K = info_scale<RK>(V.ep_rk, V.ep_rd, k, 0.0); if (K.kind) c = K.rho0(c); }
   }
   return c;
 }
-// the kernel that edge e of segment sg is under: its own, else DCS(dcs_phi) on a landmark edge, else none
-__device__ __forceinline__ void edge_kernel_of(const BatchView& V, const GraphSeg& sg, int e, int& kind, double& delta) {
-  kind = 0; delta = 0.0;
-  const bool own = V.eo_rk != nullptr;
-  if (e < sg.neo) { if (own) { kind = V.eo_rk[sg.eo0 + e]; delta = V.eo_rd[sg.eo0 + e]; } }
-  else if (e < sg.neo + sg.nel) {
-    const int k = sg.el0 + (e - sg.neo);
-    if (own) { kind = V.el_rk[k]; delta = V.el_rd[k]; }
-    if (!kind && V.dcs_phi > 0) { kind = RK_DCS; delta = V.dcs_phi; }
-  } else if (e < sg.neo + sg.nel + sg.nell) { const int k = sg.ell0 + (e - sg.neo - sg.nel); if (own) { kind = V.ell_rk[k]; delta = V.ell_rd[k]; } }
-  else if (e < edge_count(sg)) { const int k = sg.ep0 + (e - sg.neo - sg.nel - sg.nell); if (own) { kind = V.ep_rk[k]; delta = V.ep_rd[k]; } }
+// the kernel that edge e of segment sg is under (edge_chi2's order of edges)
+template <bool RK>
+__device__ __forceinline__ EdgeKernel<RK> edge_kernel_of(const BatchView& V, const GraphSeg& sg, int e) {
+  if (e < sg.neo) return info_scale<RK>(V.eo_rk, V.eo_rd, sg.eo0 + e, 0.0);
+  if (e < sg.neo + sg.nel) return info_scale<RK>(V.el_rk, V.el_rd, sg.el0 + (e - sg.neo), V.dcs_phi);
+  if (e < sg.neo + sg.nel + sg.nell) return info_scale<RK>(V.ell_rk, V.ell_rd, sg.ell0 + (e - sg.neo - sg.nel), 0.0);
+  if (e < edge_count(sg)) return info_scale<RK>(V.ep_rk, V.ep_rd, sg.ep0 + (e - sg.neo - sg.nel - sg.nell), 0.0);
+  return {RK_NONE, 0.0};
 }
 
 }  // namespace sslam

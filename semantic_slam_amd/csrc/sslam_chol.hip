@@ -159,7 +159,6 @@ void chol_plan_free(CholPlan* p) {
 template <int K>
 __device__ __forceinline__ int quad_bcast(int v) { return __builtin_amdgcn_mov_dpp(v, K * 0x55, 0xF, 0xF, true); }
 
-struct alignas(16) D2 { double a, b; };
 // one update S(i,j) -= L(i,k) L(j,k)^T (and rhs_j -= L(j,k) y_k on the diagonal) restricted to this lane's 3 x 3 tile.
 // Ls / Ys: the piece's LDS mirror of L / y.  DK (width of the source column k) is a template parameter so that every offset is an
 // instruction immediate; for DK = 6 the three rows of each operand are 16-byte aligned (blocks are stored at even offsets) and

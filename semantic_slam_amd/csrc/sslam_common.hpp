@@ -52,6 +52,10 @@ struct PinnedScratch {
   ~PinnedScratch() { if (p) (void)hipHostFree(p); }
 };
 
+// two doubles that travel as one 16-byte load or store
+struct alignas(16) D2 { double a, b; };
+__device__ __forceinline__ void store2(double* p, double a, double b) { *reinterpret_cast<D2*>(p) = D2{a, b}; }
+
 }  // namespace sslam
 
 #define SSLAM_HIP_TRY(expr)                                                                          \

@@ -49,25 +49,21 @@ __global__ __launch_bounds__(kEdgeChunk) void k_chi2(BatchView V, const double* 
 
 // sslam_graph_edge_chi2: one thread per requested edge (loc: its graph-local index in edge_chi2's order) -> e^T Omega e, rho0 and rho1 of the
 // kernel the edge is under, at the current estimates.  out: [3][n].  No atomics, no reduction.
+template <bool RK>
 __global__ __launch_bounds__(64) void k_edge_chi2(BatchView V, int g, const int* __restrict__ loc, int n, double* __restrict__ out) {
   const int t = blockIdx.x * 64 + threadIdx.x;
   if (t >= n) return;
   const GraphSeg sg = V.seg[g];
   const int e = loc[t];
   const double e2 = edge_chi2<false, true>(V, sg, e, V.pose, V.lmk);
-  int kind; double delta, r0, r1;
-  edge_kernel_of(V, sg, e, kind, delta);
-  robust_rho(kind, delta, e2, r0, r1);
+  double r0 = e2, r1 = 1.0;
+  const auto K = edge_kernel_of<RK>(V, sg, e);
+  if (K.kind) K.rho(e2, r0, r1);
   out[t] = e2; out[(size_t)n + t] = r0; out[2 * (size_t)n + t] = r1;
 }
 
 // off-diagonal block codes: >= 0 owner edge, <= -2 a further edge on the same vertex pair, -1 none
 __device__ __forceinline__ int decode_blk(int code) { return code <= -2 ? -2 - code : code; }
-__device__ __forceinline__ Pose load_meas_pose(const double* z, int n, int k) {
-  return Pose{{z[0 * (size_t)n + k], z[1 * (size_t)n + k], z[2 * (size_t)n + k]},
-              {z[3 * (size_t)n + k], z[4 * (size_t)n + k], z[5 * (size_t)n + k], z[6 * (size_t)n + k]}};
-}
-struct alignas(16) D2 { double a, b; };
 
 // ---- Jacobian build (gather form, deterministic, no atomics): one THREAD per pose row ---------------
 // No redundancy across lanes: a thread evaluates each incident edge once, keeps the 6x6 Jacobian of
@@ -77,7 +73,6 @@ struct alignas(16) D2 { double a, b; };
 // are 16-byte (two doubles): half the write requests of scalar stores at a 288-byte lane stride.
 constexpr int kRowThreads = 64;
 __device__ __forceinline__ int tri21(int a, int c) { return a * 6 - (a * (a - 1)) / 2 + (c - a); }   // a <= c
-__device__ __forceinline__ void store2(double* p, double a, double b) { *reinterpret_cast<D2*>(p) = D2{a, b}; }
 
 __device__ __forceinline__ Pose load_pose16(const double* a, int idx) {   // four 16-byte loads of the 64-byte record
   const D2* p = reinterpret_cast<const D2*>(a + (size_t)idx * 8);
@@ -87,13 +82,11 @@ __device__ __forceinline__ Pose load_pose16(const double* a, int idx) {   // fou
 
 // EdgeSE3Plane (reference include/g2o/edge_se3_plane.hpp:8-48; g2o's BaseBinaryEdge numeric Jacobian: central differences, delta 1e-9): 19
 // evaluations of the error per edge -- the error itself, +/- delta on the six components of the pose and on the three of the plane -- each ~900
-// FP64 instructions (four atan2, two sincos pairs).  Until round 6 the pose row's thread did all 19 for every plane slot (at one wave per SIMD:
-// the kernel holds 304 VGPRs) and the landmark row's lanes the 7 of the plane side again: 15.6 ms per 512-graph build against 2.1 ms with
-// point landmarks.  Now a thread per (edge, evaluation) -- a pair of + / - evaluations sits in neighbouring lanes and meets through one shuffle --,
-// full occupancy, every evaluation done once; the row kernels read the 30 doubles.  Same functions on the same inputs: the values the row kernels used to compute themselves.
+// FP64 instructions.  A thread per (edge, evaluation) -- a pair of + / - evaluations sits in neighbouring lanes and meets through one shuffle --
+// at full occupancy, every evaluation done once; the row kernels read the 30 doubles (DESIGN.md section 5 has the timings).
 constexpr int kPjDoubles = 30;   // {e 3 | J_l 3 x 3 row-major | J_i 3 x 6 row-major}
 // Two regions of workgroups so that a wave runs ONE of the two perturbation paths (se3_oplus / pl_oplus: ~150 / ~300 instructions next to the
-// ~400 of the error itself; mixed in one wave both were paid by every lane: 4.84 -> 3.5 ms per 512 graphs): blocks [0, blocksA) hold fourteen
+// ~400 of the error itself; mixed in one wave both would be paid by every lane): blocks [0, blocksA) hold fourteen
 // lanes per edge -- lane 0 the error, lane 1 idle, lanes 2 + 2 d / 3 + 2 d the + / - evaluations of pose component d --, the blocks behind them
 // six lanes per edge, the + / - evaluations of the three plane components.  A pair sits in neighbouring lanes (even lane counts per edge).
 __global__ __launch_bounds__(256) void k_plane_jacobians(BatchView V, int blocksA) {
@@ -114,6 +107,7 @@ __global__ __launch_bounds__(256) void k_plane_jacobians(BatchView V, int blocks
   const double delta = 1e-9;
   double err[3] = {0, 0, 0};
   if (live) {
+    // (loads spelled out: through load_plane / el_meas_plane the error contracts differently, 3e-10 of H after the central differences)
     const size_t n = (size_t)V.nEl;
     Pose Xi = load_pose(V.pose, pi);
     const double* lp = V.lmk + (size_t)li * 4;
@@ -149,21 +143,11 @@ __global__ __launch_bounds__(256) void k_plane_jacobians(BatchView V, int blocks
 }
 
 // Pose-row kernel: every slot (incident edge) of a row evaluated by the row's own thread, contributions summed in slot order.
-// What rounds 2-4 built and measured against it -- all correct, none faster, all removed from the library in round 5 (DESIGN.md section 5
-// keeps the numbers): a hand-over form that evaluates a chain edge once (1.97 vs 2.00 ms per 512-graph build, but it adds the handed block
-// last and LM's accept / reject decisions at convergence follow the last bit of H: 13 extra rejected trials per 20 iterations); two
-// role-specialised waves per 64-row tile (216 VGPRs, two waves per SIMD: 2.23 vs 1.89 ms); EdgeSE3 and landmark slots in two launches
-// (2.52 vs 2.01 ms); a row-wise EdgeSE3 form with 222 VGPRs (2.04 vs 1.96 ms); the kernel compiled for two / three waves per SIMD (50 / 164
-// spilled registers: 2.46 / 4.26 vs 2.12 ms); staged, coalesced block stores, also with the next round's operands requested before the
-// stores (2.06 vs 2.02, 2.09 vs 2.07 ms).  What they established: the build is bound by the life time of ONE wave per SIMD (304 VGPRs: both
-// Jacobians 45, Omega 27, J^T Omega 36, an off-diagonal block 36 doubles) -- instruction issue of a single FP64 wave plus the round trips it
-// cannot overlap -- not by bytes, occupancy alone, or the shape of its stores.  Round 5 closed the occupancy question: the SAME arithmetic
-// with shorter live ranges (J_j built where the off-diagonal block is formed, that block two rows at a time, the own pose re-fetched per
-// slot) compiles to 231 VGPRs -- two waves per SIMD, no spill -- and ran 2.33 vs 2.10 ms per 512-graph build.  By the raw counters the build
-// moves ~13 MB per graph (both endpoint rows read an EdgeSE3, the landmark rows read every landmark edge again) at ~3.2 TB/s of mixed reads
-// and scattered 16-byte writes: it sits at what HBM gives such a mix, and only fewer bytes would make it faster.
-// RK: the batch carries per-edge robust kernels; an edge's Omega is scaled by its rho1 (e2 from the unmasked Omega: shards scale alike, and both
-// endpoint rows of an EdgeSE3 form the same value).  RK = false is the kernel above, untouched: its live ranges are what bounds it.
+// The kernel is bound by the life time of ONE wave per SIMD (both Jacobians 45, Omega 27, J^T Omega 36, an off-diagonal block 36 doubles live
+// at once: 256 VGPRs + AGPRs) -- the instruction issue of a single FP64 wave plus the round trips it cannot overlap -- not by bytes,
+// occupancy alone or the shape of its stores (DESIGN.md section 5 keeps the forms measured against it).  So nothing here may lengthen a
+// live range: the 3 x 3 block algebra below stays written out.  PL: the batch holds plane landmarks.  SHARD: edge-sharded mode, an edge
+// outside this rank's range counts with Omega = 0.  RK: the batch carries per-edge robust kernels; <RK = false> holds no code for them.
 template <bool PL, bool SHARD, bool RK>
 __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchView V) {
   __shared__ double accD[27][kRowThreads];   // this row's diagonal block (upper triangle) and rhs: a thread-private LDS column, conflict free
@@ -176,7 +160,7 @@ __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchVie
   for (int k = 0; k < 27; ++k) accD[k][tid] = 0.0;
   const int s0 = V.pslot_ptr[row], s1 = V.pslot_ptr[row + 1];
   const int own = V.prow_pose[row];
-  const int sh_lo = SHARD ? V.shard_lo[V.prow_graph[row]] : 0, sh_hi = SHARD ? V.shard_hi[V.prow_graph[row]] : 0;
+  const int g = V.prow_graph[row];
   const Pose Xown = load_pose16(V.pose, own);   // this row's vertex: loaded once, reused by every slot
   for (int s = s0; s < s1; ++s) {
     const int4 rec = V.pslot_rec[s];
@@ -194,13 +178,10 @@ __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchVie
       double P[9], Q[9], R[9];   // Omega = [[P, Q], [Q^T, R]]
       // edge-sharded mode: an edge outside this rank's range contributes nothing (everything below is linear in Omega; the owner
       // of an off-diagonal block still writes it, as zeros)
-      const int eid = SHARD ? V.eo_id[e] : 0;
-      double mk = (!SHARD || (eid >= sh_lo && eid < sh_hi)) ? 1.0 : 0.0;
+      double mk = in_shard<SHARD>(V, g, V.eo_id, e) ? 1.0 : 0.0;
       auto w21 = [&](int q) { return V.eo_w[(size_t)q * n + e]; };
-      if constexpr (RK) {
-        const int rk = V.eo_rk[e];
-        if (rk) mk *= robust_rho1(rk, V.eo_rd[e], se3_e2(V.eo_w, n, e, L.e));
-      }
+      const auto K = info_scale<RK>(V.eo_rk, V.eo_rd, e, 0.0);
+      if (K.kind) mk *= K.rho1(se3_e2(V.eo_w, n, e, L.e));
 #pragma unroll
       for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -311,14 +292,10 @@ __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchVie
                              M22[a * 3] * L.e[3] + M22[a * 3 + 1] * L.e[4] + M22[a * 3 + 2] * L.e[5];
       }
     } else {
-      const int n = V.nEl;
-      const Pose Xi = Xown;
-      const double* lp = V.lmk + (size_t)ib * 4;
-      auto zl = [&](int k) { return V.el_z[k * (size_t)n + e]; };
       double err[3], Ji[18], Jl[9];   // Ji row-major 3x6, Jl row-major 3x3
       if (!PL || V.lm_kind[ib] == VT_POINT) {
         PointLin L;
-        point_error(Xi, Vec3{lp[0], lp[1], lp[2]}, Vec3{zl(0), zl(1), zl(2)}, L);
+        point_error(Xown, load_point(V.lmk, ib), el_meas_point(V, e), L);
         point_jacobians(L, Ji, Jl);
         err[0] = L.e[0]; err[1] = L.e[1]; err[2] = L.e[2];
       } else {
@@ -335,19 +312,17 @@ __global__ __launch_bounds__(kRowThreads, 1) void k_linearize_rowthread(BatchVie
         for (int q = 0; q < 18; ++q) Ji[q] = v[12 + q];
       }
       double W[9];
-      load_sym3(V.el_w, n, e, W);
-      double dcs = 1.0;
-      const int rk = RK ? V.el_rk[e] : 0;
-      if (RK && rk) dcs = robust_rho1(rk, V.el_rd[e], quad3(W, err));
-      else if (V.dcs_phi > 0) dcs = dcs_rho1(V.dcs_phi, quad3(W, err));   // from the unmasked Omega: every rank scales its share alike
-      const int lid = SHARD ? V.el_id[e] : 0;
-      if (SHARD && !(lid >= sh_lo && lid < sh_hi)) {
+      load_sym3(V.el_w, V.nEl, e, W);
+      const auto K = info_scale<RK>(V.el_rk, V.el_rd, e, V.dcs_phi);
+      const double rho1 = K.kind ? K.rho1(quad3(W, err)) : 1.0;   // from the unmasked Omega: every rank scales its share alike
+      // (the zero and scale loops stay written out, here and in the other kernels: as functions they change this kernel's instructions)
+      if (!in_shard<SHARD>(V, g, V.el_id, e)) {
 #pragma unroll
         for (int q = 0; q < 9; ++q) W[q] = 0.0;
       }
-      if ((RK && rk) || V.dcs_phi > 0) {
+      if (K.kind) {
 #pragma unroll
-        for (int q = 0; q < 9; ++q) W[q] *= dcs;
+        for (int q = 0; q < 9; ++q) W[q] *= rho1;
       }
       double WJi[18], We[3];
 #pragma unroll
@@ -410,15 +385,13 @@ __global__ __launch_bounds__(64) void k_linearize_priors(BatchView V) {
     const int k = V.ep_edge[s];
     double err[3], W[9];
     prior_error(V, k, X, err, W);
-    if constexpr (RK) {
-      const int rk = V.ep_rk[k];
-      if (rk) {
-        const double r1 = robust_rho1(rk, V.ep_rd[k], quad3(W, err));
+    const auto K = info_scale<RK>(V.ep_rk, V.ep_rd, k, 0.0);
+    if (K.kind) {
+      const double rho1 = K.rho1(quad3(W, err));
 #pragma unroll
-        for (int q = 0; q < 9; ++q) W[q] *= r1;
-      }
+      for (int q = 0; q < 9; ++q) W[q] *= rho1;
     }
-    if (SHARD && !(V.ep_id[k] >= V.shard_lo[g] && V.ep_id[k] < V.shard_hi[g])) {
+    if (!in_shard<SHARD>(V, g, V.ep_id, k)) {
 #pragma unroll
       for (int q = 0; q < 9; ++q) W[q] = 0.0;
     }
@@ -454,6 +427,8 @@ __global__ __launch_bounds__(64) void k_linearize_priors(BatchView V) {
 
 // landmark rows: 16 lanes per landmark, each lane walks a strided subset of the incident edges,
 // butterfly reduction in a fixed order.
+// (Three things stay spelled out here, because each one alone, written through its helper, changes bytes of H: the point loads and
+// ll_edge_error in the unsharded <PL = true> forms, 1e-20 of max |H|, and in_shard in the <SHARD = true> forms, 2e-18.)
 template <bool PL, bool SHARD, bool RK>
 __global__ __launch_bounds__(256) void k_linearize_lm_rows(BatchView V) {
   const int l = blockIdx.x * 16 + (threadIdx.x >> 4);
@@ -489,15 +464,11 @@ __global__ __launch_bounds__(256) void k_linearize_lm_rows(BatchView V) {
       }
       double W[9];
       load_sym3(V.el_w, n, e, W);
-      const int rk = RK ? V.el_rk[e] : 0;
-      if (RK && rk) {
-        const double r1 = robust_rho1(rk, V.el_rd[e], quad3(W, err));
+      const auto K = info_scale<RK>(V.el_rk, V.el_rd, e, V.dcs_phi);
+      if (K.kind) {
+        const double rho1 = K.rho1(quad3(W, err));
 #pragma unroll
-        for (int q = 0; q < 9; ++q) W[q] *= r1;
-      } else if (V.dcs_phi > 0) {
-        const double r1 = dcs_rho1(V.dcs_phi, quad3(W, err));
-#pragma unroll
-        for (int q = 0; q < 9; ++q) W[q] *= r1;
+        for (int q = 0; q < 9; ++q) W[q] *= rho1;
       }
       if (SHARD) {
         const int g = V.lrow_graph[l];
@@ -533,13 +504,11 @@ __global__ __launch_bounds__(256) void k_linearize_lm_rows(BatchView V) {
 #pragma unroll
       for (int r = 0; r < 3; ++r) err[r] = (pb[r] - pa[r]) - V.ell_z[r * n + k];
       load_sym3(V.ell_w, (int)n, k, W);
-      if constexpr (RK) {
-        const int rk = V.ell_rk[k];
-        if (rk) {
-          const double r1 = robust_rho1(rk, V.ell_rd[k], quad3(W, err));
+      const auto K = info_scale<RK>(V.ell_rk, V.ell_rd, k, 0.0);
+      if (K.kind) {
+        const double rho1 = K.rho1(quad3(W, err));
 #pragma unroll
-          for (int q = 0; q < 9; ++q) W[q] *= r1;
-        }
+        for (int q = 0; q < 9; ++q) W[q] *= rho1;
       }
       if (SHARD) {
         const int g = V.lrow_graph[l];
@@ -582,22 +551,16 @@ __global__ __launch_bounds__(64) void k_linearize_ll(BatchView V) {
   double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int e = e0; e < e1; ++e) {
     const int k = V.llblk_edge[e];
-    if (SHARD && !(V.ell_id[k] >= V.shard_lo[g] && V.ell_id[k] < V.shard_hi[g])) continue;
+    if (!in_shard<SHARD>(V, g, V.ell_id, k)) continue;
     double W[9];
     load_sym3(V.ell_w, V.nEll, k, W);
-    if constexpr (RK) {
-      const int rk = V.ell_rk[k];
-      if (rk) {   // the same e2 from the same inputs as the two landmark rows of the edge form
-        const size_t n = V.nEll;
-        const double* pa = V.lmk + (size_t)V.ell_a[k] * 4;
-        const double* pb = V.lmk + (size_t)V.ell_b[k] * 4;
-        double err[3];
+    const auto K = info_scale<RK>(V.ell_rk, V.ell_rd, k, 0.0);
+    if (K.kind) {   // the same e2 from the same inputs as the two landmark rows of the edge form
+      double err[3];
+      ll_edge_error(V, V.lmk, k, err);
+      const double rho1 = K.rho1(quad3(W, err));
 #pragma unroll
-        for (int r = 0; r < 3; ++r) err[r] = (pb[r] - pa[r]) - V.ell_z[r * n + k];
-        const double r1 = robust_rho1(rk, V.ell_rd[k], quad3(W, err));
-#pragma unroll
-        for (int q = 0; q < 9; ++q) W[q] *= r1;
-      }
+      for (int q = 0; q < 9; ++q) W[q] *= rho1;
     }
 #pragma unroll
     for (int q = 0; q < 9; ++q) acc[q] -= W[q];
@@ -606,31 +569,35 @@ __global__ __launch_bounds__(64) void k_linearize_ll(BatchView V) {
   for (int q = 0; q < 9; ++q) V.Hll_off[(size_t)i * 9 + q] = acc[q];
 }
 
-// Further edges on an already-owned vertex pair (e.g. a repeated loop closure): their off-diagonal
-// contributions are added serially, in edge order, after the owners have written the blocks.
-template <bool RK>
+// The duplicate lists (dup[0 .. n), edges whose off-diagonal block another edge owns) are ordered by block.  One past the end of the run that
+// entry t heads, or t when its predecessor lies on the same block.  shift: the low bits of a block code outside its index (an SE3 block's swap bit).
+__device__ __forceinline__ int dup_run_end(const int* __restrict__ dup, const int* __restrict__ blk_of, int shift, int n, int t) {
+  auto blk = [&](int d) { return decode_blk(blk_of[dup[d]]) >> shift; };
+  if (t >= n || (t > 0 && blk(t - 1) == blk(t))) return t;
+  int d = t + 1;
+  while (d < n && blk(d) == blk(t)) ++d;
+  return d;
+}
+
+// Further edges on an already-owned vertex pair (e.g. a repeated loop closure): their off-diagonal contributions are added after the
+// owners have written the blocks.  Thread t owns the run of duplicates that share a block with entry t and adds them serially, in edge order.
+template <bool SHARD, bool RK>
 __global__ void k_linearize_dups(BatchView V) {
-  // the host orders the duplicate lists by block; thread t owns the run of entries that share its block
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  for (int d = t; d < V.nDupEo; d = V.nDupEo) {
-    if (d > 0 && (decode_blk(V.eo_blk[V.dup_eo[d - 1]]) >> 1) == (decode_blk(V.eo_blk[V.dup_eo[d]]) >> 1)) break;  // not a run head
-    for (; d < V.nDupEo && (d == t || (decode_blk(V.eo_blk[V.dup_eo[d]]) >> 1) == (decode_blk(V.eo_blk[V.dup_eo[t]]) >> 1)); ++d) {
+  for (int d = t, end = dup_run_end(V.dup_eo, V.eo_blk, 1, V.nDupEo, t); d < end; ++d) {
     const int k = V.dup_eo[d];
     const int pi = V.eo_i[k], pj = V.eo_j[k];
-    const int gk = V.prow_graph[V.pose_row[pi]];
-    if (!V.lm[gk].lin) continue;
-    if (!(V.eo_id[k] >= V.shard_lo[gk] && V.eo_id[k] < V.shard_hi[gk])) continue;
+    const int g = V.prow_graph[V.pose_row[pi]];
+    if (!V.lm[g].lin || !in_shard<SHARD>(V, g, V.eo_id, k)) continue;
     Se3Lin L;
     se3_error(load_pose(V.pose, pi), load_pose(V.pose, pj), load_meas_pose(V.eo_z, V.nEo, k), L);
     double Ji[36], Jj[36], W[36], WJ[36];
     se3_full_jacobians(L, Ji, Jj);
     load_sym6(V.eo_w, V.nEo, k, W);
-    if constexpr (RK) {
-      const int rk = V.eo_rk[k];
-      if (rk) {
-        const double r1 = robust_rho1(rk, V.eo_rd[k], se3_e2(V.eo_w, V.nEo, k, L.e));
-        for (int q = 0; q < 36; ++q) W[q] *= r1;
-      }
+    const auto K = info_scale<RK>(V.eo_rk, V.eo_rd, k, 0.0);
+    if (K.kind) {
+      const double rho1 = K.rho1(se3_e2(V.eo_w, V.nEo, k, L.e));
+      for (int q = 0; q < 36; ++q) W[q] *= rho1;
     }
     for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) { double a = 0; for (int s = 0; s < 6; ++s) a += W[r * 6 + s] * Jj[s * 6 + c]; WJ[r * 6 + c] = a; }
     const int blk = decode_blk(V.eo_blk[k]);
@@ -639,48 +606,34 @@ __global__ void k_linearize_dups(BatchView V) {
       double a = 0; for (int s = 0; s < 6; ++s) a += Ji[s * 6 + r] * WJ[s * 6 + c];
       O[(blk & 1) ? c * 6 + r : r * 6 + c] += a;
     }
-    }
   }
-  for (int d = t; d < V.nDupEl; d = V.nDupEl) {
-    if (d > 0 && decode_blk(V.el_blk[V.dup_el[d - 1]]) == decode_blk(V.el_blk[V.dup_el[d]])) break;
-    for (; d < V.nDupEl && (d == t || decode_blk(V.el_blk[V.dup_el[d]]) == decode_blk(V.el_blk[V.dup_el[t]])); ++d) {
+  for (int d = t, end = dup_run_end(V.dup_el, V.el_blk, 0, V.nDupEl, t); d < end; ++d) {
     const int k = V.dup_el[d];
     const int pi = V.el_p[k], li = V.el_l[k];
-    const int gk = V.prow_graph[V.pose_row[pi]];
-    if (!V.lm[gk].lin) continue;
-    if (!(V.el_id[k] >= V.shard_lo[gk] && V.el_id[k] < V.shard_hi[gk])) continue;
+    const int g = V.prow_graph[V.pose_row[pi]];
+    if (!V.lm[g].lin || !in_shard<SHARD>(V, g, V.el_id, k)) continue;
     const Pose Xi = load_pose(V.pose, pi);
-    const double* lp = V.lmk + (size_t)li * 4;
-    const int n = V.nEl;
-    double Ji[18], Jl[9], W[9];
-    if (V.lm_kind[li] == VT_POINT) {
+    const bool is_point = V.lm_kind[li] == VT_POINT;
+    double err[3], Ji[18], Jl[9], W[9];
+    if (is_point) {
       PointLin L;
-      point_error(Xi, Vec3{lp[0], lp[1], lp[2]}, Vec3{V.el_z[0 * (size_t)n + k], V.el_z[1 * (size_t)n + k], V.el_z[2 * (size_t)n + k]}, L);
+      point_error(Xi, load_point(V.lmk, li), el_meas_point(V, k), L);
       point_jacobians(L, Ji, Jl);
+      err[0] = L.e[0]; err[1] = L.e[1]; err[2] = L.e[2];
     } else {
-      plane_jacobians(Xi, Plane{{lp[0], lp[1], lp[2]}, lp[3]},
-                      Plane{{V.el_z[0 * (size_t)n + k], V.el_z[1 * (size_t)n + k], V.el_z[2 * (size_t)n + k]}, V.el_z[3 * (size_t)n + k]}, Ji, Jl);
+      plane_jacobians(Xi, load_plane(V.lmk, li), el_meas_plane(V, k), Ji, Jl);
     }
-    load_sym3(V.el_w, n, k, W);
-    const int rk = RK ? V.el_rk[k] : 0;
-    if ((RK && rk) || V.dcs_phi > 0) {
-      double err[3];
-      if (V.lm_kind[li] == VT_POINT) {
-        PointLin L;
-        point_error(Xi, Vec3{lp[0], lp[1], lp[2]}, Vec3{V.el_z[0 * (size_t)n + k], V.el_z[1 * (size_t)n + k], V.el_z[2 * (size_t)n + k]}, L);
-        err[0] = L.e[0]; err[1] = L.e[1]; err[2] = L.e[2];
-      } else {
-        plane_error(Xi, Plane{{lp[0], lp[1], lp[2]}, lp[3]},
-                    Plane{{V.el_z[0 * (size_t)n + k], V.el_z[1 * (size_t)n + k], V.el_z[2 * (size_t)n + k]}, V.el_z[3 * (size_t)n + k]}, err);
-      }
-      const double r1 = (RK && rk) ? robust_rho1(rk, V.el_rd[k], quad3(W, err)) : dcs_rho1(V.dcs_phi, quad3(W, err));
-      for (int q = 0; q < 9; ++q) W[q] *= r1;
+    load_sym3(V.el_w, V.nEl, k, W);
+    const auto K = info_scale<RK>(V.el_rk, V.el_rd, k, V.dcs_phi);
+    if (K.kind) {
+      if (!is_point) lm_edge_error(V, k, Xi, V.lmk, err);   // a plane's Jacobians are central differences: they leave no error behind
+      const double rho1 = K.rho1(quad3(W, err));
+      for (int q = 0; q < 9; ++q) W[q] *= rho1;
     }
     double WJl[9];
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) WJl[r * 3 + c] = W[r * 3 + 0] * Jl[c] + W[r * 3 + 1] * Jl[3 + c] + W[r * 3 + 2] * Jl[6 + c];
     double* O = V.Hpl + (size_t)decode_blk(V.el_blk[k]) * 18;
     for (int r = 0; r < 6; ++r) for (int c = 0; c < 3; ++c) O[r * 3 + c] += Ji[r] * WJl[c] + Ji[6 + r] * WJl[3 + c] + Ji[12 + r] * WJl[6 + c];
-    }
   }
 }
 
@@ -1317,54 +1270,56 @@ static int launch_check(const char* what) {
   return 0;
 }
 
+// f(std::bool_constant<v>) for a run-time bool: how a launch picks a kernel's bool template arguments
+template <class F>
+static void with_bool(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+
+// The launches of one linearisation into the H and b arrays of V.  PL: the batch holds plane landmarks; SHARD: edge-sharded mode; RK: the
+// batch carries per-edge robust kernels.  Stream order matters: the priors and the duplicates add onto what the row kernels wrote.
+template <bool PL, bool SHARD, bool RK>
+static void launch_linearize(Batch& b, const BatchView& V) {
+  if (PL && V.nEl > 0) {
+    const long long bA = ((long long)V.nEl * 14 + 255) / 256, bB = ((long long)V.nEl * 6 + 255) / 256;
+    hipLaunchKernelGGL(k_plane_jacobians, dim3((unsigned)(bA + bB)), dim3(256), 0, b.stream, V, (int)bA);
+  }
+  if (V.nPr > 0) hipLaunchKernelGGL((k_linearize_rowthread<PL, SHARD, RK>), dim3((V.nPr + kRowThreads - 1) / kRowThreads), dim3(kRowThreads), 0, b.stream, V);
+  if (V.nEpRows > 0) hipLaunchKernelGGL((k_linearize_priors<SHARD, RK>), dim3((V.nEpRows + 63) / 64), dim3(64), 0, b.stream, V);
+  if (V.nLr > 0) hipLaunchKernelGGL((k_linearize_lm_rows<PL, SHARD, RK>), dim3((V.nLr + 15) / 16), dim3(256), 0, b.stream, V);
+  if (V.nLL > 0) hipLaunchKernelGGL((k_linearize_ll<SHARD, RK>), dim3((V.nLL + 63) / 64), dim3(64), 0, b.stream, V);
+  if (V.nDupEo + V.nDupEl > 0) hipLaunchKernelGGL((k_linearize_dups<SHARD, RK>), dim3((std::max(V.nDupEo, V.nDupEl) + 63) / 64), dim3(64), 0, b.stream, V);
+}
+
 // BlockSolver::buildSystem for the active graphs of the batch
 static int batch_linearize(Batch& b) {
   ScopedTimer t(b, "linearize");
-  b.V.dcs_phi = b.graphs[0]->opt.dcs_phi;   // read live like pcg_tol / solver: an option set after the batch was built must not be ignored (ADVICE r3)
+  b.V.dcs_phi = b.graphs[0]->opt.dcs_phi;   // read live like pcg_tol / solver: an option set after the batch was built must not be ignored
   const BatchView& V = b.V;
-  const int nblk = (V.nPr + kRowThreads - 1) / kRowThreads;
-#define SSLAM_LAUNCH_LIN(PLV, SHV, RKV)                                                                                               \
-  {                                                                                                                                   \
-    if (PLV && V.nEl > 0) {                                                                                                           \
-      const long long bA = ((long long)V.nEl * 14 + 255) / 256, bB = ((long long)V.nEl * 6 + 255) / 256;                                \
-      hipLaunchKernelGGL(k_plane_jacobians, dim3((unsigned)(bA + bB)), dim3(256), 0, b.stream, V, (int)bA);                              \
-    }                                                                                                                                 \
-    if (V.nPr > 0) hipLaunchKernelGGL((k_linearize_rowthread<PLV, SHV, RKV>), dim3(nblk), dim3(kRowThreads), 0, b.stream, V);          \
-    if (V.nEpRows > 0) hipLaunchKernelGGL((k_linearize_priors<SHV, RKV>), dim3((V.nEpRows + 63) / 64), dim3(64), 0, b.stream, V);     \
-    if (V.nLr > 0) hipLaunchKernelGGL((k_linearize_lm_rows<PLV, SHV, RKV>), dim3((V.nLr + 15) / 16), dim3(256), 0, b.stream, V);       \
-    if (V.nLL > 0) hipLaunchKernelGGL((k_linearize_ll<SHV, RKV>), dim3((V.nLL + 63) / 64), dim3(64), 0, b.stream, V);                  \
-    if (V.nDupEo + V.nDupEl > 0) hipLaunchKernelGGL(k_linearize_dups<RKV>, dim3((std::max(V.nDupEo, V.nDupEl) + 63) / 64), dim3(64), 0, b.stream, V); \
+  const auto launch = [&](auto sh, const BatchView& Vl) {
+    with_bool(b.T.has_planes, [&](auto pl) {
+      with_bool(b.has_robust, [&](auto rk) { launch_linearize<decltype(pl)::value, decltype(sh)::value, decltype(rk)::value>(b, Vl); });
+    });
+  };
+  if (!b.sharded) {
+    launch(std::false_type{}, V);
+    return launch_check("linearize");
   }
-  // a batch with per-edge robust kernels takes the <RK = true> instantiations; every other batch the kernels as they always were
-#define SSLAM_LAUNCH_LIN_RK(PLV, SHV) { if (b.has_robust) SSLAM_LAUNCH_LIN(PLV, SHV, true) else SSLAM_LAUNCH_LIN(PLV, SHV, false) }
-  // (Round 4 could run the landmark-row kernel on a second stream next to the pose-row kernel: +4 % on one stream, -24 % inside a stream
-  // group, where every part forked and joined its own second stream at every step -- removed in round 5.)
-  if (b.sharded) {
-    // edge-sharded mode: the rank-partial system is built in its own buffer and summed OUT OF PLACE into [H || b].  A graph that does not
-    // re-linearise in this step (a rejected trial being retried, a finished graph) keeps its old partial system there, so the sum over
-    // ranks is again the system it already had: the all-reduce is idempotent for it.  (Summing in place would multiply the H of such a
-    // graph by `world` on every step: the damping of a retried trial would fall instead of rising -- round-2 ADVICE.)
-    BatchView Vp = V;
-    Vp.Hpp_diag = b.d_hb_part; Vp.Hll_diag = b.d_hb_part + b.T.hll_base; Vp.Hpp_off = b.d_hb_part + b.T.hpp_off_base;
-    Vp.Hpl = b.d_hb_part + b.T.hpl_base; Vp.Hll_off = b.d_hb_part + b.T.hll_off_base; Vp.bvec = b.d_hb_part + (V.bvec - V.Hpp_diag);
-    {
-      const BatchView& V = Vp;
-      if (b.T.has_planes) SSLAM_LAUNCH_LIN_RK(true, true) else SSLAM_LAUNCH_LIN_RK(false, true)
-    }
-    if (b.comm) {
-      // the partial [H || b] arrays of all ranks -> their sum on every rank: ONE all-reduce over xGMI (RCCL), in stream order;
-      // everything after it (solve, update, chi2, LM control) runs replicated and bit-identical on all ranks
-      const ncclResult_t r = rccl_api().AllReduce(b.d_hb_part, V.Hpp_diag, (size_t)b.hb_doubles, ncclDouble, ncclSum, (ncclComm_t)b.comm, b.stream);
-      if (r != ncclSuccess) return set_error(SSLAM_ERR_HIP, "ncclAllReduce of the normal equations: %s", rccl_api().GetErrorString(r));
-      b.allreduce_calls++;
-    } else {   // no communicator (single-device parity hook): the partial system is what the caller reads
-      SSLAM_HIP_TRY(hipMemcpyAsync(V.Hpp_diag, b.d_hb_part, (size_t)b.hb_doubles * sizeof(double), hipMemcpyDeviceToDevice, b.stream));
-    }
-  } else {
-    if (b.T.has_planes) SSLAM_LAUNCH_LIN_RK(true, false) else SSLAM_LAUNCH_LIN_RK(false, false)
+  // edge-sharded mode: the rank-partial system is built in its own buffer and summed OUT OF PLACE into [H || b].  A graph that does not
+  // re-linearise in this step (a rejected trial being retried, a finished graph) keeps its old partial system there, so the sum over
+  // ranks is again the system it already had: the all-reduce is idempotent for it.  (Summing in place would multiply the H of such a
+  // graph by `world` on every step: the damping of a retried trial would fall instead of rising.)
+  BatchView Vp = V;
+  Vp.Hpp_diag = b.d_hb_part; Vp.Hll_diag = b.d_hb_part + b.T.hll_base; Vp.Hpp_off = b.d_hb_part + b.T.hpp_off_base;
+  Vp.Hpl = b.d_hb_part + b.T.hpl_base; Vp.Hll_off = b.d_hb_part + b.T.hll_off_base; Vp.bvec = b.d_hb_part + (V.bvec - V.Hpp_diag);
+  launch(std::true_type{}, Vp);
+  if (b.comm) {
+    // the partial [H || b] arrays of all ranks -> their sum on every rank: ONE all-reduce over xGMI (RCCL), in stream order;
+    // everything after it (solve, update, chi2, LM control) runs replicated and bit-identical on all ranks
+    const ncclResult_t r = rccl_api().AllReduce(b.d_hb_part, V.Hpp_diag, (size_t)b.hb_doubles, ncclDouble, ncclSum, (ncclComm_t)b.comm, b.stream);
+    if (r != ncclSuccess) return set_error(SSLAM_ERR_HIP, "ncclAllReduce of the normal equations: %s", rccl_api().GetErrorString(r));
+    b.allreduce_calls++;
+  } else {   // no communicator (single-device parity hook): the partial system is what the caller reads
+    SSLAM_HIP_TRY(hipMemcpyAsync(V.Hpp_diag, b.d_hb_part, (size_t)b.hb_doubles * sizeof(double), hipMemcpyDeviceToDevice, b.stream));
   }
-#undef SSLAM_LAUNCH_LIN_RK
-#undef SSLAM_LAUNCH_LIN
   return launch_check("linearize");
 }
 
@@ -1814,7 +1769,7 @@ int sslam_graph_edge_chi2(sslam_graph* h, const int* edge_ids, int n, double* e2
   if (e == hipSuccess) e = hipMalloc((void**)&d_out, out.size() * sizeof(double));
   if (e == hipSuccess) e = hipMemcpyAsync(d_loc, loc.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, b.stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_edge_chi2, dim3((n + 63) / 64), dim3(64), 0, b.stream, b.V, 0, (const int*)d_loc, n, d_out);
+    with_bool(b.has_robust, [&](auto rk) { hipLaunchKernelGGL(k_edge_chi2<decltype(rk)::value>, dim3((n + 63) / 64), dim3(64), 0, b.stream, b.V, 0, (const int*)d_loc, n, d_out); });
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, b.stream);

@@ -132,6 +132,55 @@ def test_linearize_mixed_kinds(gpu_lib, lk, tol):
         assert np.abs(a - f).max() <= (1e-9 if lk == "point" else 1e-6) * np.abs(f).max()
 
 
+def _with_repeated_edges(g0, seed=1):
+    """the construction of test_graph_gpu.test_linearize_with_repeated_edges on the synthetic graph itself, so that GraphProblem.from_synth
+    and NpRobustGraph both see the further edges: EdgeSE3 edges 3 and 17 and landmark edges 5 and 40 once more, edge 3 a third time.  The
+    first repeat of edge 3 and the repeat of landmark edge 5 carry a gross error, the others a small one.  Returns the graph and the edge
+    ids (from_synth order) of the SE3 repeats [gross, small, small] and of the landmark repeats [gross, small]."""
+    rng = np.random.default_rng(seed)
+    g = copy.copy(g0)
+    Eo, El = len(g0.odom_ij), len(g0.lm_ij)
+    so, sl = [3, 17, 3], [5, 40]
+    zo = g0.odom_z[so].copy()
+    zo[:, :3] += rng.normal(0, 1e-3, (3, 3)); zo[0, :3] += [1.0, -1.5, 0.5]
+    zl = g0.lm_z[sl].copy()
+    if g0.landmark_kind == "point":
+        zl[:, :3] += rng.normal(0, 1e-3, (2, 3)); zl[0, :3] += [1.0, 1.5, -1.0]
+    else:
+        zl[:, 3] += rng.normal(0, 1e-3, 2); zl[0, 3] += 1.5
+    g.odom_ij = np.concatenate([g0.odom_ij, g0.odom_ij[so]]); g.odom_z = np.concatenate([g0.odom_z, zo])
+    g.odom_info = np.concatenate([g0.odom_info, g0.odom_info[so]])
+    g.lm_ij = np.concatenate([g0.lm_ij, g0.lm_ij[sl]]); g.lm_z = np.concatenate([g0.lm_z, zl])
+    g.lm_info = np.concatenate([g0.lm_info, g0.lm_info[sl]])
+    return g, Eo + np.arange(3), Eo + 3 + El + np.arange(2)
+
+
+@pytest.mark.parametrize("lk,tol", [("point", 1e-11), ("plane", 2e-5)])
+@pytest.mark.parametrize("mode", ["kernels", "dcs"])
+def test_repeated_edges_take_kernels(gpu_lib, mode, lk, tol):
+    """Further edges on an owned vertex pair go through k_linearize_dups: its robust branch (per-edge kernels on owners and repeats,
+    Huber with one repeat beyond its threshold and one inside, Cauchy) and its DCS branch ("robust_kernel_dcs", no per-edge kernels)."""
+    g, dup_o, dup_l = _with_repeated_edges(make_graph(60, 12, seed=8, landmark_kind=lk))
+    G = _graph(g, [])
+    if mode == "kernels":
+        ref = R.NpRobustGraph(g)
+        n = ref.Eo + ref.El
+        kinds = np.where(np.arange(n) % 2 == 0, R.HUBER, R.CAUCHY)
+        kinds[dup_o] = [R.HUBER, R.CAUCHY, R.HUBER]; kinds[dup_l] = [R.HUBER, R.CAUCHY]
+        _set_all(G, ref, kinds, _widths(ref, bad=[dup_o[0], dup_l[0]]))
+        _, _, r1 = ref.edge_chi2()
+        assert r1[dup_o[0]] < 1 and r1[dup_l[0]] < 1                 # Huber beyond the threshold on a repeat of either class ...
+        assert r1[dup_o[2]] == 1                                     # ... and inside it
+        assert r1[dup_o[1]] < 1 and r1[dup_l[1]] < 1                 # Cauchy
+    else:
+        G.set_option("robust_kernel_dcs", 1.0)
+        ref = R.NpRobustGraph(g, dcs_phi=1.0)
+        _, _, r1 = ref.edge_chi2()
+        assert r1[dup_l[0]] < 1 and np.count_nonzero(r1[ref.Eo:] == 1) > 0
+        assert np.all(r1[:ref.Eo] == 1)                              # DCS follows the landmark edges only
+    _assert_system(G, ref, tol)
+
+
 def test_point_point_edges_take_kernels(gpu_lib):
     """g2o::EdgePointXYZ (the fourth storage class): H, b and chi2 of a small graph against a dense NumPy build"""
     from semantic_slam_amd import GraphSLAM
