@@ -227,6 +227,10 @@ int sslam_graph_oplus(sslam_graph* g, const double* dx);
 void* sslam_debug_plan_create(sslam_graph* const* graphs, int n);
 void sslam_debug_plan_destroy(void* plan);
 int64_t sslam_debug_plan_array(void* plan, const char* name, void* out, int64_t cap_bytes);
+/* The grid sslam_seg_voxel_grid lays over the bounding box lo .. hi of the finite points (host only, the driver's own rule): minb[k] =
+ * floor(lo[k] * (1 / leaf)) in float32, div[k] = cells along axis k.  Returns 0, SSLAM_ERR_INVALID (NULL, leaf not > 0) or
+ * SSLAM_ERR_UNSUPPORTED in the cases listed at sslam_seg_voxel_grid; the outputs are unwritten on an error. */
+int sslam_debug_voxel_geometry(const float lo[3], const float hi[3], float leaf, int32_t minb[3], int64_t div[3]);
 /* ---- batched, device-resident form (MI355X extension) ---------------------------------------
  * B independent graphs laid out contiguously in HBM and optimised together: every kernel runs
  * over the union, LM control (rho, lambda, accept/reject) is per graph on the device. */
@@ -519,11 +523,18 @@ int sslam_seg_distance_filter(sslam_seg* s, const float* xyz, int n, double dmin
 /* plane_segmentation::downsamplePointcloud -> pcl::VoxelGrid (plane_segmentation.cpp:565-581; leaf 0.1 upstream): one centroid per
  * occupied voxel of the bounding box of the finite points, in ascending voxel index (x fastest), optionally with the voxel's point
  * count.  Sums are kept in 2^-20 fixed point with integer atomics (order independent; PCL accumulates in float in the order of an
- * unstable sort).  Returns the number of occupied voxels. */
+ * unstable sort).  Returns the number of occupied voxels (0 for a cloud without a finite point); at most max_out centroids / counts are
+ * written.  The cell of a coordinate x is floor(x * (1 / leaf)) in float32, as in PCL.  SSLAM_ERR_UNSUPPORTED, before any cell is sized or
+ * written: 1 / leaf is not finite; that floor for the lower or the upper bound of the box, taken as a float, lies outside [-2^31, 2^31)
+ * (one absurd finite coordinate does that); an axis with fewer than one cell; more than 2^26 cells (sslam_debug_voxel_geometry is that
+ * rule alone). */
 int sslam_seg_voxel_grid(sslam_seg* s, const float* xyz, int n, float leaf, float* centroids_out, int32_t* counts_out, int max_out);
 /* plane_segmentation::removeOutliers -> pcl::StatisticalOutlierRemoval (plane_segmentation.cpp:583-605; meanK 50, multiplier 1.0
  * upstream): a point stays when its mean distance to its mean_k nearest neighbours (exact search) is not above mean + stddev_mul *
- * standard deviation of those mean distances.  mean_dist_out (optional, n floats; -1 for non-finite points).  Returns the inlier count. */
+ * standard deviation of those mean distances.  mean_dist_out (optional, n floats; -1 for non-finite points).  Returns the inlier count.
+ * xyz is a host pointer.  Only finite points are neighbours: SSLAM_ERR_INVALID when fewer than mean_k + 1 points are finite (n = 0
+ * returns 0), so no mean distance is ever built from a missing neighbour.  A squared distance that overflows float32 is +inf and stays
+ * +inf: the mean distance of such a point is +inf, and when one occurs the threshold is NaN and every finite point is kept. */
 int sslam_seg_statistical_outlier_removal(sslam_seg* s, const float* xyz, int n, int mean_k, double stddev_mul, int32_t* keep_out, int max_out,
                                           float* mean_dist_out);
 

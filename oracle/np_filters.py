@@ -21,17 +21,34 @@ def distance_filter(xyz, dmin=0.3, dmax=3.0):
     return np.nonzero(keep)[0].astype(np.int32)
 
 
+def voxel_geometry(lo, hi, leaf):
+    """(inv, minb[3], div[3]) of the grid over the box lo .. hi, or ValueError where sslam.h refuses with SSLAM_ERR_UNSUPPORTED: 1 / leaf
+    not finite, a bound whose cell index (compared as a float, before any cast) is outside [-2^31, 2^31), an axis without a cell, more
+    than 2^26 cells"""
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        inv = F(1.0) / F(leaf)
+        fl = np.floor((np.asarray(lo, F) * inv).astype(F))
+        fh = np.floor((np.asarray(hi, F) * inv).astype(F))
+    if not np.isfinite(inv):
+        raise ValueError(f"voxel grid: 1 / leaf is not finite (leaf {leaf})")
+    if not ((fl >= -2.0 ** 31) & (fl < 2.0 ** 31) & (fh >= -2.0 ** 31) & (fh < 2.0 ** 31)).all():
+        raise ValueError("voxel grid: the cell index of a bound does not fit 32 bits")
+    minb = fl.astype(np.int64)
+    div = fh.astype(np.int64) - minb + 1
+    if (div < 1).any():
+        raise ValueError("voxel grid: upper bound below the lower bound")
+    if int(div[0]) * int(div[1]) * int(div[2]) > 1 << 26:
+        raise ValueError("voxel grid of more than 2^26 cells")
+    return inv, minb, div
+
+
 def voxel_grid(xyz, leaf=0.1):
     p = np.asarray(xyz, F).reshape(-1, 3)
     fin = np.isfinite(p).all(1)
     q = p[fin]
     if len(q) == 0:
         return np.zeros((0, 3), F), np.zeros(0, np.int32)
-    inv = F(1.0) / F(leaf)
-    lo, hi = q.min(0), q.max(0)
-    minb = np.floor((lo * inv).astype(F)).astype(np.int64)
-    maxb = np.floor((hi * inv).astype(F)).astype(np.int64)
-    div = maxb - minb + 1
+    inv, minb, div = voxel_geometry(q.min(0), q.max(0), leaf)
     ijk = np.floor((q * inv).astype(F)).astype(np.int64) - minb
     cell = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]
     fixed = np.rint(q.astype(np.float64) * 1048576.0).astype(np.int64)
@@ -49,10 +66,13 @@ def statistical_outlier_removal(xyz, mean_k=50, stddev_mul=1.0):
     md = np.full(n, -1.0, F)
     idx = np.nonzero(fin)[0]
     q = p[idx]
+    if n and len(q) < mean_k + 1:       # sslam.h: only finite points are neighbours
+        raise ValueError(f"fewer finite points ({len(q)} of {n}) than mean_k + 1 = {mean_k + 1}")
     for a in range(0, len(q), 512):      # exact k nearest neighbours by brute force, squared distances in float32 like flann::L2_Simple
         blk = q[a:a + 512]
         dx = (blk[:, None, 0] - q[None, :, 0]).astype(F); dy = (blk[:, None, 1] - q[None, :, 1]).astype(F); dz = (blk[:, None, 2] - q[None, :, 2]).astype(F)
-        d2 = ((dx * dx).astype(F) + (dy * dy).astype(F)).astype(F) + (dz * dz).astype(F)
+        with np.errstate(over="ignore"):    # a squared distance past float32 is +inf, as on the device
+            d2 = ((dx * dx).astype(F) + (dy * dy).astype(F)).astype(F) + (dz * dz).astype(F)
         part = np.sort(np.partition(d2, mean_k, axis=1)[:, :mean_k + 1], axis=1)
         s = np.zeros(len(blk), np.float64)
         for k in range(1, mean_k + 1):
@@ -65,9 +85,10 @@ def statistical_outlier_removal(xyz, mean_k=50, stddev_mul=1.0):
     total, sq = 0.0, 0.0
     for x in v:                           # sequential double sums, index order (applyFilterIndices)
         total += x; sq += x * x
-    mean = total / len(v)
-    std = np.sqrt((sq - total * total / len(v)) / (len(v) - 1.0))
-    thr = mean + stddev_mul * std
+    with np.errstate(invalid="ignore"):     # infinite mean distances: inf - inf, a NaN threshold, every finite point kept
+        mean = total / len(v)
+        std = np.sqrt((sq - total * total / len(v)) / (len(v) - 1.0))
+        thr = mean + stddev_mul * std
     keep = valid & ~(md.astype(np.float64) > thr)
     return np.nonzero(keep)[0].astype(np.int32), md
 

@@ -1858,8 +1858,9 @@ __global__ __launch_bounds__(128) void k_sor_mean_distance(const float* __restri
   bool fin = false;
   if (valid_i) { qx = pts[3 * (size_t)i]; qy = pts[3 * (size_t)i + 1]; qz = pts[3 * (size_t)i + 2]; fin = isfinite(qx) && isfinite(qy) && isfinite(qz); }
   const int K = k + 1;
-  for (int j = 0; j < K; ++j) best[j * 128 + tid] = 3.402823466e+38f;
-  float cur_max = 3.402823466e+38f;
+  const float inf = __int_as_float(0x7f800000);   // the sentinel: a squared distance that overflows is +inf as well and stands as such
+  for (int j = 0; j < K; ++j) best[j * 128 + tid] = inf;
+  float cur_max = inf;
   int arg_max = 0;
   for (int t0 = 0; t0 < n; t0 += 128) {
     __syncthreads();
@@ -2961,6 +2962,45 @@ int sslam_seg_distance_filter(sslam_seg* s, const float* xyz, int n, double dmin
   return total;
 }
 
+// pcl::VoxelGrid::applyFilter: inverse leaf size, integer bounds of the box of the finite points, cells per axis.  Host only, and the
+// one copy of the rule: the cell of a point is (int)floorf(x * inv) - minb on the device, which stays inside [0, div) exactly when both
+// bounds are representable, so every bound is compared as a float BEFORE its cast (a cast out of range is undefined on the host and
+// saturates on the device), and the cell count is bounded before anything is sized by it.
+static int voxel_geometry(const float lo[3], const float hi[3], float leaf, VoxelGeom* G, long long div[3], long long* ncell_out) {
+  if (!(leaf > 0)) return set_error(SSLAM_ERR_INVALID, "bad argument (leaf must be positive)");
+  const float inv = 1.0f / leaf;
+  if (!std::isfinite(inv)) return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid: 1 / leaf is not finite (leaf %g)", (double)leaf);
+  const long long max_cells = 1ll << 26;
+  long long ncell = 1;
+  bool too_many = false;
+  for (int k = 0; k < 3; ++k) {
+    const float fl = std::floor(lo[k] * inv), fh = std::floor(hi[k] * inv);
+    if (!(fl >= -2147483648.0f && fl < 2147483648.0f && fh >= -2147483648.0f && fh < 2147483648.0f))
+      return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid: the cell index of a bound (%g .. %g at leaf %g) does not fit 32 bits", (double)lo[k], (double)hi[k], (double)leaf);
+    G->inv[k] = inv;
+    G->minb[k] = (int)fl;
+    div[k] = (long long)(int)fh - G->minb[k] + 1;
+    if (div[k] < 1) return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid: upper bound below the lower bound on axis %d", k);
+  }
+  for (int k = 0; k < 3; ++k) {
+    if (div[k] > max_cells / ncell) too_many = true; else ncell *= div[k];
+  }
+  if (too_many)
+    return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid of %.0f cells: leaf size too small for the extent of the cloud (PCL refuses as well)",
+                     (double)div[0] * (double)div[1] * (double)div[2]);
+  *ncell_out = ncell;
+  return 0;
+}
+int sslam_debug_voxel_geometry(const float lo[3], const float hi[3], float leaf, int32_t minb[3], int64_t div[3]) {
+  if (!lo || !hi || !minb || !div) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  VoxelGeom G;
+  long long d[3], ncell = 0;
+  const int rc = voxel_geometry(lo, hi, leaf, &G, d, &ncell);
+  if (rc) return rc;
+  for (int k = 0; k < 3; ++k) { minb[k] = G.minb[k]; div[k] = d[k]; }
+  return 0;
+}
+
 int sslam_seg_voxel_grid(sslam_seg* s, const float* xyz, int n, float leaf, float* centroids_out, int32_t* counts_out, int max_out) {
   if (!s || !xyz || n < 0 || !(leaf > 0) || (!centroids_out && max_out > 0)) return set_error(SSLAM_ERR_INVALID, "bad argument");
   int rc = seg_device(s);
@@ -2978,17 +3018,9 @@ int sslam_seg_voxel_grid(sslam_seg* s, const float* xyz, int n, float leaf, floa
   float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
   for (int b = 0; b < nblk; ++b) for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], part[(size_t)b * 6 + k]); hi[k] = std::max(hi[k], part[(size_t)b * 6 + 3 + k]); }
   if (!(lo[0] <= hi[0])) return 0;   // no finite point
-  // pcl::VoxelGrid::applyFilter: inverse leaf size, integer bounds of the box, cell strides
   VoxelGeom G;
-  long long div[3];
-  for (int k = 0; k < 3; ++k) {
-    G.inv[k] = 1.0f / leaf;
-    G.minb[k] = (int)std::floor(lo[k] * G.inv[k]);
-    const int maxb = (int)std::floor(hi[k] * G.inv[k]);
-    div[k] = (long long)maxb - G.minb[k] + 1;
-  }
-  const long long ncell = div[0] * div[1] * div[2];
-  if (ncell > (1ll << 26)) return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid of %lld cells: leaf size too small for the extent of the cloud (PCL refuses as well)", ncell);
+  long long div[3], ncell = 0;
+  if ((rc = voxel_geometry(lo, hi, leaf, &G, div, &ncell))) return rc;
   G.mul[0] = 1; G.mul[1] = (int)div[0]; G.mul[2] = (int)(div[0] * div[1]);
   int* d_count = nullptr; long long* d_sums = nullptr; unsigned char* d_flag = nullptr; int* d_cells = nullptr;
   if ((rc = g.alloc(&d_count, (size_t)ncell)) || (rc = g.alloc(&d_sums, (size_t)ncell * 3)) || (rc = g.alloc(&d_flag, (size_t)ncell)) || (rc = g.alloc(&d_cells, (size_t)ncell))) return rc;
@@ -3018,7 +3050,9 @@ int sslam_seg_statistical_outlier_removal(sslam_seg* s, const float* xyz, int n,
   int rc = seg_device(s);
   if (rc) return rc;
   if (n == 0) return 0;
-  if (n < mean_k + 1) return set_error(SSLAM_ERR_INVALID, "fewer points (%d) than neighbours asked for (%d)", n, mean_k);
+  int n_fin = 0;   // only finite points are neighbours: with fewer than mean_k + 1 of them no point has mean_k neighbours
+  for (int i = 0; i < n; ++i) n_fin += std::isfinite(xyz[3 * (size_t)i]) && std::isfinite(xyz[3 * (size_t)i + 1]) && std::isfinite(xyz[3 * (size_t)i + 2]);
+  if (n_fin < mean_k + 1) return set_error(SSLAM_ERR_INVALID, "fewer finite points (%d of %d) than mean_k + 1 = %d", n_fin, n, mean_k + 1);
   DevGuard g;
   float *d_pts = nullptr, *d_md = nullptr;
   if ((rc = g.alloc(&d_pts, (size_t)n * 3)) || (rc = g.alloc(&d_md, n))) return rc;
