@@ -270,6 +270,9 @@ int sslam_batch_optimize(sslam_batch* b, int max_iters, sslam_opt_stats* out /* 
  * the two over the columns the paths share -- no right-hand side matrix, no backward substitution, only the requested blocks cross PCIe.
  * Paths of any length (the L configuration included): what fits the LDS of a wave runs there, the rest in a device scratch buffer, with
  * bitwise the same result; SSLAM_MARGINAL_LDS_BYTES in the environment (read per call, default and ceiling 61440) lowers the LDS budget.
+ * A call whose elimination-tree paths hold more than SSLAM_PATH_ROUND_INTS columns in all (read per call, default and ceiling 16777216,
+ * floor 1), or need more than 1 GB of scratch, runs in rounds of requests, each with its own upload, launches and download -- bitwise
+ * the blocks of one round.  (The placement rule and the rounds are csrc/path_rounds.hpp, shared with the gate below.)
  * The call leaves the batch as it found it: sslam_batch_optimize / sslam_batch_download after it give, bitwise, what they give without it. */
 int sslam_batch_marginals(sslam_batch* b, const int32_t* req, int n, double* out_blocks);
 /* Loop-closure gate: the Mahalanobis distance of candidate edges that are NOT in the graph (their measurement is independent of the
@@ -296,7 +299,8 @@ int sslam_batch_marginals(sslam_batch* b, const int32_t* req, int n, double* out
  * One linearisation and one flat factorisation of the whole batch, then ONE WAVE PER CANDIDATE (k_chol_gate_pairs): the forward
  * substitutions along path(u) and path(v), each once, the three blocks of H^-1 out of them, e, the Jacobians, S and d2 -- 43 doubles per
  * candidate cross PCIe.  Paths of any length, a path of length 0 (a fixed end) included; LDS or device scratch with bitwise the same
- * result, SSLAM_MARGINAL_LDS_BYTES as for the marginals (the budget of the whole workgroup, the kernel's fixed 2368 bytes included).
+ * result, SSLAM_MARGINAL_LDS_BYTES and SSLAM_PATH_ROUND_INTS as for the marginals (the budget of the whole workgroup, the kernel's
+ * fixed 2368 bytes included).
  * The call leaves the batch as it found it: optimize, download and marginals after it give, bitwise, what they give without it. */
 #define SSLAM_GATE_SE3 0
 #define SSLAM_GATE_SE3_POINT 1

@@ -236,6 +236,7 @@ int chol_spec_mode(const Batch& b);               // 0 off, 1 adaptive (lanes jo
 int chol_lm_step_spec(Batch& b, int max_iters);   // one LM iteration: up to ten speculative trials + the accept / reject replay
 int chol_factor_flat_flow(Batch& b);        // flat factor (marginals) through the single launch
 int chol_flow_check(Batch& b);              // error flag of that launch (synchronises the stream)
+// The requests of the path kernels are plain ints, read as such by the planner of their rounds (path_rounds.hpp): four for the ends, then the payload
 struct MarginalReq { int xoff_u, dim_u, xoff_v, dim_v; };   // first unknown (internal row order) and dimension of the row / column vertex; xoff_v == xoff_u: a diagonal block
 int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double* out36);   // blocks Z(u, v) of H^-1 for pairs of vertices of a batch, paths of any length
 struct GateReq { int xoff_u, dim_u, xoff_v, dim_v, kind, idx_u, idx_v, has_info; };   // as MarginalReq, xoff < 0: fixed or edge-less; SSLAM_GATE_* kind; index of u in V.pose, of v in V.pose / V.lmk

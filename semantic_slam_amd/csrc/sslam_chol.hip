@@ -7,14 +7,17 @@
 //                          external updates from HBM, internal levels out of LDS, one coalesced write of L and y
 //   k_chol_tail<NT>        one workgroup per graph walks the top pieces of its tree in elimination order
 //   k_chol_back_pieces / k_chol_back_tail   the same pieces top-down for x = L^-T y
-//   k_chol_marginal_pairs<SCRATCH>   blocks of H^-1 along elimination-tree paths of the flat factor (marginals)
-//   k_chol_gate_pairs<SCRATCH>       Mahalanobis distance of candidate edges from the same paths (loop-closure gate)
+//   k_chol_marginal_pairs<SCRATCH> / k_chol_gate_pairs<SCRATCH> (path_kernels.hpp)   blocks of H^-1 along elimination-tree paths of the
+//                          flat factor (marginals), and the Mahalanobis distance of candidate edges from the same paths (loop-closure gate)
 // Everything is gather-form: every L entry is written by exactly one thread, sums run in a fixed order -> bitwise
 // repeatable.  Forward substitution is fused into the factorisation (b rides along as an extra row of the diagonal block).
 //   k_front_pieces / k_front_tail (front_kernels.hpp, round 6)   the same pieces through the front tables of front_plan.hpp: the default of batches >= 32
 // Tuning: ONE environment variable, read when a plan is built -- SSLAM_CHOL_OPTS="key=value,..." with the field names of CholOpts
 // (chol_plan.hpp).  The per-knob variables of rounds 2-4 (SSLAM_CHOL_CAP_LEAF, SSLAM_CHOL_FLOW, SSLAM_FLOW_DEFER, ...) are gone; setting one
 // earns a warning on stderr, once, instead of a sweep that silently measures the default plan.
+// Host rules, each written once: the largest LDS of a plan plan_lds_max; the workgroups of a launch with and without the LM endgame's
+// compaction plan_range; the (USTAGE, RK) instantiation of the persistent kernels flow_kernels; begin + single launch + end flow_factor;
+// the requests of the path kernels -> rounds of records path_rounds.hpp (host-only), one round on the device path_rounds_run.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -26,6 +29,7 @@
 #include "../../include/sslam.h"
 #include "graph_engine.hpp"
 #include "chol_plan.hpp"
+#include "path_rounds.hpp"
 
 namespace sslam {
 
@@ -109,17 +113,31 @@ struct CholPlan {
   int spec_epoch = 0;           // rounds of the speculative lanes (k_chol_spec_round)
   int2* d_dep = nullptr;        // per launch-order piece: {parent (launch order) or -1, children}
   int* d_flow = nullptr;        // [children done | backward done | forward done] per piece, then [0] error flag at 3 * npiece
-  // marginals along the elimination-tree paths (k_chol_marginal_pairs)
+  // the path kernels (path_kernels.hpp) and the device buffers of a round of their requests (path_rounds_run); capacities in bytes
   std::vector<int> h_cparent;   // parent column in the elimination tree, -1: root
   std::vector<int> h_xoff_col;  // offset in the unknown vector (internal row order) -> column, -1 elsewhere
-  int* d_mpath = nullptr;       // [path_ptr | dims | path columns] of a request
-  double* d_mout = nullptr;     // [requests][36]
-  size_t mpath_cap = 0, mout_cap = 0;
-  char* d_mscratch = nullptr;   // k_chol_marginal_pairs: the Y slices of the requests whose paths LDS does not hold
-  size_t mscratch_cap = 0;      // bytes
-  double* d_gin = nullptr;      // k_chol_gate_pairs: measurement and information matrix of every candidate
-  size_t gin_cap = 0;           // bytes
+  int* d_mpath = nullptr;       // [records | path columns] of a round (path_rounds.hpp)
+  double* d_mout = nullptr;     // results: [requests][36] (marginals) or [candidates][44] (gate)
+  char* d_mscratch = nullptr;   // the Y slices of the requests whose paths LDS does not hold
+  double* d_gin = nullptr;      // gate: measurement and information matrix of every candidate
+  size_t mpath_cap = 0, mout_cap = 0, mscratch_cap = 0, gin_cap = 0;
 };
+
+// LDS bytes of the largest piece of a plan, whichever kernels run it: the opt-in limit is checked against it, the persistent launches
+// (k_chol_flow, k_chol_spec_round) reserve it and their grids are sized by the occupancy at it
+static size_t plan_lds_max(const CholPlan& P) {
+  size_t lds = (size_t)std::max(std::max(P.tail_lds_f, P.tail_lds_b), P.tail_lds_ff);
+  for (size_t l = 0; l < P.plv_lds_f.size(); ++l) lds = std::max(lds, (size_t)std::max(P.plv_lds_f[l], P.plv_lds_b[l]));
+  for (int v : P.plv_lds_ff) lds = std::max(lds, (size_t)v);
+  return lds * sizeof(double);
+}
+// The workgroups of launch l: every piece of depth l (l == launches per depth: a tail workgroup per graph, B), *idx = nullptr; under
+// the compaction of the LM endgame (chol_set_active) the entries of the launch's index list, *idx
+static int plan_range(const CholPlan& P, int l, int B, const int** idx) {
+  *idx = P.compact ? P.d_idx + P.c_ptr[l] : nullptr;
+  if (P.compact) return P.c_ptr[l + 1] - P.c_ptr[l];
+  return l < (int)P.plv_lds_f.size() ? P.plv_ptr[l + 1] - P.plv_ptr[l] : B;
+}
 
 void chol_plan_free(CholPlan* p) {
   if (!p) return;
@@ -543,7 +561,17 @@ __device__ __forceinline__ void row_solve(double* v, const double* Ljj, const do
 // DEFER (k_chol_flow): the piece's tables and its part of H are fetched BEFORE the wait for the child pieces (they do not depend on
 // them); only the children's update-matrix blocks are read after it -- two dependent round trips less on the critical path of a piece.
 // The sums are those of the one-pass gather, in its order: (H + lambda I) first, then the sources one after the other.
-__device__ __forceinline__ bool flow_wait(const int* p, int target, int* err, int* fail = nullptr);
+// The wait of a persistent launch for a counter that other workgroups of the same launch advance (k_chol_flow, below).
+// fail (optional): the failure flag of the graph the waiting piece belongs to -- a wait that gives up must not let the trial go on as if the
+// data it waited for were there: the graph's trial counts as a failed factorisation (lm_control rejects it) and the host reports the flag
+__device__ __forceinline__ bool flow_wait(const int* p, int target, int* err, int* fail = nullptr) {
+  int spins = 0;
+  while (__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
+    __builtin_amdgcn_s_sleep(2);
+    if (++spins > (1 << 22)) { atomicExch(err, 1); if (fail) atomicExch(fail, 1); return false; }
+  }
+  return true;
+}
 template <int NT, bool USTAGE, bool RIGHT, bool DEFER = false>
 __device__ __forceinline__ void chol_piece(const BatchView& V, const CholView& C, const PieceMeta pm, double* sm, long long* dbg,
                                            const int* wait_p = nullptr, int wait_target = 0, int* wait_err = nullptr) {
@@ -1062,315 +1090,9 @@ __global__ __launch_bounds__(NT) void k_chol_back_tail(CholView C, const double*
     __syncthreads();
   }
 }
-
-// ------------------------------------------------------------------------------------------------
-// Blocks of H^-1 = (L L^T)^-1 along elimination-tree paths (computeLandmarkMarginals, reference src/ps_graph_slam/graph_slam.cpp:221-234
-// -> g2o MarginalCovarianceCholesky; sslam_batch_marginals).  Z(w, w) = E_w^T L^-T L^-1 E_w = Y^T Y with Y = L^-1 E_w, and Y is non-zero
-// only on the PATH from w's column to the root of the elimination tree; every off-diagonal block of a column on that path has its row
-// further up the same path (struct(k) is a subset of the ancestors of k).  marginal_path_forward: one wave walks the path bottom-up with a
-// right-looking forward substitution: finalise Y_s = L_ss^-1 acc_s, then every block (i, path[s]) of the column subtracts L(i, s) Y_s from
-// acc_i -- one lane per block, distinct rows, no conflicts, fixed order.  Work O(path^2) per vertex instead of two triangular solves over
-// the whole factor per right-hand side column.  Needs the flat factor (chol_factor_and_forward(b, true)).
-// cols: the P columns of the path; D = d(w); Y: P x 36; sD: the diagonal block of a step, 36; prec: {first block, blocks, diagonal offset,
-// dim} P x int4; pyoff: y offsets P x int.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void marginal_path_forward(const CholView& C, const int* __restrict__ cols, int P, int D, double* Y, double* sD,
-                                                      int4* prec, int* pyoff) {
-  const int lane = threadIdx.x;
-  const double* __restrict__ L = C.Lval;
-  for (int t = lane; t < P; t += 64) {
-    const ColMeta cm = C.col[cols[t]];
-    prec[t] = make_int4(cm.b0, cm.nb, cm.base, cm.dim);
-    pyoff[t] = cm.yoff;
-  }
-  for (int e = lane; e < P * 36; e += 64) Y[e] = 0.0;
-  __syncthreads();
-  if (lane < D) Y[lane * 6 + lane] = 1.0;   // E_w: identity in the vertex' own rows (path entry 0)
-  __syncthreads();
-  for (int s = 0; s < P; ++s) {
-    const int4 pr = prec[s];
-    const int da = pr.w;
-    if (lane < da * da) sD[lane] = L[pr.z + lane];
-    __syncthreads();
-    if (lane < D) {   // one lane per right-hand side column: Y_s = L_ss^-1 acc_s
-      double yv[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        if (i < da) {
-          double a = Y[s * 36 + i * 6 + lane];
-#pragma unroll
-          for (int m = 0; m < 6; ++m) if (m < i) a -= sD[i * da + m] * yv[m];
-          yv[i] = a / sD[i * da + i];
-          Y[s * 36 + i * 6 + lane] = yv[i];
-        }
-      }
-    }
-    __syncthreads();
-    for (int bq = lane; bq < pr.y - 1; bq += 64) {   // the blocks below the diagonal: acc_t -= L(t, s) Y_s
-      const BlkMeta bm = C.blk[pr.x + 1 + bq];
-      const int di = bm.info & 15;
-      int lo = s + 1, hi = P - 1;                    // the row's place on the path (y offsets ascend along it)
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (pyoff[mid] < bm.yoff_row) lo = mid + 1; else hi = mid; }
-      const double* Lb = L + bm.off;
-      double* acc = Y + lo * 36;
-      for (int i = 0; i < di; ++i) {
-        double lrow[6];
-#pragma unroll
-        for (int m = 0; m < 6; ++m) lrow[m] = m < da ? Lb[i * da + m] : 0.0;
-        for (int c = 0; c < D; ++c) {
-          double a = 0;
-#pragma unroll
-          for (int m = 0; m < 6; ++m) a += lrow[m] * Y[s * 36 + m * 6 + c];   // rows >= da of Y_s are zero
-          acc[i * 6 + c] -= a;
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// Z(u, v) for (row vertex, column vertex) PAIRS, diagonal or not, and for paths of any length.  Z(u, v) = Y_u^T Y_v: the product runs over
-// the columns the two paths share -- in a tree their common suffix, from the lowest common ancestor to the root (none when u and v lie
-// in different components: zeros).  One wave per request: marginal_path_forward along path(u), then, for u != v, along path(v), then the
-// sum over the suffix.  A request with u == v keeps ONE Y (the whole LDS budget for its one path).
-// SCRATCH = false: Y and the path records in LDS [diagonal block 36 | Y: ylen x 36 | records ylen x int4 | y offsets ylen x int].
-// SCRATCH = true: the same three arrays in the request's slice of a device buffer (req[7], in units of 16 bytes), for paths that LDS does
-// not hold; only the diagonal block stays in LDS.  Same body, same order of operations: the two placements agree bitwise.  The wave is the
-// whole workgroup, its lanes hand Y to one another between the phases of a step: the workgroup-scope release / acquire of __syncthreads()
-// orders plain global stores and loads of one workgroup as it orders LDS (its waves share the CU's L1; the compiler waits for the stores
-// before the barrier).
-// req: 8 ints per request {first entry of path(u) in path_cols, its length, the same for path(v) (length 0: u == v), d(u), d(v), length of
-// the common suffix, scratch slice}.  out: [requests][36], the leading d(u) x d(v) entries row-major.
-template <bool SCRATCH>
-__global__ __launch_bounds__(64) void k_chol_marginal_pairs(CholView C, const int* __restrict__ req, const int* __restrict__ path_cols,
-                                                            double* __restrict__ out, int ylen, char* scratch) {
-  extern __shared__ double sm[];
-  const int r = blockIdx.x, lane = threadIdx.x;
-  const int* __restrict__ q = req + (size_t)r * 8;
-  const int Pu = q[1], Pv = q[3], Du = q[4], Dv = q[5], nc = q[6];
-  double* sD = sm;
-  double* Y;
-  int4* prec;
-  int* pyoff;
-  if (SCRATCH) {
-    const int yl = Pu + Pv;
-    Y = reinterpret_cast<double*>(scratch + (size_t)q[7] * 16);
-    prec = reinterpret_cast<int4*>(Y + (size_t)yl * 36);
-    pyoff = reinterpret_cast<int*>(prec + yl);
-  } else {
-    Y = sm + 36;
-    prec = reinterpret_cast<int4*>(Y + (size_t)ylen * 36);
-    pyoff = reinterpret_cast<int*>(prec + ylen);
-  }
-  marginal_path_forward(C, path_cols + q[0], Pu, Du, Y, sD, prec, pyoff);
-  if (Pv > 0) marginal_path_forward(C, path_cols + q[2], Pv, Dv, Y + (size_t)Pu * 36, sD, prec + Pu, pyoff + Pu);
-  // the common suffix: its first entry in either path (u == v: the whole path, nc == Pu)
-  const double* Yu = Y + (size_t)(Pu - nc) * 36;
-  const double* Yv = Pv > 0 ? Y + (size_t)(Pu + Pv - nc) * 36 : Yu;
-  if (lane < Du * Dv) {
-    const int rr = lane / Dv, cc = lane - rr * Dv;
-    double z = 0;
-    for (int t = 0; t < nc; ++t)
-#pragma unroll
-      for (int i = 0; i < 6; ++i) z += Yu[t * 36 + i * 6 + rr] * Yv[t * 36 + i * 6 + cc];
-    out[(size_t)r * 36 + lane] = z;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Mahalanobis gate of candidate edges (sslam_batch_gate): d2 = e^T S^-1 e with S = Ju Zuu Ju^T + Ju Zuv Jv^T + Jv Zvu Ju^T + Jv Zvv Jv^T
-// + Omega^-1, for an EdgeSE3 (u, v poses) or an EdgeSE3PointXYZ (u pose, v point) that is NOT in the graph.  One wave per candidate:
-// marginal_path_forward along path(u) and along path(v), each ONCE; the three blocks Zuu, Zvv (whole paths) and Zuv (common suffix) out of
-// the two Ys; e and the analytic Jacobians of sslam_math.hpp at the estimates the device holds; Omega^-1 and S^-1 e through 6 x 6 / 3 x 3
-// Choleskys.  Only d2, e and S cross PCIe.
-// A fixed or edge-less end has no column: its path has length 0, nothing of Y / prec / pyoff is touched for it and its blocks are zero.
-// Placement as in k_chol_marginal_pairs, with a fixed LDS area after the diagonal block in both placements:
-//   [diagonal block 36 | Zuu 36 | Zuv 36 | Zvv 36 | Ju 36 | Jv 36 | S 36 | Omega / its factor 36 | e 6, flags 2 | Y ... ]
-// (the 6 x 6 areas hold rows of stride 6, S and Omega rows of stride d).  Same body, same order of operations: the placements agree bitwise.
-// req: kGateReq ints per candidate {the 8 of k_chol_marginal_pairs (length 0: no column), kind, index of u in pose, index of v in pose /
-// lmk, Omega given}.  in: [candidates][kGateIO] = z 7, pad, Omega 36.  out: [candidates][kGateIO] = d2, e 6, pad, S 36.
-// ------------------------------------------------------------------------------------------------
-constexpr int kGateReq = 12, kGateIO = 44;
-constexpr int kGateZuu = 36, kGateZuv = 72, kGateZvv = 108, kGateJu = 144, kGateJv = 180, kGateS = 216, kGateW = 252, kGateE = 288;
-constexpr int kGateFixed = 296;   // doubles of the fixed LDS area, the diagonal block included
-
-// in-place Cholesky of the d x d matrix A (rows of stride d, lower triangle read and written) by ONE lane; false: a pivot <= 0 or not finite
-__device__ __forceinline__ bool gate_chol_small(double* A, int d) {
-  for (int j = 0; j < d; ++j) {
-    double p = A[j * d + j];
-    for (int m = 0; m < j; ++m) p -= A[j * d + m] * A[j * d + m];
-    if (!(p > 0.0) || !isfinite(p)) return false;
-    p = sqrt(p);
-    A[j * d + j] = p;
-    for (int i = j + 1; i < d; ++i) {
-      double a = A[i * d + j];
-      for (int m = 0; m < j; ++m) a -= A[i * d + m] * A[j * d + m];
-      A[i * d + j] = a / p;
-    }
-  }
-  return true;
-}
-
-template <bool SCRATCH>
-__global__ __launch_bounds__(64) void k_chol_gate_pairs(CholView C, const int* __restrict__ req, const int* __restrict__ path_cols,
-                                                        const double* __restrict__ in, const double* __restrict__ pose,
-                                                        const double* __restrict__ lmk, double* __restrict__ out, int ylen, char* scratch) {
-  extern __shared__ double sm[];
-  const int r = blockIdx.x, lane = threadIdx.x;
-  const int* __restrict__ q = req + (size_t)r * kGateReq;
-  const int Pu = q[1], Pv = q[3], Du = q[4], Dv = q[5], nc = q[6];
-  const bool se3 = q[8] == SSLAM_GATE_SE3, has_info = q[11] != 0;
-  const int d = se3 ? 6 : 3;
-  const double* __restrict__ zin = in + (size_t)r * kGateIO;
-  double* o = out + (size_t)r * kGateIO;
-  double* sD = sm;
-  double* Y;
-  int4* prec;
-  int* pyoff;
-  if (SCRATCH) {
-    const int yl = Pu + Pv;
-    Y = reinterpret_cast<double*>(scratch + (size_t)q[7] * 16);
-    prec = reinterpret_cast<int4*>(Y + (size_t)yl * 36);
-    pyoff = reinterpret_cast<int*>(prec + yl);
-  } else {
-    Y = sm + kGateFixed;
-    prec = reinterpret_cast<int4*>(Y + (size_t)ylen * 36);
-    pyoff = reinterpret_cast<int*>(prec + ylen);
-  }
-  for (int k = 36 + lane; k < kGateFixed; k += 64) sm[k] = 0.0;
-  // 1. the two paths, each once; a side without a column is skipped whole
-  if (Pu > 0) marginal_path_forward(C, path_cols + q[0], Pu, Du, Y, sD, prec, pyoff);
-  if (Pv > 0) marginal_path_forward(C, path_cols + q[2], Pv, Dv, Y + (size_t)Pu * 36, sD, prec + Pu, pyoff + Pu);
-  __syncthreads();
-  // 2. Zuu, Zvv over the whole paths, Zuv over the common suffix (nc == 0: different components, or a side without a column)
-  if (lane < 36) {
-    const int a = lane / 6, c = lane - a * 6;
-    const double* Yu = Y;
-    const double* Yv = Y + (size_t)Pu * 36;
-    double zuu = 0, zvv = 0, zuv = 0;
-    if (a < Du && c < Du)
-      for (int t = 0; t < Pu; ++t)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) zuu += Yu[t * 36 + i * 6 + a] * Yu[t * 36 + i * 6 + c];
-    if (a < Dv && c < Dv)
-      for (int t = 0; t < Pv; ++t)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) zvv += Yv[t * 36 + i * 6 + a] * Yv[t * 36 + i * 6 + c];
-    if (a < Du && c < Dv) {
-      const double* Yus = Yu + (size_t)(Pu - nc) * 36;
-      const double* Yvs = Yv + (size_t)(Pv - nc) * 36;
-      for (int t = 0; t < nc; ++t)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) zuv += Yus[t * 36 + i * 6 + a] * Yvs[t * 36 + i * 6 + c];
-    }
-    sm[kGateZuu + lane] = zuu; sm[kGateZvv + lane] = zvv; sm[kGateZuv + lane] = zuv;
-  }
-  // 3. e and the Jacobians at the estimates the device holds
-  const Pose Xu = load_pose(pose, q[9]);
-  if (se3) {
-    const Pose Xv = load_pose(pose, q[10]);
-    const Pose Z{{zin[0], zin[1], zin[2]}, {zin[3], zin[4], zin[5], zin[6]}};
-    Se3Lin L;
-    se3_error(Xu, Xv, Z, L);
-    L.Re = qmat(L.qe);
-    if (lane < 12) {   // one lane per Jacobian column
-      double col[6];
-      if (lane < 6) se3_Ji_col(L, lane, col);
-      else se3_Jj_col(L, lane - 6, col);
-      double* J = sm + (lane < 6 ? kGateJu + lane : kGateJv + lane - 6);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) J[i * 6] = col[i];
-    } else if (lane == 12) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) sm[kGateE + i] = L.e[i];
-    }
-  } else {
-    const double* lp = lmk + (size_t)q[10] * 4;
-    PointLin L;
-    point_error(Xu, Vec3{lp[0], lp[1], lp[2]}, Vec3{zin[0], zin[1], zin[2]}, L);
-    if (lane == 0) {
-      double Ji[18], Jl[9];
-      point_jacobians(L, Ji, Jl);
-#pragma unroll
-      for (int k = 0; k < 18; ++k) sm[kGateJu + k] = Ji[k];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) sm[kGateJv + (k / 3) * 6 + k % 3] = Jl[k];
-    } else if (lane == 12) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) sm[kGateE + i] = L.e[i];
-    }
-  }
-  // 4. Omega^-1: Cholesky by one lane, then one lane per column of the inverse -> sD (free after the paths)
-  if (has_info && lane < d * d) sm[kGateW + lane] = zin[8 + lane];
-  __syncthreads();
-  if (has_info && lane == 0) sm[kGateE + 6] = gate_chol_small(sm + kGateW, d) ? 1.0 : 0.0;
-  __syncthreads();
-  const bool w_ok = !has_info || sm[kGateE + 6] != 0.0;
-  if (has_info && w_ok && lane < d) {
-    const double* W = sm + kGateW;
-    double x[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {   // L y = unit vector `lane`
-      if (i < d) {
-        double a = i == lane ? 1.0 : 0.0;
-#pragma unroll
-        for (int m = 0; m < 6; ++m) if (m < i) a -= W[i * d + m] * x[m];
-        x[i] = a / W[i * d + i];
-      }
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {   // L^T x = y
-      if (i < d) {
-        double a = x[i];
-#pragma unroll
-        for (int m = 5; m >= 0; --m) if (m > i && m < d) a -= W[m * d + i] * x[m];
-        x[i] = a / W[i * d + i];
-        sD[i * d + lane] = x[i];
-      }
-    }
-  }
-  __syncthreads();
-  // S by lanes < d * d; entry (r, c) and entry (c, r) run the same sums: S is symmetric to the bit
-  if (lane < 36) {
-    double s = 0;
-    if (lane < d * d) {
-      const int r0 = lane / d, c0 = lane - r0 * d;
-      const int hi = r0 > c0 ? r0 : c0, lo = r0 > c0 ? c0 : r0;
-      const double *Ju = sm + kGateJu, *Jv = sm + kGateJv;
-      for (int a = 0; a < Du; ++a)
-        for (int c = 0; c < Du; ++c) s += Ju[hi * 6 + a] * sm[kGateZuu + a * 6 + c] * Ju[lo * 6 + c];
-      for (int a = 0; a < Du; ++a)
-        for (int c = 0; c < Dv; ++c) s += Ju[hi * 6 + a] * sm[kGateZuv + a * 6 + c] * Jv[lo * 6 + c];
-      for (int a = 0; a < Dv; ++a)
-        for (int c = 0; c < Du; ++c) s += Jv[hi * 6 + a] * sm[kGateZuv + c * 6 + a] * Ju[lo * 6 + c];
-      for (int a = 0; a < Dv; ++a)
-        for (int c = 0; c < Dv; ++c) s += Jv[hi * 6 + a] * sm[kGateZvv + a * 6 + c] * Jv[lo * 6 + c];
-      if (has_info && w_ok) s += sD[hi * d + lo];
-      sm[kGateS + lane] = s;
-    }
-    o[8 + lane] = s;
-  }
-  __syncthreads();
-  // 5. Cholesky of S, forward substitution, d2 = |L^-1 e|^2
-  if (lane == 0) {
-    double* S = sm + kGateS;
-    double* y = sm + kGateW;
-    double d2 = __longlong_as_double(0x7ff8000000000000ll);   // NaN: Omega or S broke down
-    if (w_ok && gate_chol_small(S, d)) {
-      d2 = 0;
-      for (int i = 0; i < d; ++i) {
-        double a = sm[kGateE + i];
-        for (int m = 0; m < i; ++m) a -= S[i * d + m] * y[m];
-        y[i] = a / S[i * d + i];
-        d2 += y[i] * y[i];
-      }
-    }
-    o[0] = d2;
-    o[7] = 0.0;
-  } else if (lane <= 6) {
-    o[lane] = lane - 1 < d ? sm[kGateE + lane - 1] : 0.0;
-  }
-}
+}  // namespace sslam
+#include "path_kernels.hpp"   // k_chol_marginal_pairs, k_chol_gate_pairs: blocks of H^-1 along elimination-tree paths of the flat factor
+namespace sslam {
 
 // ------------------------------------------------------------------------------------------------
 // One LM iteration of a SMALL graph after its linearisation, in ONE launch (the orchestrator's tick re-optimises a
@@ -1579,16 +1301,6 @@ __device__ __forceinline__ void spec_control(const BatchView& V, const SpecLanes
 // counters are never reset -- launch number `epoch` waits for epoch x (children).  A wait that does not end (it cannot, short of a lost
 // workgroup) gives up after ~2^22 polls and raises the error flag instead of hanging the GPU.
 // ------------------------------------------------------------------------------------------------
-// fail (optional): the failure flag of the graph the waiting piece belongs to -- a wait that gives up must not let the trial go on as if the
-// data it waited for were there: the graph's trial counts as a failed factorisation (lm_control rejects it) and the host reports the flag
-__device__ __forceinline__ bool flow_wait(const int* p, int target, int* err, int* fail) {
-  int spins = 0;
-  while (__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) {
-    __builtin_amdgcn_s_sleep(2);
-    if (++spins > (1 << 22)) { atomicExch(err, 1); if (fail) atomicExch(fail, 1); return false; }
-  }
-  return true;
-}
 }  // namespace sslam
 #include "front_kernels.hpp"
 namespace sslam {
@@ -1775,7 +1487,6 @@ using MidWidths = Widths<128, 256, 512>;              // k_chol_pieces of the mi
 using TailWidths = Widths<512, 1024>;                 // k_chol_tail
 using FrontTailWidths = Widths<128, 256, 512, 1024>;  // k_front_tail
 using BackTailWidths = Widths<128, 256, 512>;         // k_chol_back_tail
-using Flag = Widths<0, 1>;                            // a bool template argument
 template <int... W, class F>
 static int with_width(Widths<W...>, int v, F&& f) {
   if (((v == W && (f(std::integral_constant<int, W>{}), true)) || ...)) return 0;
@@ -1783,6 +1494,13 @@ static int with_width(Widths<W...>, int v, F&& f) {
 }
 template <int... W, class F>
 static void for_each_width(Widths<W...>, F&& f) { (f(std::integral_constant<int, W>{}), ...); }
+// The instantiations of the two persistent kernels for a plan's USTAGE and, rk, the per-edge robust kernels in their LM halves: the
+// attribute list, the occupancy queries and the launches all come here
+struct FlowKernels { decltype(&k_chol_flow<512, false>) flow; decltype(&k_chol_spec_round<512, false>) spec; };
+static FlowKernels flow_kernels(bool ustage, bool rk) {
+  if (ustage) return rk ? FlowKernels{k_chol_flow<512, true, true>, k_chol_spec_round<512, true, true>} : FlowKernels{k_chol_flow<512, true>, k_chol_spec_round<512, true>};
+  return rk ? FlowKernels{k_chol_flow<512, false, true>, k_chol_spec_round<512, false, true>} : FlowKernels{k_chol_flow<512, false>, k_chol_spec_round<512, false>};
+}
 
 namespace {
 template <typename T>
@@ -1941,10 +1659,7 @@ int chol_plan_build(Batch& b) {
     P->idx_cap = cap;
   }
   // LDS opt-in above 64 KiB
-  size_t lds_max = (size_t)std::max(std::max(P->tail_lds_f, P->tail_lds_b), P->tail_lds_ff);
-  for (size_t l = 0; l < P->plv_lds_f.size(); ++l) lds_max = std::max(lds_max, (size_t)std::max(P->plv_lds_f[l], P->plv_lds_b[l]));
-  for (int v : P->plv_lds_ff) lds_max = std::max(lds_max, (size_t)v);
-  lds_max *= sizeof(double);
+  const size_t lds_max = plan_lds_max(*P);
   const int lds_lim = lds_optin_limit(b.device, 160 * 1024 - 2048, 2048);
   if (lds_max > (size_t)lds_lim) return set_error(SSLAM_ERR_UNSUPPORTED, "a piece of the factor needs %zu B of LDS (device limit %d B)", lds_max, lds_lim);
   if (lds_max > 48 * 1024) {
@@ -1954,10 +1669,8 @@ int chol_plan_build(Batch& b) {
     static std::vector<int> done;
     std::lock_guard<std::mutex> lk(mu);
     if (std::find(done.begin(), done.end(), b.device) == done.end()) {
-      std::vector<const void*> fns = {(const void*)k_chol_flow<512, true>, (const void*)k_chol_flow<512, false>,
-                                      (const void*)k_chol_spec_round<512, true>, (const void*)k_chol_spec_round<512, false>,
-                                      (const void*)k_chol_flow<512, true, true>, (const void*)k_chol_flow<512, false, true>,
-                                      (const void*)k_chol_spec_round<512, true, true>, (const void*)k_chol_spec_round<512, false, true>};
+      std::vector<const void*> fns;
+      for (int v = 0; v < 4; ++v) { const FlowKernels K = flow_kernels(v & 1, v >> 1); fns.insert(fns.end(), {(const void*)K.flow, (const void*)K.spec}); }
       for_each_width(LeafWidths{}, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
         fns.insert(fns.end(), {(const void*)k_chol_pieces<NT, true>, (const void*)k_chol_pieces<NT, false>, (const void*)k_chol_back_pieces<NT>,
@@ -1975,8 +1688,9 @@ int chol_plan_build(Batch& b) {
     // persistent grid: at most half of what the device holds at once of these workgroups (two such launches may run side by side),
     // never more workgroups than pieces
     int per_cu = 0, cus = 0;
-    const void* fn = P->ustage ? (const void*)k_chol_flow<512, true> : (const void*)k_chol_flow<512, false>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 512, lds_max) != hipSuccess || per_cu < 1 ||
+    const FlowKernels K0 = flow_kernels(P->ustage, false), Krk = flow_kernels(P->ustage, true);
+    auto resident = [&](auto* fn, int* per) { *per = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(per, (const void*)fn, 512, lds_max) == hipSuccess; };
+    if (!resident(K0.flow, &per_cu) || per_cu < 1 ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b.device) != hipSuccess || cus < 1) P->flow = false;
     else {
       // Every workgroup of the grid is resident (at most half of what the device holds at once), workgroup w takes the pieces w, w + G, ...
@@ -1987,11 +1701,9 @@ int chol_plan_build(Batch& b) {
       // no wider than the grid at the bottom depth (the orchestrator's graphs: 5.1 vs 5.7 ms per tick at 110 keyframes); flow=2 takes it
       // on any tree (tests: a persistent workgroup walks many pieces)
       const int cap = std::max(1, per_cu * cus / 2);
-      {   // a batch with per-edge robust kernels launches the <RK = true> form into the same grid: only if the device holds as many of it
-        int per_cu_rk = 0;
-        const void* fn_rk = P->ustage ? (const void*)k_chol_flow<512, true, true> : (const void*)k_chol_flow<512, false, true>;
-        P->rk_flow_ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_rk, fn_rk, 512, lds_max) == hipSuccess && per_cu_rk >= per_cu;
-      }
+      // a batch with per-edge robust kernels launches the <RK = true> form into the same grid: only if the device holds as many of it
+      int per_cu_rk = 0;
+      P->rk_flow_ok = resident(Krk.flow, &per_cu_rk) && per_cu_rk >= per_cu;
       P->flow_narrow = P->plv_lds_f.empty() || P->plv_ptr[1] - P->plv_ptr[0] <= cap;
       if (!P->flow_narrow && flow_mode != 2) P->flow = false;
       P->flow_grid = std::max(1, std::min((int)dep.size(), cap));
@@ -2010,13 +1722,8 @@ int chol_plan_build(Batch& b) {
         // has been rejected (adaptive form) -- gets a workgroup per piece like the plain single-launch solve, the others share the rest
         SpecLanes& SL = P->spec;
         int per_cu_s = 0;   // what the device holds at once of the round's own kernel (ten lanes at work must all be resident)
-        const void* fn_s = P->ustage ? (const void*)k_chol_spec_round<512, true> : (const void*)k_chol_spec_round<512, false>;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_s, fn_s, 512, lds_max) != hipSuccess || per_cu_s < 1) per_cu_s = 1;
-        {
-          int per_cu_rk = 0;
-          const void* fn_rk = P->ustage ? (const void*)k_chol_spec_round<512, true, true> : (const void*)k_chol_spec_round<512, false, true>;
-          P->rk_spec_ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_rk, fn_rk, 512, lds_max) == hipSuccess && per_cu_rk >= per_cu_s;
-        }
+        if (!resident(K0.spec, &per_cu_s) || per_cu_s < 1) per_cu_s = 1;
+        P->rk_spec_ok = resident(Krk.spec, &per_cu_rk) && per_cu_rk >= per_cu_s;
         const int full = std::max(K, std::min(2 * cap, per_cu_s * cus));
         SL.g0 = std::max(1, std::min((int)dep.size(), std::min(cap, full / 2)));
         SL.g1 = std::max(1, std::min((int)dep.size(), (full - SL.g0) / (K - 1)));
@@ -2125,14 +1832,6 @@ void persist_forget_stream(int device, hipStream_t stream) {
     if (g.entries[i].stream == stream) { if (g.entries[i].ev) (void)hipEventDestroy(g.entries[i].ev); g.entries.erase(g.entries.begin() + i); return; }
 }
 
-// LDS bytes the dependency-driven launches reserve: the largest piece of the plan, whichever kernels run it
-static size_t plan_flow_lds(const CholPlan& P) {
-  size_t lds = (size_t)std::max(std::max(P.tail_lds_f, P.tail_lds_b), P.tail_lds_ff);
-  for (size_t l = 0; l < P.plv_lds_f.size(); ++l) lds = std::max(lds, (size_t)std::max(P.plv_lds_f[l], P.plv_lds_b[l]));
-  for (int v : P.plv_lds_ff) lds = std::max(lds, (size_t)v);
-  return lds * sizeof(double);
-}
-
 // (H + lambda I) dx = b in ONE launch (k_chol_flow) for plans that allow it; false: the caller takes the launch-per-depth path
 bool chol_plan_flow(const Batch& b) { return b.chol && b.chol->flow && !b.chol->compact; }
 // the fused LM halves / the speculative lanes may take a batch with per-edge robust kernels (their <RK = true> forms fit the sized grids)
@@ -2146,37 +1845,25 @@ static int flow_launch(Batch& b, bool backward, bool lmstep = false, int max_ite
   const int epoch = ++P.flow_epoch;
   const int lm_epoch = lmstep ? ++P.lm_epoch : 0;
   PersistScope gate(b.device, b.stream, P.flow_need);
-  return with_width(Flag{}, P.ustage ? 1 : 0, [&](auto us) {
-    if (lmstep && b.has_robust)   // (only the LM halves read edges; a plain solve stays on the plain form)
-      hipLaunchKernelGGL((k_chol_flow<512, (bool)decltype(us)::value, true>), dim3(P.flow_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C, (int)P.lp_graph.size(),
-                         epoch, (const int2*)P.d_dep, P.d_flow, backward ? 1 : 0, 1, b.d_part_e, max_iters, lm_epoch);
-    else
-    hipLaunchKernelGGL((k_chol_flow<512, (bool)decltype(us)::value>), dim3(P.flow_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C, (int)P.lp_graph.size(),
-                       epoch, (const int2*)P.d_dep, P.d_flow, backward ? 1 : 0, lmstep ? 1 : 0, b.d_part_e, max_iters, lm_epoch);
-  });
+  // (only the LM halves read edges; a plain solve stays on the plain form)
+  hipLaunchKernelGGL(flow_kernels(P.ustage, lmstep && b.has_robust).flow, dim3(P.flow_grid), dim3(512), plan_lds_max(P), b.stream, b.V, P.C, (int)P.lp_graph.size(),
+                     epoch, (const int2*)P.d_dep, P.d_flow, backward ? 1 : 0, lmstep ? 1 : 0, b.d_part_e, max_iters, lm_epoch);
+  return 0;
 }
-int chol_solve_flow(Batch& b) {
+// begin, the single launch, end: the whole solve (chol_solve_flow), or, flat, the flat factor alone for the path kernels: L only, no
+// backward substitution (chol_factor_flat_flow)
+static int flow_factor(Batch& b, bool flat) {
   CholPlan& P = *b.chol;
-  P.C.flat_L = 0;
-  ScopedTimer t(b, "factor");
+  P.C.flat_L = flat ? 1 : 0;
   hipLaunchKernelGGL(k_chol_begin, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, P.C);
-  if (int rc = flow_launch(b, true)) return rc;
+  if (int rc = flow_launch(b, !flat)) return rc;
   hipLaunchKernelGGL(k_chol_end, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, P.C);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "cholesky flow launch: %s", hipGetErrorString(e));
   return 0;
 }
-// the flat factor (marginals kernel) through the single launch: L only, no backward substitution
-int chol_factor_flat_flow(Batch& b) {
-  CholPlan& P = *b.chol;
-  P.C.flat_L = 1;
-  hipLaunchKernelGGL(k_chol_begin, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, P.C);
-  if (int rc = flow_launch(b, false)) return rc;
-  hipLaunchKernelGGL(k_chol_end, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, P.C);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "cholesky flow launch: %s", hipGetErrorString(e));
-  return 0;
-}
+int chol_solve_flow(Batch& b) { ScopedTimer t(b, "factor"); return flow_factor(b, false); }
+int chol_factor_flat_flow(Batch& b) { return flow_factor(b, true); }
 // one damping trial of every active graph of a small batch after the Jacobian kernels: begin step, single-launch solve, the rest of the step
 int chol_lm_step_flow(Batch& b, int max_iters) {
   CholPlan& P = *b.chol;
@@ -2201,19 +1888,11 @@ int chol_lm_step_spec(Batch& b, int max_iters) {
   CholPlan& P = *b.chol;
   P.C.flat_L = 0;
   const int round = ++P.spec_epoch;
-  int rc;
   {
     PersistScope gate(b.device, b.stream, P.spec_need);
-    rc = with_width(Flag{}, P.ustage ? 1 : 0, [&](auto us) {
-      if (b.has_robust)
-        hipLaunchKernelGGL((k_chol_spec_round<512, (bool)decltype(us)::value, true>), dim3(P.spec_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C,
-                           (int)P.lp_graph.size(), (const int2*)P.d_dep, P.spec, round, max_iters);
-      else
-      hipLaunchKernelGGL((k_chol_spec_round<512, (bool)decltype(us)::value>), dim3(P.spec_grid), dim3(512), plan_flow_lds(P), b.stream, b.V, P.C,
-                         (int)P.lp_graph.size(), (const int2*)P.d_dep, P.spec, round, max_iters);
-    });
+    hipLaunchKernelGGL(flow_kernels(P.ustage, b.has_robust).spec, dim3(P.spec_grid), dim3(512), plan_lds_max(P), b.stream, b.V, P.C,
+                       (int)P.lp_graph.size(), (const int2*)P.d_dep, P.spec, round, max_iters);
   }
-  if (rc) return rc;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "speculative LM step launch: %s", hipGetErrorString(e));
   return 0;
@@ -2284,9 +1963,9 @@ int chol_factor_and_forward(Batch& b, bool flat) {
   hipLaunchKernelGGL(k_chol_begin, dim3((b.V.B + 63) / 64), dim3(64), 0, b.stream, b.V, C);
   const int nplv = (int)P.plv_lds_f.size();
   for (int l = 0; l < nplv; ++l) {
-    const int n = P.compact ? P.c_ptr[l + 1] - P.c_ptr[l] : P.plv_ptr[l + 1] - P.plv_ptr[l];
+    const int* idx;
+    const int n = plan_range(P, l, b.V.B, &idx);
     if (n <= 0) continue;
-    const int* idx = P.compact ? P.d_idx + P.c_ptr[l] : nullptr;
     const int begin = P.plv_ptr[l];
     const bool mid = P.plv_cls[l] == 1;
     int rc;
@@ -2314,9 +1993,9 @@ int chol_factor_and_forward(Batch& b, bool flat) {
     }
     if (rc) return rc;
   }
-  const int n = P.compact ? P.c_ptr[nplv + 1] - P.c_ptr[nplv] : b.V.B;
+  const int* idx;
+  const int n = plan_range(P, nplv, b.V.B, &idx);
   if (P.tail_total > 0 && n > 0) {
-    const int* idx = P.compact ? P.d_idx + P.c_ptr[nplv] : nullptr;
     const int rc = P.front ? with_width(FrontTailWidths{}, P.nt_ftail, [&](auto nt) {
       hipLaunchKernelGGL(k_front_tail<decltype(nt)::value>, dim3(n), dim3(nt), (size_t)P.tail_lds_ff * sizeof(double), b.stream, b.V, C, idx);
     }) : with_width(TailWidths{}, P.nt_tail, [&](auto nt) {
@@ -2336,9 +2015,9 @@ int chol_backward(Batch& b) {
   if (C.flat_L) return set_error(SSLAM_ERR_INVALID, "chol_backward needs the class-interleaved factor (the last factorisation was a flat one)");
   ScopedTimer t(b, "solve");
   const int nplv = (int)P.plv_lds_b.size();
-  const int ntail = P.compact ? P.c_ptr[nplv + 1] - P.c_ptr[nplv] : b.V.B;
+  const int* idx;
+  const int ntail = plan_range(P, nplv, b.V.B, &idx);
   if (P.tail_total > 0 && ntail > 0) {
-    const int* idx = P.compact ? P.d_idx + P.c_ptr[nplv] : nullptr;
     const int rc = with_width(BackTailWidths{}, P.nt_btail, [&](auto w) {
       hipLaunchKernelGGL(k_chol_back_tail<decltype(w)::value>, dim3(ntail), dim3(w), (size_t)P.tail_lds_b * sizeof(double), b.stream, C, (const double*)C.y, b.V.x,
                          (const LmState*)b.V.lm, idx);
@@ -2346,9 +2025,9 @@ int chol_backward(Batch& b) {
     if (rc) return rc;
   }
   for (int l = nplv - 1; l >= 0; --l) {
-    const int n = P.compact ? P.c_ptr[l + 1] - P.c_ptr[l] : P.plv_ptr[l + 1] - P.plv_ptr[l];
+    const int* idx;
+    const int n = plan_range(P, l, b.V.B, &idx);
     if (n <= 0) continue;
-    const int* idx = P.compact ? P.d_idx + P.c_ptr[l] : nullptr;
     const int ovr = P.plv_cls[l] == 1 ? P.nt_bmid : P.nt_bleaf;   // 0: the workgroup of the factorisation
     const int rc = with_width(LeafWidths{}, ovr > 0 ? ovr : P.plv_nt[l], [&](auto w) {
       hipLaunchKernelGGL(k_chol_back_pieces<decltype(w)::value>, dim3(n), dim3(w), (size_t)P.plv_lds_b[l] * sizeof(double), b.stream, C, P.plv_ptr[l],
@@ -2371,178 +2050,93 @@ static int plan_grow(CholPlan& P, void** p, size_t& cap, size_t bytes) {
   return 0;
 }
 
-// Z(u, v) of (L L^T)^-1 for pairs of vertices of the graphs of a batch (k_chol_marginal_pairs), from the last FLAT factorisation; out:
-// [n][36], the leading dim_u x dim_v entries row-major.  Any path length: a request whose Y fits the LDS budget (SSLAM_MARGINAL_LDS_BYTES,
-// read per call; default and ceiling 60 KB) runs out of LDS, every other one out of its slice of a device scratch buffer -- one upload, at
-// most one launch per placement and one download, through the page-locked staging buffer.  (Requests beyond 64 MB of path lists or 1 GB of
-// scratch go in further rounds of the same: the memory of a call is bounded, whatever the batch.)
-int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double* out) {
+
+// What differs between the two path kernels on the host side; everything else of a call is path_rounds_run.
+struct PathCall {
+  int width;             // ints per record (path_rounds.hpp)
+  int fixed;             // doubles of the kernel's fixed LDS area
+  bool no_column, fold;  // the planner's two switches
+  int in_dbl, out_dbl;   // doubles per request that go up / come back
+  const char *name, *noun, *launch;   // the entry point, its subject and its launch in the messages
+};
+static size_t env_clamped(const char* name, long long lo, long long hi) {   // hi: default and ceiling
+  const char* e = getenv(name);
+  return (size_t)(e ? std::min(std::max(atoll(e), lo), hi) : hi);
+}
+
+// Requests of a path kernel from the last FLAT factorisation, in rounds (path_rounds.hpp: the records, the placement, the caps).  A request
+// whose Y fits the LDS budget (SSLAM_MARGINAL_LDS_BYTES, read per call; default and ceiling 60 KB) runs out of LDS, every other one out of
+// its slice of a device scratch buffer -- per round one upload, at most one launch per placement and one download, through the page-locked
+// staging buffer (none: one host vector).  A round ends at SSLAM_PATH_ROUND_INTS path ints (read per call; default and ceiling 16 Mi,
+// floor 1) or 1 GB of scratch: the memory of a call is bounded, whatever the batch.
+// reqs: width - 4 ints each; in: [n][in_dbl] or nullptr; out: [n][out_dbl].
+// launch(placement tag, workgroups, LDS bytes, records, path columns, in, out, ylen, scratch) starts the kernel.
+template <class Launch>
+static int path_rounds_run(Batch& b, const PathCall& pc, const int* reqs, size_t n, const double* in, double* out, Launch&& launch) {
   CholPlan& P = *b.chol;
-  const CholView& C = P.C;
-  const size_t n = reqs.size();
   if (n == 0) return 0;
-  if (!C.flat_L) return set_error(SSLAM_ERR_INVALID, "chol_marginal_blocks needs the flat factor (chol_factor_and_forward(b, true))");
-  size_t budget = 60 * 1024;
-  if (const char* e = getenv("SSLAM_MARGINAL_LDS_BYTES")) budget = (size_t)std::min<long long>(std::max<long long>(atoll(e), 0), 60 * 1024);
-  auto col_of = [&](int xo) { return (xo >= 0 && xo < (int)P.h_xoff_col.size()) ? P.h_xoff_col[xo] : -1; };
-  for (const MarginalReq& rq : reqs)
-    if (col_of(rq.xoff_u) < 0 || col_of(rq.xoff_v) < 0) return set_error(SSLAM_ERR_INVALID, "marginal of an unknown that is not the start of a block row");
-  auto grow = [&](void** p, size_t& cap, size_t bytes) { return plan_grow(P, p, cap, bytes); };
-  constexpr size_t kPathCap = (size_t)16 << 20, kScratchCap = (size_t)1 << 30;   // ints of path lists, bytes of Y slices per round
-  constexpr size_t kEntry = 36 * sizeof(double) + sizeof(int4) + sizeof(int);      // Y block, path record, y offset of one path entry
-  struct Rec { int v[8]; size_t src; bool scratch; };
-  std::vector<Rec> recs;
-  std::vector<int> cols, up;
-  for (size_t k0 = 0; k0 < n;) {
-    recs.clear(); cols.clear();
-    size_t scr_bytes = 0, k = k0;
-    int ylen_lds = 0, n_lds = 0;
-    for (; k < n && (k == k0 || (cols.size() < kPathCap && scr_bytes < kScratchCap)); ++k) {
-      const MarginalReq& rq = reqs[k];
-      Rec q{};
-      q.src = k;
-      q.v[0] = (int)cols.size();
-      for (int j = col_of(rq.xoff_u); j >= 0; j = P.h_cparent[j]) cols.push_back(j);
-      q.v[1] = (int)cols.size() - q.v[0];
-      q.v[2] = q.v[0]; q.v[3] = 0; q.v[4] = rq.dim_u; q.v[5] = rq.dim_u; q.v[6] = q.v[1];
-      if (rq.xoff_v != rq.xoff_u) {
-        q.v[2] = (int)cols.size();
-        for (int j = col_of(rq.xoff_v); j >= 0; j = P.h_cparent[j]) cols.push_back(j);
-        q.v[3] = (int)cols.size() - q.v[2];
-        q.v[5] = rq.dim_v;
-        int nc = 0;   // common suffix of the two paths: from the root down to their lowest common ancestor
-        while (nc < q.v[1] && nc < q.v[3] && cols[q.v[0] + q.v[1] - 1 - nc] == cols[q.v[2] + q.v[3] - 1 - nc]) ++nc;
-        q.v[6] = nc;
-      }
-      const int ylen = q.v[1] + q.v[3];
-      q.scratch = 36 * sizeof(double) + (size_t)ylen * kEntry + 16 > budget;
-      if (q.scratch) { q.v[7] = (int)(scr_bytes / 16); scr_bytes += ((size_t)ylen * kEntry + 15) & ~(size_t)15; }
-      else { ylen_lds = std::max(ylen_lds, ylen); ++n_lds; }
-      recs.push_back(q);
-    }
-    const int m = (int)recs.size(), n_scr = m - n_lds;
-    std::stable_partition(recs.begin(), recs.end(), [](const Rec& r) { return !r.scratch; });   // [LDS requests | scratch requests]
-    up.resize((size_t)m * 8 + cols.size());
-    for (int i = 0; i < m; ++i) std::copy(recs[i].v, recs[i].v + 8, up.begin() + (size_t)i * 8);
-    std::copy(cols.begin(), cols.end(), up.begin() + (size_t)m * 8);
+  if (!P.C.flat_L) return set_error(SSLAM_ERR_INVALID, "%s needs the flat factor (chol_factor_and_forward(b, true))", pc.name);
+  if (!path_reqs_valid(P.h_xoff_col, reqs, n, pc.width, pc.no_column))
+    return set_error(SSLAM_ERR_INVALID, "%s of an unknown that is not the start of a block row", pc.noun);
+  const PathRules rules{pc.width, pc.fixed * sizeof(double), env_clamped("SSLAM_MARGINAL_LDS_BYTES", 0, 60 * 1024), pc.no_column, pc.fold,
+                        env_clamped("SSLAM_PATH_ROUND_INTS", 1, 16 << 20), (size_t)1 << 30};
+  PathRound R;
+  std::vector<char> fallback;
+  for (size_t k0 = 0; k0 < n; k0 = R.next) {
+    path_round(P.h_xoff_col, P.h_cparent, reqs, n, k0, rules, R);
+    const int m = R.m, n_lds = R.n_lds, n_scr = m - n_lds, W = pc.width;
+    const size_t up_bytes = R.up.size() * sizeof(int), rec_bytes = (up_bytes + 7) & ~(size_t)7;
+    const size_t in_bytes = (size_t)m * pc.in_dbl * sizeof(double), out_bytes = (size_t)m * pc.out_dbl * sizeof(double);
     int rc;
-    size_t mpath_bytes = P.mpath_cap * sizeof(int), mout_bytes = P.mout_cap * sizeof(double);
-    if ((rc = grow((void**)&P.d_mpath, mpath_bytes, up.size() * sizeof(int)))) return rc;
-    P.mpath_cap = mpath_bytes / sizeof(int);
-    if ((rc = grow((void**)&P.d_mout, mout_bytes, (size_t)m * 36 * sizeof(double)))) return rc;
-    P.mout_cap = mout_bytes / sizeof(double);
-    if (n_scr > 0 && (rc = grow((void**)&P.d_mscratch, P.mscratch_cap, scr_bytes))) return rc;
-    const size_t in_bytes = (up.size() * sizeof(int) + 7) & ~(size_t)7, out_bytes = (size_t)m * 36 * sizeof(double);
-    char* stage = b.pin->get(in_bytes + out_bytes);
-    std::vector<double> fallback;
-    const void* src = up.data();
-    double* res;
-    if (stage) { memcpy(stage, up.data(), up.size() * sizeof(int)); src = stage; res = reinterpret_cast<double*>(stage + in_bytes); }
-    else { fallback.resize((size_t)m * 36); res = fallback.data(); }
-    SSLAM_HIP_TRY(hipMemcpyAsync(P.d_mpath, src, up.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
-    const int* d_cols = P.d_mpath + (size_t)m * 8;
+    if ((rc = plan_grow(P, (void**)&P.d_mpath, P.mpath_cap, up_bytes))) return rc;
+    if ((rc = plan_grow(P, (void**)&P.d_mout, P.mout_cap, out_bytes))) return rc;
+    if (in_bytes && (rc = plan_grow(P, (void**)&P.d_gin, P.gin_cap, in_bytes))) return rc;
+    if (n_scr > 0 && (rc = plan_grow(P, (void**)&P.d_mscratch, P.mscratch_cap, R.scr_bytes))) return rc;
+    char* stage = b.pin->get(rec_bytes + in_bytes + out_bytes);
+    if (!stage) { fallback.resize(rec_bytes + in_bytes + out_bytes); stage = fallback.data(); }
+    memcpy(stage, R.up.data(), up_bytes);
+    double* zin = reinterpret_cast<double*>(stage + rec_bytes);
+    double* res = zin + (size_t)m * pc.in_dbl;
+    for (int i = 0; i < m && in_bytes; ++i) std::copy(in + R.src[i] * pc.in_dbl, in + (R.src[i] + 1) * pc.in_dbl, zin + (size_t)i * pc.in_dbl);
+    SSLAM_HIP_TRY(hipMemcpyAsync(P.d_mpath, stage, up_bytes, hipMemcpyHostToDevice, b.stream));
+    if (in_bytes) SSLAM_HIP_TRY(hipMemcpyAsync(P.d_gin, zin, in_bytes, hipMemcpyHostToDevice, b.stream));
+    const int* d_cols = P.d_mpath + (size_t)m * W;
     if (n_lds > 0)
-      hipLaunchKernelGGL(k_chol_marginal_pairs<false>, dim3(n_lds), dim3(64), 36 * sizeof(double) + (size_t)ylen_lds * kEntry + 16, b.stream, C,
-                         (const int*)P.d_mpath, d_cols, P.d_mout, ylen_lds, (char*)nullptr);
+      launch(std::false_type{}, n_lds, rules.fixed + (size_t)R.ylen_lds * kPathEntry + 16, (const int*)P.d_mpath, d_cols, (const double*)P.d_gin,
+             P.d_mout, R.ylen_lds, (char*)nullptr);
     if (n_scr > 0)
-      hipLaunchKernelGGL(k_chol_marginal_pairs<true>, dim3(n_scr), dim3(64), 36 * sizeof(double), b.stream, C,
-                         (const int*)(P.d_mpath + (size_t)n_lds * 8), d_cols, P.d_mout + (size_t)n_lds * 36, 0, P.d_mscratch);
+      launch(std::true_type{}, n_scr, rules.fixed, (const int*)(P.d_mpath + (size_t)n_lds * W), d_cols,
+             (const double*)(P.d_gin + (size_t)n_lds * pc.in_dbl), P.d_mout + (size_t)n_lds * pc.out_dbl, 0, P.d_mscratch);
     SSLAM_HIP_TRY(hipMemcpyAsync(res, P.d_mout, out_bytes, hipMemcpyDeviceToHost, b.stream));
-    SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // up is reused by the next round
+    SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // R and the staging are reused by the next round
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "pair marginals launch: %s", hipGetErrorString(e));
-    for (int i = 0; i < m; ++i) std::copy(res + (size_t)i * 36, res + (size_t)i * 36 + 36, out + recs[i].src * 36);
-    k0 = k;
+    if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "%s launch: %s", pc.launch, hipGetErrorString(e));
+    for (int i = 0; i < m; ++i) std::copy(res + (size_t)i * pc.out_dbl, res + (size_t)(i + 1) * pc.out_dbl, out + R.src[i] * pc.out_dbl);
   }
   return 0;
 }
 
-// The gate of candidate edges (k_chol_gate_pairs) from the last FLAT factorisation.  in / out: [n][44], see the kernel.  The rounds, the
-// placement rule and the staging are those of chol_marginal_blocks; the LDS of a candidate counts the kernel's fixed area, and a side with
-// xoff < 0 (fixed or edge-less) has a path of length 0.
+static_assert(sizeof(MarginalReq) == 4 * sizeof(int) && sizeof(GateReq) == (kGateReq - 4) * sizeof(int), "the requests are the planner's ints");
+
+// Z(u, v) of (L L^T)^-1 for pairs of vertices of the graphs of a batch (k_chol_marginal_pairs); out: [n][36], the leading dim_u x dim_v
+// entries row-major.  Any path length.
+int chol_marginal_blocks(Batch& b, const std::vector<MarginalReq>& reqs, double* out) {
+  const CholView& C = b.chol->C;
+  return path_rounds_run(b, PathCall{8, 36, false, true, 0, 36, "chol_marginal_blocks", "marginal", "pair marginals"}, &reqs.data()->xoff_u, reqs.size(), nullptr, out,
+                         [&](auto scr, int n, size_t lds, const int* req, const int* cols, const double*, double* o, int ylen, char* scratch) {
+                           hipLaunchKernelGGL(k_chol_marginal_pairs<decltype(scr)::value>, dim3(n), dim3(64), lds, b.stream, C, req, cols, o, ylen, scratch);
+                         });
+}
+
+// The gate of candidate edges (k_chol_gate_pairs).  in / out: [n][44], see the kernel.  A side with xoff < 0 (fixed or edge-less) has a
+// path of length 0.
 int chol_gate_pairs(Batch& b, const std::vector<GateReq>& reqs, const double* in, double* out) {
-  CholPlan& P = *b.chol;
-  const CholView& C = P.C;
-  const size_t n = reqs.size();
-  if (n == 0) return 0;
-  if (!C.flat_L) return set_error(SSLAM_ERR_INVALID, "chol_gate_pairs needs the flat factor (chol_factor_and_forward(b, true))");
-  size_t budget = 60 * 1024;
-  if (const char* e = getenv("SSLAM_MARGINAL_LDS_BYTES")) budget = (size_t)std::min<long long>(std::max<long long>(atoll(e), 0), 60 * 1024);
-  auto col_of = [&](int xo) { return (xo >= 0 && xo < (int)P.h_xoff_col.size()) ? P.h_xoff_col[xo] : -1; };
-  for (const GateReq& rq : reqs)
-    if ((rq.xoff_u >= 0 && col_of(rq.xoff_u) < 0) || (rq.xoff_v >= 0 && col_of(rq.xoff_v) < 0))
-      return set_error(SSLAM_ERR_INVALID, "gate of an unknown that is not the start of a block row");
-  constexpr size_t kPathCap = (size_t)16 << 20, kScratchCap = (size_t)1 << 30;
-  constexpr size_t kEntry = 36 * sizeof(double) + sizeof(int4) + sizeof(int);
-  constexpr size_t kFixed = kGateFixed * sizeof(double);
-  struct Rec { int v[kGateReq]; size_t src; bool scratch; };
-  std::vector<Rec> recs;
-  std::vector<int> cols, up;
-  for (size_t k0 = 0; k0 < n;) {
-    recs.clear(); cols.clear();
-    size_t scr_bytes = 0, k = k0;
-    int ylen_lds = 0, n_lds = 0;
-    for (; k < n && (k == k0 || (cols.size() < kPathCap && scr_bytes < kScratchCap)); ++k) {
-      const GateReq& rq = reqs[k];
-      Rec q{};
-      q.src = k;
-      q.v[0] = (int)cols.size();
-      for (int j = col_of(rq.xoff_u); j >= 0; j = P.h_cparent[j]) cols.push_back(j);
-      q.v[1] = (int)cols.size() - q.v[0];
-      q.v[2] = (int)cols.size();
-      for (int j = col_of(rq.xoff_v); j >= 0; j = P.h_cparent[j]) cols.push_back(j);
-      q.v[3] = (int)cols.size() - q.v[2];
-      q.v[4] = rq.dim_u; q.v[5] = rq.dim_v;
-      int nc = 0;   // common suffix of the two paths (none when a side has no column)
-      while (nc < q.v[1] && nc < q.v[3] && cols[q.v[0] + q.v[1] - 1 - nc] == cols[q.v[2] + q.v[3] - 1 - nc]) ++nc;
-      q.v[6] = nc;
-      q.v[8] = rq.kind; q.v[9] = rq.idx_u; q.v[10] = rq.idx_v; q.v[11] = rq.has_info;
-      const int ylen = q.v[1] + q.v[3];
-      q.scratch = kFixed + (size_t)ylen * kEntry + 16 > budget;
-      if (q.scratch) { q.v[7] = (int)(scr_bytes / 16); scr_bytes += ((size_t)ylen * kEntry + 15) & ~(size_t)15; }
-      else { ylen_lds = std::max(ylen_lds, ylen); ++n_lds; }
-      recs.push_back(q);
-    }
-    const int m = (int)recs.size(), n_scr = m - n_lds;
-    std::stable_partition(recs.begin(), recs.end(), [](const Rec& r) { return !r.scratch; });   // [LDS candidates | scratch candidates]
-    up.resize((size_t)m * kGateReq + cols.size());
-    for (int i = 0; i < m; ++i) std::copy(recs[i].v, recs[i].v + kGateReq, up.begin() + (size_t)i * kGateReq);
-    std::copy(cols.begin(), cols.end(), up.begin() + (size_t)m * kGateReq);
-    int rc;
-    const size_t io_bytes = (size_t)m * kGateIO * sizeof(double);
-    size_t mpath_bytes = P.mpath_cap * sizeof(int), mout_bytes = P.mout_cap * sizeof(double);
-    if ((rc = plan_grow(P, (void**)&P.d_mpath, mpath_bytes, up.size() * sizeof(int)))) return rc;
-    P.mpath_cap = mpath_bytes / sizeof(int);
-    if ((rc = plan_grow(P, (void**)&P.d_mout, mout_bytes, io_bytes))) return rc;
-    P.mout_cap = mout_bytes / sizeof(double);
-    if ((rc = plan_grow(P, (void**)&P.d_gin, P.gin_cap, io_bytes))) return rc;
-    if (n_scr > 0 && (rc = plan_grow(P, (void**)&P.d_mscratch, P.mscratch_cap, scr_bytes))) return rc;
-    const size_t rec_bytes = (up.size() * sizeof(int) + 7) & ~(size_t)7;
-    char* stage = b.pin->get(rec_bytes + 2 * io_bytes);
-    std::vector<char> fallback;
-    if (!stage) { fallback.resize(rec_bytes + 2 * io_bytes); stage = fallback.data(); }
-    memcpy(stage, up.data(), up.size() * sizeof(int));
-    double* zin = reinterpret_cast<double*>(stage + rec_bytes);
-    double* res = zin + (size_t)m * kGateIO;
-    for (int i = 0; i < m; ++i) std::copy(in + recs[i].src * kGateIO, in + (recs[i].src + 1) * kGateIO, zin + (size_t)i * kGateIO);
-    SSLAM_HIP_TRY(hipMemcpyAsync(P.d_mpath, stage, up.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
-    SSLAM_HIP_TRY(hipMemcpyAsync(P.d_gin, zin, io_bytes, hipMemcpyHostToDevice, b.stream));
-    const int* d_cols = P.d_mpath + (size_t)m * kGateReq;
-    if (n_lds > 0)
-      hipLaunchKernelGGL(k_chol_gate_pairs<false>, dim3(n_lds), dim3(64), kFixed + (size_t)ylen_lds * kEntry + 16, b.stream, C, (const int*)P.d_mpath,
-                         d_cols, (const double*)P.d_gin, (const double*)b.V.pose, (const double*)b.V.lmk, P.d_mout, ylen_lds, (char*)nullptr);
-    if (n_scr > 0)
-      hipLaunchKernelGGL(k_chol_gate_pairs<true>, dim3(n_scr), dim3(64), kFixed, b.stream, C, (const int*)(P.d_mpath + (size_t)n_lds * kGateReq), d_cols,
-                         (const double*)(P.d_gin + (size_t)n_lds * kGateIO), (const double*)b.V.pose, (const double*)b.V.lmk,
-                         P.d_mout + (size_t)n_lds * kGateIO, 0, P.d_mscratch);
-    SSLAM_HIP_TRY(hipMemcpyAsync(res, P.d_mout, io_bytes, hipMemcpyDeviceToHost, b.stream));
-    SSLAM_HIP_TRY(hipStreamSynchronize(b.stream));   // up and the staging are reused by the next round
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(SSLAM_ERR_HIP, "gate launch: %s", hipGetErrorString(e));
-    for (int i = 0; i < m; ++i) std::copy(res + (size_t)i * kGateIO, res + (size_t)(i + 1) * kGateIO, out + recs[i].src * kGateIO);
-    k0 = k;
-  }
-  return 0;
+  const CholView& C = b.chol->C;
+  return path_rounds_run(b, PathCall{kGateReq, kGateFixed, true, false, kGateIO, kGateIO, "chol_gate_pairs", "gate", "gate"}, &reqs.data()->xoff_u, reqs.size(), in, out,
+                         [&](auto scr, int n, size_t lds, const int* req, const int* cols, const double* zin, double* o, int ylen, char* scratch) {
+                           hipLaunchKernelGGL(k_chol_gate_pairs<decltype(scr)::value>, dim3(n), dim3(64), lds, b.stream, C, req, cols, zin,
+                                              (const double*)b.V.pose, (const double*)b.V.lmk, o, ylen, scratch);
+                         });
 }
 
 }  // namespace sslam

@@ -1950,6 +1950,21 @@ static int vertex_xoff(const Batch& b, int g, int v) {
   return r < 0 ? -1 : 6 * b.V.nPr + 3 * r;
 }
 
+// The requests of chol_marginal_blocks for n (graph, row vertex, column vertex) triples at(k); slot[k]: the triple's place among them, -1:
+// an end is fixed or without edges (its block is zeros, nothing is asked).
+static std::vector<MarginalReq> marginal_requests(const Batch& b, size_t n, const std::function<std::array<int, 3>(size_t)>& at, std::vector<int>& slot) {
+  std::vector<MarginalReq> mr;
+  slot.assign(n, -1);
+  for (size_t k = 0; k < n; ++k) {
+    const std::array<int, 3> q = at(k);
+    const int g = q[0], xr = vertex_xoff(b, g, q[1]), xc = vertex_xoff(b, g, q[2]);
+    if (xr < 0 || xc < 0) continue;
+    slot[k] = (int)mr.size();
+    mr.push_back({xr, vertex_dim(b.graphs[g]->vtype[q[1]]), xc, vertex_dim(b.graphs[g]->vtype[q[2]])});
+  }
+  return mr;
+}
+
 // The flat factor of the undamped H of every graph of a linearised batch, what chol_marginal_blocks reads: through the single launch
 // where the plan has one, else the launches per depth.  *bad: the first graph whose H is not positive definite, -1: none.
 static int factor_undamped_flat(Batch& b, int* bad) {
@@ -1980,15 +1995,8 @@ static int marginal_blocks(sslam_graph* h, const std::vector<std::pair<int, int>
     int bad;
     if ((rc = factor_undamped_flat(b, &bad))) return rc;
     if (bad >= 0) return set_error(SSLAM_ERR_NUMERIC, "H is not positive definite: no marginals");
-    std::vector<MarginalReq> mr;
-    std::vector<int> slot(pairs.size(), -1);
-    for (size_t k = 0; k < pairs.size(); ++k) {
-      const int vr = pairs[k].first, vc = pairs[k].second;
-      const int xr = vertex_xoff(b, 0, vr), xc = vertex_xoff(b, 0, vc);
-      if (xr < 0 || xc < 0) continue;
-      slot[k] = (int)mr.size();
-      mr.push_back({xr, vertex_dim(h->g.vtype[vr]), xc, vertex_dim(h->g.vtype[vc])});
-    }
+    std::vector<int> slot;
+    const std::vector<MarginalReq> mr = marginal_requests(b, pairs.size(), [&](size_t k) { return std::array<int, 3>{0, pairs[k].first, pairs[k].second}; }, slot);
     std::vector<double> Z(mr.size() * 36 + 1);
     if ((rc = chol_marginal_blocks(b, mr, Z.data()))) return rc;
     size_t o = 0;
@@ -2208,6 +2216,24 @@ int sslam_batch_optimize(sslam_batch* h, int max_iters, sslam_opt_stats* out) {
     return for_each_part(h, true, [&](sslam_batch* p, int k) { return batch_optimize(p->b, max_iters, out + h->part0[k]); });
   return batch_optimize(h->b, max_iters, out);
 }
+// The requests of a batch call (marginals, gate) over the parts of a stream group; a plain batch is its own single part.
+struct PartSplit {
+  sslam_batch* h; const bool group; const int K, ng;   // K parts, ng graphs in the whole batch
+  std::vector<std::vector<int>> src;   // per part: the requests it got, in call order
+  explicit PartSplit(sslam_batch* h_) : h(h_), group(!h_->parts.empty()), K(group ? (int)h_->parts.size() : 1),
+                                        ng(group ? h_->part0.back() : (int)h_->b.graphs.size()), src(K) {}
+  Batch& batch(int p) const { return group ? h->parts[p]->b : h->b; }
+  // request k (`what` in the message) names graph g of the batch: its part *p, the graph's index *gl there; k joins src[*p]
+  int place(const char* what, int k, int g, int* p, int* gl) {
+    if (g < 0 || g >= ng) return set_error(SSLAM_ERR_INVALID, "%s %d: graph index %d out of range (the batch holds %d graphs)", what, k, g, ng);
+    *p = group ? (int)(std::upper_bound(h->part0.begin(), h->part0.end(), g) - h->part0.begin()) - 1 : 0;
+    *gl = group ? g - h->part0[*p] : g;
+    src[*p].push_back(k);
+    return 0;
+  }
+  // f(p) for the parts one after the other, from the calling thread
+  int run(const std::function<int(int)>& f) { return group ? for_each_part(h, false, [&](sslam_batch*, int p) { return f(p); }) : f(0); }
+};
 // ---- covariance blocks of the graphs of a batch -------------------------------------------------------------------------------
 // What the path kernels (marginals, gate) cannot serve: the iterative solvers have no factor to walk, an edge shard only a partial H.
 static int batch_direct_only(const Batch& b, const char* what) {
@@ -2244,15 +2270,8 @@ static int batch_with_flat_factor(Batch& b, const char* what, const std::functio
 static int batch_marginals(Batch& b, const std::vector<std::array<int, 3>>& req, double* out) {
   if (req.empty()) return 0;
   if (const int rc = batch_direct_only(b, "marginals")) return rc;
-  std::vector<MarginalReq> mr;
-  std::vector<int> slot(req.size(), -1);
-  for (size_t k = 0; k < req.size(); ++k) {
-    const int g = req[k][0], vr = req[k][1], vc = req[k][2];
-    const int xr = vertex_xoff(b, g, vr), xc = vertex_xoff(b, g, vc);
-    if (xr < 0 || xc < 0) continue;
-    slot[k] = (int)mr.size();
-    mr.push_back({xr, vertex_dim(b.graphs[g]->vtype[vr]), xc, vertex_dim(b.graphs[g]->vtype[vc])});
-  }
+  std::vector<int> slot;
+  const std::vector<MarginalReq> mr = marginal_requests(b, req.size(), [&](size_t k) { return req[k]; }, slot);
   std::fill(out, out + req.size() * 36, 0.0);
   if (mr.empty()) return 0;
   return batch_with_flat_factor(b, "marginals", [&]() -> int {
@@ -2269,37 +2288,26 @@ int sslam_batch_marginals(sslam_batch* h, const int32_t* req, int n, double* out
   int rc = batch_check(h);
   if (rc) return rc;
   if (n == 0) return 0;
-  const bool group = !h->parts.empty();
-  const int K = group ? (int)h->parts.size() : 1;
-  const int ng = group ? h->part0.back() : (int)h->b.graphs.size();
-  auto part_batch = [&](int k) -> Batch& { return group ? h->parts[k]->b : h->b; };
+  PartSplit S(h);
   // every request is checked before anything runs: a bad one leaves out_blocks unwritten
-  std::vector<std::vector<std::array<int, 3>>> preq(K);
-  std::vector<std::vector<int>> psrc(K);
+  std::vector<std::vector<std::array<int, 3>>> preq(S.K);
   std::vector<int> dr(n), dc(n);
   for (int k = 0; k < n; ++k) {
     const int g = req[3 * k], vr = req[3 * k + 1], vc = req[3 * k + 2];
-    if (g < 0 || g >= ng) return set_error(SSLAM_ERR_INVALID, "request %d: graph index %d out of range (the batch holds %d graphs)", k, g, ng);
-    int p = 0;
-    if (group) p = (int)(std::upper_bound(h->part0.begin(), h->part0.end(), g) - h->part0.begin()) - 1;
-    const int gl = group ? g - h->part0[p] : g;
-    const HostGraph& G = *part_batch(p).graphs[gl];
+    int p, gl;
+    if ((rc = S.place("request", k, g, &p, &gl))) return rc;
+    const HostGraph& G = *S.batch(p).graphs[gl];
     if (vr < 0 || vr >= G.nv() || vc < 0 || vc >= G.nv()) return set_error(SSLAM_ERR_INVALID, "request %d: bad vertex id (%d, %d) in graph %d", k, vr, vc, g);
     dr[k] = vertex_dim(G.vtype[vr]); dc[k] = vertex_dim(G.vtype[vc]);
     preq[p].push_back({gl, vr, vc});
-    psrc[p].push_back(k);
   }
-  // the parts of a stream group one after the other, from the calling thread
-  std::vector<std::vector<double>> pz(K);
-  auto run = [&](int p) { pz[p].resize(preq[p].size() * 36 + 1); return batch_marginals(part_batch(p), preq[p], pz[p].data()); };
-  if (group) rc = for_each_part(h, false, [&](sslam_batch*, int p) { return run(p); });
-  else rc = run(0);
-  if (rc) return rc;
+  std::vector<std::vector<double>> pz(S.K);
+  if ((rc = S.run([&](int p) { pz[p].resize(preq[p].size() * 36 + 1); return batch_marginals(S.batch(p), preq[p], pz[p].data()); }))) return rc;
   std::vector<size_t> off(n + 1, 0);
   for (int k = 0; k < n; ++k) off[k + 1] = off[k] + (size_t)dr[k] * dc[k];
-  for (int p = 0; p < K; ++p)
-    for (size_t i = 0; i < psrc[p].size(); ++i) {
-      const int k = psrc[p][i];
+  for (int p = 0; p < S.K; ++p)
+    for (size_t i = 0; i < S.src[p].size(); ++i) {
+      const int k = S.src[p][i];
       std::copy(pz[p].begin() + i * 36, pz[p].begin() + i * 36 + (size_t)dr[k] * dc[k], out + off[k]);
     }
   return 0;
@@ -2343,34 +2351,23 @@ int sslam_batch_gate(sslam_batch* h, const int32_t* cand, const double* z, const
   int rc = batch_check(h);
   if (rc) return rc;
   if (n == 0) return 0;
-  const bool group = !h->parts.empty();
-  const int K = group ? (int)h->parts.size() : 1;
-  const int ng = group ? h->part0.back() : (int)h->b.graphs.size();
-  auto part_batch = [&](int k) -> Batch& { return group ? h->parts[k]->b : h->b; };
+  PartSplit S(h);
   // every candidate is checked before anything runs: a bad one leaves the outputs unwritten
-  std::vector<std::vector<GateReq>> preq(K);
-  std::vector<std::vector<double>> pin(K), pout(K);
-  std::vector<std::vector<int>> psrc(K);
+  std::vector<std::vector<GateReq>> preq(S.K);
+  std::vector<std::vector<double>> pin(S.K), pout(S.K);
   for (int k = 0; k < n; ++k) {
     const int g = cand[4 * k], kind = cand[4 * k + 1], vu = cand[4 * k + 2], vv = cand[4 * k + 3];
-    if (g < 0 || g >= ng) return set_error(SSLAM_ERR_INVALID, "candidate %d: graph index %d out of range (the batch holds %d graphs)", k, g, ng);
-    int p = 0;
-    if (group) p = (int)(std::upper_bound(h->part0.begin(), h->part0.end(), g) - h->part0.begin()) - 1;
-    const int gl = group ? g - h->part0[p] : g;
-    const Batch& pb = part_batch(p);
+    int p, gl;
+    if ((rc = S.place("candidate", k, g, &p, &gl))) return rc;
+    const Batch& pb = S.batch(p);
     const double *zk = z + (size_t)k * 7, *wk = info ? info + (size_t)k * 36 : nullptr;
     if ((rc = gate_check(*pb.graphs[gl], k, kind, vu, vv, zk, wk))) return rc;
     pin[p].resize(pin[p].size() + 44);
     preq[p].push_back(gate_request(pb, gl, kind, vu, vv, zk, wk, pin[p].data() + pin[p].size() - 44));
-    psrc[p].push_back(k);
   }
-  // the parts of a stream group one after the other, from the calling thread
-  auto run = [&](int p) { pout[p].resize(pin[p].size() + 1); return batch_gate(part_batch(p), preq[p], pin[p].data(), pout[p].data()); };
-  if (group) rc = for_each_part(h, false, [&](sslam_batch*, int p) { return run(p); });
-  else rc = run(0);
-  if (rc) return rc;
-  for (int p = 0; p < K; ++p)
-    for (size_t i = 0; i < psrc[p].size(); ++i) gate_result(pout[p].data() + i * 44, psrc[p][i], d2_out, e_out, cov_out);
+  if ((rc = S.run([&](int p) { pout[p].resize(pin[p].size() + 1); return batch_gate(S.batch(p), preq[p], pin[p].data(), pout[p].data()); }))) return rc;
+  for (int p = 0; p < S.K; ++p)
+    for (size_t i = 0; i < S.src[p].size(); ++i) gate_result(pout[p].data() + i * 44, S.src[p][i], d2_out, e_out, cov_out);
   return 0;
 }
 

@@ -39,16 +39,22 @@ def _ref_block(gp, Hinv, vr, vc):
     return Hinv[h[vr]:h[vr] + dr, h[vc]:h[vc] + dc]
 
 
-def _with_lds_budget(nbytes, f):
-    old = os.environ.get("SSLAM_MARGINAL_LDS_BYTES")
-    os.environ["SSLAM_MARGINAL_LDS_BYTES"] = str(nbytes)
+def _with_env(name, value, f):
+    """f() with the variable set (None: as it is); the library reads both per call"""
+    old = os.environ.get(name)
+    if value is not None:
+        os.environ[name] = str(value)
     try:
         return f()
     finally:
         if old is None:
-            os.environ.pop("SSLAM_MARGINAL_LDS_BYTES")
+            os.environ.pop(name, None)
         else:
-            os.environ["SSLAM_MARGINAL_LDS_BYTES"] = old
+            os.environ[name] = old
+
+
+def _with_lds_budget(nbytes, f):
+    return _with_env("SSLAM_MARGINAL_LDS_BYTES", nbytes, f)
 
 
 @pytest.fixture(scope="module")
@@ -103,6 +109,19 @@ def test_scratch_placement_equals_lds_bitwise(three):
         mixed = _with_lds_budget(36 * 8 + 16 + 308 * entries, lambda: B.marginals(req))
         for a, c in zip(blocks, mixed):
             assert np.array_equal(a, c)
+
+
+def test_rounds_agree_bitwise(three):
+    """SSLAM_PATH_ROUND_INTS cuts a call into rounds of requests (each its own upload, launches, download and scatter): at 1 every request
+    is a round, at 64 a round takes a few; the blocks are those of the one-round call.  With the default budget (every path in LDS), and
+    with a budget of 16 path entries that puts both placements into one round."""
+    gps, graphs, B, req, blocks = three
+    for budget in (None, 288 + 16 + 308 * 16):
+        for ints in (1, 64):
+            got = _with_env("SSLAM_PATH_ROUND_INTS", ints, lambda: _with_lds_budget(budget, lambda: B.marginals(req)))
+            assert len(got) == len(blocks)
+            for a, c in zip(blocks, got):
+                assert np.array_equal(a, c), (budget, ints)
 
 
 def test_front_kernel_family(gpu_lib):

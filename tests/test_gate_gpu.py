@@ -41,16 +41,22 @@ def _candidates(gp, g):
             + [pose_candidate(gp, g, 10, 30, info=None)])
 
 
-def _with_lds_budget(nbytes, f):
-    old = os.environ.get("SSLAM_MARGINAL_LDS_BYTES")
-    os.environ["SSLAM_MARGINAL_LDS_BYTES"] = str(nbytes)
+def _with_env(name, value, f):
+    """f() with the variable set (None: as it is); the library reads both per call"""
+    old = os.environ.get(name)
+    if value is not None:
+        os.environ[name] = str(value)
     try:
         return f()
     finally:
         if old is None:
-            os.environ.pop("SSLAM_MARGINAL_LDS_BYTES")
+            os.environ.pop(name, None)
         else:
-            os.environ["SSLAM_MARGINAL_LDS_BYTES"] = old
+            os.environ[name] = old
+
+
+def _with_lds_budget(nbytes, f):
+    return _with_env("SSLAM_MARGINAL_LDS_BYTES", nbytes, f)
 
 
 def _same(a, b):
@@ -121,9 +127,9 @@ def test_quaternion_sign(three):
     assert np.array_equal(f2, d2) and _same(fe, e) and _same(fS, S)
 
 
-def test_zero_length_paths(gpu_lib):
-    """two fixed poses: a candidate between them has no path on either side (S = Omega^-1, d2 = e^T Omega e; without Omega S = 0 and d2 is
-    NaN with the call succeeding); a candidate with one fixed end matches the reference with that end's blocks zero"""
+@pytest.fixture(scope="module")
+def fixed_ends(gpu_lib):
+    """a graph with two fixed poses, and candidates with one or both ends at them"""
     from semantic_slam_amd import GraphSLAM, GraphBatch
     gp = GraphProblem.from_synth(make_graph(40, 8, seed=4), interleave=True)
     f0, f1 = int(gp.pose_ids[0]), int(gp.pose_ids[20])
@@ -138,7 +144,13 @@ def test_zero_length_paths(gpu_lib):
     both = pose_candidate(gp, 0, 0, 20)
     cand = [both, both[:5] + (None,), pose_candidate(gp, 0, 20, 30), pose_candidate(gp, 0, 31, 0), point_candidate(gp, 0, 20, 3),
             pose_candidate(gp, 0, 0, 39, info=None)]
-    d2, e, S = B.gate(cand, return_cov=True)
+    return gp, B, both, cand, B.gate(cand, return_cov=True)
+
+
+def test_zero_length_paths(fixed_ends):
+    """two fixed poses: a candidate between them has no path on either side (S = Omega^-1, d2 = e^T Omega e; without Omega S = 0 and d2 is
+    NaN with the call succeeding); a candidate with one fixed end matches the reference with that end's blocks zero"""
+    gp, B, both, cand, (d2, e, S) = fixed_ends
     re_ = error_jac(gp.est, "se3", both[2], both[3], both[4])[0]
     want = float(re_ @ OMEGA6 @ re_)
     print(f"both ends fixed: d2 {d2[0]:.17g} e^T Omega e {want:.17g} rel err {abs(d2[0] - want) / want:.3e}")
@@ -150,6 +162,21 @@ def test_zero_length_paths(gpu_lib):
         _check_against_ref(gp, Hinv, cand[k], d2[k], e[k], S[k], "one fixed end")
     for lds in (1, 296 * 8 + 16):                                # the same in scratch, and with LDS for the fixed area alone
         assert all(_same(a, b) for a, b in zip((d2, e, S), _with_lds_budget(lds, lambda: B.gate(cand, return_cov=True))))
+
+
+def test_rounds_agree_bitwise(three, fixed_ends):
+    """SSLAM_PATH_ROUND_INTS cuts a call into rounds of candidates (each its own upload, launches, download and scatter): at 1 every
+    candidate with a column is a round, at 64 a round takes a few; d2, e and S are those of the one-round call, NaN included.  With the
+    default budget (every path in LDS), and with a budget of 8 path entries that puts both placements into one round.  The candidates
+    with fixed ends add records without columns, which do not close a round."""
+    _, _, B3, cand3, first3 = three
+    _, B1, _, cand1, first1 = fixed_ends
+    assert np.isnan(first1[0][1])
+    for B, cand, first in ((B3, cand3, first3), (B1, cand1, first1)):
+        for budget in (None, 2368 + 16 + 308 * 8):
+            for ints in (1, 64):
+                got = _with_env("SSLAM_PATH_ROUND_INTS", ints, lambda: _with_lds_budget(budget, lambda: B.gate(cand, return_cov=True)))
+                assert all(_same(a, c) for a, c in zip(first, got)), (len(cand), budget, ints)
 
 
 def test_batch_of_one_against_the_single_graph_handle(gpu_lib):
