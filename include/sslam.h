@@ -347,6 +347,9 @@ int sslam_batch_time_solver(sslam_batch* b, int repeats, double* factor_ms, doub
 int64_t sslam_batch_linearize_bytes(const sslam_batch* b);
 /* structural facts of a batch (doubles): "factor_lnz" (doubles in the Cholesky factor), "factor_levels", "factor_front" (1: the
  * factorisation runs the front kernels, the default of batches of 32 graphs and more),
+ * "front_groups_per_cu_leaf" / "front_groups_per_cu_mid" (front workgroups a CU holds by the runtime's own count, the minimum over the
+ * leaf / mid launches at their LDS sizes; a class without launches reports what its kernel's registers allow; 0 without front tables; the
+ * minimum over the parts of a stream group),
  * "compact_rounds" (times so far that the LM endgame, or sslam_batch_solve with graphs sitting out, sized the factor / solve launches by
  * index lists of the graphs still taking part; summed over the parts of a stream group),
  * "h_doubles" (doubles in H), "dim" (scalar unknowns), "factor_bytes" = algorithmic HBM bytes of one numeric

@@ -176,7 +176,16 @@ struct CholOpts {
   // 128-thread groups of 2800 (cap_leaf 700) 7.9-8.3 / 2.3 (the default); 256-thread groups of 4000-5000 8.5-9.3 / 2.3-2.4.
   int group_cap = -1;      // -1: 2800 for batches >= 32, else 0 (no groups: small batches run the dependency-driven launch, one piece per workgroup)
   int group_blocks = 1024;
-  int ustage = -1;         // 1: the per-depth kernels stage the update-matrix records in LDS too (one round trip for all tables: shorter
+  // LDS budget of the front kernels (round 7), bytes; 0: off.  In the throughput regime with front tables no group of a per-depth launch
+  // needs more LDS in k_front_pieces than this -- L, y, blob and derived tables, as FrontHost::lds counts them -- so a launch's residency is
+  // set by the budget (160 KiB / 20480 B: eight workgroups per CU), not by its fattest group.  The groups are packed by an upper estimate of
+  // those bytes next to group_cap and group_blocks (which stay upper limits); a group the estimate let through that the built tables still
+  // put above the budget is split and the plan built again.  A component that exceeds the budget alone stays a group of one.
+  // Off by default.  Measured on 1024 L graphs: 20480 B takes the factorisation from 11.9 to 11.3 ms per batch and the
+  // backward substitution from 4.25 to 4.48; L and y keep their bits, but the backward kernel sizes a column's teams by the columns of
+  // its GROUP's level, so x moves in the last bit and with it LM's accept / reject decisions (21261 trials against 21277).
+  int lds_budget = 0;
+  int ustage = -1;        // 1: the per-depth kernels stage the update-matrix records in LDS too (one round trip for all tables: shorter
                            //    piece latency, fewer pieces per CU); -1: 1 for batches < 32 (latency-bound), else 0 (residency-bound)
   int order = 1;           // 0: minimum degree, lowest index first (rounds 1-3: eliminates a pose chain from one end -> a tree as deep as the chain);
                            // 1: multiple minimum degree over independent sets (below): a chain halves per round -> O(log n) levels.  Small
@@ -231,6 +240,7 @@ struct CholOpts {
       else if (k == "min_chunk") min_chunk = std::max(1, iv); else if (k == "split_min") split_min = std::max(2, iv);
       else if (k == "pcap_leaf") pcap_leaf = iv; else if (k == "pcap_mid") pcap_mid = iv; else if (k == "pcap_tail") pcap_tail = iv;
       else if (k == "group_cap") group_cap = iv; else if (k == "group_blocks") group_blocks = iv; else if (k == "ustage") ustage = iv;
+      else if (k == "lds_budget") lds_budget = std::max(0, iv);
       else if (k == "order_bits_max") order_bits_max = iv; else if (k == "flow") flow = iv; else if (k == "front") front = iv; else if (k == "compact") compact = iv; else if (k == "dump") dump = iv != 0;
       else if (k == "order") order = (v == "mindeg" || v == "0") ? 0 : 1;
       else if (k == "order_mul") order_mul = atof(v.c_str()); else if (k == "order_add") order_add = iv;
@@ -290,6 +300,8 @@ struct CholHost {
   std::vector<uint32_t> fblob;
   std::vector<FrontGrp> fgrp, lfgrp;        // by piece id / in launch order (like lpiece)
   std::vector<int> plv_lds_ff;              // LDS doubles of the front factor kernel per launch
+  std::vector<int> flds;                    // ... and by piece id (FrontHost::lds); col_comp: the connected piece of every column (host tables: the
+  std::vector<int> col_comp;                //     LDS budget splits groups by them, the plan introspection shows them)
   int tail_lds_ff = 0;
   int64_t funz = 0;                         // doubles of update matrices in the front layout
   std::string error;
@@ -518,8 +530,9 @@ inline int cut_pieces(int n, const std::vector<int>& parent, const std::vector<i
 
 }  // namespace chol_detail
 
-// Symbolic factorisation + piece plan of a whole batch.  Returns 0, or -1 with out.error set.
-inline int chol_symbolic(const SymIn& in, CholOpts opt, CholHost& out) {
+// Symbolic factorisation + piece plan of a whole batch.  Returns 0, or -1 with out.error set.  split_before (by component id, may be null): the
+// components that must open a group of their own (chol_symbolic below: the groups the LDS budget splits after their tables are built).
+inline int chol_symbolic_pass(const SymIn& in, CholOpts opt, CholHost& out, const std::vector<char>* split_before) {
   using namespace chol_detail;
   SSLAM_PT_INIT
   const int nPr = in.nPr, nLr = in.nLr, nrow = nPr + nLr, B = in.B;
@@ -582,15 +595,17 @@ inline int chol_symbolic(const SymIn& in, CholOpts opt, CholHost& out) {
     }
     std::vector<int> pos(n);
     for (int s = 0; s < n; ++s) pos[S.order[s]] = s;
-    std::vector<int> parent(n, -1), colsz(n), colnb(n);
+    std::vector<int> parent(n, -1), colsz(n), colnb(n), colpad(n), colrows(n);
     for (int s = 0; s < n; ++s) {
       const int v = S.order[s];
       const int d = row_dim(loc2row(v));
-      int rows = 0, par = n;
-      for (int q = S.cs_start[v]; q < S.cs_start[v] + S.cs_len[v]; ++q) { const int w = S.cs_idx[q]; rows += row_dim(loc2row(w)); par = std::min(par, pos[w]); }
+      int rows = 0, par = n, pad = blk_doubles(d, d);
+      for (int q = S.cs_start[v]; q < S.cs_start[v] + S.cs_len[v]; ++q) { const int w = S.cs_idx[q], dw = row_dim(loc2row(w)); rows += dw; pad += blk_doubles(dw, d); par = std::min(par, pos[w]); }
       parent[s] = par == n ? -1 : par;
       colsz[s] = d * d + d * rows;
       colnb[s] = 1 + S.cs_len[v];
+      colpad[s] = pad;      // doubles of the column in L (blocks padded to even sizes), dimensions of its off-diagonal rows: the LDS budget below
+      colrows[s] = rows;
     }
     // pass 1: leaf-sized pieces everywhere; depth of every piece in the piece tree
     std::vector<int> pc, none(n, -1);
@@ -654,18 +669,70 @@ inline int chol_symbolic(const SymIn& in, CholOpts opt, CholHost& out) {
     std::stable_sort(gorder.begin(), gorder.end(), [&](int a, int b) { return cplev[a] < cplev[b]; });
     std::vector<int> grank(np2, -1);
     int ngroup = 0;
+    std::vector<int> crank(np2, -1);
+    for (size_t k = 0; k < ids.size(); ++k) crank[ids[k]] = (int)k;
+    // LDS budget: what a component adds to its group's need in the front kernel, term by term as front_build lays the blob out.  Everything
+    // but the target tiles is known here: the boundary of a connected piece is the structure of its root column, and a child's update matrix
+    // meets the blocks (a, b) of its boundary rows with column b inside the piece -- the boundary rows up to the piece's root.  The tiles are
+    // counted as if every block had sources (an upper estimate).
+    struct CompLds { int L = 0, y = 0, words = 0, tiles = 0, items = 0, dbytes = 0, nlv = 0; };
+    std::vector<CompLds> clds;
+    const bool budget = opt.lds_budget > 0 && opt.group_cap > 0 && opt.front > 0;   // (groups and front tables: the throughput regime, or options that force it)
+    if (budget) {
+      clds.assign(np2, CompLds());
+      std::vector<int> cnc(np2, 0);
+      for (int s = 0; s < n; ++s) {
+        CompLds& e = clds[pc2[s]];
+        const int d = row_dim(loc2row(S.order[s]));
+        cnc[pc2[s]]++;
+        e.L += colpad[s]; e.y += d;
+        e.tiles += (d == 6 ? 3 : 1) + (colrows[s] / 3) * (d / 3);
+        e.items += d / 3 + colrows[s] / 3;
+        e.words += kFrontCol + kFrontBlk * colnb[s];
+      }
+      auto boundary = [&](int c, int upto, int& nR, int& T, int& inside) {   // rows of c's boundary, their tile rows, those at or below column upto
+        const int v = S.order[proot[c]];
+        nR = S.cs_len[v]; T = 0; inside = 0;
+        for (int q = S.cs_start[v]; q < S.cs_start[v] + S.cs_len[v]; ++q) { T += row_dim(loc2row(S.cs_idx[q])) / 3; inside += pos[S.cs_idx[q]] <= upto; }
+      };
+      std::vector<int> nch(np2, 0);
+      for (int c : ids) {
+        int nR, T, k;
+        if (cpar[c] >= 0) {
+          boundary(c, proot[cpar[c]], nR, T, k);
+          nch[cpar[c]]++;
+          clds[cpar[c]].words += kFrontChild + 2 * nR + 2 * (k * nR - k * (k - 1) / 2);   // header, copy of the boundary table, child sources
+        }
+      }
+      for (int c : ids) {
+        int nR, T, k;
+        boundary(c, -1, nR, T, k);
+        clds[c].words += kFrontComp + 2 * nR;
+        clds[c].dbytes = front_derived_bytes(cnc[c], cnc[c] + nR, T, nch[c]);
+        clds[c].nlv = il[proot[c]] + 1;
+      }
+    }
     {
       int gsz = 0, gnb = 0, glev = -1;
+      CompLds gl;
+      auto lds_bytes = [&](const CompLds& a, const CompLds& b) {   // FrontHost::lds of a group of a and b, in bytes
+        const int words = kFrontHdr + a.words + b.words + kFrontLv * std::max(a.nlv, b.nlv) + (a.tiles + b.tiles + 1) / 2 + (a.items + b.items + 1) / 2 + 3;
+        return 8 * (((a.L + b.L + 1) & ~1) + ((a.y + b.y + 1) & ~1) + words / 2 + (a.dbytes + b.dbytes + 7) / 8 + 2);
+      };
       for (int c : gorder) {
-        const bool fits = opt.group_cap > 0 && glev == cplev[c] && pcls[c] == 0 && gsz + csize[c] <= opt.group_cap && gnb + cblk[c] <= opt.group_blocks;
-        if (!fits) { ++ngroup; gsz = 0; gnb = 0; glev = cplev[c]; }
+        bool fits = opt.group_cap > 0 && glev == cplev[c] && pcls[c] == 0 && gsz + csize[c] <= opt.group_cap && gnb + cblk[c] <= opt.group_blocks;
+        if (fits && budget && lds_bytes(gl, clds[c]) > opt.lds_budget) fits = false;
+        if (fits && split_before && (*split_before)[ncomp + crank[c]]) fits = false;
+        if (!fits) { ++ngroup; gsz = 0; gnb = 0; glev = cplev[c]; gl = CompLds(); }
         gsz += csize[c]; gnb += cblk[c];
+        if (budget) {
+          const CompLds& e = clds[c];
+          gl.L += e.L; gl.y += e.y; gl.words += e.words; gl.tiles += e.tiles; gl.items += e.items; gl.dbytes += e.dbytes; gl.nlv = std::max(gl.nlv, e.nlv);
+        }
         grank[c] = ngroup - 1;
       }
       for (int c : ids) if (is_tail[c]) grank[c] = ngroup++;
     }
-    std::vector<int> crank(np2, -1);
-    for (size_t k = 0; k < ids.size(); ++k) crank[ids[k]] = (int)k;
     // final order: groups; inside a group by (level inside the component, component, position): one contiguous column range per level
     std::vector<int> perm(n);
     for (int s = 0; s < n; ++s) perm[s] = s;
@@ -1244,6 +1311,7 @@ inline int chol_symbolic(const SymIn& in, CholOpts opt, CholHost& out) {
       for (int l = 0; l < nlaunch; ++l)
         for (int q = out.plv_ptr[l]; q < out.plv_ptr[l + 1]; ++q) out.plv_lds_ff[l] = std::max(out.plv_lds_ff[l], F.lds[out.plv_pieces[q]]);
       for (int p : out.tail_pieces) out.tail_lds_ff = std::max(out.tail_lds_ff, F.lds[p]);
+      out.flds.swap(F.lds);
     }
     SSLAM_PT("front tables")
   }
@@ -1258,6 +1326,53 @@ inline int chol_symbolic(const SymIn& in, CholOpts opt, CholHost& out) {
     for (int q = out.tail_ptr[0]; q < out.tail_ptr[std::min(1, B)]; ++q) tlv += out.piece[out.tail_pieces[q]].nilv;
     fprintf(stderr, "[chol-dump]   tail: <= %d pieces per graph (graph 0: %d internal levels), LDS factor %d B backward %d B\n", tmax, tlv,
             out.tail_lds_f * 8, out.tail_lds_b * 8);
+  }
+  out.col_comp = col_comp;
+  return 0;
+}
+
+// The plan of a batch.  With an LDS budget (CholOpts::lds_budget) the groups are packed by an upper estimate of their bytes; should the built
+// front tables still put a group of several components above the budget, it is split where its share of L reaches the budget's share and the
+// plan is built again (a few rounds at most: every round adds a split to every offender, the last one splits them into their components).
+inline int chol_symbolic(const SymIn& in, CholOpts opt, CholHost& out) {
+  int rc = chol_symbolic_pass(in, opt, out, nullptr);
+  if (rc || opt.lds_budget <= 0 || !out.front) return rc;
+  std::vector<char> split;
+  for (int round = 0; round < 4; ++round) {
+    std::vector<std::vector<int>> comps(out.npiece);   // the components of the groups above the budget, ascending: the order they were packed in
+    bool any = false;
+    for (int l = 0; l + 1 < (int)out.plv_ptr.size(); ++l)
+      for (int q = out.plv_ptr[l]; q < out.plv_ptr[l + 1]; ++q) {
+        const int p = out.plv_pieces[q];
+        if (8 * out.flds[p] <= opt.lds_budget) continue;
+        const PieceMeta& pm = out.piece[p];
+        std::vector<int>& cs = comps[p];
+        for (int j = pm.c0; j < pm.c0 + pm.nc; ++j) cs.push_back(out.col_comp[j]);
+        std::sort(cs.begin(), cs.end());
+        cs.erase(std::unique(cs.begin(), cs.end()), cs.end());
+        if (cs.size() < 2) { cs.clear(); continue; }   // a component above the budget on its own: a group of one, plv_lds_ff says what it takes
+        any = true;
+      }
+    if (!any) return 0;
+    if (split.empty()) split.assign((size_t)*std::max_element(out.col_comp.begin(), out.col_comp.end()) + 1, 0);
+    for (int p = 0; p < out.npiece; ++p) {
+      const std::vector<int>& cs = comps[p];
+      if (cs.empty()) continue;
+      const PieceMeta& pm = out.piece[p];
+      std::vector<int> cl(cs.size(), 0);   // doubles of L per component
+      for (int j = pm.c0; j < pm.c0 + pm.nc; ++j) {
+        const int e = (int)(std::lower_bound(cs.begin(), cs.end(), out.col_comp[j]) - cs.begin());
+        for (int t = out.col[j].b0; t < out.col[j].b0 + out.col[j].nb; ++t) cl[e] += blk_doubles(out.blk[t].info & 15, (out.blk[t].info >> 4) & 15);
+      }
+      const double share = round == 3 ? 0.0 : 0.9 * (double)pm.lsize * (double)opt.lds_budget / (8.0 * (double)out.flds[p]);
+      int acc = cl[0], nsplit = 0;
+      for (size_t e = 1; e < cs.size(); ++e) {
+        if (acc + cl[e] > share) { split[cs[e]] = 1; acc = 0; ++nsplit; }
+        acc += cl[e];
+      }
+      if (!nsplit) split[cs[cs.size() / 2]] = 1;
+    }
+    if ((rc = chol_symbolic_pass(in, opt, out, &split))) return rc;
   }
   return 0;
 }

@@ -180,7 +180,6 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
     }
   };
   const int n1 = sB[9] & 0xFFFF, n2 = sB[9] >> 16, nmore = h2 >> 20;   // child sources by rank: the first ones are also named in the block records
-  double m2[6], m2y = 0;
   {
     bool derived = false;
     if (wait_p) {
@@ -236,22 +235,7 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
             uyv[g2] = U[(on && dg) ? cc.ubase + cc.usize + 6 * qa + rw : 0];
           }
         }
-        if (t0 == tid) {
-          // second child sources of the piece's blocks (a few per group; one (block, row) per thread): their loads travel with the main ones
-          if (SRC && n2 > 0) {
-            const int t = min(tid, min(n2, NT / 6) * 6 - 1);
-            const uint2 me = sMulti[n1 + t / 6];
-            const uint4 bm = sBlk[me.x & 0xFFFF];
-            const int di = ((bm.w >> 16) & 1) ? 6 : 3, dj = ((bm.w >> 17) & 1) ? 6 : 3;
-            const int rw = min(t % 6, di - 1);
-            const FrontChild cc = front_child(sB, sChild, (int)(sB[kFrontHdr + kFrontComp * (bm.w & 255) + 4] & 0xFFFF) + (int)(me.x >> 16));
-            const double* pu = U + front_child_block(cc, me.y & 255, (me.y >> 8) & 255, di) + rw * dj;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) m2[c] = pu[min(c, dj - 1)];
-            m2y = U[cc.ubase + cc.usize + 6 * (int)(me.y & 255) + rw];
-          }
-          if (!derived) { derive(); derived = true; }
-        }
+        if (!derived) { derive(); derived = true; }
 #pragma unroll
         for (int g2 = 0; g2 < KG; ++g2) {
           const int t = t0 + g2 * NT;
@@ -274,14 +258,14 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
         }
       }
     };
-    if (nchild == 0) gather(std::integral_constant<int, 5>{}, std::false_type{});
-    else gather(std::integral_constant<int, 3>{}, std::true_type{});
+    if (nchild == 0) gather(std::integral_constant<int, 4>{}, std::false_type{});
+    else gather(std::integral_constant<int, 2>{}, std::true_type{});
   }
   __syncthreads();
   SSLAM_FSTAMP(1)
   if (n2 + nmore > 0) {
-    // further child sources, in list order: the second ones (loaded above) now that the first are in LDS, one (block, row) per thread; what does
-    // not fit a pass, and third and later sources (rare), one source after the other by the first lanes of the workgroup
+    // further child sources, in list order, now that the first are in LDS.  (Round 7: the second sources no longer travel with the gather -- their
+    // six doubles and rhs entry were live in every lane across the whole gather and its barrier; they take the chunked trips below like the rest.)
     auto apply = [&](const uint2 me, int row, const double (&u)[6], double uy) {
       const uint4 bm = sBlk[me.x & 0xFFFF];
       const int di = ((bm.w >> 16) & 1) ? 6 : 3, dj = ((bm.w >> 17) & 1) ? 6 : 3;
@@ -291,33 +275,28 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
       for (int c = 0; c < 6; ++c) if (c < dj) o[c] -= u[c];
       if (bm.y >> 31) smY[(sCol[(bm.y >> 22) & 255].x >> 16) + row] -= uy;
     };
-    const int npar = min(n2, NT / 6);
-    if (tid < npar * 6) apply(sMulti[n1 + tid / 6], tid % 6, m2, m2y);
-    __syncthreads();
-    if (n2 > npar || nmore > 0) {
-      // what is left, a chunk of NT / 6 sources at a time, one (source, row) per thread: the loads of a chunk travel together (ONE trip to HBM per
-      // chunk -- the lists of the upper leaf depths and of the mid pieces ran to dozens of dependent trips by six lanes); a block has at most one
-      // source of every rank and the list is sorted by rank, so the ranks of a chunk are applied one after the other: list order per block
-      constexpr int CH = NT / 6;
-      const int eend = n1 + n2 + nmore;
-      for (int e0 = n1 + npar; e0 < eend; e0 += CH) {
-        const int e = e0 + tid / 6, row = tid % 6;
-        const bool have = tid < CH * 6 && e < eend;
-        const uint2 me = sMulti[have ? e : e0];
-        const uint4 bm = sBlk[me.x & 0xFFFF];
-        const int di = ((bm.w >> 16) & 1) ? 6 : 3, dj = ((bm.w >> 17) & 1) ? 6 : 3;
-        const int rw = min(row, di - 1);
-        const FrontChild cc = front_child(sB, sChild, (int)(sB[kFrontHdr + kFrontComp * (bm.w & 255) + 4] & 0xFFFF) + (int)(me.x >> 16));
-        const double* pu = U + front_child_block(cc, me.y & 255, (me.y >> 8) & 255, di) + rw * dj;
-        double u[6];
+    // a chunk of NT / 6 sources at a time, one (source, row) per thread: the loads of a chunk travel together (ONE trip to HBM per
+    // chunk -- the lists of the upper leaf depths and of the mid pieces ran to dozens of dependent trips by six lanes); a block has at most one
+    // source of every rank and the list is sorted by rank, so the ranks of a chunk are applied one after the other: list order per block
+    constexpr int CH = NT / 6;
+    const int eend = n1 + n2 + nmore;
+    for (int e0 = n1; e0 < eend; e0 += CH) {
+      const int e = e0 + tid / 6, row = tid % 6;
+      const bool have = tid < CH * 6 && e < eend;
+      const uint2 me = sMulti[have ? e : e0];
+      const uint4 bm = sBlk[me.x & 0xFFFF];
+      const int di = ((bm.w >> 16) & 1) ? 6 : 3, dj = ((bm.w >> 17) & 1) ? 6 : 3;
+      const int rw = min(row, di - 1);
+      const FrontChild cc = front_child(sB, sChild, (int)(sB[kFrontHdr + kFrontComp * (bm.w & 255) + 4] & 0xFFFF) + (int)(me.x >> 16));
+      const double* pu = U + front_child_block(cc, me.y & 255, (me.y >> 8) & 255, di) + rw * dj;
+      double u[6];
 #pragma unroll
-        for (int c = 0; c < 6; ++c) u[c] = pu[min(c, dj - 1)];
-        const double uy = U[cc.ubase + cc.usize + 6 * (int)(me.y & 255) + rw];
-        const int r0 = (int)(sMulti[e0].y >> 16), r1 = (int)(sMulti[min(e0 + CH, eend) - 1].y >> 16), myr = (int)(me.y >> 16);
-        for (int r = r0; r <= r1; ++r) {
-          if (have && myr == r) apply(me, row, u, uy);
-          __syncthreads();
-        }
+      for (int c = 0; c < 6; ++c) u[c] = pu[min(c, dj - 1)];
+      const double uy = U[cc.ubase + cc.usize + 6 * (int)(me.y & 255) + rw];
+      const int r0 = (int)(sMulti[e0].y >> 16), r1 = (int)(sMulti[min(e0 + CH, eend) - 1].y >> 16), myr = (int)(me.y >> 16);
+      for (int r = r0; r <= r1; ++r) {
+        if (have && myr == r) apply(me, row, u, uy);
+        __syncthreads();
       }
     }
   }
@@ -366,10 +345,12 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
     while (W < NT && ncl * (2 * W) <= NT) W *= 2;   // (a lone column's team is the whole workgroup: its rows are solved in one round)
     const int teams = NT / W, team = tid / W, lt = tid % W;
     constexpr int kKeep = 2;   // (the plan refuses levels of more than kKeep * NT / 8 columns)
-    double keep[kKeep][6];
-#pragma unroll
-    for (int r2 = 0; r2 < kKeep; ++r2) {
+    // One round of columns at a time, each closed by its own barrier and the store of its rows of L_jj (round 7: both rounds' rows used to be
+    // held by every lane across ONE barrier, 24 registers next to the factor of the second round).  A second round runs only on levels of more
+    // columns than teams; its columns are other columns, so it neither reads nor writes what the first round's lanes store.
+    for (int r2 = 0; r2 < kKeep && (r2 == 0 || r2 * teams < ncl); ++r2) {
       const int cc = team + r2 * teams;
+      double keep[6];
       if (cc < ncl) {
         const uint4 col = sCol[c0 + cc];
         const int dj = ((col.y >> 16) & 1) ? 6 : 3;
@@ -388,7 +369,7 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
         for (int r = 0; r < 6; ++r)
           if (r == lt) {
 #pragma unroll
-            for (int c = 0; c < 6; ++c) keep[r2][c] = c <= r ? a[r * 6 + c] : 0.0;
+            for (int c = 0; c < 6; ++c) keep[c] = c <= r ? a[r * 6 + c] : 0.0;
             if (r < dj) py[r] = tv[r];
           }
         const int cb0 = col.w & 0x3FFF, nro = (int)(((col.w >> 14) & 255) - 1) * 6;
@@ -410,22 +391,18 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
           for (int c = 0; c < 6; ++c) if (c < dj) pv[c] = x[c];
         }
       }
-    }
-    __syncthreads();
-    SSLAM_FSTAMP(4)
-#pragma unroll
-    for (int r2 = 0; r2 < kKeep; ++r2) {
-      const int cc = team + r2 * teams;
+      __syncthreads();
       if (cc < ncl) {
         const uint4 col = sCol[c0 + cc];
         const int dj = ((col.y >> 16) & 1) ? 6 : 3;
         if (lt < dj) {
           double* pv = smL + (col.x & 0xFFFF) + lt * dj;
 #pragma unroll
-          for (int c = 0; c < 6; ++c) if (c < dj) pv[c] = keep[r2][c];
+          for (int c = 0; c < 6; ++c) if (c < dj) pv[c] = keep[c];
         }
       }
     }
+    SSLAM_FSTAMP(4)
     // 2c. right-looking (mid and tail pieces: chains of columns): a finished column updates every later block of its piece at once, all tile
     //     pairs in parallel, one tile update deep; one column per round (two columns of a level may meet in a target).  The pairs (p >= q) of the
     //     column's off-diagonal blocks with block q's row inside the piece are enumerated by arithmetic: 4 lanes per pair, one per 3 x 3 tile.
@@ -493,44 +470,18 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
       const int li = cp.nc + ia, lj = cp.nc + ib;
       const int di = ((cp.p6 >> li) & 1) ? 6 : 3, dj = ((cp.p6 >> lj) & 1) ? 6 : 3;
       const bool diag = ia == ib, wy = diag && trb == 0;
-      // the first child block of the tile travels while the own updates are computed
-      double c0v[9], c0y[3];
-      int f = -1;
-      {
-        int qa = 0, qb = 0;
-        // the children that hold both rows: the AND of two masks (a component with more than 64 children scans the rest)
-        unsigned long long cm = cp.cmask[li] & cp.cmask[lj];
-        if (cm) { f = __builtin_ctzll(cm); qa = cp.inv[f * cp.NR + li] - 1; qb = cp.inv[f * cp.NR + lj] - 1; }
-        else
-          for (int ch = 64; ch < cp.nch; ++ch) {
-            const int a = cp.inv[ch * cp.NR + li], c2 = cp.inv[ch * cp.NR + lj];
-            if (a && c2) { f = ch; qa = a - 1; qb = c2 - 1; break; }
-          }
-        const FrontChild cc = front_child(sB, sChild, min(cp.child0 + max(f, 0), max(nchild - 1, 0)));
-        const double* o = U + (f >= 0 ? front_child_block(cc, qa, qb, di) : 0);
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr)
-#pragma unroll
-          for (int c = 0; c < 3; ++c) c0v[rr * 3 + c] = o[f >= 0 ? (3 * tra + rr) * dj + 3 * trb + c : 0];
-        const double* oy = U + ((f >= 0 && wy) ? cc.ubase + cc.usize + 6 * qa + 3 * tra : 0);
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr) c0y[rr] = oy[(f >= 0 && wy) ? rr : 0];
-      }
       double acc[9], accy[3];
 #pragma unroll
       for (int k = 0; k < 9; ++k) acc[k] = 0;
 #pragma unroll
       for (int k = 0; k < 3; ++k) accy[k] = 0;
       front_tile_sources(cp, cp.rw[li] & cp.rw[lj], li, lj, tra, trb, smL, smY, acc, accy);
-      if (f >= 0) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) acc[k] += c0v[k];
-        if (wy) {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) accy[k] += c0y[k];
-        }
-        unsigned long long cm = f < 63 ? (cp.cmask[li] & cp.cmask[lj]) >> (f + 1) << (f + 1) : 0ull;   // the children after f that hold both rows
-        for (int ch = f + 1; ch < cp.nch; ++ch) {
+      // then the children that hold both rows, in list order: the AND of two masks names those among the first 64, a component with more
+      // children scans the rest.  (Round 7: the first child's block no longer travels while the own updates are computed -- its twelve doubles
+      // next to the operands of a tile update were what kept the kernel above 128 registers; a fourth wave per SIMD hides the trip instead.)
+      {
+        unsigned long long cm = cp.cmask[li] & cp.cmask[lj];
+        for (int ch = 0; ch < cp.nch; ++ch) {
           if (ch < 64) {
             if (!cm) { ch = 63; continue; }
             ch = __builtin_ctzll(cm);
@@ -584,7 +535,7 @@ __device__ __forceinline__ void front_piece(const BatchView& V, const CholView& 
 #undef SSLAM_FSTAMP
 
 template <int NT, bool RIGHT>
-__global__ __launch_bounds__(NT, NT <= 256 ? 3 : 1) void k_front_pieces(BatchView V, CholView C, int begin, const int* __restrict__ idx) {
+__global__ __launch_bounds__(NT, NT == 128 ? 4 : (NT <= 256 ? 3 : 1)) void k_front_pieces(BatchView V, CholView C, int begin, const int* __restrict__ idx) {
   extern __shared__ double sm[];
   const int q = idx ? idx[blockIdx.x] : begin + blockIdx.x;
   const PieceMeta pm = C.lpiece[q];

@@ -225,6 +225,7 @@ int chol_set_active(Batch& b, const std::vector<char>* active);   // LM endgame:
 int64_t chol_plan_lnz(const Batch& b);
 int chol_plan_levels(const Batch& b);
 bool chol_plan_front(const Batch& b);       // the factorisation runs the front kernels (front_kernels.hpp)
+int chol_plan_front_per_cu(const Batch& b, bool mid);   // front workgroups a CU holds: the minimum over the leaf / mid launches (0: none)
 bool chol_plan_flow(const Batch& b);        // the plan runs factor + both solves in one dependency-driven launch (small batches)
 int chol_solve_flow(Batch& b);              // (H + lambda I) dx = b for in_trial graphs -> V.x, one launch
 int chol_lm_step_flow(Batch& b, int max_iters);   // begin step + one-launch solve + update / chi2 / accept-reject / commit: 3 launches per damping trial

@@ -89,6 +89,7 @@ struct CholPlan {
   std::vector<int> plv_ptr, plv_lds_f, plv_lds_b, plv_nt, plv_cls;
   std::vector<int> plv_lds_ff;  // front kernels (front_kernels.hpp): LDS doubles per launch; front: the per-depth launches run them
   int tail_lds_ff = 0;
+  int front_per_cu[2] = {0, 0};  // front workgroups a CU holds, by the runtime's count: the minimum over the leaf / the mid launches (chol_plan_build)
   bool front = false;
   int tail_lds_f = 0, tail_lds_b = 0, tail_total = 0, nt_tail = 512, nt_ftail = 256, nt_bleaf = 0, nt_bmid = 0, nt_btail = 0, ustage = 0;
   std::vector<void*> allocs;
@@ -1684,6 +1685,26 @@ int chol_plan_build(Batch& b) {
       done.push_back(b.device);
     }
   }
+  if (P->front) {
+    // What the runtime says a CU holds of every per-depth front launch at its LDS size (info keys front_groups_per_cu_leaf / _mid): the
+    // LDS budget of the plan counts bytes, the allocation granularity of the device is the runtime's to know.
+    // A class without launches reports what its kernel's registers allow.
+    auto held = [&](bool mid, int width, size_t lds) {
+      int per = 0;
+      with_width(LeafWidths{}, width, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        const void* fn = mid ? (const void*)k_front_pieces<NT, true> : (const void*)k_front_pieces<NT, false>;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, NT, lds) != hipSuccess) per = 0;
+      });
+      return per;
+    };
+    P->front_per_cu[0] = held(false, H.nt_leaf, 0);
+    P->front_per_cu[1] = held(true, H.nt_mid, 0);
+    for (size_t l = 0; l < P->plv_lds_ff.size(); ++l) {
+      const bool mid = P->plv_cls[l] == 1;
+      P->front_per_cu[mid] = std::min(P->front_per_cu[mid], held(mid, P->plv_nt[l], (size_t)P->plv_lds_ff[l] * sizeof(double)));
+    }
+  }
   if (P->flow) {
     // persistent grid: at most half of what the device holds at once of these workgroups (two such launches may run side by side),
     // never more workgroups than pieces
@@ -1917,6 +1938,7 @@ int chol_flow_check(Batch& b) {
 int64_t chol_plan_lnz(const Batch& b) { return b.chol ? b.chol->lnz : 0; }
 int chol_plan_levels(const Batch& b) { return b.chol ? b.chol->C.nlevels : 0; }
 bool chol_plan_front(const Batch& b) { return b.chol && b.chol->front; }
+int chol_plan_front_per_cu(const Batch& b, bool mid) { return b.chol ? b.chol->front_per_cu[mid ? 1 : 0] : 0; }
 int chol_plan_launches(const Batch& b) { return b.chol ? (int)b.chol->plv_lds_f.size() + (b.chol->tail_total > 0 ? 1 : 0) : 0; }
 
 // LM endgame: from now on only the graphs flagged in `active` can be in a trial (a terminated graph never comes back within an

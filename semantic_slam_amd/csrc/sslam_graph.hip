@@ -2661,12 +2661,13 @@ int sslam_batch_info(sslam_batch* h, const char* key, double* value) {
   if (!h->parts.empty()) {   // sums over the parts; the depth of the plans is their maximum
     const std::string kk(key);
     if (kk == "streams") { *value = (double)h->parts.size(); return 0; }
+    const bool least = kk == "front_groups_per_cu_leaf" || kk == "front_groups_per_cu_mid";   // (residency of the front launches: the parts' minimum)
     double acc = 0;
     for (sslam_batch* p : h->parts) {
       double v = 0;
       const int rc = sslam_batch_info(p, key, &v);
       if (rc) return rc;
-      acc = kk == "factor_levels" ? std::max(acc, v) : acc + v;
+      acc = kk == "factor_levels" ? std::max(acc, v) : (least ? (p == h->parts.front() ? v : std::min(acc, v)) : acc + v);
     }
     *value = acc;
     return 0;
@@ -2675,12 +2676,14 @@ int sslam_batch_info(sslam_batch* h, const char* key, double* value) {
   Batch& b = h->b;
   const std::string k(key);
   int rc;
-  if ((k == "factor_lnz" || k == "factor_levels" || k == "factor_launches" || k == "factor_front" || k == "factor_bytes") && !b.chol && (rc = chol_plan_build(b))) return rc;
+  const bool per_cu = k == "front_groups_per_cu_leaf" || k == "front_groups_per_cu_mid";
+  if ((k == "factor_lnz" || k == "factor_levels" || k == "factor_launches" || k == "factor_front" || k == "factor_bytes" || per_cu) && !b.chol && (rc = chol_plan_build(b))) return rc;
   const double dim = 6.0 * b.V.nPr + 3.0 * b.V.nLr;
   if (k == "factor_lnz") *value = (double)chol_plan_lnz(b);
   else if (k == "factor_levels") *value = (double)chol_plan_levels(b);
   else if (k == "factor_launches") *value = (double)chol_plan_launches(b);
   else if (k == "factor_front") *value = chol_plan_front(b) ? 1.0 : 0.0;
+  else if (per_cu) *value = (double)chol_plan_front_per_cu(b, k == "front_groups_per_cu_mid");   // front workgroups a CU holds (0: no front tables)
   else if (k == "h_doubles") *value = (double)b.V.h_total;
   else if (k == "dim") *value = dim;
   else if (k == "allreduce_calls") *value = (double)b.allreduce_calls;
@@ -2751,7 +2754,7 @@ int64_t sslam_debug_plan_array(void* p, const char* name, void* out, int64_t cap
   ARR("ppoff", T.ppoff) ARR("plblk", T.plblk) ARR("tail_ptr", H.tail_ptr)
   ARR("asrc", H.asrc) ARR("usrc", H.usrc) ARR("fwd", H.fwd) ARR("uitem", H.uitem) ARR("umb", H.umb) ARR("tail_pieces", H.tail_pieces) ARR("plv_lds_f", H.plv_lds_f) ARR("plv_lds_b", H.plv_lds_b)
   ARR("rcol", H.rcol) ARR("rupd", H.rupd) ARR("plv_nt", H.plv_nt) ARR("plv_cls", H.plv_cls)
-  ARR("fblob", H.fblob) ARR("fgrp", H.fgrp) ARR("plv_lds_ff", H.plv_lds_ff)
+  ARR("fblob", H.fblob) ARR("fgrp", H.fgrp) ARR("plv_lds_ff", H.plv_lds_ff) ARR("flds", H.flds) ARR("col_comp", H.col_comp)
   // the batch tables, under the names of BatchTables; a storage class's arrays are <class>_{a, b, blk, id, z, w} with class eo, el, ell, ep
   ARR("seg", T.seg) ARR("pose_row", T.pose_row) ARR("lm_row", T.lm_row) ARR("prow_pose", T.prow_pose) ARR("lrow_lm", T.lrow_lm)
   ARR("prow_graph", T.prow_graph) ARR("lrow_graph", T.lrow_graph) ARR("pose_vertex", T.pose_vertex) ARR("lm_vertex", T.lm_vertex)
@@ -2771,7 +2774,7 @@ int64_t sslam_debug_plan_array(void* p, const char* name, void* out, int64_t cap
   if (k == "scalars") { src = scal; bytes = sizeof scal; }
   static const char* known[] = {"col", "blk", "upd", "item", "mb", "ilv", "piece", "lvl_ptr", "lvl_cols", "plv_ptr", "plv_pieces", "ppoff", "plblk",
                                 "tail_ptr", "tail_pieces", "plv_lds_f", "plv_lds_b", "scalars", "asrc", "usrc", "fwd", "uitem", "umb", "rcol", "rupd", "plv_nt", "plv_cls",
-                                "fblob", "fgrp", "plv_lds_ff", "fscalars",
+                                "fblob", "fgrp", "plv_lds_ff", "fscalars", "flds", "col_comp",
                                 "seg", "pose_row", "lm_row", "prow_pose", "lrow_lm", "prow_graph", "lrow_graph", "pose_vertex", "lm_vertex", "lm_kind", "prow_perm", "llblk",
                                 "eo_a", "eo_b", "eo_blk", "eo_id", "eo_z", "eo_w", "el_a", "el_b", "el_blk", "el_id", "el_z", "el_w",
                                 "ell_a", "ell_b", "ell_blk", "ell_id", "ell_z", "ell_w", "ep_a", "ep_id", "ep_z", "ep_w", "ep_dim",
