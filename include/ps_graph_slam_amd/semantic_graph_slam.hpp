@@ -65,6 +65,27 @@ class semantic_graph_slam {
     check(sslam_slam_set_segmented_objects(h_, objects.data(), (int)objects.size()), "sslam_slam_set_segmented_objects");
   }
 
+  // loop closing inside the tick (hdl_graph_slam's LoopDetector::detect; sslam_slam_set_loop_closure): nullptr turns it off.  After
+  // init(), which needs the frontend handle for it.
+  void set_loop_closure(const sslam_loop_params* params) { check(sslam_slam_set_loop_closure(h_, params), "sslam_slam_set_loop_closure"); }
+  // the records of the last run(): one per new keyframe that reached the selection with at least one candidate
+  std::vector<sslam_loop> last_loops() const {
+    const int n = check(sslam_slam_last_loops(h_, nullptr, 0), "sslam_slam_last_loops");
+    std::vector<sslam_loop> out(n);
+    if (n) check(sslam_slam_last_loops(h_, out.data(), n), "sslam_slam_last_loops");
+    return out;
+  }
+  // LoopDetector::find_candidates on its own: keys / news hold x, y, accum_distance per old / new keyframe; returns the counts, cand gets
+  // news.size() / 3 rows of `cap` indices (-1 where not filled)
+  std::vector<int32_t> loop_candidates(const std::vector<double>& keys, const std::vector<double>& news, const sslam_loop_params& params, int cap,
+                                       std::vector<int32_t>& cand) {
+    const int n_keys = (int)(keys.size() / 3), n_new = (int)(news.size() / 3);
+    cand.assign((size_t)n_new * cap, -1);
+    std::vector<int32_t> count(n_new);
+    check(sslam_slam_loop_candidates(h_, keys.data(), n_keys, news.data(), n_new, &params, cand.data(), count.data(), cap), "sslam_slam_loop_candidates");
+    return count;
+  }
+
   // getRobotPose / getMap2OdomTrans (semantic_graph_slam.cpp:375-381)
   void getRobotPose(sslam::Isometry& robot_pose) const {
     double tq[7];

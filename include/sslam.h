@@ -726,6 +726,94 @@ int sslam_slam_set_fitness_information(sslam_slam* s, const sslam_inf_params* p,
  * for an edge that took the constant matrix.  Returns the number of edges (copies min(n, max); either output may be NULL); 0 when
  * the model was not set during that run. */
 int sslam_slam_last_fitness(const sslam_slam* s, double* score, int32_t* used, int max);
+
+/* ---- loop closing inside the tick (hdl_graph_slam's LoopDetector::detect [UPSTREAM]: find_candidates, matching, an EdgeSE3 with a robust
+ * kernel; the reference has no loop detector).  Off until sslam_slam_set_loop_closure is called with parameters; a handle on which it
+ * never was, or was last called with NULL, runs its ticks bit for bit as before this call existed and keeps no cloud for it. ---------------
+ * sslam_loop_default_params: 5.0, 8.0, 5.0, DBL_MAX, 0.5, 64, 0.01, 0, 0.1, 0, Huber 1.0, sslam_inf_default_params -- hdl_graph_slam's defaults
+ * [UPSTREAM, unverified here]: quoted from memory, hdl_graph_slam is not part of the reference tree. */
+typedef struct sslam_loop_params {
+  double  distance_thresh;                 /* 5.0   candidate: xy distance of the two estimates */
+  double  accum_distance_thresh;           /* 8.0   candidate: travelled distance between the two keyframes */
+  double  distance_from_last_edge_thresh;  /* 5.0   travelled distance since the keyframe of the last accepted loop */
+  double  fitness_score_max_range;         /* DBL_MAX   bound on the SQUARED correspondence distance (max_corr2 of the scan matcher) */
+  double  fitness_score_thresh;            /* 0.5   a best score above it: no loop */
+  int32_t max_iterations;                  /* 64    of sslam_seg_register_pairs */
+  double  epsilon;                         /* 0.01  of sslam_seg_register_pairs */
+  int32_t max_candidates;                  /* 0 = all that pass; M in 1 .. 64 = the M nearest */
+  float   voxel_leaf;                      /* 0.1   downsampling of a keyframe's cloud (0 -> 0.1) */
+  double  gate_chi2;                       /* 0 = no gate; else a loop is accepted only with d2 < gate_chi2 (12.59: 6 degrees of freedom, 95 %) */
+  int32_t robust_kernel;                   /* SSLAM_ROBUST_* of the loop edge: SSLAM_ROBUST_HUBER; SSLAM_ROBUST_NONE = none */
+  double  robust_delta;                    /* 1.0 */
+  sslam_inf_params inf;                    /* information of the loop edge from its score */
+} sslam_loop_params;
+void sslam_loop_default_params(sslam_loop_params* p);
+#define SSLAM_LOOP_ADDED 0      /* the loop edge was added */
+#define SSLAM_LOOP_SCORE 1      /* the best score is above fitness_score_thresh */
+#define SSLAM_LOOP_GATE 2       /* d2 >= gate_chi2, or d2 is NaN */
+#define SSLAM_LOOP_NO_MATCH 3   /* no pair ended with status 0 and used > 0 */
+/* one record per new keyframe that reached the selection (step 5 below) with at least one candidate */
+typedef struct sslam_loop {
+  int32_t new_vertex, cand_vertex;         /* graph vertex ids of the target (the new keyframe) and the source (the best candidate; -1: NO_MATCH) */
+  int32_t n_candidates;
+  int32_t outcome;                         /* SSLAM_LOOP_* */
+  int32_t edge_id;                         /* -1 unless ADDED */
+  int32_t used, iterations, converged;     /* of the best pair, as sslam_reg_result has them; 0 with NO_MATCH */
+  double  T[12];                           /* of the best pair: R row-major, then t, candidate -> new keyframe (zero with NO_MATCH) */
+  double  score;                           /* of the best pair (DBL_MAX with NO_MATCH) */
+  double  d2;                              /* of the gate; NaN when the gate is off or was not reached */
+} sslam_loop;
+/* p = NULL: off, and the downsampled clouds kept so far are dropped.  Otherwise the following ticks do, after the association loop and
+ * before the optimisation (where hdl calls detect):
+ *   0. sslam_slam_vio keeps the latest cloud on every keyframe that has a fresh one (as under sslam_slam_set_fitness_information).  The
+ *      finite points of each new keyframe's cloud are voxel-grid downsampled once (sslam_seg_voxel_grid, voxel_leaf); the result stays on
+ *      the keyframe for the rest of the run, the raw cloud is dropped as before.  A keyframe without a cloud (or without a finite point)
+ *      is neither a candidate nor matched.  Clouds are taken to be in the frame of the keyframe's pose, as the fitness model does.
+ *   1. the estimates of all keyframes are read from the graph; new ones sit at the estimate their vertex was added with.
+ *   2. new keyframes with accum_distance - last_edge_accum < distance_from_last_edge_thresh are dropped, at the value last_edge_accum
+ *      has when the tick starts (0 before the first loop; it only grows, so these would be skipped in any order).
+ *   3. candidates: ONE k_loop_candidates launch (sslam_slam_loop_candidates below) over the processed keyframes, never over the same
+ *      tick's new ones.
+ *   4. ONE sslam_seg_register_pairs call for every (new, candidate) pair of the tick: target = the new keyframe's cloud, source = the
+ *      candidate's, max_corr2 = fitness_score_max_range, T0 = estimate_new^-1 * estimate_cand -- both estimates with their quaternion
+ *      normalised, q = conj(q_new) q_cand normalised again, R0 = the matrix of q, t0 = -(Rn t_new) + Rn t_cand with Rn the matrix of
+ *      conj(q_new).  hdl zeroes the z of its guess for ground vehicles; this does not (DEVIATION: the reference flies).
+ *   5. the new keyframes in order, the rule of step 2 applied again with the running last_edge_accum, which makes the result that of
+ *      hdl's sequential loop.  The best pair of a keyframe is the one of lowest score among those with status == 0 and used > 0, equal
+ *      scores going to the lowest keyframe index.  `converged` is reported, not demanded: PCL counts a loop that ran out of iterations
+ *      as converged [UPSTREAM, unverified].  A best score above fitness_score_thresh: SCORE.
+ *   6. info = sslam_information_from_fitness(&inf, score); z = (t, quaternion of R by the branch with the largest pivot, as INTEGRATION.md
+ *      section 2 spells out).  With gate_chi2 > 0, ONE sslam_graph_gate call for the best pairs of the tick that passed the score test,
+ *      before any loop edge is added; d2 >= gate_chi2 or NaN: GATE.
+ *   7. sslam_graph_add_edge_se3(new vertex, candidate vertex, z, info), the robust kernel unless it is SSLAM_ROBUST_NONE,
+ *      last_edge_accum = the new keyframe's accum_distance: ADDED.
+ * An error of any step ends sslam_slam_run the way its other errors do (the keyframes stay in the graph, nothing is optimised).
+ * Returns 0.  SSLAM_ERR_INVALID: a NULL handle; with p: a threshold (the three distances, both fitness values, gate_chi2, voxel_leaf) that
+ * is negative or not finite, max_candidates outside 0 .. 64, a negative max_iterations, a negative or NaN epsilon, a robust_kernel that is
+ * not a SSLAM_ROBUST_* kind or a robust_delta that sslam_graph_set_edge_robust_kernel would refuse for it, no frontend handle given to
+ * sslam_slam_create.  Host only: needs no device. */
+int sslam_slam_set_loop_closure(sslam_slam* s, const sslam_loop_params* p);
+/* the records of the last sslam_slam_run, in the order of the new keyframes; returns their number (copies min(n, max); out may be NULL) */
+int sslam_slam_last_loops(const sslam_slam* s, sslam_loop* out, int max);
+/* wall seconds inside the last sslam_slam_run: [0] the candidate launch with its copies, [1] sslam_seg_register_pairs, [2] sslam_graph_gate,
+ * [3] the whole loop stage, the downsampling of the new clouds included.  All zero with loop closure off. */
+int sslam_slam_last_loop_timing(const sslam_slam* s, double seconds[4]);
+/* LoopDetector::find_candidates for all new keyframes of a tick in one launch (k_loop_candidates), on its own.  keys: x, y, accum_distance
+ * per old keyframe; news: the same per new keyframe.  Old keyframe k passes for new keyframe n when
+ *   accum_n - accum_k >= accum_distance_thresh,   d2 <= distance_thresh * distance_thresh with d2 = dx dx + dy dy,
+ * and all six values, the difference and d2 are finite.  d2 is formed in double without fused multiply-add (a NumPy float64 restatement
+ * matches bit for bit), the squared threshold once on the host.  DEVIATION in form: hdl compares the norm with the threshold; comparing
+ * the squares is the same test except in the last bit at the boundary.
+ * max_candidates == 0: count_out[n] = the number that pass, row n of cand_out = the first `cap` of them in ascending index.
+ * max_candidates == M: row n = the M smallest under the order (d2, index) -- equal d2 goes to the lowest index -- written in that order,
+ * the first `cap` of them; count_out[n] = min(M, the number that pass).  Entries of cand_out that are not filled hold -1.
+ * One wave per new keyframe, its lanes striding over the old ones; ballot-and-prefix compaction, or M rounds of a per-lane scan for the
+ * smallest key above the last one chosen and a wave reduction: no atomics, no dependence on the launch geometry.  The tables travel
+ * through the handle's pinned scratch on the handle's stream.  Only the two distance thresholds and max_candidates of p are read.
+ * Returns n_new.  SSLAM_ERR_INVALID: a NULL handle or p, negative n_keys, n_new or cap, a NULL keys / news / count_out with entries, a NULL
+ * cand_out with n_new * cap > 0, a threshold that is negative or not finite, max_candidates outside 0 .. 64.  SSLAM_ERR_NO_DEVICE without a GPU. */
+int sslam_slam_loop_candidates(sslam_slam* s, const double* keys, int n_keys, const double* news, int n_new, const sslam_loop_params* p,
+                               int32_t* cand_out, int32_t* count_out, int cap);
 /* setPointCloudData (semantic_graph_slam.cpp:341-345): the cloud is copied */
 int sslam_slam_set_point_cloud(sslam_slam* s, const uint8_t* cloud, int width, int height, int point_step, int row_step,
                                int off_x, int off_y, int off_z);

@@ -263,6 +263,74 @@ __global__ __launch_bounds__(kAssocThreads) void k_associate(AssocArgs A, const 
   if (tid == 0) *L.count = s_n;
 }
 
+// ---- loop candidates on the device (hdl_graph_slam's LoopDetector::find_candidates [UPSTREAM]) ----------------------------------------
+struct LoopCandArgs {
+  const double* keys;    // x, y, accum_distance per old keyframe
+  const double* news;    // the same per new keyframe
+  int n_keys, n_new;
+  double accum_thresh;   // accum_distance_thresh
+  double d2_thresh;      // distance_thresh * distance_thresh, formed once on the host
+  int m;                 // max_candidates: 0 = all that pass, else the m nearest
+  int cap;               // row length of cand
+  int32_t* cand;         // n_new x cap, filled with -1 by the host
+  int32_t* count;        // n_new
+};
+
+// whether old keyframe (kx, ky, ka) is a candidate of the new keyframe (qx, qy, qa), and its squared xy distance.  No fused multiply-add.
+__device__ __forceinline__ bool loop_pass(double qx, double qy, double qa, double kx, double ky, double ka, double accum_thresh, double d2_thresh, double& d2) {
+  const double dx = qx - kx, dy = qy - ky, da = qa - ka;
+  d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+  const bool fin = isfinite(qx) && isfinite(qy) && isfinite(qa) && isfinite(kx) && isfinite(ky) && isfinite(ka) && isfinite(da) && isfinite(d2);
+  return fin && da >= accum_thresh && d2 <= d2_thresh;
+}
+
+constexpr int kLoopWave = 64;
+
+// One wave per new keyframe, its lanes striding over the old keyframes.  m == 0: the passing indices in ascending order by ballot and
+// prefix count.  m > 0: m rounds; in each, every lane finds the smallest key (d2, index) of its stride above the key chosen last, and a
+// wave reduction picks the smallest of the lanes.  No atomics: the result does not depend on the launch geometry.
+__global__ __launch_bounds__(kLoopWave) void k_loop_candidates(LoopCandArgs A) {
+  const int n = blockIdx.x, lane = threadIdx.x;
+  if (n >= A.n_new) return;
+  const double qx = A.news[3 * (size_t)n], qy = A.news[3 * (size_t)n + 1], qa = A.news[3 * (size_t)n + 2];
+  int32_t* row = A.cand + (size_t)n * A.cap;
+  int total = 0;
+  if (A.m == 0) {
+    for (int base = 0; base < A.n_keys; base += kLoopWave) {
+      const int k = base + lane;
+      double d2;
+      const bool p = k < A.n_keys && loop_pass(qx, qy, qa, A.keys[3 * (size_t)k], A.keys[3 * (size_t)k + 1], A.keys[3 * (size_t)k + 2], A.accum_thresh, A.d2_thresh, d2);
+      const unsigned long long b = __ballot(p);
+      const int pos = total + __popcll(b & ((1ull << lane) - 1ull));
+      if (p && pos < A.cap) row[pos] = k;
+      total += __popcll(b);
+    }
+  } else {
+    double last_d = -1.0;   // d2 >= 0: below every key
+    int last_k = -1;
+    for (int r = 0; r < A.m; ++r) {
+      double best_d = 0.0;
+      int best_k = -1;
+      for (int k = lane; k < A.n_keys; k += kLoopWave) {
+        double d2;
+        if (!loop_pass(qx, qy, qa, A.keys[3 * (size_t)k], A.keys[3 * (size_t)k + 1], A.keys[3 * (size_t)k + 2], A.accum_thresh, A.d2_thresh, d2)) continue;
+        if (!(d2 > last_d || (d2 == last_d && k > last_k))) continue;             // chosen in an earlier round
+        if (best_k < 0 || d2 < best_d) { best_d = d2; best_k = k; }               // ascending k: equal d2 keeps the lowest index
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        const double od = __shfl_xor(best_d, off);
+        const int ok = __shfl_xor(best_k, off);
+        if (ok >= 0 && (best_k < 0 || od < best_d || (od == best_d && ok < best_k))) { best_d = od; best_k = ok; }
+      }
+      if (best_k < 0) break;                                                      // uniform: every lane holds the wave's result
+      if (lane == 0 && r < A.cap) row[r] = best_k;
+      last_d = best_d; last_k = best_k;
+      ++total;
+    }
+  }
+  if (lane == 0) A.count[n] = total;
+}
+
 // ---- host state ---------------------------------------------------------------------------------------------------------------
 struct KeyFrame {
   int32_t sec = 0, nsec = 0;
@@ -274,6 +342,8 @@ struct KeyFrame {
   std::vector<sslam_box> boxes;           // obj_info
   std::vector<sslam_plane> objects;       // pre-segmented (extension)
   bool presegmented = false;
+  std::vector<float> ds;                  // loop closure: the downsampled cloud (xyz), kept for the rest of the run
+  bool has_ds = false;
 };
 
 template <class T>
@@ -336,6 +406,14 @@ struct sslam_slam {
   std::vector<float> fit_prev;
   std::vector<double> fit_score;          // odometry edges of the last run(), in order; -1 / -1: constant matrix
   std::vector<int32_t> fit_used;
+  // sslam_slam_set_loop_closure: candidate search, scan match, gate and loop edge inside the tick
+  bool loop_on = false;
+  sslam_loop_params loop_P{};
+  double last_edge_accum = 0;             // accum_distance of the keyframe that got the last loop edge (hdl's last_edge_accum_distance)
+  std::vector<sslam_loop> loops;          // records of the last run()
+  double loop_seconds[4] = {0, 0, 0, 0};  // candidates, registration, gate, the whole stage (downsampling included) of the last run()
+  DevBuf<double> d_ltab;                  // [keys 3 n_keys | news 3 n_new]
+  DevBuf<int32_t> d_lout;                 // [cand n_new x cap | count n_new]
   ~sslam_slam() {
     if (graph) sslam_graph_destroy(graph);
     if (stream) { (void)hipSetDevice(P.device); (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
@@ -461,7 +539,7 @@ void odometry_information(const sslam_slam* s, double info[36]) {
 }
 
 // the finite points of a keyframe's cloud, voxel-grid downsampled on the device -> out (xyz)
-int downsampled_cloud(sslam_slam* s, const KeyFrame& kf, std::vector<float>& out) {
+int downsampled_cloud(sslam_slam* s, const KeyFrame& kf, float leaf, std::vector<float>& out) {
   std::vector<float> pts;
   pts.reserve((size_t)kf.width * kf.height * 3);
   for (int r = 0; r < kf.height; ++r)
@@ -474,7 +552,7 @@ int downsampled_cloud(sslam_slam* s, const KeyFrame& kf, std::vector<float>& out
   const int n = (int)(pts.size() / 3);
   out.assign(pts.size(), 0.0f);
   if (n == 0) return 0;
-  const int m = sslam_seg_voxel_grid(s->seg, pts.data(), n, s->fit_leaf, out.data(), nullptr, n);
+  const int m = sslam_seg_voxel_grid(s->seg, pts.data(), n, leaf, out.data(), nullptr, n);
   if (m < 0) return m;
   out.resize((size_t)m * 3);
   return 0;
@@ -502,7 +580,7 @@ int fitness_of_tick(sslam_slam* s, int n, std::vector<double>& score, std::vecto
     if (cloud_of[i + 1] >= 0) return 0;
     std::vector<float> ds;
     if (i < 0) ds = s->fit_prev;
-    else { const int rc = downsampled_cloud(s, *s->keyframe_queue[i], ds); if (rc < 0) return rc; }
+    else { const int rc = downsampled_cloud(s, *s->keyframe_queue[i], s->fit_leaf, ds); if (rc < 0) return rc; }
     cloud_of[i + 1] = (int)start.size() - 1;
     xyz.insert(xyz.end(), ds.begin(), ds.end());
     start.push_back((int32_t)(xyz.size() / 3));
@@ -685,6 +763,215 @@ int segment_new_keyframes(sslam_slam* s) {
   return 0;
 }
 
+// ---- loop closing (hdl_graph_slam's LoopDetector::detect [UPSTREAM]) -------------------------------------------------------------------
+int check_loop_params(const sslam_loop_params* p, bool tick) {
+  auto bad = [](double v) { return !std::isfinite(v) || v < 0; };
+  if (bad(p->distance_thresh) || bad(p->accum_distance_thresh)) return set_error(SSLAM_ERR_INVALID, "loop closure: a distance threshold is negative or not finite");
+  if (p->max_candidates < 0 || p->max_candidates > 64) return set_error(SSLAM_ERR_INVALID, "loop closure: max_candidates %d outside 0 .. 64", p->max_candidates);
+  if (!tick) return 0;
+  if (bad(p->distance_from_last_edge_thresh) || bad(p->fitness_score_max_range) || bad(p->fitness_score_thresh) || bad(p->gate_chi2) || bad(p->voxel_leaf))
+    return set_error(SSLAM_ERR_INVALID, "loop closure: a threshold is negative or not finite");
+  if (p->max_iterations < 0) return set_error(SSLAM_ERR_INVALID, "loop closure: negative max_iterations");
+  if (!(p->epsilon >= 0)) return set_error(SSLAM_ERR_INVALID, "loop closure: epsilon is negative or NaN");
+  if (p->robust_kernel < SSLAM_ROBUST_NONE || p->robust_kernel > SSLAM_ROBUST_DCS)
+    return set_error(SSLAM_ERR_INVALID, "loop closure: robust kernel kind %d: 0 .. 7 (SSLAM_ROBUST_*)", p->robust_kernel);
+  if (p->robust_kernel != SSLAM_ROBUST_NONE && !(std::isfinite(p->robust_delta) && p->robust_delta > 0))
+    return set_error(SSLAM_ERR_INVALID, "loop closure: robust kernel width must be finite and > 0");
+  return 0;
+}
+
+// k_loop_candidates over host tables: both go up, the rows and counts come down, through the pinned scratch on the handle's stream
+int loop_candidates(sslam_slam* s, const double* keys, int n_keys, const double* news, int n_new, const sslam_loop_params& P,
+                    int32_t* cand_out, int32_t* count_out, int cap) {
+  if (n_new == 0) return 0;
+  int rc = ensure_stream(s);
+  if (rc) return rc;
+  SSLAM_HIP_TRY(hipSetDevice(s->P.device));
+  const size_t n_tab = 3 * ((size_t)n_keys + n_new), n_cand = (size_t)n_new * cap, n_out = n_cand + n_new;
+  if ((rc = s->d_ltab.reserve(n_tab, s->stream, 0))) return rc;
+  if ((rc = s->d_lout.reserve(n_out, s->stream, 0))) return rc;
+  const size_t tab_bytes = n_tab * sizeof(double), out_bytes = n_out * sizeof(int32_t);
+  std::vector<char> fallback;
+  char* stage = s->pin.get(tab_bytes + out_bytes);
+  if (!stage) { fallback.resize(tab_bytes + out_bytes); stage = fallback.data(); }
+  double* tab = reinterpret_cast<double*>(stage);
+  if (n_keys) std::memcpy(tab, keys, 3 * (size_t)n_keys * sizeof(double));
+  std::memcpy(tab + 3 * (size_t)n_keys, news, 3 * (size_t)n_new * sizeof(double));
+  LoopCandArgs A;
+  A.keys = s->d_ltab.p; A.news = s->d_ltab.p + 3 * (size_t)n_keys;
+  A.n_keys = n_keys; A.n_new = n_new;
+  A.accum_thresh = P.accum_distance_thresh;
+  A.d2_thresh = P.distance_thresh * P.distance_thresh;
+  A.m = P.max_candidates; A.cap = cap;
+  A.cand = s->d_lout.p; A.count = s->d_lout.p + n_cand;
+  SSLAM_HIP_TRY(hipMemcpyAsync(s->d_ltab.p, tab, tab_bytes, hipMemcpyHostToDevice, s->stream));
+  if (n_cand) SSLAM_HIP_TRY(hipMemsetAsync(s->d_lout.p, 0xff, n_cand * sizeof(int32_t), s->stream));   // -1: not filled
+  hipLaunchKernelGGL(k_loop_candidates, dim3(n_new), dim3(kLoopWave), 0, s->stream, A);
+  SSLAM_HIP_TRY(hipGetLastError());
+  SSLAM_HIP_TRY(hipMemcpyAsync(stage + tab_bytes, s->d_lout.p, out_bytes, hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if (n_cand) std::memcpy(cand_out, stage + tab_bytes, n_cand * sizeof(int32_t));
+  std::memcpy(count_out, stage + tab_bytes + n_cand * sizeof(int32_t), (size_t)n_new * sizeof(int32_t));
+  return 0;
+}
+
+// T (R row-major, then t) -> the edge's measurement (t, q xyzw): the quaternion of a rotation matrix by the branch with the largest
+// pivot, operation for operation as INTEGRATION.md section 2 spells it out for a caller
+void measurement_of_T(const double* R, double z[7]) {
+  z[0] = R[9]; z[1] = R[10]; z[2] = R[11]; z[3] = 0; z[4] = 0; z[5] = 0; z[6] = 1;
+  const double tr = R[0] + R[4] + R[8];
+  if (tr > 0)                          { const double q = 2 * std::sqrt(1 + tr);                 z[6] = q / 4; z[3] = (R[7] - R[5]) / q; z[4] = (R[2] - R[6]) / q; z[5] = (R[3] - R[1]) / q; }
+  else if (R[0] > R[4] && R[0] > R[8]) { const double q = 2 * std::sqrt(1 + R[0] - R[4] - R[8]); z[3] = q / 4; z[6] = (R[7] - R[5]) / q; z[4] = (R[1] + R[3]) / q; z[5] = (R[2] + R[6]) / q; }
+  else if (R[4] > R[8])                { const double q = 2 * std::sqrt(1 + R[4] - R[0] - R[8]); z[4] = q / 4; z[6] = (R[2] - R[6]) / q; z[3] = (R[1] + R[3]) / q; z[5] = (R[5] + R[7]) / q; }
+  else                                 { const double q = 2 * std::sqrt(1 + R[8] - R[0] - R[4]); z[5] = q / 4; z[6] = (R[3] - R[1]) / q; z[3] = (R[2] + R[6]) / q; z[4] = (R[5] + R[7]) / q; }
+}
+
+// the downsampled cloud of every new keyframe that carries one; before the association loop, which drops the raw clouds
+int downsample_new_keyframes(sslam_slam* s) {
+  for (auto& kf : s->new_keyframes) {
+    if (kf->cloud.empty() || kf->has_ds) continue;
+    const int rc = downsampled_cloud(s, *kf, s->loop_P.voxel_leaf, kf->ds);
+    if (rc < 0) return rc;
+    kf->has_ds = !kf->ds.empty();
+  }
+  return 0;
+}
+
+// steps 1 - 7 of sslam_slam_set_loop_closure (include/sslam.h)
+int close_loops(sslam_slam* s) {
+  const sslam_loop_params& P = s->loop_P;
+  struct Entry { int kf; Pose est; };
+  auto entry = [&](const std::vector<std::shared_ptr<KeyFrame>>& list, int i, std::vector<Entry>& out, std::vector<double>& tab) -> int {
+    double tq[7];
+    if (sslam_graph_get_vertex(s->graph, list[i]->node, tq) < 0) return SSLAM_ERR_INVALID;
+    out.push_back(Entry{i, from_tq(tq)});
+    tab.push_back(tq[0]); tab.push_back(tq[1]); tab.push_back(list[i]->accum_distance);
+    return 0;
+  };
+  std::vector<Entry> olds, news;
+  std::vector<double> keys, qs;
+  int rc;
+  for (int i = 0; i < (int)s->new_keyframes.size(); ++i) {
+    const KeyFrame& kf = *s->new_keyframes[i];
+    if (!kf.has_ds || kf.accum_distance - s->last_edge_accum < P.distance_from_last_edge_thresh) continue;
+    if ((rc = entry(s->new_keyframes, i, news, qs)) < 0) return rc;
+  }
+  if (news.empty()) return 0;
+  for (int i = 0; i < (int)s->keyframes.size(); ++i)
+    if (s->keyframes[i]->has_ds && (rc = entry(s->keyframes, i, olds, keys)) < 0) return rc;
+  if (olds.empty()) return 0;
+  const int n_new = (int)news.size(), n_keys = (int)olds.size();
+  const int cap = P.max_candidates ? P.max_candidates : n_keys;
+  std::vector<int32_t> cand((size_t)n_new * cap), count(n_new);
+  double t0 = now_s();
+  if ((rc = loop_candidates(s, keys.data(), n_keys, qs.data(), n_new, P, cand.data(), count.data(), cap)) < 0) return rc;
+  s->loop_seconds[0] = now_s() - t0;
+  // every (new, candidate) pair of the tick through one registration call; each cloud is packed once
+  std::vector<float> xyz;
+  std::vector<int32_t> start{0};
+  std::vector<int> cloud_of_old(n_keys, -1), first_pair(n_new, 0);
+  auto pack = [&](const std::vector<float>& ds) { xyz.insert(xyz.end(), ds.begin(), ds.end()); start.push_back((int32_t)(xyz.size() / 3)); return (int)start.size() - 2; };
+  std::vector<sslam_reg_pair> pairs;
+  for (int j = 0; j < n_new; ++j) {
+    first_pair[j] = (int)pairs.size();
+    const int nc = std::min<int>(count[j], cap);
+    if (nc == 0) continue;
+    const int target = pack(s->new_keyframes[news[j].kf]->ds);
+    const Pose inv = inverse(news[j].est);
+    for (int c = 0; c < nc; ++c) {
+      const int k = cand[(size_t)j * cap + c];
+      if (cloud_of_old[k] < 0) cloud_of_old[k] = pack(s->keyframes[olds[k].kf]->ds);
+      const Pose rel = compose(inv, olds[k].est);
+      sslam_reg_pair R;
+      R.target = target; R.source = cloud_of_old[k];
+      const Mat3 M = qmat(rel.q);
+      for (int q = 0; q < 9; ++q) R.T0[q] = M.m[q];
+      R.T0[9] = rel.t.x; R.T0[10] = rel.t.y; R.T0[11] = rel.t.z;
+      R.max_corr2 = P.fitness_score_max_range;
+      pairs.push_back(R);
+    }
+  }
+  if (pairs.empty()) return 0;
+  std::vector<sslam_reg_result> reg(pairs.size());
+  t0 = now_s();
+  rc = sslam_seg_register_pairs(s->seg, xyz.data(), start.data(), (int)start.size() - 1, pairs.data(), (int)pairs.size(), P.max_iterations, P.epsilon,
+                                reg.data(), nullptr, nullptr, nullptr);
+  s->loop_seconds[1] = now_s() - t0;
+  if (rc < 0) return rc;
+  // the best pair of every new keyframe; its measurement and information where it passes the score test
+  struct Best { int pair = -1, key = -1; double z[7], info[36], d2 = NAN; bool scored = false; };
+  std::vector<Best> best(n_new);
+  std::vector<int32_t> gate_cand;
+  std::vector<double> gate_z, gate_info;
+  std::vector<int> gate_of;
+  for (int j = 0; j < n_new; ++j) {
+    Best& B = best[j];
+    const int nc = std::min<int>(count[j], cap);
+    for (int c = 0; c < nc; ++c) {
+      const sslam_reg_result& r = reg[first_pair[j] + c];
+      const int k = cand[(size_t)j * cap + c];
+      if (r.status != 0 || r.used <= 0) continue;
+      if (B.pair < 0 || r.score < reg[B.pair].score || (r.score == reg[B.pair].score && k < B.key)) { B.pair = first_pair[j] + c; B.key = k; }
+    }
+    if (B.pair < 0 || reg[B.pair].score > P.fitness_score_thresh) continue;
+    B.scored = true;
+    measurement_of_T(reg[B.pair].T, B.z);
+    if ((rc = sslam_information_from_fitness(&P.inf, reg[B.pair].score, B.info)) < 0) return rc;
+    if (P.gate_chi2 > 0) {
+      gate_cand.push_back(SSLAM_GATE_SE3);
+      gate_cand.push_back(s->new_keyframes[news[j].kf]->node);
+      gate_cand.push_back(s->keyframes[olds[B.key].kf]->node);
+      gate_z.insert(gate_z.end(), B.z, B.z + 7);
+      gate_info.insert(gate_info.end(), B.info, B.info + 36);
+      gate_of.push_back(j);
+    }
+  }
+  if (!gate_of.empty()) {   // one call for the whole tick, before any loop edge is added
+    std::vector<double> d2(gate_of.size());
+    t0 = now_s();
+    rc = sslam_graph_gate(s->graph, gate_cand.data(), gate_z.data(), gate_info.data(), (int)gate_of.size(), d2.data(), nullptr, nullptr);
+    s->loop_seconds[2] = now_s() - t0;
+    if (rc < 0) return rc;
+    for (size_t g = 0; g < gate_of.size(); ++g) best[gate_of[g]].d2 = d2[g];
+  }
+  // the new keyframes in order, as hdl's sequential loop meets them
+  for (int j = 0; j < n_new; ++j) {
+    const KeyFrame& kf = *s->new_keyframes[news[j].kf];
+    if (kf.accum_distance - s->last_edge_accum < P.distance_from_last_edge_thresh) continue;
+    if (count[j] <= 0) continue;
+    const Best& B = best[j];
+    sslam_loop L;
+    std::memset(&L, 0, sizeof L);
+    L.new_vertex = kf.node; L.cand_vertex = -1; L.n_candidates = count[j]; L.edge_id = -1;
+    L.score = DBL_MAX; L.d2 = NAN;
+    if (B.pair < 0) {
+      L.outcome = SSLAM_LOOP_NO_MATCH;
+    } else {
+      const sslam_reg_result& r = reg[B.pair];
+      const KeyFrame& ck = *s->keyframes[olds[B.key].kf];
+      L.cand_vertex = ck.node;
+      std::memcpy(L.T, r.T, sizeof L.T);
+      L.score = r.score; L.used = r.used; L.iterations = r.iterations; L.converged = r.converged;
+      if (!B.scored) {
+        L.outcome = SSLAM_LOOP_SCORE;
+      } else {
+        L.d2 = B.d2;
+        if (P.gate_chi2 > 0 && !(B.d2 < P.gate_chi2)) {
+          L.outcome = SSLAM_LOOP_GATE;
+        } else {
+          const int eid = sslam_graph_add_edge_se3(s->graph, kf.node, ck.node, B.z, B.info);
+          if (eid < 0) return eid;
+          if (P.robust_kernel != SSLAM_ROBUST_NONE && (rc = sslam_graph_set_edge_robust_kernel(s->graph, eid, P.robust_kernel, P.robust_delta)) < 0) return rc;
+          s->last_edge_accum = kf.accum_distance;
+          L.outcome = SSLAM_LOOP_ADDED; L.edge_id = eid;
+        }
+      }
+    }
+    s->loops.push_back(L);
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -810,7 +1097,7 @@ int sslam_slam_vio(sslam_slam* s, int32_t sec, int32_t nsec, const double odom_t
       for (int k = 0; k < 3; ++k) kf->off[k] = s->latest.off[k];
     }
   }
-  if (s->fit_on && fresh_cloud && kf->cloud.empty() && !s->latest.cloud.empty()) {   // the fitness model reads the cloud of a keyframe without boxes too
+  if ((s->fit_on || s->loop_on) && fresh_cloud && kf->cloud.empty() && !s->latest.cloud.empty()) {   // the fitness model and loop closure read the cloud of a keyframe without boxes too
     kf->cloud = s->latest.cloud;
     kf->width = s->latest.width; kf->height = s->latest.height; kf->point_step = s->latest.point_step; kf->row_step = s->latest.row_step;
     for (int k = 0; k < 3; ++k) kf->off[k] = s->latest.off[k];
@@ -825,6 +1112,8 @@ int sslam_slam_run(sslam_slam* s, sslam_tick_stats* st) {
   sslam_tick_stats local;
   if (!st) st = &local;
   std::memset(st, 0, sizeof *st);
+  s->loops.clear();
+  for (double& v : s->loop_seconds) v = 0;
   // on an error after the queue was touched the bookkeeping is completed before the error is returned (the keyframes that reached the
   // graph move to `keyframes`): the next call must neither add them again nor associate them a second time
   auto fail = [&](int code) {
@@ -838,6 +1127,12 @@ int sslam_slam_run(sslam_slam* s, sslam_tick_stats* st) {
   if (rc == 0) return 0;
   st->keyframes_added = (int)s->new_keyframes.size();
   double t0 = now_s();
+  const double t_loop = t0;
+  if (s->loop_on) {
+    if ((rc = downsample_new_keyframes(s)) < 0) return fail(rc);
+    s->loop_seconds[3] = now_s() - t_loop;
+    t0 = now_s();
+  }
   if ((rc = segment_new_keyframes(s)) < 0) return fail(rc);
   st->seconds_frontend = now_s() - t0;
   t0 = now_s();
@@ -852,8 +1147,14 @@ int sslam_slam_run(sslam_slam* s, sslam_tick_stats* st) {
     kf.cloud.clear(); kf.cloud.shrink_to_fit();
   }
   st->seconds_association = now_s() - t0;
+  if (s->loop_on) {   // where hdl calls LoopDetector::detect: the new keyframes are in the graph, nothing is optimised yet
+    t0 = now_s();
+    rc = close_loops(s);
+    s->loop_seconds[3] += now_s() - t0;
+    if (rc < 0) return fail(rc);
+  }
   for (auto& kf : s->new_keyframes) {
-    if (s->fit_on) { kf->cloud.clear(); kf->cloud.shrink_to_fit(); }   // only the downsampled cloud of the last keyframe is kept
+    if (s->fit_on || s->loop_on) { kf->cloud.clear(); kf->cloud.shrink_to_fit(); }   // only downsampled clouds are kept
     s->keyframes.push_back(kf);
   }
   s->new_keyframes.clear();
@@ -924,6 +1225,60 @@ int sslam_slam_last_fitness(const sslam_slam* s, double* score, int32_t* used, i
     if (used) used[i] = s->fit_used[i];
   }
   return n;
+}
+
+void sslam_loop_default_params(sslam_loop_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  // hdl_graph_slam's defaults [UPSTREAM, unverified here]
+  p->distance_thresh = 5.0; p->accum_distance_thresh = 8.0; p->distance_from_last_edge_thresh = 5.0;
+  p->fitness_score_max_range = DBL_MAX; p->fitness_score_thresh = 0.5;
+  p->max_iterations = 64; p->epsilon = 0.01;
+  p->max_candidates = 0; p->voxel_leaf = 0.1f; p->gate_chi2 = 0;
+  p->robust_kernel = SSLAM_ROBUST_HUBER; p->robust_delta = 1.0;
+  sslam_inf_default_params(&p->inf);
+}
+
+int sslam_slam_set_loop_closure(sslam_slam* s, const sslam_loop_params* p) {
+  if (!s) return set_error(SSLAM_ERR_INVALID, "null handle");
+  if (!p) {
+    s->loop_on = false;
+    s->last_edge_accum = 0;
+    for (auto* list : {&s->keyframes, &s->new_keyframes})
+      for (auto& kf : *list) { kf->ds.clear(); kf->ds.shrink_to_fit(); kf->has_ds = false; }
+    return 0;
+  }
+  const int rc = check_loop_params(p, true);
+  if (rc < 0) return rc;
+  if (!s->seg) return set_error(SSLAM_ERR_INVALID, "loop closure needs the frontend handle: none was given to sslam_slam_create");
+  s->loop_on = true;
+  s->loop_P = *p;
+  if (s->loop_P.voxel_leaf == 0) s->loop_P.voxel_leaf = 0.1f;
+  return 0;
+}
+
+int sslam_slam_last_loops(const sslam_slam* s, sslam_loop* out, int max) {
+  if (!s) return set_error(SSLAM_ERR_INVALID, "null handle");
+  const int n = (int)s->loops.size();
+  for (int i = 0; i < n && i < max && out; ++i) out[i] = s->loops[i];
+  return n;
+}
+
+int sslam_slam_last_loop_timing(const sslam_slam* s, double seconds[4]) {
+  if (!s || !seconds) return set_error(SSLAM_ERR_INVALID, "null argument");
+  for (int k = 0; k < 4; ++k) seconds[k] = s->loop_seconds[k];
+  return 0;
+}
+
+int sslam_slam_loop_candidates(sslam_slam* s, const double* keys, int n_keys, const double* news, int n_new, const sslam_loop_params* p,
+                               int32_t* cand_out, int32_t* count_out, int cap) {
+  if (!s || !p || n_keys < 0 || n_new < 0 || cap < 0 || (n_keys > 0 && !keys) || (n_new > 0 && (!news || !count_out)) ||
+      ((size_t)n_new * cap > 0 && !cand_out))
+    return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = check_loop_params(p, false);
+  if (rc < 0) return rc;
+  if ((rc = loop_candidates(s, keys, n_keys, news, n_new, *p, cand_out, count_out, cap)) < 0) return rc;
+  return n_new;
 }
 
 int sslam_slam_find_matches(sslam_slam* s, const sslam_plane* objects, int n, const float robot_pose[6], sslam_landmark* out) {

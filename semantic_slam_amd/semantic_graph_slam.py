@@ -38,6 +38,21 @@ class TickStats(C.Structure):    # sslam_tick_stats
                 ("seconds_marginals", C.c_double)]
 
 
+class LoopParams(C.Structure):   # sslam_loop_params
+    _fields_ = [("distance_thresh", C.c_double), ("accum_distance_thresh", C.c_double), ("distance_from_last_edge_thresh", C.c_double),
+                ("fitness_score_max_range", C.c_double), ("fitness_score_thresh", C.c_double), ("max_iterations", C.c_int32),
+                ("epsilon", C.c_double), ("max_candidates", C.c_int32), ("voxel_leaf", C.c_float), ("gate_chi2", C.c_double),
+                ("robust_kernel", C.c_int32), ("robust_delta", C.c_double), ("inf", InfParams)]
+
+
+class Loop(C.Structure):         # sslam_loop
+    _fields_ = [("new_vertex", C.c_int32), ("cand_vertex", C.c_int32), ("n_candidates", C.c_int32), ("outcome", C.c_int32),
+                ("edge_id", C.c_int32), ("used", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32),
+                ("T", C.c_double * 12), ("score", C.c_double), ("d2", C.c_double)]
+
+
+LOOP_ADDED, LOOP_SCORE, LOOP_GATE, LOOP_NO_MATCH = 0, 1, 2, 3   # SSLAM_LOOP_*
+
 _BOUND = False
 
 
@@ -61,6 +76,12 @@ def _bind(lib):
     lib.sslam_slam_graph.restype = vp; lib.sslam_slam_graph.argtypes = [vp]
     lib.sslam_slam_find_matches.restype = ci; lib.sslam_slam_find_matches.argtypes = [vp, vp, ci, vp, vp]
     # sslam_slam_set_fitness_information, sslam_slam_last_fitness: declared in _lib.load_library
+    lib.sslam_loop_default_params.restype = None; lib.sslam_loop_default_params.argtypes = [C.POINTER(LoopParams)]
+    lib.sslam_slam_set_loop_closure.restype = ci; lib.sslam_slam_set_loop_closure.argtypes = [vp, C.POINTER(LoopParams)]
+    lib.sslam_slam_last_loops.restype = ci; lib.sslam_slam_last_loops.argtypes = [vp, vp, ci]
+    lib.sslam_slam_last_loop_timing.restype = ci; lib.sslam_slam_last_loop_timing.argtypes = [vp, vp]
+    lib.sslam_slam_loop_candidates.restype = ci
+    lib.sslam_slam_loop_candidates.argtypes = [vp, vp, ci, vp, ci, C.POINTER(LoopParams), vp, vp, ci]
     _BOUND = True
 
 
@@ -69,6 +90,14 @@ def default_slam_params(device: int = 0) -> SlamParams:
     p = SlamParams()
     lib.sslam_slam_default_params(C.byref(p))
     p.device = device
+    return p
+
+
+def default_loop_params() -> LoopParams:
+    """``sslam_loop_default_params``: hdl_graph_slam's LoopDetector defaults, Huber 1.0 on the loop edge, no gate"""
+    lib = load_library(); _bind(lib)
+    p = LoopParams()
+    lib.sslam_loop_default_params(C.byref(p))
     return p
 
 
@@ -143,6 +172,42 @@ class SemanticGraphSLAM:
         score = np.zeros(max(n, 1)); used = np.zeros(max(n, 1), np.int32)
         self._check(self._lib.sslam_slam_last_fitness(self._h, score.ctypes.data, used.ctypes.data, n))
         return score[:n], used[:n]
+
+    def set_loop_closure(self, params: LoopParams | None = "default") -> None:
+        """``sslam_slam_set_loop_closure``: the following ticks search loop candidates among the processed keyframes, scan-match them,
+        gate the best match and add the loop edge (hdl_graph_slam's LoopDetector::detect).  ``params``: a ``LoopParams``, the defaults, or
+        None to turn it off.  Needs the frontend handle given to the constructor."""
+        if isinstance(params, str):
+            params = default_loop_params()
+        self._check(self._lib.sslam_slam_set_loop_closure(self._h, None if params is None else C.byref(params)))
+
+    def last_loops(self):
+        """the ``Loop`` records of the last ``run``: one per new keyframe that reached the selection with at least one candidate"""
+        n = self._check(self._lib.sslam_slam_last_loops(self._h, None, 0))
+        arr = (Loop * max(n, 1))()
+        self._check(self._lib.sslam_slam_last_loops(self._h, C.cast(arr, C.c_void_p), n))
+        return [arr[k] for k in range(n)]
+
+    def last_loop_timing(self) -> np.ndarray:
+        """wall seconds inside the last ``run``: candidate launch, registration, gate, the whole loop stage"""
+        out = np.zeros(4)
+        self._check(self._lib.sslam_slam_last_loop_timing(self._h, out.ctypes.data))
+        return out
+
+    def loop_candidates(self, keys, news, params: LoopParams | None = None, cap: int | None = None):
+        """``sslam_slam_loop_candidates`` (k_loop_candidates on its own).  ``keys`` / ``news``: [n, 3] float64 rows of x, y, accum_distance of
+        the old / new keyframes.  Returns (cand [n_new, cap] int32 with -1 where not filled, count [n_new] int32); ``cap`` defaults to
+        max_candidates, or the number of keys when that is 0."""
+        p = params if params is not None else default_loop_params()
+        k = np.ascontiguousarray(keys, np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(news, np.float64).reshape(-1, 3)
+        if cap is None:
+            cap = p.max_candidates if p.max_candidates else len(k)
+        cand = np.full((len(q), cap), -1, np.int32)
+        count = np.zeros(len(q), np.int32)
+        self._check(self._lib.sslam_slam_loop_candidates(self._h, k.ctypes.data if len(k) else None, len(k), q.ctypes.data if len(q) else None, len(q),
+                                                         C.byref(p), cand.ctypes.data if cand.size else None, count.ctypes.data if len(q) else None, cap))
+        return cand, count
 
     # -- getters --------------------------------------------------------------------------------------------------------------
     def getRobotPose(self) -> np.ndarray:
