@@ -86,6 +86,30 @@ class semantic_graph_slam {
     return count;
   }
 
+  // the map of the run (sslam_slam_set_map_clouds / sslam_slam_map_cloud; where the reference has its commented-out mapping thread,
+  // semantic_graph_slam.cpp:72-73, 85-86).  set_map_clouds after init(), which needs the frontend handle for it: from then on every
+  // keyframe's downsampled cloud stays on the device.  map_cloud puts them at the current estimates: one centroid per occupied voxel.
+  void set_map_clouds(bool on = true, float keyframe_leaf = 0.1f) { check(sslam_slam_set_map_clouds(h_, on ? 1 : 0, keyframe_leaf), "sslam_slam_set_map_clouds"); }
+  struct MapCloud {
+    std::vector<float> xyz;          // 3 per voxel: the centroid
+    std::vector<int32_t> cells;      // 3 per voxel: the global cell; its centre is (cell + 0.5) * resolution
+    std::vector<int32_t> counts;
+    std::vector<int32_t> vertices;   // the keyframes the map was built from
+    std::vector<double> poses;       // 12 per keyframe: R row-major, then t
+    sslam_map_stats stats{};
+  };
+  MapCloud map_cloud(float resolution, int min_points = 1) {
+    MapCloud M;
+    int32_t n_points = 0;
+    const int n_clouds = check(sslam_slam_map_clouds_kept(h_, &n_points), "sslam_slam_map_clouds_kept");
+    M.xyz.resize(3 * (size_t)n_points); M.cells.resize(3 * (size_t)n_points); M.counts.resize((size_t)n_points);
+    M.vertices.resize((size_t)n_clouds); M.poses.resize(12 * (size_t)n_clouds);
+    const int m = check(sslam_slam_map_cloud(h_, resolution, min_points, M.xyz.data(), M.cells.data(), M.counts.data(), n_points, M.vertices.data(),
+                                             M.poses.data(), n_clouds, &M.stats), "sslam_slam_map_cloud");
+    M.xyz.resize(3 * (size_t)m); M.cells.resize(3 * (size_t)m); M.counts.resize((size_t)m);
+    return M;
+  }
+
   // getRobotPose / getMap2OdomTrans (semantic_graph_slam.cpp:375-381)
   void getRobotPose(sslam::Isometry& robot_pose) const {
     double tq[7];

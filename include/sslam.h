@@ -643,6 +643,58 @@ typedef struct sslam_reg_result {
 int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
                              int max_iterations, double epsilon, sslam_reg_result* out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms);
 
+/* ---- map cloud: every cloud at its pose, reduced to one cloud over a SPARSE voxel grid (hdl_graph_slam's
+ * MapCloudGenerator::generate(keyframes, resolution) [UPSTREAM, quoted from memory]: transform, concatenate, octree-downsample; the
+ * reference planned the call -- mapping::generateMap / opitmizeMap at semantic_graph_slam.cpp:36-40, 72-73, 85-86, commented out) ------
+ * sslam_seg_map_cloud: clouds laid out as for sslam_seg_fitness_scores (cloud_start: n_clouds + 1 entries, non-decreasing, first >= 0);
+ * T: 12 doubles per cloud, R row-major, then t, taking the cloud into the map frame.  sslam_seg_voxel_grid cannot serve here: it sizes a
+ * dense grid over the bounding box and refuses more than 2^26 cells, and nearly all of a map's box is empty.
+ * Transform, in float32 without fused multiply-add (a NumPy restatement matches bit for bit; the arithmetic of the fitness pass):
+ *   R, t = T cast from double to float once;   x' = ((r00 x + r01 y) + r02 z) + tx  (y', z' alike).
+ * A point takes no part when one of its three coordinates, or one of its three transformed coordinates, is not finite.
+ * Cell: i = (int)floorf(x' * inv) per axis with inv = 1.0f / resolution, the rule of sslam_seg_voxel_grid.  Cells are GLOBAL: they do not
+ * depend on the bounding box, so two calls over different sets of clouds put the same point into the same cell.
+ * Sparse grid, two levels: a brick is 8 x 8 x 8 cells, brick index b = i >> 3 (arithmetic shift: floor division), local index l = i & 7.
+ *   0. min / max pass over the transformed points.  The cell bounds of that box must pass the 32-bit test of sslam_seg_voxel_grid, and the
+ *      dense grid of BRICKS over it may hold at most 2^26 bricks (the same rule, applied to cell >> 3): otherwise SSLAM_ERR_UNSUPPORTED,
+ *      before anything is sized or written.
+ *   1. the occupied bricks are flagged; an ordered compaction gives their ascending list and a brick -> slot table.  More than 2^20
+ *      occupied bricks (2^29 cells, about 15 GB of tables): SSLAM_ERR_UNSUPPORTED, the number in the message.
+ *   2. per voxel slot * 512 + local: the point count (int32) and the sums of x', y', z' in 2^-20 fixed point, llrint((double)x' * 1048576.0),
+ *      by 64-bit integer atomics as in sslam_seg_voxel_grid.  Integer sums are exact and independent of arrival order: the result does
+ *      not depend on the launch geometry, and repeating a call repeats its bits.  A sum is an int64: |x'| times the voxel's count must
+ *      stay below 2^43, which a map's metres do by many orders of magnitude; beyond it the centroid is undefined.  (The direct form:
+ *      one 32-bit and three 64-bit atomics per point, no merge of equal cells inside a wave.  Never float atomics.)
+ *   3. the voxels with count >= max(min_points, 1) are compacted; one record each:
+ *      xyz_out: the CENTROID (float)(((double)sum / 1048576.0) / (double)count); cells_out: the global cell ix, iy, iz; counts_out: count.
+ * DEVIATION: hdl's octree returns the voxel CENTRES (getOccupiedVoxelCenters); the centre of record k is (cells_out[3 k + a] + 0.5) *
+ * resolution, for a caller that wants it.
+ * Output order: ascending occupied brick in the dense brick grid, x fastest -- (bz, by, bx) -- and inside a brick ascending local index,
+ * x fastest -- (lz, ly, lx).  It is the order of the two ordered compactions: no sort, and fixed by the points alone, not by the order
+ * of the clouds or of the points in them.
+ * A workgroup never spans two clouds (R, t are uniform in the wave); each pass recomputes the transform instead of storing it.
+ * cells_out, counts_out, stats are optional.  Returns the number of voxels that pass min_points -- the true count; at most max_out
+ * records are written -- and 0 for no clouds or no usable point.
+ * stats: kernel_ms sums the hipEvent times of the four passes (the copies between them excluded; the 4-byte read of a compaction's total
+ * inside pass 3 included); sslam_seg_last_map_timing gives the four of the last call: min / max, bricks, accumulate, voxels + records.
+ * SSLAM_ERR_INVALID: a NULL handle; cloud_start or T NULL with clouds; xyz NULL with points; xyz_out NULL with max_out > 0; a negative
+ * n_clouds, max_out or min_points; a cloud_start that decreases or starts below 0; a resolution that is not finite and positive, or
+ * whose 1 / resolution is not finite in float; a non-finite entry of T; a batch in flight (sslam_seg_submit_batch).
+ * SSLAM_ERR_UNSUPPORTED also for more than 2^22 clouds.  SSLAM_ERR_NO_DEVICE without a GPU. */
+typedef struct sslam_map_stats {
+  int32_t n_clouds, n_points;      /* given; n_points counts every row, finite or not */
+  int32_t n_used;                  /* points that landed in a voxel */
+  int32_t n_bricks, n_voxels;      /* occupied bricks; occupied voxels BEFORE min_points */
+  int64_t upload_bytes;            /* host -> device bytes this call moved: points, poses and cloud_start */
+  double  kernel_ms;               /* hipEvent time of the passes, copies excluded */
+} sslam_map_stats;
+int sslam_seg_map_cloud(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds,
+                        const double* T /* 12 per cloud: R row-major, then t; cloud -> map frame */,
+                        float resolution, int min_points,
+                        float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out,
+                        sslam_map_stats* stats);
+int sslam_seg_last_map_timing(const sslam_seg* s, double ms[4]);
+
 /* parity hooks: per-box products of the last sslam_seg_segment call.
  * normals: w*h*4 floats (nx,ny,nz,curvature), labels: w*h int32 (-1 = no plane; otherwise the
  * region index in output order of pcl::OrganizedMultiPlaneSegmentation::segmentAndRefine). */
@@ -814,6 +866,37 @@ int sslam_slam_last_loop_timing(const sslam_slam* s, double seconds[4]);
  * cand_out with n_new * cap > 0, a threshold that is negative or not finite, max_candidates outside 0 .. 64.  SSLAM_ERR_NO_DEVICE without a GPU. */
 int sslam_slam_loop_candidates(sslam_slam* s, const double* keys, int n_keys, const double* news, int n_new, const sslam_loop_params* p,
                                int32_t* cand_out, int32_t* count_out, int cap);
+/* ---- the map of a run: keyframe clouds kept on the device, put at their current estimates by sslam_seg_map_cloud's kernels (where the
+ * reference has its commented-out mapping thread, semantic_graph_slam.cpp:72-73, 85-86).  Off until sslam_slam_set_map_clouds is called
+ * with on != 0; a handle on which it never was, or was last called with on = 0, runs its ticks bit for bit as before this call existed
+ * and keeps nothing.  Turning it off drops what was kept. -----------------------------------------------------------------------------
+ * With it on: sslam_slam_vio keeps the latest cloud on every keyframe that has a fresh one (as under sslam_slam_set_fitness_information).
+ * In the tick, before the raw cloud is dropped, the finite points of each new keyframe's cloud are voxel-grid downsampled once
+ * (sslam_seg_voxel_grid, keyframe_leaf; 0 -> 0.1) and the result is appended ONCE to a device buffer of the handle.  The leaf is
+ * independent of loop closure's voxel_leaf (with both on and equal leaves the one downsampled cloud serves both).  A keyframe without a
+ * cloud, or without a finite point, holds no map cloud.  Clouds are taken to be in the frame of the keyframe's pose, as the fitness
+ * model and the loop stage take them.  Neither switch position changes an estimate: the map clouds feed nothing back into the graph.
+ * The kept clouds live on the orchestrator's device (sslam_slam_params.device) and are read there by the frontend handle's kernels, so
+ * both handles must name the SAME device: on != 0 with sslam_seg_params.device != sslam_slam_params.device is refused here, on the host.
+ * Returns 0; SSLAM_ERR_INVALID for a NULL handle, a negative or non-finite keyframe_leaf, on != 0 without a frontend handle;
+ * SSLAM_ERR_UNSUPPORTED for on != 0 with the two handles on different devices. */
+int sslam_slam_set_map_clouds(sslam_slam* s, int on, float keyframe_leaf /* 0 -> 0.1 */);
+/* the number of map clouds kept so far and, in *n_points (optional), their points: a bound on the voxels sslam_slam_map_cloud can return.
+ * Host only. */
+int sslam_slam_map_clouds_kept(const sslam_slam* s, int32_t* n_points);
+/* sslam_seg_map_cloud (resolution, min_points, the outputs, the order and the limits as stated there) over the processed keyframes that
+ * hold a map cloud, in keyframe order.  Pose of a cloud: its keyframe's current graph estimate with the quaternion normalised, R the
+ * matrix of that quaternion (the function of step 4 of the loop stage), t the translation.  Only the poses travel per call: after the
+ * first call stats->upload_bytes is 48 bytes per cloud (12 floats) when no keyframe arrived in between, else that plus 12 bytes per
+ * point of the clouds appended since the last call (a new cloud's boundary is written by a device fill, not a copy).
+ * vertex_out / poses_out (optional, at most max_clouds clouds are written): the vertex id and the 12 doubles, before their cast to
+ * float, of every cloud used -- what the map was built from; the same call through sslam_seg_map_cloud with the same clouds repeats it.
+ * Returns the voxel count; 0 with map clouds off or none kept.  Errors: those of sslam_seg_map_cloud; SSLAM_ERR_INVALID also for a
+ * negative max_clouds or an estimate that is not finite; SSLAM_ERR_UNSUPPORTED when clouds are kept and the two handles name different
+ * devices (sslam_slam_set_map_clouds refuses that already; checked again because the kernels would read another device's memory). */
+int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points,
+                         float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out,
+                         int32_t* vertex_out, double* poses_out, int max_clouds, sslam_map_stats* stats);
 /* setPointCloudData (semantic_graph_slam.cpp:341-345): the cloud is copied */
 int sslam_slam_set_point_cloud(sslam_slam* s, const uint8_t* cloud, int width, int height, int point_step, int row_step,
                                int off_x, int off_y, int off_z);

@@ -37,6 +37,16 @@ class OptStats(C.Structure):
                 f"seconds={self.seconds:.4f}, solver_iterations={self.solver_iterations})")
 
 
+class MapStats(C.Structure):
+    """``sslam_map_stats`` (include/sslam.h)"""
+    _fields_ = [("n_clouds", C.c_int32), ("n_points", C.c_int32), ("n_used", C.c_int32), ("n_bricks", C.c_int32), ("n_voxels", C.c_int32),
+                ("upload_bytes", C.c_int64), ("kernel_ms", C.c_double)]
+
+    def __repr__(self):
+        return (f"MapStats(n_clouds={self.n_clouds}, n_points={self.n_points}, n_used={self.n_used}, n_bricks={self.n_bricks}, "
+                f"n_voxels={self.n_voxels}, upload_bytes={self.upload_bytes}, kernel_ms={self.kernel_ms:.4f})")
+
+
 def load_library():
     global _LIB
     if _LIB is not None:
@@ -112,6 +122,11 @@ def load_library():
         "sslam_information_from_fitness": (ci, [vp, cd, dp]),
         "sslam_slam_set_fitness_information": (ci, [vp, vp, C.c_float, cd]),
         "sslam_slam_last_fitness": (ci, [vp, vp, vp, ci]),
+        "sslam_seg_map_cloud": (ci, [vp, vp, vp, ci, vp, C.c_float, ci, vp, vp, vp, ci, C.POINTER(MapStats)]),
+        "sslam_seg_last_map_timing": (ci, [vp, vp]),
+        "sslam_slam_set_map_clouds": (ci, [vp, ci, C.c_float]),
+        "sslam_slam_map_clouds_kept": (ci, [vp, C.POINTER(C.c_int32)]),
+        "sslam_slam_map_cloud": (ci, [vp, C.c_float, ci, vp, vp, vp, ci, vp, vp, ci, C.POINTER(MapStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/sslam.h"
+#include "map_cloud.hpp"
 #include "sslam_common.hpp"
 #include "sslam_math.hpp"
 
@@ -1203,6 +1204,26 @@ __global__ void k_exclusive_scan(const int* counts, int nblocks, int* off, int* 
   for (int b = 0; b < nblocks; ++b) { const int c = counts[b]; off[b] = acc; acc += c; }
   *total = acc;
 }
+// the same scan by one workgroup, for compactions over millions of entries (the map cloud's brick and voxel tables): every thread sums
+// a run of consecutive blocks, the 1024 sums are scanned in LDS, then every thread writes the offsets of its run.  off may be counts.
+__global__ __launch_bounds__(1024) void k_exclusive_scan_wide(const int* counts, int nblocks, int* off, int* total) {
+  __shared__ int part[1024];
+  const int t = threadIdx.x, run = (nblocks + 1023) / 1024;
+  const int b0 = min(t * run, nblocks), b1 = min(b0 + run, nblocks);
+  int mine = 0;
+  for (int b = b0; b < b1; ++b) mine += counts[b];
+  part[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int acc = part[t] - mine;
+  for (int b = b0; b < b1; ++b) { const int c = counts[b]; off[b] = acc; acc += c; }
+  if (t == 1023) *total = part[1023];
+}
 template <class Pred>
 __global__ __launch_bounds__(256) void k_write_if(Pred pred, int n, const int* __restrict__ block_off) {
   __shared__ int woff[4];
@@ -1844,6 +1865,118 @@ __global__ __launch_bounds__(256) void k_voxel_centroids(const int* __restrict__
   for (int d = 0; d < 3; ++d) out[3 * (size_t)k + d] = (float)(((double)sums[3 * (size_t)c + d] / 1048576.0) / (double)m);
   if (out_count) out_count[k] = m;
 }
+// ---- map cloud: many clouds, each at its pose, into one sparse voxel grid (hdl_graph_slam's MapCloudGenerator::generate [UPSTREAM]) ------
+// Launch geometry of the three point passes: blockIdx.x = the cloud, blockIdx.y strides over its points in blocks of 256, so a workgroup
+// never spans two clouds and R, t are uniform in the wave.  Every pass recomputes the transform (12 B read per point) with the
+// arithmetic of k_nn_pairs; a point takes part when its three coordinates and its three transformed coordinates are finite.
+struct MapIn { const float* xyz; const int* start; const float* pose; };   // pose: 12 floats per cloud, R row-major then t
+__device__ __forceinline__ bool map_point(const MapIn& M, const float* R, int p, float& tx, float& ty, float& tz) {
+  const float* q = M.xyz + 3 * (size_t)p;
+  const float x = q[0], y = q[1], z = q[2];
+  if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
+  tx = ((R[0] * x + R[1] * y) + R[2] * z) + R[9];
+  ty = ((R[3] * x + R[4] * y) + R[5] * z) + R[10];
+  tz = ((R[6] * x + R[7] * y) + R[8] * z) + R[11];
+  return isfinite(tx) && isfinite(ty) && isfinite(tz);
+}
+// a float as an int of the same order (-0 sorts below +0; both floor to cell 0)
+__device__ __forceinline__ int map_ordered(float f) { const int i = __float_as_int(f); return i ^ ((i >> 31) & 0x7fffffff); }
+// bounding box of the transformed points: box[0..2] = min, box[3..5] = max, as ordered ints (integer atomics, one set per workgroup; the
+// host keeps the launch at about 2048 workgroups: every one of them ends on the same six addresses)
+__global__ __launch_bounds__(256) void k_map_minmax(MapIn M, int* __restrict__ box) {
+  __shared__ float red[4][6];
+  const int c = blockIdx.x, p0 = M.start[c], n = M.start[c + 1] - p0;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = M.pose[12 * (size_t)c + k];
+  float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
+  bool any = false;
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+    float t[3];
+    if (!map_point(M, R, p0 + i, t[0], t[1], t[2])) continue;
+    any = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], t[k]); hi[k] = fmaxf(hi[k], t[k]); }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    for (int o = 32; o > 0; o >>= 1) { lo[k] = fminf(lo[k], __shfl_down(lo[k], o, 64)); hi[k] = fmaxf(hi[k], __shfl_down(hi[k], o, 64)); }
+  if ((threadIdx.x & 63) == 0) for (int k = 0; k < 3; ++k) { red[threadIdx.x >> 6][k] = lo[k]; red[threadIdx.x >> 6][3 + k] = hi[k]; }
+  if (__syncthreads_or(any) == 0) return;   // no usable point in this workgroup
+  const int k = threadIdx.x;
+  if (k < 3) atomicMin(&box[k], map_ordered(fminf(fminf(red[0][k], red[1][k]), fminf(red[2][k], red[3][k]))));
+  else if (k < 6) atomicMax(&box[k], map_ordered(fmaxf(fmaxf(red[0][k], red[1][k]), fmaxf(red[2][k], red[3][k]))));
+}
+// G: inv, and minb / mul of the dense grid of BRICKS (8 x 8 x 8 cells).  Cell i = (int)floorf(x' * inv) is global; brick i >> 3, local i & 7.
+__device__ __forceinline__ void map_cell(const VoxelGeom& G, float tx, float ty, float tz, size_t& brick, int& local) {
+  const int ix = (int)floorf(tx * G.inv[0]), iy = (int)floorf(ty * G.inv[1]), iz = (int)floorf(tz * G.inv[2]);
+  brick = (size_t)((ix >> 3) - G.minb[0]) * G.mul[0] + (size_t)((iy >> 3) - G.minb[1]) * G.mul[1] + (size_t)((iz >> 3) - G.minb[2]) * G.mul[2];
+  local = (ix & 7) | ((iy & 7) << 3) | ((iz & 7) << 6);
+}
+// pass 1: the occupied bricks
+__global__ __launch_bounds__(256) void k_map_flag_bricks(MapIn M, VoxelGeom G, unsigned char* __restrict__ flag) {
+  const int c = blockIdx.x, p0 = M.start[c], n = M.start[c + 1] - p0;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = M.pose[12 * (size_t)c + k];
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+    float tx, ty, tz;
+    if (!map_point(M, R, p0 + i, tx, ty, tz)) continue;
+    size_t b; int l;
+    map_cell(G, tx, ty, tz, b, l);
+    flag[b] = 1;
+  }
+}
+struct BrickPred {     // occupied bricks -> their ascending list and the brick -> slot table
+  const unsigned char* flag; int* list; int* slot;
+  __device__ bool keep(int i) const { return flag[i]; }
+  __device__ void put(int pos, int i) const { list[pos] = i; slot[i] = pos; }
+};
+// pass 2: per voxel slot * 512 + local the point count and the sums of x', y', z' in 2^-20 fixed point, as k_voxel_accumulate keeps them
+// (direct form: one 32-bit and three 64-bit integer atomics per point.  Merging runs of equal voxels inside a wave before the atomic
+// measured no faster, DESIGN.md section 4: a downsampled cloud has about one point per voxel, the sharing is between clouds, and those
+// sit in different workgroups); used: the points that landed, one add per wave
+__global__ __launch_bounds__(256) void k_map_accumulate(MapIn M, VoxelGeom G, const int* __restrict__ slot, int* __restrict__ count,
+                                                       long long* __restrict__ sums, int* __restrict__ used) {
+  const int c = blockIdx.x, p0 = M.start[c], n = M.start[c + 1] - p0;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = M.pose[12 * (size_t)c + k];
+  int mine = 0;
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+    float tx, ty, tz;
+    if (!map_point(M, R, p0 + i, tx, ty, tz)) continue;
+    size_t b; int l;
+    map_cell(G, tx, ty, tz, b, l);
+    const size_t v = (size_t)slot[b] * 512 + l;
+    atomicAdd(&count[v], 1);
+    atomicAdd((unsigned long long*)&sums[3 * v], (unsigned long long)llrint((double)tx * 1048576.0));
+    atomicAdd((unsigned long long*)&sums[3 * v + 1], (unsigned long long)llrint((double)ty * 1048576.0));
+    atomicAdd((unsigned long long*)&sums[3 * v + 2], (unsigned long long)llrint((double)tz * 1048576.0));
+    ++mine;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(used, mine);
+}
+struct VoxelPred {     // voxels with at least `thr` points -> their ascending list (out may be NULL: count only)
+  const int* count; int thr; int* out; int max_out;
+  __device__ bool keep(int i) const { return count[i] >= thr; }
+  __device__ void put(int pos, int i) const { if (pos < max_out) out[pos] = i; }
+};
+// pass 3: one record per kept voxel: centroid, global cell, count
+__global__ __launch_bounds__(256) void k_map_emit(const int* __restrict__ voxels, int m, const int* __restrict__ bricks, VoxelGeom G, int divx, int divy,
+                                                 const int* __restrict__ count, const long long* __restrict__ sums, float* __restrict__ out,
+                                                 int* __restrict__ out_cell, int* __restrict__ out_count) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= m) return;
+  const int v = voxels[k], n = count[v], l = v & 511, b = bricks[v >> 9];
+  const int bx = b % divx + G.minb[0], by = (b / divx) % divy + G.minb[1], bz = b / divx / divy + G.minb[2];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) out[3 * (size_t)k + d] = (float)(((double)sums[3 * (size_t)v + d] / 1048576.0) / (double)n);
+  out_cell[3 * (size_t)k] = bx * 8 + (l & 7); out_cell[3 * (size_t)k + 1] = by * 8 + ((l >> 3) & 7); out_cell[3 * (size_t)k + 2] = bz * 8 + (l >> 6);
+  out_count[k] = n;
+}
 // pcl::StatisticalOutlierRemoval (meanK 50, plane_segmentation.cpp:583-605): mean distance of every point to its k nearest
 // neighbours, exact (brute force): candidates stream through LDS tiles, every thread keeps the k + 1 smallest squared distances of
 // its query in an LDS column (replace-the-maximum; after the first tiles almost every candidate is rejected by one compare)
@@ -2174,6 +2307,8 @@ struct sslam_seg {
   int r_nbox = -1;                    // boxes the flags belong to (-1: no RANSAC has run on the resident batch)
   hipEvent_t f_e0 = nullptr, f_e1 = nullptr;   // sslam_seg_fitness_scores: around the kernels of the pass
   int n_cu = 0;                       // compute units of the device (sizes the target split of k_nn_pairs)
+  hipEvent_t m_ev[8] = {};            // the map cloud: start / stop around each of its four passes
+  double map_pass_ms[4] = {0, 0, 0, 0};
   sslam_seg* twin = nullptr;
   int fifo[2] = {0, 0};            // which pipeline (0 = this, 1 = twin) holds the oldest / the newer submitted batch
   int n_inflight = 0;
@@ -2190,6 +2325,7 @@ struct sslam_seg {
     if (q_e1) (void)hipEventDestroy(q_e1);
     if (f_e0) (void)hipEventDestroy(f_e0);
     if (f_e1) (void)hipEventDestroy(f_e1);
+    for (hipEvent_t e : m_ev) if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
   }
   void free_all() {
@@ -2244,11 +2380,13 @@ int seg_device(sslam_seg* s) {
 }
 // ordered compaction of [0, n) under `pred` on the handle's stream (k_count_if -> k_exclusive_scan -> k_write_if).  d_blk: one int per
 // block of 256, d_total: one int, which keeps the number kept; with total_out the call waits and returns that number on the host too.
+// wide: the scan by a whole workgroup (k_exclusive_scan_wide), for an n in the millions.
 template <class Pred>
-int compact_if(sslam_seg* s, Pred pred, int n, int* d_blk, int* d_total, int* total_out) {
+int compact_if(sslam_seg* s, Pred pred, int n, int* d_blk, int* d_total, int* total_out, bool wide = false) {
   const int nblk = (n + 255) / 256;
   hipLaunchKernelGGL(k_count_if<Pred>, dim3(nblk), dim3(256), 0, s->stream, pred, n, d_blk);
-  hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(64), 0, s->stream, d_blk, nblk, d_blk, d_total);
+  if (wide) hipLaunchKernelGGL(k_exclusive_scan_wide, dim3(1), dim3(1024), 0, s->stream, d_blk, nblk, d_blk, d_total);
+  else hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(64), 0, s->stream, d_blk, nblk, d_blk, d_total);
   hipLaunchKernelGGL(k_write_if<Pred>, dim3(nblk), dim3(256), 0, s->stream, pred, n, d_blk);
   SSLAM_HIP_TRY(hipGetLastError());
   if (!total_out) return 0;
@@ -2966,7 +3104,9 @@ int sslam_seg_distance_filter(sslam_seg* s, const float* xyz, int n, double dmin
 // one copy of the rule: the cell of a point is (int)floorf(x * inv) - minb on the device, which stays inside [0, div) exactly when both
 // bounds are representable, so every bound is compared as a float BEFORE its cast (a cast out of range is undefined on the host and
 // saturates on the device), and the cell count is bounded before anything is sized by it.
-static int voxel_geometry(const float lo[3], const float hi[3], float leaf, VoxelGeom* G, long long div[3], long long* ncell_out) {
+// With shift > 0 the grid is one of BRICKS of 2^shift cells per axis (the map cloud, shift 3): the cell bounds pass the same 32-bit test,
+// minb and div are in bricks (cell >> shift, an arithmetic shift), and the bound of 2^26 is on the bricks.
+static int voxel_geometry(const float lo[3], const float hi[3], float leaf, VoxelGeom* G, long long div[3], long long* ncell_out, int shift = 0) {
   if (!(leaf > 0)) return set_error(SSLAM_ERR_INVALID, "bad argument (leaf must be positive)");
   const float inv = 1.0f / leaf;
   if (!std::isfinite(inv)) return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid: 1 / leaf is not finite (leaf %g)", (double)leaf);
@@ -2978,16 +3118,16 @@ static int voxel_geometry(const float lo[3], const float hi[3], float leaf, Voxe
     if (!(fl >= -2147483648.0f && fl < 2147483648.0f && fh >= -2147483648.0f && fh < 2147483648.0f))
       return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid: the cell index of a bound (%g .. %g at leaf %g) does not fit 32 bits", (double)lo[k], (double)hi[k], (double)leaf);
     G->inv[k] = inv;
-    G->minb[k] = (int)fl;
-    div[k] = (long long)(int)fh - G->minb[k] + 1;
+    G->minb[k] = (int)fl >> shift;
+    div[k] = (long long)((int)fh >> shift) - G->minb[k] + 1;
     if (div[k] < 1) return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid: upper bound below the lower bound on axis %d", k);
   }
   for (int k = 0; k < 3; ++k) {
     if (div[k] > max_cells / ncell) too_many = true; else ncell *= div[k];
   }
   if (too_many)
-    return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid of %.0f cells: leaf size too small for the extent of the cloud (PCL refuses as well)",
-                     (double)div[0] * (double)div[1] * (double)div[2]);
+    return set_error(SSLAM_ERR_UNSUPPORTED, "voxel grid of %.0f %s: leaf size too small for the extent of the cloud (PCL refuses as well)",
+                     (double)div[0] * (double)div[1] * (double)div[2], shift ? "bricks" : "cells");
   *ncell_out = ncell;
   return 0;
 }
@@ -3042,6 +3182,170 @@ int sslam_seg_voxel_grid(sslam_seg* s, const float* xyz, int n, float leaf, floa
   }
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
   return nocc;
+}
+
+// ---- map cloud (the contract is at sslam_seg_map_cloud in include/sslam.h) -------------------------------------------------------------
+}  // extern "C"
+namespace sslam {
+int seg_map_cloud_device(sslam_seg* s, const MapCloudIn& in, float resolution, int min_points, float* xyz_out, int32_t* cells_out, int32_t* counts_out,
+                         int max_out, sslam_map_stats* stats) {
+  if (!s || in.n_clouds < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = map_cloud_check_args(resolution, min_points, xyz_out, max_out);
+  if (rc) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  if (in.n_clouds > (1 << 22)) return set_error(SSLAM_ERR_UNSUPPORTED, "map cloud: %d clouds, more than 2^22 (one launch row per cloud)", in.n_clouds);
+  if ((rc = seg_device(s))) return rc;
+  sslam_map_stats st;
+  std::memset(&st, 0, sizeof st);
+  const int nc = in.n_clouds;
+  st.n_clouds = nc;
+  int max_len = 0;
+  if (nc > 0) {
+    st.n_points = in.h_start[nc] - in.h_start[0];
+    for (int c = 0; c < nc; ++c) max_len = std::max(max_len, in.h_start[c + 1] - in.h_start[c]);
+  }
+  for (double& v : s->map_pass_ms) v = 0;
+  if (stats) *stats = st;
+  if (max_len == 0) return 0;
+  for (hipEvent_t& e : s->m_ev) if (!e) SSLAM_HIP_TRY(hipEventCreate(&e));
+  const MapIn M{in.d_xyz, in.d_start, in.d_pose};
+  const dim3 grid((unsigned)nc, (unsigned)std::min((max_len + 255) / 256, 8192)), block(256);
+  DevGuard g;
+  // pass 0: the box of the transformed points
+  int* d_box = nullptr;
+  if ((rc = g.alloc(&d_box, 8))) return rc;
+  int h_box[8] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0, 0};   // [6]: points used; [7]: voxels occupied before min_points
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_box, h_box, sizeof h_box, hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[0], s->stream));
+  const dim3 grid_box((unsigned)nc, std::min(grid.y, (unsigned)std::max(1, 2048 / nc)));
+  hipLaunchKernelGGL(k_map_minmax, grid_box, block, 0, s->stream, M, d_box);
+  SSLAM_HIP_TRY(hipGetLastError());
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[1], s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(h_box, d_box, 6 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  auto pass_ms = [&](int k) -> int {
+    float ms = 0.0f;
+    SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->m_ev[2 * k], s->m_ev[2 * k + 1]));
+    s->map_pass_ms[k] = (double)ms;
+    st.kernel_ms += (double)ms;
+    return 0;
+  };
+  if ((rc = pass_ms(0))) return rc;
+  if (stats) *stats = st;
+  if (h_box[0] > h_box[3]) return 0;   // no usable point
+  float lo[3], hi[3];
+  for (int k = 0; k < 3; ++k) {        // map_ordered is its own inverse
+    const int a = h_box[k] ^ ((h_box[k] >> 31) & 0x7fffffff), b = h_box[3 + k] ^ ((h_box[3 + k] >> 31) & 0x7fffffff);
+    std::memcpy(&lo[k], &a, 4); std::memcpy(&hi[k], &b, 4);
+  }
+  VoxelGeom G;
+  long long div[3], nbrick = 0;
+  if ((rc = voxel_geometry(lo, hi, resolution, &G, div, &nbrick, 3))) return rc;
+  G.mul[0] = 1; G.mul[1] = (int)div[0]; G.mul[2] = (int)(div[0] * div[1]);
+  // pass 1: the occupied bricks, their ascending list and the brick -> slot table
+  unsigned char* d_flag = nullptr; int *d_list = nullptr, *d_slot = nullptr, *d_blk = nullptr, *d_total = nullptr;
+  if ((rc = g.alloc(&d_flag, (size_t)nbrick)) || (rc = g.alloc(&d_list, (size_t)std::min<long long>(nbrick, st.n_points))) || (rc = g.alloc(&d_slot, (size_t)nbrick)) ||
+      (rc = g.alloc(&d_blk, (size_t)((nbrick + 255) / 256))) || (rc = g.alloc(&d_total, 1))) return rc;
+  SSLAM_HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)nbrick, s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[2], s->stream));
+  hipLaunchKernelGGL(k_map_flag_bricks, grid, block, 0, s->stream, M, G, d_flag);
+  int nocc = 0;
+  if ((rc = compact_if(s, BrickPred{d_flag, d_list, d_slot}, (int)nbrick, d_blk, d_total, nullptr, true))) return rc;
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[3], s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(&nocc, d_total, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if ((rc = pass_ms(1))) return rc;
+  if (nocc > (1 << 20))
+    return set_error(SSLAM_ERR_UNSUPPORTED, "map cloud: %d occupied bricks of 8 x 8 x 8 cells, more than 2^20: resolution %g is too fine for these clouds", nocc, (double)resolution);
+  st.n_bricks = nocc;
+  // pass 2: count and fixed-point sums of every voxel of the occupied bricks
+  const size_t nvox = (size_t)nocc * 512;
+  int* d_count = nullptr; long long* d_sums = nullptr;
+  if ((rc = g.alloc(&d_count, nvox)) || (rc = g.alloc(&d_sums, nvox * 3))) return rc;
+  SSLAM_HIP_TRY(hipMemsetAsync(d_count, 0, nvox * sizeof(int), s->stream));
+  SSLAM_HIP_TRY(hipMemsetAsync(d_sums, 0, nvox * 3 * sizeof(long long), s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[4], s->stream));
+  hipLaunchKernelGGL(k_map_accumulate, grid, block, 0, s->stream, M, G, d_slot, d_count, d_sums, d_box + 6);
+  SSLAM_HIP_TRY(hipGetLastError());
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[5], s->stream));
+  // pass 3: the voxels that pass min_points, in ascending slot * 512 + local, and their records
+  const int thr = std::max(min_points, 1);
+  const int cap_list = (int)std::min<size_t>(nvox, (size_t)std::min(max_out, st.n_points));
+  int *d_vox = nullptr, *d_vblk = nullptr;
+  if ((rc = g.alloc(&d_vox, (size_t)cap_list)) || (rc = g.alloc(&d_vblk, (nvox + 255) / 256))) return rc;
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[6], s->stream));
+  int total = 0;
+  if (thr > 1) {   // n_voxels counts before min_points; it is read with n_used at the end
+    hipLaunchKernelGGL(k_count_if<VoxelPred>, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, s->stream, VoxelPred{d_count, 1, nullptr, 0}, (int)nvox, d_vblk);
+    hipLaunchKernelGGL(k_exclusive_scan_wide, dim3(1), dim3(1024), 0, s->stream, d_vblk, (int)((nvox + 255) / 256), d_vblk, d_box + 7);
+  }
+  if ((rc = compact_if(s, VoxelPred{d_count, thr, d_vox, cap_list}, (int)nvox, d_vblk, d_total, &total, true))) return rc;
+  const int m = std::min(total, cap_list);
+  float* d_out = nullptr; int *d_cell = nullptr, *d_oc = nullptr;
+  if (m > 0) {
+    if ((rc = g.alloc(&d_out, (size_t)m * 3)) || (rc = g.alloc(&d_cell, (size_t)m * 3)) || (rc = g.alloc(&d_oc, (size_t)m))) return rc;
+    hipLaunchKernelGGL(k_map_emit, dim3((m + 255) / 256), dim3(256), 0, s->stream, d_vox, m, d_list, G, (int)div[0], (int)div[1], d_count, d_sums, d_out, d_cell, d_oc);
+    SSLAM_HIP_TRY(hipGetLastError());
+  }
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[7], s->stream));
+  int tail[2] = {0, 0};   // n_used, n_voxels: waited for below, and on an error return by the guard's hipFree before this frame ends
+  SSLAM_HIP_TRY(hipMemcpyAsync(tail, d_box + 6, sizeof tail, hipMemcpyDeviceToHost, s->stream));
+  if (m > 0) {
+    SSLAM_HIP_TRY(hipMemcpyAsync(xyz_out, d_out, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (cells_out) SSLAM_HIP_TRY(hipMemcpyAsync(cells_out, d_cell, (size_t)m * 3 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    if (counts_out) SSLAM_HIP_TRY(hipMemcpyAsync(counts_out, d_oc, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  }
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if ((rc = pass_ms(2)) || (rc = pass_ms(3))) return rc;
+  st.n_used = tail[0];
+  st.n_voxels = thr > 1 ? tail[1] : total;
+  if (stats) *stats = st;
+  return total;
+}
+int seg_device_index(const sslam_seg* s) { return s->P.device; }
+}  // namespace sslam
+extern "C" {
+
+int sslam_seg_map_cloud(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, float resolution, int min_points,
+                        float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out, sslam_map_stats* stats) {
+  if (!s || n_clouds < 0 || (n_clouds > 0 && (!cloud_start || !T))) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int n_points = 0;
+  if (n_clouds > 0) {
+    if (cloud_start[0] < 0) return set_error(SSLAM_ERR_INVALID, "cloud_start[0] is negative");
+    for (int c = 0; c < n_clouds; ++c)
+      if (cloud_start[c + 1] < cloud_start[c]) return set_error(SSLAM_ERR_INVALID, "cloud_start decreases at cloud %d", c);
+    n_points = cloud_start[n_clouds];   // rows of xyz that are read; those below cloud_start[0] belong to no cloud
+    if (n_points > 0 && !xyz) return set_error(SSLAM_ERR_INVALID, "null xyz");
+    for (size_t k = 0; k < 12 * (size_t)n_clouds; ++k)
+      if (!std::isfinite(T[k])) return set_error(SSLAM_ERR_INVALID, "map cloud: entry %d of the pose of cloud %d is not finite", (int)(k % 12), (int)(k / 12));
+  }
+  MapCloudIn in{nullptr, nullptr, nullptr, cloud_start, n_clouds};
+  if (n_points == 0) return seg_map_cloud_device(s, in, resolution, min_points, xyz_out, cells_out, counts_out, max_out, stats);   // the checks, then 0
+  // the argument checks of the device entry come before anything is staged
+  int rc = map_cloud_check_args(resolution, min_points, xyz_out, max_out);
+  if (rc) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  if ((rc = seg_device(s))) return rc;
+  DevGuard g;
+  float *d_xyz = nullptr, *d_pose = nullptr; int* d_start = nullptr;
+  if ((rc = g.alloc(&d_xyz, (size_t)n_points * 3)) || (rc = g.alloc(&d_pose, (size_t)n_clouds * 12)) || (rc = g.alloc(&d_start, (size_t)n_clouds + 1))) return rc;
+  std::vector<float> pose(12 * (size_t)n_clouds);
+  for (size_t k = 0; k < pose.size(); ++k) pose[k] = (float)T[k];
+  const size_t bytes[3] = {(size_t)n_points * 3 * sizeof(float), pose.size() * sizeof(float), ((size_t)n_clouds + 1) * sizeof(int32_t)};
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_xyz, xyz, bytes[0], hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_pose, pose.data(), bytes[1], hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_start, cloud_start, bytes[2], hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  in.d_xyz = d_xyz; in.d_start = d_start; in.d_pose = d_pose;
+  rc = seg_map_cloud_device(s, in, resolution, min_points, xyz_out, cells_out, counts_out, max_out, stats);
+  if (stats) stats->upload_bytes = (int64_t)(bytes[0] + bytes[1] + bytes[2]);
+  return rc;
+}
+
+int sslam_seg_last_map_timing(const sslam_seg* s, double ms[4]) {
+  if (!s || !ms) return set_error(SSLAM_ERR_INVALID, "null argument");
+  for (int k = 0; k < 4; ++k) ms[k] = s->map_pass_ms[k];
+  return 0;
 }
 
 int sslam_seg_statistical_outlier_removal(sslam_seg* s, const float* xyz, int n, int mean_k, double stddev_mul, int32_t* keep_out, int max_out,

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/sslam.h"
+#include "map_cloud.hpp"
 #include "sslam_common.hpp"
 #include "sslam_math.hpp"
 
@@ -344,6 +345,7 @@ struct KeyFrame {
   bool presegmented = false;
   std::vector<float> ds;                  // loop closure: the downsampled cloud (xyz), kept for the rest of the run
   bool has_ds = false;
+  bool map_done = false;                  // map clouds: this keyframe's cloud has been looked at (appended, or found empty)
 };
 
 template <class T>
@@ -362,7 +364,8 @@ struct DevBuf {
     p = q; cap = nc;
     return 0;
   }
-  ~DevBuf() { if (p) (void)hipFree(p); }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  ~DevBuf() { release(); }
 };
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -414,6 +417,14 @@ struct sslam_slam {
   double loop_seconds[4] = {0, 0, 0, 0};  // candidates, registration, gate, the whole stage (downsampling included) of the last run()
   DevBuf<double> d_ltab;                  // [keys 3 n_keys | news 3 n_new]
   DevBuf<int32_t> d_lout;                 // [cand n_new x cap | count n_new]
+  // sslam_slam_set_map_clouds: the downsampled cloud of every keyframe, resident on the device for sslam_slam_map_cloud
+  bool map_on = false;
+  float map_leaf = 0.1f;
+  DevBuf<float> d_map_xyz, d_map_pose;    // the clouds one after the other; 12 floats per cloud, rewritten by every map call
+  DevBuf<int32_t> d_map_start;            // cloud_start of the resident clouds
+  std::vector<int32_t> map_start{0};      // its host copy
+  std::vector<std::shared_ptr<KeyFrame>> map_kf;   // the keyframe of every resident cloud, in keyframe order
+  int64_t map_pending_bytes = 0;          // cloud bytes sent since the last sslam_slam_map_cloud
   ~sslam_slam() {
     if (graph) sslam_graph_destroy(graph);
     if (stream) { (void)hipSetDevice(P.device); (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
@@ -837,6 +848,53 @@ int downsample_new_keyframes(sslam_slam* s) {
   return 0;
 }
 
+// map clouds: the downsampled cloud of every new keyframe that carries one goes to the device ONCE, behind the clouds already there;
+// before the association loop, which drops the raw clouds.  The boundary of a new cloud is written by a device fill: only points travel.
+int keep_map_clouds(sslam_slam* s) {
+  for (auto& kf : s->new_keyframes) {
+    if (kf->cloud.empty() || kf->map_done) continue;
+    std::vector<float> own;
+    const bool share = s->loop_on && kf->has_ds && s->loop_P.voxel_leaf == s->map_leaf;   // equal leaves: the same cloud
+    int rc;
+    if (!share && (rc = downsampled_cloud(s, *kf, s->map_leaf, own)) < 0) return rc;
+    const std::vector<float>& ds = share ? kf->ds : own;
+    kf->map_done = true;
+    if (ds.empty()) continue;
+    if ((rc = ensure_stream(s))) return rc;
+    SSLAM_HIP_TRY(hipSetDevice(s->P.device));
+    const size_t have = 3 * (size_t)s->map_start.back(), n_cl = s->map_kf.size();
+    if (have / 3 + ds.size() / 3 > (size_t)INT32_MAX) return set_error(SSLAM_ERR_UNSUPPORTED, "map clouds: more than 2^31 - 1 points kept");
+    if ((rc = s->d_map_xyz.reserve(have + ds.size(), s->stream, have))) return rc;
+    if ((rc = s->d_map_start.reserve(n_cl + 2, s->stream, n_cl + 1))) return rc;
+    const int32_t end = (int32_t)((have + ds.size()) / 3);
+    SSLAM_HIP_TRY(hipMemcpyAsync(s->d_map_xyz.p + have, ds.data(), ds.size() * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    if (n_cl == 0) SSLAM_HIP_TRY(hipMemsetAsync(s->d_map_start.p, 0, sizeof(int32_t), s->stream));
+    SSLAM_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(s->d_map_start.p + n_cl + 1), end, 1, s->stream));
+    SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+    s->map_start.push_back(end);
+    s->map_kf.push_back(kf);
+    s->map_pending_bytes += (int64_t)(ds.size() * sizeof(float));
+  }
+  return 0;
+}
+
+// The resident clouds are allocated on the orchestrator's device and read by the frontend's kernels on the frontend's: one device, or no map.
+int map_same_device(const sslam_slam* s) {
+  const int d = seg_device_index(s->seg);
+  if (d == s->P.device) return 0;
+  return set_error(SSLAM_ERR_UNSUPPORTED, "map clouds: the orchestrator runs on device %d and its frontend handle on device %d; the kept clouds are read by "
+                   "the frontend's kernels, so both must be the same device", s->P.device, d);
+}
+
+void drop_map_clouds(sslam_slam* s) {
+  s->d_map_xyz.release(); s->d_map_pose.release(); s->d_map_start.release();
+  s->map_start.assign(1, 0);
+  s->map_kf.clear();
+  s->map_pending_bytes = 0;
+  for (auto* list : {&s->keyframes, &s->new_keyframes})
+    for (auto& kf : *list) kf->map_done = false;
+}
+
 // steps 1 - 7 of sslam_slam_set_loop_closure (include/sslam.h)
 int close_loops(sslam_slam* s) {
   const sslam_loop_params& P = s->loop_P;
@@ -1097,7 +1155,7 @@ int sslam_slam_vio(sslam_slam* s, int32_t sec, int32_t nsec, const double odom_t
       for (int k = 0; k < 3; ++k) kf->off[k] = s->latest.off[k];
     }
   }
-  if ((s->fit_on || s->loop_on) && fresh_cloud && kf->cloud.empty() && !s->latest.cloud.empty()) {   // the fitness model and loop closure read the cloud of a keyframe without boxes too
+  if ((s->fit_on || s->loop_on || s->map_on) && fresh_cloud && kf->cloud.empty() && !s->latest.cloud.empty()) {   // the fitness model, loop closure and the map clouds read the cloud of a keyframe without boxes too
     kf->cloud = s->latest.cloud;
     kf->width = s->latest.width; kf->height = s->latest.height; kf->point_step = s->latest.point_step; kf->row_step = s->latest.row_step;
     for (int k = 0; k < 3; ++k) kf->off[k] = s->latest.off[k];
@@ -1133,6 +1191,10 @@ int sslam_slam_run(sslam_slam* s, sslam_tick_stats* st) {
     s->loop_seconds[3] = now_s() - t_loop;
     t0 = now_s();
   }
+  if (s->map_on) {
+    if ((rc = keep_map_clouds(s)) < 0) return fail(rc);
+    t0 = now_s();
+  }
   if ((rc = segment_new_keyframes(s)) < 0) return fail(rc);
   st->seconds_frontend = now_s() - t0;
   t0 = now_s();
@@ -1154,7 +1216,7 @@ int sslam_slam_run(sslam_slam* s, sslam_tick_stats* st) {
     if (rc < 0) return fail(rc);
   }
   for (auto& kf : s->new_keyframes) {
-    if (s->fit_on || s->loop_on) { kf->cloud.clear(); kf->cloud.shrink_to_fit(); }   // only downsampled clouds are kept
+    if (s->fit_on || s->loop_on || s->map_on) { kf->cloud.clear(); kf->cloud.shrink_to_fit(); }   // only downsampled clouds are kept
     s->keyframes.push_back(kf);
   }
   s->new_keyframes.clear();
@@ -1268,6 +1330,69 @@ int sslam_slam_last_loop_timing(const sslam_slam* s, double seconds[4]) {
   if (!s || !seconds) return set_error(SSLAM_ERR_INVALID, "null argument");
   for (int k = 0; k < 4; ++k) seconds[k] = s->loop_seconds[k];
   return 0;
+}
+
+int sslam_slam_set_map_clouds(sslam_slam* s, int on, float keyframe_leaf) {
+  if (!s || !std::isfinite(keyframe_leaf) || keyframe_leaf < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  if (on && !s->seg) return set_error(SSLAM_ERR_INVALID, "map clouds need the frontend handle: none was given to sslam_slam_create");
+  int rc;
+  if (on && (rc = map_same_device(s))) return rc;
+  s->map_on = on != 0;
+  s->map_leaf = keyframe_leaf == 0 ? 0.1f : keyframe_leaf;
+  if (!s->map_on) drop_map_clouds(s);
+  return 0;
+}
+
+int sslam_slam_map_clouds_kept(const sslam_slam* s, int32_t* n_points) {
+  if (!s) return set_error(SSLAM_ERR_INVALID, "null handle");
+  if (n_points) *n_points = s->map_start.back();
+  return (int)s->map_kf.size();
+}
+
+int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points, float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out,
+                         int32_t* vertex_out, double* poses_out, int max_clouds, sslam_map_stats* stats) {
+  if (!s || max_clouds < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = map_cloud_check_args(resolution, min_points, xyz_out, max_out);
+  if (rc) return rc;
+  if (stats) std::memset(stats, 0, sizeof *stats);
+  const int n = (int)s->map_kf.size();
+  if (!s->map_on || n == 0) return 0;   // nothing is kept
+  if ((rc = map_same_device(s))) return rc;
+  std::vector<float> pose(12 * (size_t)n);
+  for (int c = 0; c < n; ++c) {   // the current estimate of every cloud's keyframe, quaternion normalised, R by qmat as in the loop stage
+    const KeyFrame& kf = *s->map_kf[c];
+    double tq[7], T[12];
+    if (sslam_graph_get_vertex(s->graph, kf.node, tq) < 0) return SSLAM_ERR_INVALID;
+    const Pose est = from_tq(tq);
+    const Mat3 R = qmat(est.q);
+    for (int k = 0; k < 9; ++k) T[k] = R.m[k];
+    T[9] = est.t.x; T[10] = est.t.y; T[11] = est.t.z;
+    for (int k = 0; k < 12; ++k) {
+      if (!std::isfinite(T[k])) return set_error(SSLAM_ERR_INVALID, "map cloud: the estimate of vertex %d is not finite", kf.node);
+      pose[12 * (size_t)c + k] = (float)T[k];
+    }
+    if (c < max_clouds) {
+      if (vertex_out) vertex_out[c] = kf.node;
+      if (poses_out) std::memcpy(poses_out + 12 * (size_t)c, T, sizeof T);
+    }
+  }
+  MapCloudIn in{nullptr, nullptr, nullptr, s->map_start.data(), n};
+  if ((rc = ensure_stream(s))) return rc;
+  SSLAM_HIP_TRY(hipSetDevice(s->P.device));
+  if ((rc = s->d_map_pose.reserve(pose.size(), s->stream, 0))) return rc;
+  const size_t bytes = pose.size() * sizeof(float);
+  std::vector<char> fallback;
+  char* stage = s->pin.get(bytes);
+  if (!stage) { fallback.resize(bytes); stage = fallback.data(); }
+  std::memcpy(stage, pose.data(), bytes);
+  SSLAM_HIP_TRY(hipMemcpyAsync(s->d_map_pose.p, stage, bytes, hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  in.d_xyz = s->d_map_xyz.p; in.d_start = s->d_map_start.p; in.d_pose = s->d_map_pose.p;
+  const int64_t sent = s->map_pending_bytes + (int64_t)bytes;
+  rc = seg_map_cloud_device(s->seg, in, resolution, min_points, xyz_out, cells_out, counts_out, max_out, stats);
+  if (rc >= 0) s->map_pending_bytes = 0;
+  if (stats) stats->upload_bytes = sent;
+  return rc;
 }
 
 int sslam_slam_loop_candidates(sslam_slam* s, const double* keys, int n_keys, const double* news, int n_new, const sslam_loop_params* p,

@@ -13,7 +13,7 @@ from typing import List, Sequence
 
 import numpy as np
 
-from ._lib import load_library
+from ._lib import load_library, MapStats
 from . import synth
 
 CLASS_NAMES = ["other", "chair", "tvmonitor", "book", "keyboard", "laptop", "bucket", "car"]  # point_cloud_segmentation.h:126-130
@@ -151,7 +151,7 @@ def _bind(lib):
     lib.sslam_seg_icp_boxes.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, ci, C.POINTER(C.c_double)]
     lib.sslam_seg_icp_point_to_plane.restype = ci
     lib.sslam_seg_icp_point_to_plane.argtypes = [vp, vp, vp, ci, vp, ci, ci, vp, vp, C.POINTER(C.c_double)]
-    # sslam_seg_fitness_scores, sslam_inf_default_params, sslam_information_from_fitness: declared in _lib.load_library
+    # sslam_seg_fitness_scores, sslam_inf_default_params, sslam_information_from_fitness, sslam_seg_map_cloud: declared in _lib.load_library
     _BOUND = True
 
 
@@ -543,6 +543,40 @@ class PointCloudSegmentation:
             return out
         cuts = np.cumsum(n_src)[:-1] if n_src else []
         return out, list(zip(np.split(idx[:sum(n_src)], cuts), np.split(d2[:sum(n_src)], cuts)))
+
+    def map_cloud(self, clouds, poses, resolution: float, min_points: int = 1, return_cells: bool = False, max_out: int | None = None):
+        """``sslam_seg_map_cloud``: every cloud at its pose, reduced to one centroid per occupied voxel of a sparse grid (hdl_graph_slam's
+        MapCloudGenerator::generate).  ``clouds``: a sequence of [n, 3] float arrays.  ``poses``: per cloud 12 doubles (R row-major, then
+        t) or a 4x4 / 3x4 matrix taking the cloud into the map frame.  Returns (xyz [m, 3] float32, counts [m] int32[, cells [m, 3] int32],
+        ``MapStats``) in the order the header states; ``max_out`` (default: room for every voxel) caps the records written, the true voxel
+        count is left in ``last_map_count``."""
+        cl = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in clouds]
+        start = np.zeros(len(cl) + 1, np.int32)
+        start[1:] = np.cumsum([len(c) for c in cl])
+        xyz = np.ascontiguousarray(np.concatenate(cl, 0)) if cl else np.zeros((0, 3), np.float32)
+        T = np.zeros((max(len(cl), 1), 12))
+        if len(poses) != len(cl):
+            raise ValueError(f"{len(cl)} clouds but {len(poses)} poses")
+        for k, P in enumerate(poses):
+            P = np.asarray(P, np.float64)
+            if P.shape in ((4, 4), (3, 4)):
+                P = np.concatenate([P[:3, :3].reshape(-1), P[:3, 3]])
+            T[k] = P.reshape(12)
+        cap = len(xyz) if max_out is None else int(max_out)
+        out = np.zeros((max(cap, 1), 3), np.float32); cnt = np.zeros(max(cap, 1), np.int32); cells = np.zeros((max(cap, 1), 3), np.int32)
+        st = MapStats()
+        m = self._check(self._lib.sslam_seg_map_cloud(self._h, xyz.ctypes.data if len(xyz) else None, start.ctypes.data, len(cl), T.ctypes.data,
+                                                      C.c_float(resolution), int(min_points), out.ctypes.data if cap > 0 else None,
+                                                      cells.ctypes.data, cnt.ctypes.data, cap, C.byref(st)))
+        self.last_map_count = m
+        m = min(m, cap)
+        return (out[:m], cnt[:m], cells[:m], st) if return_cells else (out[:m], cnt[:m], st)
+
+    def last_map_timing(self) -> np.ndarray:
+        """hipEvent milliseconds of the four passes of the last map cloud: min / max, bricks, accumulate, voxels + records"""
+        out = np.zeros(4)
+        self._check(self._lib.sslam_seg_last_map_timing(self._h, out.ctypes.data))
+        return out
 
     def compute2DConvexHull(self, xyz, seed: int = 0):
         """plane_segmentation::compute2DConvexHull (plane_segmentation.cpp:631-665): RANSAC plane (threshold 0.01, refined

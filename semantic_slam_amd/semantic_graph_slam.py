@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import numpy as np
 
-from ._lib import load_library, OptStats
+from ._lib import load_library, MapStats, OptStats
 from .graph_slam import SslamError, _pose7
 from .segmentation import DBL_MAX, InfParams, Plane, PointCloudSegmentation, default_inf_params
 
@@ -75,7 +75,7 @@ def _bind(lib):
     lib.sslam_slam_keyframes.restype = ci; lib.sslam_slam_keyframes.argtypes = [vp, vp, vp, ci]
     lib.sslam_slam_graph.restype = vp; lib.sslam_slam_graph.argtypes = [vp]
     lib.sslam_slam_find_matches.restype = ci; lib.sslam_slam_find_matches.argtypes = [vp, vp, ci, vp, vp]
-    # sslam_slam_set_fitness_information, sslam_slam_last_fitness: declared in _lib.load_library
+    # sslam_slam_set_fitness_information, sslam_slam_last_fitness, sslam_slam_set_map_clouds, sslam_slam_map_cloud: declared in _lib.load_library
     lib.sslam_loop_default_params.restype = None; lib.sslam_loop_default_params.argtypes = [C.POINTER(LoopParams)]
     lib.sslam_slam_set_loop_closure.restype = ci; lib.sslam_slam_set_loop_closure.argtypes = [vp, C.POINTER(LoopParams)]
     lib.sslam_slam_last_loops.restype = ci; lib.sslam_slam_last_loops.argtypes = [vp, vp, ci]
@@ -193,6 +193,26 @@ class SemanticGraphSLAM:
         out = np.zeros(4)
         self._check(self._lib.sslam_slam_last_loop_timing(self._h, out.ctypes.data))
         return out
+
+    def set_map_clouds(self, on: bool = True, keyframe_leaf: float = 0.1) -> None:
+        """``sslam_slam_set_map_clouds``: the following ticks keep the downsampled cloud (``keyframe_leaf``) of every keyframe on the
+        device for :meth:`map_cloud`; ``on=False`` drops what was kept.  Needs the frontend handle given to the constructor."""
+        self._check(self._lib.sslam_slam_set_map_clouds(self._h, int(bool(on)), C.c_float(keyframe_leaf)))
+
+    def map_cloud(self, resolution: float, min_points: int = 1):
+        """``sslam_slam_map_cloud``: the kept keyframe clouds at their current estimates, one centroid per occupied voxel.  Returns
+        (xyz [m, 3] float32, counts [m] int32, cells [m, 3] int32, vertex_ids [c] int32, poses [c, 12] float64, ``MapStats``); the poses
+        (R row-major, then t) are what the map was built from."""
+        st = MapStats()
+        npts = C.c_int32(0)
+        nc = self._check(self._lib.sslam_slam_map_clouds_kept(self._h, C.byref(npts)))
+        cap = npts.value                                               # a voxel holds at least one point
+        xyz = np.zeros((max(cap, 1), 3), np.float32); cnt = np.zeros(max(cap, 1), np.int32); cells = np.zeros((max(cap, 1), 3), np.int32)
+        ids = np.zeros(max(nc, 1), np.int32); poses = np.zeros((max(nc, 1), 12))
+        m = self._check(self._lib.sslam_slam_map_cloud(self._h, C.c_float(resolution), int(min_points), xyz.ctypes.data, cells.ctypes.data,
+                                                       cnt.ctypes.data, cap, ids.ctypes.data, poses.ctypes.data, nc, C.byref(st)))
+        nc = min(nc, st.n_clouds)                                      # 0 with map clouds off
+        return xyz[:m].copy(), cnt[:m].copy(), cells[:m].copy(), ids[:nc], poses[:nc], st
 
     def loop_candidates(self, keys, news, params: LoopParams | None = None, cap: int | None = None):
         """``sslam_slam_loop_candidates`` (k_loop_candidates on its own).  ``keys`` / ``news``: [n, 3] float64 rows of x, y, accum_distance of
