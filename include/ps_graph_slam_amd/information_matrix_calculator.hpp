@@ -87,6 +87,7 @@ class InformationMatrixCalculator {
  private:
   friend class ScanMatcher;         // scan_matcher.hpp: the same cloud and pose types, the same handle
   friend class MapCloudGenerator;   // map_cloud_generator.hpp: likewise
+  friend class OccupancyMapGenerator;   // occupancy_map_generator.hpp: likewise
   struct Handle {
     sslam_seg* s;
     Handle() : s(sslam_seg_create(nullptr)) {}

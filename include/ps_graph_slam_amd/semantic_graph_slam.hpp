@@ -17,6 +17,7 @@
 
 #include "../sslam.h"
 #include "graph_slam.hpp"
+#include "occupancy_map_generator.hpp"
 
 class semantic_graph_slam {
  public:
@@ -107,6 +108,18 @@ class semantic_graph_slam {
     const int m = check(sslam_slam_map_cloud(h_, resolution, min_points, M.xyz.data(), M.cells.data(), M.counts.data(), n_points, M.vertices.data(),
                                              M.poses.data(), n_clouds, &M.stats), "sslam_slam_map_cloud");
     M.xyz.resize(3 * (size_t)m); M.cells.resize(3 * (size_t)m); M.counts.resize((size_t)m);
+    return M;
+  }
+
+  // the occupancy map of the run (sslam_slam_occupancy_map; where the reference's launch file runs octomap_server): the clouds set_map_clouds
+  // keeps, at the current estimates, ray-cast into the sparse grid.  Empty with map clouds off or none kept.
+  ps_graph_slam::OccupancyMap occupancy_map(const sslam_occ_params& params) {
+    ps_graph_slam::OccupancyMap M;
+    M.params = params;
+    const int cap = check(sslam_slam_occupancy_map(h_, &params, nullptr, nullptr, nullptr, nullptr, 0, nullptr), "sslam_slam_occupancy_map");   // count, then fetch
+    M.resize((size_t)cap);
+    const int m = check(sslam_slam_occupancy_map(h_, &params, M.cells.data(), M.hits.data(), M.misses.data(), M.logodds.data(), cap, &M.stats), "sslam_slam_occupancy_map");
+    M.resize((size_t)(m < cap ? m : cap));
     return M;
   }
 

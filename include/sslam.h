@@ -695,6 +695,73 @@ int sslam_seg_map_cloud(sslam_seg* s, const float* xyz, const int32_t* cloud_sta
                         sslam_map_stats* stats);
 int sslam_seg_last_map_timing(const sslam_seg* s, double ms[4]);
 
+/* ---- occupancy map: every cloud at its pose, every point a ray from the sensor, free / occupied / unknown per cell of the SPARSE grid of
+ * sslam_seg_map_cloud.  The reference's demo output: its README launch runs octomap_server (resolution 0.05, sensor_model/max_range 10,
+ * pointcloud_min_z -1, pointcloud_max_z 5) on the clouds and poses the SLAM node publishes; sslam_occ_default_params holds those values and
+ * OctoMap's sensor model [UPSTREAM, quoted from memory]: hit 0.7, miss 0.4, clamp 0.1192 .. 0.971, occupancy threshold 0.5, each
+ * probability turned into log-odds log(p / (1 - p)) on the host in double and cast to float.  The kernels only see the float log-odds.
+ * cloud_start, T, the cast of T to float, the transform x' = ((r00 x + r01 y) + r02 z) + tx without fused multiply-add and the rule for
+ * non-finite rows are those of sslam_seg_map_cloud.  The ray origin of a cloud is T applied to sensor_origin in the same arithmetic; a cloud
+ * whose ray origin is not finite takes no part.  A ray whose end point has z' outside [z_min, z_max] takes no part (n_clipped_z).
+ * The traversal is exact, in integers.  inv = 1.0f / resolution.
+ *   position of a coordinate p: u = p * inv (float), c = (int)floorf(u) -- the cell rule of the map cloud --, f = u - floorf(u),
+ *     q = min((int)(f * 1024.0f), 1023) (f rounds to 1 for a tiny negative u), Q = (int64)c * 1024 + q: an integer in 1/1024 cell.
+ *     Qo of the ray origin, Qe of the end point.  |u| must stay below 2^19 cells on every axis for every ray that takes part:
+ *     otherwise SSLAM_ERR_UNSUPPORTED (it keeps |D|^2 below 2^63).
+ *   range: D = Qe - Qo, len2 = |D|^2 in int64, R = (int64)floor((double)max_range * (double)inv * 1024.0), 1 <= R <= 2^20.  When
+ *     len2 > R^2 the ray is TRUNCATED: L = the smallest integer with L^2 >= len2 (a double square root corrected by integer checks),
+ *     D_a = (D_a * R) / L in C integer division, Qe = Qo + D.  Cell = Q >> 10, q = Q & 1023.
+ *   steps: n_a = |ce_a - co_a| per axis; the ray makes exactly n_x + n_y + n_z steps of one cell along one axis.  Per axis the numerator
+ *     of the parameter of the next face: 1024 - qo_a when D_a > 0, qo_a when D_a < 0, + 1024 per step on that axis.  The next step is on
+ *     the axis, among those with steps left, with the smallest num_a / |D_a|, compared by cross-multiplication in int64; an exact tie goes
+ *     to the lowest axis.  (Only axes with steps left: the walk arrives at the end cell also when a ray going down ends on a face.)
+ *   counts: the start cell and every cell stepped into except the last get one miss; the last cell one hit, or one miss when the ray was
+ *     truncated (also when it has no step at all).  An untruncated ray of zero steps is one hit on its cell.
+ *   log-odds of a cell: t = (float)hits * l_hit + (float)misses * l_miss, both products and the sum rounded to float (no contraction),
+ *     then fminf(fmaxf(t, l_min), l_max).  A cell is occupied when that is >= l_occ.
+ * DEVIATIONS from OctoMap [UPSTREAM, quoted from memory]: (1) per-ray integration as in insertPointCloudRays, not the per-scan
+ * de-duplication of insertPointCloud (a cell once per scan, a hit overriding a miss); (2) the clamp is applied once, to the sum, not after
+ * every update: the result is independent of the order of clouds and points and of the launch geometry, and equals OctoMap's whenever
+ * no intermediate value reaches a clamp; (3) the product is a flat list of cells at one resolution, not an octree.
+ * Passes (integer atomics only; the launch geometry, the 8 x 8 x 8 bricks and both limits -- 2^26 bricks in the box, 2^20 touched bricks,
+ * SSLAM_ERR_UNSUPPORTED before anything is written -- are the map cloud's): 0. the box of the start and end cells and the ray counters;
+ * 1. every ray is walked and the bricks it enters are flagged, then compacted; 2. every ray is walked again: one int32 atomic add per cell
+ * into misses[slot * 512 + local] or hits[...] (8 bytes per cell of a touched brick); 3. the known cells (hits + misses > 0) that pass
+ * `emit` are compacted and written.  Output order: that of the map cloud, bricks ascending with x fastest, then the local index.
+ * cells_out (3 per record), hits_out, misses_out, logodds_out, stats: each optional.  Returns the number of records that pass `emit` -- the
+ * true count; at most max_out are written -- and 0 for no clouds or no ray.
+ * SSLAM_ERR_INVALID: a NULL handle or params; cloud_start or T NULL with clouds; xyz NULL with points; negative n_clouds or max_out; a
+ * cloud_start that decreases or starts below 0; a non-finite entry of T or sensor_origin; resolution or max_range not finite and positive
+ * (or 1 / resolution not finite); R outside 1 .. 2^20; l_hit not > 0, l_miss not < 0; l_min > l_max, z_min > z_max, or a NaN among them or
+ * in l_occ; emit outside 0 .. 2; a batch in flight.  SSLAM_ERR_UNSUPPORTED also for more than 2^22 clouds.  SSLAM_ERR_NO_DEVICE without a GPU. */
+typedef struct sslam_occ_params {
+  float resolution;          /* cell edge, m */
+  float max_range;           /* m; rays longer than this are cut there and end in a miss */
+  float z_min, z_max;        /* a ray whose transformed end point has z' outside [z_min, z_max] takes no part */
+  float sensor_origin[3];    /* in the cloud frame; the ray origin is T applied to it */
+  float l_hit, l_miss;       /* log-odds added per hit (> 0) and per miss (< 0) */
+  float l_min, l_max;        /* clamp of the sum */
+  float l_occ;               /* a cell is occupied when its log-odds >= l_occ */
+  int32_t emit;              /* 0 every known cell, 1 occupied only, 2 free only */
+} sslam_occ_params;
+typedef struct sslam_occ_stats {
+  int32_t n_clouds, n_points;      /* given; n_points counts every row, finite or not */
+  int32_t n_rays;                  /* rays that took part, the truncated ones included */
+  int32_t n_truncated, n_clipped_z;
+  int32_t n_bricks, n_cells;       /* touched bricks; known cells BEFORE emit */
+  int32_t reserved;
+  int64_t n_steps;                 /* cells visited, the start and end cells included: the sum of all hits and misses, the atomics of pass 2 */
+  int64_t upload_bytes;            /* host -> device bytes this call moved */
+  double  kernel_ms;               /* hipEvent time of the four passes, copies excluded */
+} sslam_occ_stats;
+void sslam_occ_default_params(sslam_occ_params* p);
+int sslam_seg_occupancy_map(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds,
+                            const double* T /* 12 per cloud: R row-major, then t; cloud -> map frame */, const sslam_occ_params* p,
+                            int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out, int max_out,
+                            sslam_occ_stats* stats);
+/* hipEvent milliseconds of the four passes of the last call: box, bricks, accumulate, cells + records */
+int sslam_seg_last_occupancy_timing(const sslam_seg* s, double ms[4]);
+
 /* parity hooks: per-box products of the last sslam_seg_segment call.
  * normals: w*h*4 floats (nx,ny,nz,curvature), labels: w*h int32 (-1 = no plane; otherwise the
  * region index in output order of pcl::OrganizedMultiPlaneSegmentation::segmentAndRefine). */
@@ -897,6 +964,12 @@ int sslam_slam_map_clouds_kept(const sslam_slam* s, int32_t* n_points);
 int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points,
                          float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out,
                          int32_t* vertex_out, double* poses_out, int max_clouds, sslam_map_stats* stats);
+/* sslam_seg_occupancy_map (params, the outputs, the order and the limits as stated there) over the same kept clouds at the same poses as
+ * sslam_slam_map_cloud -- where the reference's launch file runs octomap_server.  Only the poses travel: stats->upload_bytes is 48 bytes per
+ * keyframe plus the bytes of the clouds appended since the last map or occupancy call.  Returns the record count; 0 with map clouds off or
+ * none kept.  Errors: those of sslam_seg_occupancy_map and of sslam_slam_map_cloud. */
+int sslam_slam_occupancy_map(sslam_slam* s, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out,
+                             float* logodds_out, int max_out, sslam_occ_stats* stats);
 /* setPointCloudData (semantic_graph_slam.cpp:341-345): the cloud is copied */
 int sslam_slam_set_point_cloud(sslam_slam* s, const uint8_t* cloud, int width, int height, int point_step, int row_step,
                                int off_x, int off_y, int off_z);

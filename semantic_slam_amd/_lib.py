@@ -47,6 +47,24 @@ class MapStats(C.Structure):
                 f"n_voxels={self.n_voxels}, upload_bytes={self.upload_bytes}, kernel_ms={self.kernel_ms:.4f})")
 
 
+class OccParams(C.Structure):
+    """``sslam_occ_params`` (include/sslam.h); ``sslam_occ_default_params`` fills it"""
+    _fields_ = [("resolution", C.c_float), ("max_range", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("sensor_origin", C.c_float * 3),
+                ("l_hit", C.c_float), ("l_miss", C.c_float), ("l_min", C.c_float), ("l_max", C.c_float), ("l_occ", C.c_float), ("emit", C.c_int32)]
+
+
+class OccStats(C.Structure):
+    """``sslam_occ_stats`` (include/sslam.h)"""
+    _fields_ = [("n_clouds", C.c_int32), ("n_points", C.c_int32), ("n_rays", C.c_int32), ("n_truncated", C.c_int32), ("n_clipped_z", C.c_int32),
+                ("n_bricks", C.c_int32), ("n_cells", C.c_int32), ("reserved", C.c_int32), ("n_steps", C.c_int64), ("upload_bytes", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+    def __repr__(self):
+        return (f"OccStats(n_clouds={self.n_clouds}, n_points={self.n_points}, n_rays={self.n_rays}, n_truncated={self.n_truncated}, "
+                f"n_clipped_z={self.n_clipped_z}, n_bricks={self.n_bricks}, n_cells={self.n_cells}, n_steps={self.n_steps}, "
+                f"upload_bytes={self.upload_bytes}, kernel_ms={self.kernel_ms:.4f})")
+
+
 def load_library():
     global _LIB
     if _LIB is not None:
@@ -127,6 +145,10 @@ def load_library():
         "sslam_slam_set_map_clouds": (ci, [vp, ci, C.c_float]),
         "sslam_slam_map_clouds_kept": (ci, [vp, C.POINTER(C.c_int32)]),
         "sslam_slam_map_cloud": (ci, [vp, C.c_float, ci, vp, vp, vp, ci, vp, vp, ci, C.POINTER(MapStats)]),
+        "sslam_occ_default_params": (None, [C.POINTER(OccParams)]),
+        "sslam_seg_occupancy_map": (ci, [vp, vp, vp, ci, vp, C.POINTER(OccParams), vp, vp, vp, vp, ci, C.POINTER(OccStats)]),
+        "sslam_seg_last_occupancy_timing": (ci, [vp, vp]),
+        "sslam_slam_occupancy_map": (ci, [vp, C.POINTER(OccParams), vp, vp, vp, vp, ci, C.POINTER(OccStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design

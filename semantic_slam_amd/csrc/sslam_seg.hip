@@ -24,6 +24,7 @@
 
 #include "../../include/sslam.h"
 #include "map_cloud.hpp"
+#include "occupancy_map.hpp"
 #include "sslam_common.hpp"
 #include "sslam_math.hpp"
 
@@ -1977,6 +1978,203 @@ __global__ __launch_bounds__(256) void k_map_emit(const int* __restrict__ voxels
   out_cell[3 * (size_t)k] = bx * 8 + (l & 7); out_cell[3 * (size_t)k + 1] = by * 8 + ((l >> 3) & 7); out_cell[3 * (size_t)k + 2] = bz * 8 + (l >> 6);
   out_count[k] = n;
 }
+// ---- occupancy map: every point of the map cloud's input is the end of a ray from its cloud's sensor origin (sslam_seg_occupancy_map in
+// include/sslam.h states the traversal; octomap_server in the reference's launch [UPSTREAM]) ---------------------------------------------
+// Launch geometry, MapIn and map_point are the map cloud's.  The ray origin is uniform in the workgroup; each pass sets its rays up again.
+struct OccDev { float inv, z_min, z_max; float org[3]; int R; };      // R: max_range in 1/1024 cell, 1 .. 2^20
+struct OccRay { int c[3], e[3], q[3], D[3]; bool cut; };              // start cell, end cell, sub-cell position of the origin, Qe - Qo (|D_a| <= R)
+__device__ __forceinline__ bool occ_far(float u) { return !(fabsf(u) < 524288.0f); }
+__device__ __forceinline__ long long occ_position(float u) {
+  const float fl = floorf(u);
+  return (long long)(int)fl * 1024 + min((int)((u - fl) * 1024.0f), 1023);
+}
+// the ray origin of cloud c: false when it is not finite (the cloud takes no part); far: it lies beyond 2^19 cells
+__device__ __forceinline__ bool occ_origin(const float* R, const OccDev& P, long long Qo[3], bool& far) {
+  const float x = P.org[0], y = P.org[1], z = P.org[2];
+  const float o[3] = {((R[0] * x + R[1] * y) + R[2] * z) + R[9], ((R[3] * x + R[4] * y) + R[5] * z) + R[10], ((R[6] * x + R[7] * y) + R[8] * z) + R[11]};
+  far = false;
+  if (!(isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]))) return false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float u = o[k] * P.inv;
+    far |= occ_far(u);
+    Qo[k] = far ? 0 : occ_position(u);
+  }
+  return true;
+}
+enum { OCC_RAY = 0, OCC_NOT_FINITE = 1, OCC_CLIPPED_Z = 2, OCC_FAR = 3 };
+__device__ __forceinline__ int occ_ray(const MapIn& M, const float* R, const OccDev& P, const long long Qo[3], bool org_far, int p, OccRay& r) {
+  float t[3];
+  if (!map_point(M, R, p, t[0], t[1], t[2])) return OCC_NOT_FINITE;
+  if (!(t[2] >= P.z_min && t[2] <= P.z_max)) return OCC_CLIPPED_Z;
+  if (org_far) return OCC_FAR;
+  long long D[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float u = t[k] * P.inv;
+    if (occ_far(u)) return OCC_FAR;
+    D[k] = occ_position(u) - Qo[k];                       // |Q| <= 2^29, |D| <= 2^30, |D|^2 < 2^62
+  }
+  const long long len2 = D[0] * D[0] + D[1] * D[1] + D[2] * D[2];
+  r.cut = len2 > (long long)P.R * P.R;
+  if (r.cut) {
+    long long L = (long long)ceil(sqrt((double)len2));
+    while (L * L < len2) ++L;
+    while ((L - 1) * (L - 1) >= len2) --L;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) D[k] = (D[k] * P.R) / L;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const long long Qe = Qo[k] + D[k];
+    r.c[k] = (int)(Qo[k] >> 10); r.e[k] = (int)(Qe >> 10); r.q[k] = (int)(Qo[k] & 1023); r.D[k] = (int)D[k];
+  }
+  return OCC_RAY;
+}
+// the walk: visit(cx, cy, cz, last) for the start cell and every cell stepped into.  num and |D| fit 32 bits (num <= 1024 * 1026,
+// |D| <= 2^20), their cross products 64.  The lanes of a wave walk rays of different lengths: the loop runs to the longest, the
+// finished lanes masked off.  Returns the cells visited.
+template <class Visit>
+__device__ __forceinline__ int occ_walk(const OccRay& r, Visit&& visit) {
+  int cx = r.c[0], cy = r.c[1], cz = r.c[2];
+  int lx = abs(r.e[0] - cx), ly = abs(r.e[1] - cy), lz = abs(r.e[2] - cz);
+  const int sx = r.D[0] > 0 ? 1 : -1, sy = r.D[1] > 0 ? 1 : -1, sz = r.D[2] > 0 ? 1 : -1;
+  const int dx = abs(r.D[0]), dy = abs(r.D[1]), dz = abs(r.D[2]);
+  int nx = r.D[0] > 0 ? 1024 - r.q[0] : r.q[0], ny = r.D[1] > 0 ? 1024 - r.q[1] : r.q[1], nz = r.D[2] > 0 ? 1024 - r.q[2] : r.q[2];
+  const int total = lx + ly + lz;
+  for (int s = 0; s < total; ++s) {
+    visit(cx, cy, cz, false);
+    const bool xo = lx > 0, yo = ly > 0, zo = lz > 0;
+    const bool xy = xo && (!yo || (long long)nx * dy <= (long long)ny * dx);          // x before y: a tie goes to the lower axis
+    const bool xz = !zo || (long long)nx * dz <= (long long)nz * dx;
+    const bool yz = !zo || (long long)ny * dz <= (long long)nz * dy;
+    if (xy && xz) { cx += sx; nx += 1024; --lx; }
+    else if (!xy && yo && yz) { cy += sy; ny += 1024; --ly; }
+    else { cz += sz; nz += 1024; --lz; }
+  }
+  visit(cx, cy, cz, true);
+  return total + 1;
+}
+// pass 0.  box[0..2] / box[3..5]: min / max over the start and end cells of the rays that take part; box[6..9]: those rays, the truncated
+// among them, the rows outside the z range, the rows beyond 2^19 cells.  Reduced in the wave and the workgroup, then integer atomics.
+__global__ __launch_bounds__(256) void k_occ_minmax(MapIn M, OccDev P, int* __restrict__ box) {
+  __shared__ int red[4][10];
+  const int c = blockIdx.x, p0 = M.start[c], n = M.start[c + 1] - p0;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = M.pose[12 * (size_t)c + k];
+  long long Qo[3]; bool org_far;
+  if (!occ_origin(R, P, Qo, org_far)) return;
+  int v[10] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0, 0, 0, 0};
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+    OccRay r;
+    const int what = occ_ray(M, R, P, Qo, org_far, p0 + i, r);
+    if (what == OCC_CLIPPED_Z) ++v[8];
+    if (what == OCC_FAR) ++v[9];
+    if (what != OCC_RAY) continue;
+    ++v[6];
+    if (r.cut) ++v[7];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { v[k] = min(v[k], min(r.c[k], r.e[k])); v[3 + k] = max(v[3 + k], max(r.c[k], r.e[k])); }
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k)
+    for (int o = 32; o > 0; o >>= 1) {
+      const int w = __shfl_down(v[k], o, 64);
+      v[k] = k < 3 ? min(v[k], w) : k < 6 ? max(v[k], w) : v[k] + w;
+    }
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < 10; ++k) red[threadIdx.x >> 6][k] = v[k];
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k >= 10) return;
+  const int a = red[0][k], b = red[1][k], d = red[2][k], e = red[3][k];
+  if (k < 3) atomicMin(&box[k], min(min(a, b), min(d, e)));
+  else if (k < 6) atomicMax(&box[k], max(max(a, b), max(d, e)));
+  else if (a + b + d + e) atomicAdd(&box[k], a + b + d + e);
+}
+// G: minb / mul of the dense grid of BRICKS, as for map_cell
+__device__ __forceinline__ size_t occ_brick(const VoxelGeom& G, int cx, int cy, int cz) {
+  return (size_t)((cx >> 3) - G.minb[0]) * G.mul[0] + (size_t)((cy >> 3) - G.minb[1]) * G.mul[1] + (size_t)((cz >> 3) - G.minb[2]) * G.mul[2];
+}
+// pass 1: every brick a ray enters; a byte is stored only when the brick changes
+__global__ __launch_bounds__(256) void k_occ_flag_bricks(MapIn M, OccDev P, VoxelGeom G, unsigned char* __restrict__ flag) {
+  const int c = blockIdx.x, p0 = M.start[c], n = M.start[c + 1] - p0;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = M.pose[12 * (size_t)c + k];
+  long long Qo[3]; bool org_far;
+  if (!occ_origin(R, P, Qo, org_far)) return;
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+    OccRay r;
+    if (occ_ray(M, R, P, Qo, org_far, p0 + i, r) != OCC_RAY) continue;
+    size_t at = ~(size_t)0;
+    occ_walk(r, [&](int cx, int cy, int cz, bool) {
+      const size_t b = occ_brick(G, cx, cy, cz);
+      if (b != at) { flag[b] = 1; at = b; }
+    });
+  }
+}
+struct OccBrickPred {  // touched bricks -> their ascending list (at most cap entries are written) and the brick -> slot table
+  const unsigned char* flag; int* list; int* slot; int cap;
+  __device__ bool keep(int i) const { return flag[i]; }
+  __device__ void put(int pos, int i) const { if (pos < cap) list[pos] = i; slot[i] = pos; }
+};
+// pass 2: one int32 atomic add per visited cell; the slot of the current brick stays in a register until the brick changes.
+// steps: the cells visited, one add per wave
+__global__ __launch_bounds__(256) void k_occ_accumulate(MapIn M, OccDev P, VoxelGeom G, const int* __restrict__ slot, int* __restrict__ hits,
+                                                       int* __restrict__ misses, unsigned long long* __restrict__ steps) {
+  const int c = blockIdx.x, p0 = M.start[c], n = M.start[c + 1] - p0;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = M.pose[12 * (size_t)c + k];
+  long long Qo[3]; bool org_far;
+  if (!occ_origin(R, P, Qo, org_far)) return;
+  long long mine = 0;
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+    OccRay r;
+    if (occ_ray(M, R, P, Qo, org_far, p0 + i, r) != OCC_RAY) continue;
+    size_t at = ~(size_t)0, base = 0;
+    const bool cut = r.cut;
+    mine += occ_walk(r, [&](int cx, int cy, int cz, bool last) {
+      const size_t b = occ_brick(G, cx, cy, cz);
+      if (b != at) { base = (size_t)slot[b] * 512; at = b; }
+      const size_t v = base + (size_t)((cx & 7) | ((cy & 7) << 3) | ((cz & 7) << 6));
+      atomicAdd(last && !cut ? &hits[v] : &misses[v], 1);
+    });
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(steps, (unsigned long long)mine);
+}
+struct OccLog { float l_hit, l_miss, l_min, l_max, l_occ; };
+__device__ __forceinline__ float occ_logodds(const OccLog& L, int h, int m) {
+  const float a = (float)h * L.l_hit, b = (float)m * L.l_miss;
+  return fminf(fmaxf(a + b, L.l_min), L.l_max);
+}
+struct OccCellPred {   // known cells that pass emit (0 all, 1 occupied, 2 free) -> their ascending list (out may be NULL: count only)
+  const int* hits; const int* misses; OccLog L; int emit; int* out; int max_out;
+  __device__ bool keep(int i) const {
+    const int h = hits[i], m = misses[i];
+    if (h + m == 0) return false;
+    if (emit == 0) return true;
+    return (occ_logodds(L, h, m) >= L.l_occ) == (emit == 1);
+  }
+  __device__ void put(int pos, int i) const { if (pos < max_out) out[pos] = i; }
+};
+// pass 3: one record per kept cell
+__global__ __launch_bounds__(256) void k_occ_emit(const int* __restrict__ list, int m, const int* __restrict__ bricks, VoxelGeom G, int divx, int divy,
+                                                 const int* __restrict__ hits, const int* __restrict__ misses, OccLog L, int* __restrict__ out_cell,
+                                                 int* __restrict__ out_hits, int* __restrict__ out_misses, float* __restrict__ out_logodds) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= m) return;
+  const int v = list[k], l = v & 511, b = bricks[v >> 9];
+  const int bx = b % divx + G.minb[0], by = (b / divx) % divy + G.minb[1], bz = b / divx / divy + G.minb[2];
+  out_cell[3 * (size_t)k] = bx * 8 + (l & 7); out_cell[3 * (size_t)k + 1] = by * 8 + ((l >> 3) & 7); out_cell[3 * (size_t)k + 2] = bz * 8 + (l >> 6);
+  out_hits[k] = hits[v]; out_misses[k] = misses[v];
+  out_logodds[k] = occ_logodds(L, hits[v], misses[v]);
+}
 // pcl::StatisticalOutlierRemoval (meanK 50, plane_segmentation.cpp:583-605): mean distance of every point to its k nearest
 // neighbours, exact (brute force): candidates stream through LDS tiles, every thread keeps the k + 1 smallest squared distances of
 // its query in an LDS column (replace-the-maximum; after the first tiles almost every candidate is rejected by one compare)
@@ -2309,6 +2507,7 @@ struct sslam_seg {
   int n_cu = 0;                       // compute units of the device (sizes the target split of k_nn_pairs)
   hipEvent_t m_ev[8] = {};            // the map cloud: start / stop around each of its four passes
   double map_pass_ms[4] = {0, 0, 0, 0};
+  double occ_pass_ms[4] = {0, 0, 0, 0};   // the occupancy map's four passes (it shares the map cloud's events)
   sslam_seg* twin = nullptr;
   int fifo[2] = {0, 0};            // which pipeline (0 = this, 1 = twin) holds the oldest / the newer submitted batch
   int n_inflight = 0;
@@ -3306,45 +3505,218 @@ int seg_device_index(const sslam_seg* s) { return s->P.device; }
 }  // namespace sslam
 extern "C" {
 
-int sslam_seg_map_cloud(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, float resolution, int min_points,
-                        float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out, sslam_map_stats* stats) {
-  if (!s || n_clouds < 0 || (n_clouds > 0 && (!cloud_start || !T))) return set_error(SSLAM_ERR_INVALID, "bad argument");
-  int n_points = 0;
-  if (n_clouds > 0) {
-    if (cloud_start[0] < 0) return set_error(SSLAM_ERR_INVALID, "cloud_start[0] is negative");
-    for (int c = 0; c < n_clouds; ++c)
-      if (cloud_start[c + 1] < cloud_start[c]) return set_error(SSLAM_ERR_INVALID, "cloud_start decreases at cloud %d", c);
-    n_points = cloud_start[n_clouds];   // rows of xyz that are read; those below cloud_start[0] belong to no cloud
-    if (n_points > 0 && !xyz) return set_error(SSLAM_ERR_INVALID, "null xyz");
-    for (size_t k = 0; k < 12 * (size_t)n_clouds; ++k)
-      if (!std::isfinite(T[k])) return set_error(SSLAM_ERR_INVALID, "map cloud: entry %d of the pose of cloud %d is not finite", (int)(k % 12), (int)(k / 12));
-  }
-  MapCloudIn in{nullptr, nullptr, nullptr, cloud_start, n_clouds};
-  if (n_points == 0) return seg_map_cloud_device(s, in, resolution, min_points, xyz_out, cells_out, counts_out, max_out, stats);   // the checks, then 0
-  // the argument checks of the device entry come before anything is staged
-  int rc = map_cloud_check_args(resolution, min_points, xyz_out, max_out);
-  if (rc) return rc;
-  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
-  if ((rc = seg_device(s))) return rc;
-  DevGuard g;
+// the cloud arguments shared by sslam_seg_map_cloud and sslam_seg_occupancy_map: their checks (n_points: the rows of xyz that are read) ...
+static int map_check_clouds(const char* what, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, int* n_points) {
+  *n_points = 0;
+  if (n_clouds < 0 || (n_clouds > 0 && (!cloud_start || !T))) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  if (n_clouds == 0) return 0;
+  if (cloud_start[0] < 0) return set_error(SSLAM_ERR_INVALID, "cloud_start[0] is negative");
+  for (int c = 0; c < n_clouds; ++c)
+    if (cloud_start[c + 1] < cloud_start[c]) return set_error(SSLAM_ERR_INVALID, "cloud_start decreases at cloud %d", c);
+  *n_points = cloud_start[n_clouds];   // rows of xyz that are read; those below cloud_start[0] belong to no cloud
+  if (*n_points > 0 && !xyz) return set_error(SSLAM_ERR_INVALID, "null xyz");
+  for (size_t k = 0; k < 12 * (size_t)n_clouds; ++k)
+    if (!std::isfinite(T[k])) return set_error(SSLAM_ERR_INVALID, "%s: entry %d of the pose of cloud %d is not finite", what, (int)(k % 12), (int)(k / 12));
+  return 0;
+}
+// ... and their way to the device (the poses cast to float once); *bytes: what travelled
+static int map_stage_clouds(sslam_seg* s, DevGuard& g, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, int n_points,
+                            MapCloudIn* in, int64_t* bytes) {
+  int rc;
   float *d_xyz = nullptr, *d_pose = nullptr; int* d_start = nullptr;
   if ((rc = g.alloc(&d_xyz, (size_t)n_points * 3)) || (rc = g.alloc(&d_pose, (size_t)n_clouds * 12)) || (rc = g.alloc(&d_start, (size_t)n_clouds + 1))) return rc;
   std::vector<float> pose(12 * (size_t)n_clouds);
   for (size_t k = 0; k < pose.size(); ++k) pose[k] = (float)T[k];
-  const size_t bytes[3] = {(size_t)n_points * 3 * sizeof(float), pose.size() * sizeof(float), ((size_t)n_clouds + 1) * sizeof(int32_t)};
-  SSLAM_HIP_TRY(hipMemcpyAsync(d_xyz, xyz, bytes[0], hipMemcpyHostToDevice, s->stream));
-  SSLAM_HIP_TRY(hipMemcpyAsync(d_pose, pose.data(), bytes[1], hipMemcpyHostToDevice, s->stream));
-  SSLAM_HIP_TRY(hipMemcpyAsync(d_start, cloud_start, bytes[2], hipMemcpyHostToDevice, s->stream));
+  const size_t b[3] = {(size_t)n_points * 3 * sizeof(float), pose.size() * sizeof(float), ((size_t)n_clouds + 1) * sizeof(int32_t)};
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_xyz, xyz, b[0], hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_pose, pose.data(), b[1], hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_start, cloud_start, b[2], hipMemcpyHostToDevice, s->stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
-  in.d_xyz = d_xyz; in.d_start = d_start; in.d_pose = d_pose;
+  in->d_xyz = d_xyz; in->d_start = d_start; in->d_pose = d_pose;
+  *bytes = (int64_t)(b[0] + b[1] + b[2]);
+  return 0;
+}
+
+int sslam_seg_map_cloud(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, float resolution, int min_points,
+                        float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out, sslam_map_stats* stats) {
+  if (!s) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int n_points = 0, rc;
+  if ((rc = map_check_clouds("map cloud", xyz, cloud_start, n_clouds, T, &n_points))) return rc;
+  MapCloudIn in{nullptr, nullptr, nullptr, cloud_start, n_clouds};
+  if (n_points == 0) return seg_map_cloud_device(s, in, resolution, min_points, xyz_out, cells_out, counts_out, max_out, stats);   // the checks, then 0
+  // the argument checks of the device entry come before anything is staged
+  if ((rc = map_cloud_check_args(resolution, min_points, xyz_out, max_out))) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  if ((rc = seg_device(s))) return rc;
+  DevGuard g;
+  int64_t bytes = 0;
+  if ((rc = map_stage_clouds(s, g, xyz, cloud_start, n_clouds, T, n_points, &in, &bytes))) return rc;
   rc = seg_map_cloud_device(s, in, resolution, min_points, xyz_out, cells_out, counts_out, max_out, stats);
-  if (stats) stats->upload_bytes = (int64_t)(bytes[0] + bytes[1] + bytes[2]);
+  if (stats) stats->upload_bytes = bytes;
   return rc;
 }
 
 int sslam_seg_last_map_timing(const sslam_seg* s, double ms[4]) {
   if (!s || !ms) return set_error(SSLAM_ERR_INVALID, "null argument");
   for (int k = 0; k < 4; ++k) ms[k] = s->map_pass_ms[k];
+  return 0;
+}
+
+// ---- occupancy map (the contract is at sslam_seg_occupancy_map in include/sslam.h) --------------------------------------------------------
+}  // extern "C"
+namespace sslam {
+int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out,
+                             float* logodds_out, int max_out, sslam_occ_stats* stats) {
+  if (!s || in.n_clouds < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = occupancy_check_args(p, max_out);
+  if (rc) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  if (in.n_clouds > (1 << 22)) return set_error(SSLAM_ERR_UNSUPPORTED, "occupancy map: %d clouds, more than 2^22 (one launch row per cloud)", in.n_clouds);
+  if ((rc = seg_device(s))) return rc;
+  sslam_occ_stats st;
+  std::memset(&st, 0, sizeof st);
+  const int nc = in.n_clouds;
+  st.n_clouds = nc;
+  int max_len = 0;
+  if (nc > 0) {
+    st.n_points = in.h_start[nc] - in.h_start[0];
+    for (int c = 0; c < nc; ++c) max_len = std::max(max_len, in.h_start[c + 1] - in.h_start[c]);
+  }
+  for (double& v : s->occ_pass_ms) v = 0;
+  if (stats) *stats = st;
+  if (max_len == 0) return 0;
+  for (hipEvent_t& e : s->m_ev) if (!e) SSLAM_HIP_TRY(hipEventCreate(&e));
+  const MapIn M{in.d_xyz, in.d_start, in.d_pose};
+  const OccDev P{1.0f / p->resolution, p->z_min, p->z_max, {p->sensor_origin[0], p->sensor_origin[1], p->sensor_origin[2]}, (int)occupancy_range_units(*p)};
+  const OccLog L{p->l_hit, p->l_miss, p->l_min, p->l_max, p->l_occ};
+  const dim3 grid((unsigned)nc, (unsigned)std::min((max_len + 255) / 256, 8192)), block(256);
+  DevGuard g;
+  // pass 0: the box of the start and end cells, and the ray counters.  d_box: [0..5] box, [6..9] rays, truncated, outside z, too far,
+  // [10] known cells before emit, [12..13] the cells visited (one 64-bit word)
+  int* d_box = nullptr;
+  if ((rc = g.alloc(&d_box, 16))) return rc;
+  int h_box[16] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_box, h_box, sizeof h_box, hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[0], s->stream));
+  const dim3 grid_box((unsigned)nc, std::min(grid.y, (unsigned)std::max(1, 2048 / nc)));
+  hipLaunchKernelGGL(k_occ_minmax, grid_box, block, 0, s->stream, M, P, d_box);
+  SSLAM_HIP_TRY(hipGetLastError());
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[1], s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(h_box, d_box, 10 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  auto pass_ms = [&](int k) -> int {
+    float ms = 0.0f;
+    SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->m_ev[2 * k], s->m_ev[2 * k + 1]));
+    s->occ_pass_ms[k] = (double)ms;
+    st.kernel_ms += (double)ms;
+    return 0;
+  };
+  if ((rc = pass_ms(0))) return rc;
+  if (h_box[9] > 0)
+    return set_error(SSLAM_ERR_UNSUPPORTED, "occupancy map: %d rays start or end beyond 2^19 cells of %g m from the map's origin", h_box[9], (double)p->resolution);
+  st.n_rays = h_box[6]; st.n_truncated = h_box[7]; st.n_clipped_z = h_box[8];
+  if (stats) *stats = st;
+  if (st.n_rays == 0) return 0;
+  // the cells are exact as floats (below 2^19), so with a leaf of 1 voxel_geometry's floorf(lo * inv) gives them back: its limits, its messages
+  const float lo[3] = {(float)h_box[0], (float)h_box[1], (float)h_box[2]}, hi[3] = {(float)h_box[3], (float)h_box[4], (float)h_box[5]};
+  VoxelGeom G;
+  long long div[3], nbrick = 0;
+  if ((rc = voxel_geometry(lo, hi, 1.0f, &G, div, &nbrick, 3))) return rc;
+  G.mul[0] = 1; G.mul[1] = (int)div[0]; G.mul[2] = (int)(div[0] * div[1]);
+  // pass 1: the touched bricks, their ascending list and the brick -> slot table
+  const int max_bricks = 1 << 20;
+  unsigned char* d_flag = nullptr; int *d_list = nullptr, *d_slot = nullptr, *d_blk = nullptr, *d_total = nullptr;
+  const int cap_bricks = (int)std::min<long long>(nbrick, max_bricks);
+  if ((rc = g.alloc(&d_flag, (size_t)nbrick)) || (rc = g.alloc(&d_list, (size_t)cap_bricks)) || (rc = g.alloc(&d_slot, (size_t)nbrick)) ||
+      (rc = g.alloc(&d_blk, (size_t)((nbrick + 255) / 256))) || (rc = g.alloc(&d_total, 1))) return rc;
+  SSLAM_HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)nbrick, s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[2], s->stream));
+  hipLaunchKernelGGL(k_occ_flag_bricks, grid, block, 0, s->stream, M, P, G, d_flag);
+  int nocc = 0;
+  if ((rc = compact_if(s, OccBrickPred{d_flag, d_list, d_slot, cap_bricks}, (int)nbrick, d_blk, d_total, nullptr, true))) return rc;
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[3], s->stream));
+  SSLAM_HIP_TRY(hipMemcpyAsync(&nocc, d_total, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if ((rc = pass_ms(1))) return rc;
+  if (nocc > max_bricks)
+    return set_error(SSLAM_ERR_UNSUPPORTED, "occupancy map: %d touched bricks of 8 x 8 x 8 cells, more than 2^20: resolution %g is too fine for these rays", nocc, (double)p->resolution);
+  st.n_bricks = nocc;
+  // pass 2: hits and misses of every cell of the touched bricks
+  const size_t ncell = (size_t)nocc * 512;
+  int *d_hits = nullptr, *d_misses = nullptr;
+  if ((rc = g.alloc(&d_hits, ncell)) || (rc = g.alloc(&d_misses, ncell))) return rc;
+  SSLAM_HIP_TRY(hipMemsetAsync(d_hits, 0, ncell * sizeof(int), s->stream));
+  SSLAM_HIP_TRY(hipMemsetAsync(d_misses, 0, ncell * sizeof(int), s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[4], s->stream));
+  hipLaunchKernelGGL(k_occ_accumulate, grid, block, 0, s->stream, M, P, G, d_slot, d_hits, d_misses, (unsigned long long*)(d_box + 12));
+  SSLAM_HIP_TRY(hipGetLastError());
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[5], s->stream));
+  // pass 3: the known cells that pass emit, in ascending slot * 512 + local, and their records
+  const int cap_list = (int)std::min<size_t>(ncell, (size_t)max_out);
+  const int nblk = (int)((ncell + 255) / 256);
+  int *d_cells = nullptr, *d_vblk = nullptr;
+  if ((rc = g.alloc(&d_cells, (size_t)cap_list)) || (rc = g.alloc(&d_vblk, (size_t)nblk))) return rc;
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[6], s->stream));
+  int total = 0;
+  if (p->emit != 0) {   // n_cells counts before emit; it is read with n_steps at the end
+    hipLaunchKernelGGL(k_count_if<OccCellPred>, dim3((unsigned)nblk), dim3(256), 0, s->stream, OccCellPred{d_hits, d_misses, L, 0, nullptr, 0}, (int)ncell, d_vblk);
+    hipLaunchKernelGGL(k_exclusive_scan_wide, dim3(1), dim3(1024), 0, s->stream, d_vblk, nblk, d_vblk, d_box + 10);
+  }
+  if ((rc = compact_if(s, OccCellPred{d_hits, d_misses, L, p->emit, d_cells, cap_list}, (int)ncell, d_vblk, d_total, &total, true))) return rc;
+  const int m = std::min(total, cap_list);
+  int *d_oc = nullptr, *d_oh = nullptr, *d_om = nullptr; float* d_ol = nullptr;
+  if (m > 0) {
+    if ((rc = g.alloc(&d_oc, (size_t)m * 3)) || (rc = g.alloc(&d_oh, (size_t)m)) || (rc = g.alloc(&d_om, (size_t)m)) || (rc = g.alloc(&d_ol, (size_t)m))) return rc;
+    hipLaunchKernelGGL(k_occ_emit, dim3((m + 255) / 256), dim3(256), 0, s->stream, d_cells, m, d_list, G, (int)div[0], (int)div[1], d_hits, d_misses, L, d_oc, d_oh, d_om, d_ol);
+    SSLAM_HIP_TRY(hipGetLastError());
+  }
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[7], s->stream));
+  int tail[4] = {0, 0, 0, 0};   // n_cells, -, n_steps (64 bits): waited for below, and on an error return by the guard's hipFree before this frame ends
+  SSLAM_HIP_TRY(hipMemcpyAsync(tail, d_box + 10, sizeof tail, hipMemcpyDeviceToHost, s->stream));
+  if (m > 0) {
+    if (cells_out) SSLAM_HIP_TRY(hipMemcpyAsync(cells_out, d_oc, (size_t)m * 3 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    if (hits_out) SSLAM_HIP_TRY(hipMemcpyAsync(hits_out, d_oh, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    if (misses_out) SSLAM_HIP_TRY(hipMemcpyAsync(misses_out, d_om, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    if (logodds_out) SSLAM_HIP_TRY(hipMemcpyAsync(logodds_out, d_ol, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  }
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if ((rc = pass_ms(2)) || (rc = pass_ms(3))) return rc;
+  st.n_cells = p->emit != 0 ? tail[0] : total;
+  std::memcpy(&st.n_steps, tail + 2, sizeof st.n_steps);
+  if (stats) *stats = st;
+  return total;
+}
+}  // namespace sslam
+extern "C" {
+
+void sslam_occ_default_params(sslam_occ_params* p) {
+  if (!p) return;
+  auto logodds = [](double prob) { return (float)std::log(prob / (1.0 - prob)); };
+  *p = sslam_occ_params{0.05f, 10.0f, -1.0f, 5.0f, {0.0f, 0.0f, 0.0f}, logodds(0.7), logodds(0.4), logodds(0.1192), logodds(0.971), logodds(0.5), 0};
+}
+
+int sslam_seg_occupancy_map(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, const sslam_occ_params* p,
+                            int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out, int max_out, sslam_occ_stats* stats) {
+  if (!s) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int n_points = 0, rc;
+  if ((rc = map_check_clouds("occupancy map", xyz, cloud_start, n_clouds, T, &n_points))) return rc;
+  MapCloudIn in{nullptr, nullptr, nullptr, cloud_start, n_clouds};
+  if (n_points == 0) return seg_occupancy_map_device(s, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);   // the checks, then 0
+  // the argument checks of the device entry come before anything is staged
+  if ((rc = occupancy_check_args(p, max_out))) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  if ((rc = seg_device(s))) return rc;
+  DevGuard g;
+  int64_t bytes = 0;
+  if ((rc = map_stage_clouds(s, g, xyz, cloud_start, n_clouds, T, n_points, &in, &bytes))) return rc;
+  rc = seg_occupancy_map_device(s, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
+  if (stats) stats->upload_bytes = bytes;
+  return rc;
+}
+
+int sslam_seg_last_occupancy_timing(const sslam_seg* s, double ms[4]) {
+  if (!s || !ms) return set_error(SSLAM_ERR_INVALID, "null argument");
+  for (int k = 0; k < 4; ++k) ms[k] = s->occ_pass_ms[k];
   return 0;
 }
 

@@ -33,6 +33,7 @@
 
 #include "../../include/sslam.h"
 #include "map_cloud.hpp"
+#include "occupancy_map.hpp"
 #include "sslam_common.hpp"
 #include "sslam_math.hpp"
 
@@ -1349,17 +1350,13 @@ int sslam_slam_map_clouds_kept(const sslam_slam* s, int32_t* n_points) {
   return (int)s->map_kf.size();
 }
 
-int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points, float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out,
-                         int32_t* vertex_out, double* poses_out, int max_clouds, sslam_map_stats* stats) {
-  if (!s || max_clouds < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
-  int rc = map_cloud_check_args(resolution, min_points, xyz_out, max_out);
-  if (rc) return rc;
-  if (stats) std::memset(stats, 0, sizeof *stats);
+// the kept clouds at the current estimates, ready for the frontend's kernels: the pose of every cloud's keyframe (quaternion normalised, R by
+// qmat as in the loop stage) goes to the device, 48 bytes each.  *sent: those bytes plus the cloud bytes sent since the last map call.
+static int map_poses_to_device(sslam_slam* s, const char* what, int32_t* vertex_out, double* poses_out, int max_clouds, MapCloudIn* in, int64_t* sent) {
   const int n = (int)s->map_kf.size();
-  if (!s->map_on || n == 0) return 0;   // nothing is kept
-  if ((rc = map_same_device(s))) return rc;
+  int rc;
   std::vector<float> pose(12 * (size_t)n);
-  for (int c = 0; c < n; ++c) {   // the current estimate of every cloud's keyframe, quaternion normalised, R by qmat as in the loop stage
+  for (int c = 0; c < n; ++c) {
     const KeyFrame& kf = *s->map_kf[c];
     double tq[7], T[12];
     if (sslam_graph_get_vertex(s->graph, kf.node, tq) < 0) return SSLAM_ERR_INVALID;
@@ -1368,7 +1365,7 @@ int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points, float*
     for (int k = 0; k < 9; ++k) T[k] = R.m[k];
     T[9] = est.t.x; T[10] = est.t.y; T[11] = est.t.z;
     for (int k = 0; k < 12; ++k) {
-      if (!std::isfinite(T[k])) return set_error(SSLAM_ERR_INVALID, "map cloud: the estimate of vertex %d is not finite", kf.node);
+      if (!std::isfinite(T[k])) return set_error(SSLAM_ERR_INVALID, "%s: the estimate of vertex %d is not finite", what, kf.node);
       pose[12 * (size_t)c + k] = (float)T[k];
     }
     if (c < max_clouds) {
@@ -1376,7 +1373,7 @@ int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points, float*
       if (poses_out) std::memcpy(poses_out + 12 * (size_t)c, T, sizeof T);
     }
   }
-  MapCloudIn in{nullptr, nullptr, nullptr, s->map_start.data(), n};
+  *in = MapCloudIn{nullptr, nullptr, nullptr, s->map_start.data(), n};
   if ((rc = ensure_stream(s))) return rc;
   SSLAM_HIP_TRY(hipSetDevice(s->P.device));
   if ((rc = s->d_map_pose.reserve(pose.size(), s->stream, 0))) return rc;
@@ -1387,9 +1384,40 @@ int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points, float*
   std::memcpy(stage, pose.data(), bytes);
   SSLAM_HIP_TRY(hipMemcpyAsync(s->d_map_pose.p, stage, bytes, hipMemcpyHostToDevice, s->stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
-  in.d_xyz = s->d_map_xyz.p; in.d_start = s->d_map_start.p; in.d_pose = s->d_map_pose.p;
-  const int64_t sent = s->map_pending_bytes + (int64_t)bytes;
+  in->d_xyz = s->d_map_xyz.p; in->d_start = s->d_map_start.p; in->d_pose = s->d_map_pose.p;
+  *sent = s->map_pending_bytes + (int64_t)bytes;
+  return 0;
+}
+
+int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points, float* xyz_out, int32_t* cells_out, int32_t* counts_out, int max_out,
+                         int32_t* vertex_out, double* poses_out, int max_clouds, sslam_map_stats* stats) {
+  if (!s || max_clouds < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = map_cloud_check_args(resolution, min_points, xyz_out, max_out);
+  if (rc) return rc;
+  if (stats) std::memset(stats, 0, sizeof *stats);
+  if (!s->map_on || s->map_kf.empty()) return 0;   // nothing is kept
+  if ((rc = map_same_device(s))) return rc;
+  MapCloudIn in;
+  int64_t sent = 0;
+  if ((rc = map_poses_to_device(s, "map cloud", vertex_out, poses_out, max_clouds, &in, &sent))) return rc;
   rc = seg_map_cloud_device(s->seg, in, resolution, min_points, xyz_out, cells_out, counts_out, max_out, stats);
+  if (rc >= 0) s->map_pending_bytes = 0;
+  if (stats) stats->upload_bytes = sent;
+  return rc;
+}
+
+int sslam_slam_occupancy_map(sslam_slam* s, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out,
+                             int max_out, sslam_occ_stats* stats) {
+  if (!s) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = occupancy_check_args(p, max_out);
+  if (rc) return rc;
+  if (stats) std::memset(stats, 0, sizeof *stats);
+  if (!s->map_on || s->map_kf.empty()) return 0;   // nothing is kept: what sslam_slam_map_cloud returns in that state
+  if ((rc = map_same_device(s))) return rc;
+  MapCloudIn in;
+  int64_t sent = 0;
+  if ((rc = map_poses_to_device(s, "occupancy map", nullptr, nullptr, 0, &in, &sent))) return rc;
+  rc = seg_occupancy_map_device(s->seg, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
   if (rc >= 0) s->map_pending_bytes = 0;
   if (stats) stats->upload_bytes = sent;
   return rc;

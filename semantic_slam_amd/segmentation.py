@@ -13,7 +13,7 @@ from typing import List, Sequence
 
 import numpy as np
 
-from ._lib import load_library, MapStats
+from ._lib import load_library, MapStats, OccParams, OccStats
 from . import synth
 
 CLASS_NAMES = ["other", "chair", "tvmonitor", "book", "keyboard", "laptop", "bucket", "car"]  # point_cloud_segmentation.h:126-130
@@ -151,7 +151,8 @@ def _bind(lib):
     lib.sslam_seg_icp_boxes.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, ci, C.POINTER(C.c_double)]
     lib.sslam_seg_icp_point_to_plane.restype = ci
     lib.sslam_seg_icp_point_to_plane.argtypes = [vp, vp, vp, ci, vp, ci, ci, vp, vp, C.POINTER(C.c_double)]
-    # sslam_seg_fitness_scores, sslam_inf_default_params, sslam_information_from_fitness, sslam_seg_map_cloud: declared in _lib.load_library
+    # sslam_seg_fitness_scores, sslam_inf_default_params, sslam_information_from_fitness, sslam_seg_map_cloud, sslam_seg_occupancy_map:
+    # declared in _lib.load_library
     _BOUND = True
 
 
@@ -161,6 +162,33 @@ def default_inf_params() -> InfParams:
     p = InfParams()
     lib.sslam_inf_default_params(C.byref(p))
     return p
+
+
+def occupancy_default_params() -> OccParams:
+    """``sslam_occ_default_params``: the reference's octomap_server launch (resolution 0.05, max_range 10, z -1 .. 5) and OctoMap's sensor model
+    (hit 0.7, miss 0.4, clamp 0.1192 .. 0.971, threshold 0.5) as float log-odds; ``emit`` 0.  Host only."""
+    lib = load_library(); _bind(lib)
+    p = OccParams()
+    lib.sslam_occ_default_params(C.byref(p))
+    return p
+
+
+def pack_clouds(clouds, poses):
+    """(xyz [n, 3] float32, cloud_start [c + 1] int32, T [max(c, 1), 12] float64) as the map entry points take them.  ``poses``: per cloud 12
+    doubles (R row-major, then t) or a 4x4 / 3x4 matrix."""
+    cl = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in clouds]
+    if len(poses) != len(cl):
+        raise ValueError(f"{len(cl)} clouds but {len(poses)} poses")
+    start = np.zeros(len(cl) + 1, np.int32)
+    start[1:] = np.cumsum([len(c) for c in cl])
+    xyz = np.ascontiguousarray(np.concatenate(cl, 0)) if cl else np.zeros((0, 3), np.float32)
+    T = np.zeros((max(len(cl), 1), 12))
+    for k, P in enumerate(poses):
+        P = np.asarray(P, np.float64)
+        if P.shape in ((4, 4), (3, 4)):
+            P = np.concatenate([P[:3, :3].reshape(-1), P[:3, 3]])
+        T[k] = P.reshape(12)
+    return xyz, start, T
 
 
 def information_from_fitness(fitness: float, params: InfParams | None = None) -> np.ndarray:
@@ -550,22 +578,11 @@ class PointCloudSegmentation:
         t) or a 4x4 / 3x4 matrix taking the cloud into the map frame.  Returns (xyz [m, 3] float32, counts [m] int32[, cells [m, 3] int32],
         ``MapStats``) in the order the header states; ``max_out`` (default: room for every voxel) caps the records written, the true voxel
         count is left in ``last_map_count``."""
-        cl = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in clouds]
-        start = np.zeros(len(cl) + 1, np.int32)
-        start[1:] = np.cumsum([len(c) for c in cl])
-        xyz = np.ascontiguousarray(np.concatenate(cl, 0)) if cl else np.zeros((0, 3), np.float32)
-        T = np.zeros((max(len(cl), 1), 12))
-        if len(poses) != len(cl):
-            raise ValueError(f"{len(cl)} clouds but {len(poses)} poses")
-        for k, P in enumerate(poses):
-            P = np.asarray(P, np.float64)
-            if P.shape in ((4, 4), (3, 4)):
-                P = np.concatenate([P[:3, :3].reshape(-1), P[:3, 3]])
-            T[k] = P.reshape(12)
+        xyz, start, T = pack_clouds(clouds, poses)
         cap = len(xyz) if max_out is None else int(max_out)
         out = np.zeros((max(cap, 1), 3), np.float32); cnt = np.zeros(max(cap, 1), np.int32); cells = np.zeros((max(cap, 1), 3), np.int32)
         st = MapStats()
-        m = self._check(self._lib.sslam_seg_map_cloud(self._h, xyz.ctypes.data if len(xyz) else None, start.ctypes.data, len(cl), T.ctypes.data,
+        m = self._check(self._lib.sslam_seg_map_cloud(self._h, xyz.ctypes.data if len(xyz) else None, start.ctypes.data, len(start) - 1, T.ctypes.data,
                                                       C.c_float(resolution), int(min_points), out.ctypes.data if cap > 0 else None,
                                                       cells.ctypes.data, cnt.ctypes.data, cap, C.byref(st)))
         self.last_map_count = m
@@ -576,6 +593,30 @@ class PointCloudSegmentation:
         """hipEvent milliseconds of the four passes of the last map cloud: min / max, bricks, accumulate, voxels + records"""
         out = np.zeros(4)
         self._check(self._lib.sslam_seg_last_map_timing(self._h, out.ctypes.data))
+        return out
+
+    def occupancy_map(self, clouds, poses, params: OccParams | None = None, max_out: int | None = None):
+        """``sslam_seg_occupancy_map``: every point of every cloud is the end of a ray from its cloud's sensor origin; per cell of the sparse
+        grid the hits, the misses and the clamped log-odds.  ``clouds`` / ``poses`` as for :meth:`map_cloud`; ``params`` defaults to
+        :func:`occupancy_default_params`.  Returns (cells [m, 3] int32, hits [m] int32, misses [m] int32, logodds [m] float32,
+        ``OccStats``) in the order the header states.  Without ``max_out`` a first call counts the records and a second one fetches them;
+        with it one call writes at most that many.  The true count is left in ``last_occupancy_count``."""
+        xyz, start, T = pack_clouds(clouds, poses)
+        p = params if params is not None else occupancy_default_params()
+        st = OccStats()
+        head = (self._h, xyz.ctypes.data if len(xyz) else None, start.ctypes.data, len(start) - 1, T.ctypes.data, C.byref(p))
+        cap = int(max_out) if max_out is not None else self._check(self._lib.sslam_seg_occupancy_map(*head, None, None, None, None, 0, C.byref(st)))
+        cells = np.zeros((max(cap, 1), 3), np.int32); hits = np.zeros(max(cap, 1), np.int32); misses = np.zeros(max(cap, 1), np.int32)
+        lo = np.zeros(max(cap, 1), np.float32)
+        m = self._check(self._lib.sslam_seg_occupancy_map(*head, cells.ctypes.data, hits.ctypes.data, misses.ctypes.data, lo.ctypes.data, cap, C.byref(st)))
+        self.last_occupancy_count = m
+        m = min(m, cap)
+        return cells[:m], hits[:m], misses[:m], lo[:m], st
+
+    def last_occupancy_timing(self) -> np.ndarray:
+        """hipEvent milliseconds of the four passes of the last occupancy map: box, bricks, accumulate, cells + records"""
+        out = np.zeros(4)
+        self._check(self._lib.sslam_seg_last_occupancy_timing(self._h, out.ctypes.data))
         return out
 
     def compute2DConvexHull(self, xyz, seed: int = 0):

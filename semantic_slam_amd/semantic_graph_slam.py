@@ -10,9 +10,9 @@ from __future__ import annotations
 import ctypes as C
 import numpy as np
 
-from ._lib import load_library, MapStats, OptStats
+from ._lib import load_library, MapStats, OccParams, OccStats, OptStats
 from .graph_slam import SslamError, _pose7
-from .segmentation import DBL_MAX, InfParams, Plane, PointCloudSegmentation, default_inf_params
+from .segmentation import DBL_MAX, InfParams, Plane, PointCloudSegmentation, default_inf_params, occupancy_default_params  # noqa: F401
 
 
 class SlamParams(C.Structure):   # sslam_slam_params
@@ -75,7 +75,8 @@ def _bind(lib):
     lib.sslam_slam_keyframes.restype = ci; lib.sslam_slam_keyframes.argtypes = [vp, vp, vp, ci]
     lib.sslam_slam_graph.restype = vp; lib.sslam_slam_graph.argtypes = [vp]
     lib.sslam_slam_find_matches.restype = ci; lib.sslam_slam_find_matches.argtypes = [vp, vp, ci, vp, vp]
-    # sslam_slam_set_fitness_information, sslam_slam_last_fitness, sslam_slam_set_map_clouds, sslam_slam_map_cloud: declared in _lib.load_library
+    # sslam_slam_set_fitness_information, sslam_slam_last_fitness, sslam_slam_set_map_clouds, sslam_slam_map_cloud,
+    # sslam_slam_occupancy_map: declared in _lib.load_library
     lib.sslam_loop_default_params.restype = None; lib.sslam_loop_default_params.argtypes = [C.POINTER(LoopParams)]
     lib.sslam_slam_set_loop_closure.restype = ci; lib.sslam_slam_set_loop_closure.argtypes = [vp, C.POINTER(LoopParams)]
     lib.sslam_slam_last_loops.restype = ci; lib.sslam_slam_last_loops.argtypes = [vp, vp, ci]
@@ -213,6 +214,20 @@ class SemanticGraphSLAM:
                                                        cnt.ctypes.data, cap, ids.ctypes.data, poses.ctypes.data, nc, C.byref(st)))
         nc = min(nc, st.n_clouds)                                      # 0 with map clouds off
         return xyz[:m].copy(), cnt[:m].copy(), cells[:m].copy(), ids[:nc], poses[:nc], st
+
+    def occupancy_map(self, params: OccParams | None = None, max_out: int | None = None):
+        """``sslam_slam_occupancy_map``: the kept keyframe clouds (:meth:`set_map_clouds`) at their current estimates, ray-cast into the sparse
+        grid.  ``params`` defaults to :func:`occupancy_default_params`.  Returns (cells [m, 3] int32, hits [m] int32, misses [m] int32,
+        logodds [m] float32, ``OccStats``); the poses are those :meth:`map_cloud` reports.  Without ``max_out`` a first call counts the
+        records and a second one fetches them."""
+        p = params if params is not None else occupancy_default_params()
+        st = OccStats()
+        cap = int(max_out) if max_out is not None else self._check(self._lib.sslam_slam_occupancy_map(self._h, C.byref(p), None, None, None, None, 0, C.byref(st)))
+        cells = np.zeros((max(cap, 1), 3), np.int32); hits = np.zeros(max(cap, 1), np.int32); misses = np.zeros(max(cap, 1), np.int32)
+        lo = np.zeros(max(cap, 1), np.float32)
+        m = min(cap, self._check(self._lib.sslam_slam_occupancy_map(self._h, C.byref(p), cells.ctypes.data, hits.ctypes.data, misses.ctypes.data,
+                                                                    lo.ctypes.data, cap, C.byref(st))))
+        return cells[:m], hits[:m], misses[:m], lo[:m], st
 
     def loop_candidates(self, keys, news, params: LoopParams | None = None, cap: int | None = None):
         """``sslam_slam_loop_candidates`` (k_loop_candidates on its own).  ``keys`` / ``news``: [n, 3] float64 rows of x, y, accum_distance of
