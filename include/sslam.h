@@ -616,6 +616,8 @@ int sslam_information_from_fitness(const sslam_inf_params* p, double fitness, do
  *      eigenvector of a symmetric 4 x 4 matrix of the cross-covariance, found by cyclic Jacobi sweeps; t = mean q - R mean p.  This is
  *      the minimiser pcl::TransformationEstimationSVD computes.  R is a proper rotation (det = +1) for coplanar correspondences too.
  *      COLLINEAR correspondences leave the rotation about their line undetermined: any of the minimisers may be returned.
+ *      The sums are not centred, so the update loses |mean|^2 / spread^2 in relative accuracy (spread^2: the smallest variance of the
+ *      cloud): about 1e-11 in t for clouds a few metres wide and 30 m from the origin of their coordinates, about 1e-6 at 1000 m.
  *   5. iterations += 1 and T = T_new; if no entry of T moved by more than epsilon (max |T_new - T| <= epsilon over the 12 entries) the
  *      pair is finished with converged = 1.  epsilon = 0 asks for T to repeat bit for bit, which happens once the correspondences
  *      repeat (equal correspondences give equal sums).

@@ -50,8 +50,21 @@ class Event:
     run_after: bool
 
 
-def _rays():
-    az = np.linspace(0.5 * FOV_H, -0.5 * FOV_H, WIDTH)
+# The half-turn replay (path="out_and_back"): one lap, then the same lap backwards, heading along the direction of travel, seen by a
+# panoramic sensor.  Every revisit then pairs two keyframes whose relative rotation is a half turn about the vertical.  A MOUNT is a fixed
+# rotation C of the sensor on the robot (sensor coordinates -> robot coordinates): the pose of a sample becomes that of the sensor,
+# q_yaw * q_C, and its cloud is in the sensor's frame, rows p @ C.  The relative pose of two samples is then conjugated, C^T R C: the half
+# turn about the robot's z is one about the sensor axis that C maps onto z, so the three mounts put the pivot of the half-turn matrix on
+# R[8], R[0] and R[4].
+FOV_PANORAMA = 2 * math.pi * (WIDTH - 1) / WIDTH         # 48 columns all the way round, the first and the last not on top of each other
+RETURN_OFFSET = 0.3                                      # of a STEP: the samples of the way back lie between those of the way out
+MOUNTS = {"I": np.eye(3),
+          "z->x": np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [1.0, 0.0, 0.0]]),      # the sensor's x is the robot's z
+          "z->y": np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])}      # the sensor's y is the robot's z
+
+
+def _rays(fov_h=FOV_H):
+    az = np.linspace(0.5 * fov_h, -0.5 * fov_h, WIDTH)
     el = np.linspace(0.5 * FOV_V, -0.5 * FOV_V, HEIGHT)
     E, A = np.meshgrid(el, az, indexing="ij")
     return np.stack([np.cos(E) * np.cos(A), np.cos(E) * np.sin(A), np.sin(E)], -1).reshape(-1, 3)
@@ -62,10 +75,17 @@ def _yaw_matrix(yaw):
     return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
 
 
-def cast(truth):
-    """the organised cloud seen from the true pose (x, y, z, yaw): the nearest hit of every ray with the room's inside or the box's outside"""
+def _quaternion_of(C):
+    """(x, y, z, w) of a rotation matrix, w >= 0; the mounts are quarter and third turns, w is far from 0"""
+    w = 0.5 * math.sqrt(1.0 + C[0, 0] + C[1, 1] + C[2, 2])
+    return np.array([(C[2, 1] - C[1, 2]) / (4 * w), (C[0, 2] - C[2, 0]) / (4 * w), (C[1, 0] - C[0, 1]) / (4 * w), w])
+
+
+def cast(truth, fov_h=FOV_H, mount=None):
+    """the organised cloud seen from the true pose (x, y, z, yaw): the nearest hit of every ray with the room's inside or the box's outside;
+    with a mount, in the sensor's frame"""
     o = np.asarray(truth[:3], np.float64)
-    d_local = _rays()
+    d_local = _rays(fov_h)
     d = d_local @ _yaw_matrix(truth[3]).T
     with np.errstate(divide="ignore", invalid="ignore"):
         # the room from the inside: the far plane along each axis
@@ -77,7 +97,8 @@ def cast(truth):
     hit = (tn <= tf) & (tn > 0)
     t = np.where(hit, np.minimum(t, tn), t)
     pts = np.zeros((len(t), 4), np.float32)
-    pts[:, :3] = (d_local * t[:, None]).astype(np.float32)
+    xyz = d_local * t[:, None]
+    pts[:, :3] = (xyz if mount is None else xyz @ np.asarray(mount, np.float64)).astype(np.float32)
     return Cloud(pts.view(np.uint8).reshape(-1).copy(), WIDTH, HEIGHT, 16, 16 * WIDTH, (0, 4, 8))
 
 
@@ -92,11 +113,32 @@ def _trajectory():
     return np.stack([CENTRE[0] + SEMI[0] * np.cos(at), CENTRE[1] + SEMI[1] * np.sin(at), 1.0 + 0.2 * np.sin(at), yaw], 1)
 
 
-def make_events(n=None):
-    """the replay: a list of Event; the odometry starts at the true first pose and integrates the true increments with the two biases"""
-    truth = _trajectory()
+def _out_and_back():
+    """true poses (x, y, z, yaw): one lap at arc-length steps of STEP, counter-clockwise, then the same lap backwards from where the way out
+    ended, its samples RETURN_OFFSET of a step off those of the way out; the yaw is the direction of travel, continuous along each way,
+    and the way back's is the way out's plus a half turn (the robot turns on the spot in between)"""
+    th = np.linspace(-0.2 * math.pi, 2.2 * math.pi, 48000)
+    x, y = CENTRE[0] + SEMI[0] * np.cos(th), CENTRE[1] + SEMI[1] * np.sin(th)
+    s = np.concatenate([[0.0], np.cumsum(np.hypot(np.diff(x), np.diff(y)))])
+    s -= np.interp(0.0, th, s)                                                 # arc length 0 at th = 0
+    lap = np.interp(2 * math.pi, th, s)
+    out = np.arange(0.0, lap, STEP)
+    back = out[::-1] - RETURN_OFFSET * STEP                                    # the last one lies just before the start of the way out
+    at = np.interp(np.concatenate([out, back]), s, th)
+    tangent = np.arctan2(SEMI[1] * np.cos(at), -SEMI[0] * np.sin(at))
+    yaw = np.concatenate([np.unwrap(tangent[:len(out)]), np.unwrap(tangent[len(out):]) + math.pi])
+    yaw[len(out):] += 2 * math.pi * np.round((yaw[len(out) - 1] - (yaw[len(out)] - math.pi)) / (2 * math.pi))   # the same branch at the turn
+    return np.stack([CENTRE[0] + SEMI[0] * np.cos(at), CENTRE[1] + SEMI[1] * np.sin(at), 1.0 + 0.2 * np.sin(at), yaw], 1)
+
+
+def make_events(n=None, path="laps", fov_h=FOV_H, mount=None):
+    """the replay: a list of Event; the odometry starts at the true first pose and integrates the true increments with the two biases.
+    path "laps" (LAPS times round, looking 0.7 rad inwards) or "out_and_back"; fov_h: the horizontal field of view of the ray table;
+    mount: a rotation C of the sensor on the robot (see MOUNTS), None for none"""
+    truth = {"laps": _trajectory, "out_and_back": _out_and_back}[path]()
     if n is not None:
         truth = truth[:n]
+    q_mount = None if mount is None else _quaternion_of(np.asarray(mount, np.float64))
     events = []
     ox, oy, oz, oyaw = truth[0]
     for k, tr in enumerate(truth):
@@ -107,14 +149,22 @@ def make_events(n=None):
             ox, oy, oz = ox + step[0], oy + step[1], oz + step[2]
             oyaw = oyaw + (tr[3] - p[3]) + YAW_BIAS
         odom = np.array([ox, oy, oz, 0.0, 0.0, math.sin(0.5 * oyaw), math.cos(0.5 * oyaw)])
-        events.append(Event((k // 10, (k % 10) * 100000000), odom, tr.copy(), cast(tr), (k + 1) % RUN_EVERY == 0))
+        if q_mount is not None:                                                # q_yaw * q_C
+            (cx, cy, cz, cw), sz, cwz = q_mount, odom[5], odom[6]
+            odom[3:] = [cwz * cx - sz * cy, cwz * cy + sz * cx, cwz * cz + sz * cw, cwz * cw - sz * cz]
+        events.append(Event((k // 10, (k % 10) * 100000000), odom, tr.copy(), cast(tr, fov_h, mount), (k + 1) % RUN_EVERY == 0))
     return events
 
 
-def truth_T(a, b):
-    """12 doubles (R row-major, then t): the true pose b in the frame of the true pose a"""
+def truth_T(a, b, mount=None):
+    """12 doubles (R row-major, then t): the true pose b in the frame of the true pose a; with a mount, of the sensor at b in the frame of
+    the sensor at a, C^T R C and C^T t"""
     Ra, Rb = _yaw_matrix(a[3]), _yaw_matrix(b[3])
-    return np.concatenate([(Ra.T @ Rb).reshape(-1), Ra.T @ (np.asarray(b[:3]) - np.asarray(a[:3]))])
+    R, t = Ra.T @ Rb, Ra.T @ (np.asarray(b[:3]) - np.asarray(a[:3]))
+    if mount is not None:
+        C = np.asarray(mount, np.float64)
+        R, t = C.T @ R @ C, C.T @ t
+    return np.concatenate([R.reshape(-1), t])
 
 
 def rms_position_error(est_xyz, truth_xyz):

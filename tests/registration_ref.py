@@ -131,6 +131,58 @@ def scene(name):
     return make_scene(seed, nt, ns, coplanar=coplanar)
 
 
+# scenes far from the identity: what a loop closure hands the matcher when the robot comes back along its own track.
+# name -> (seed, targets, sources, angle, axis, shift of both clouds on every axis).  The translation is FAR_T but for "far", which keeps
+# the default small motion.  Registered from start_T(name), never from the identity.  The fixed point of ICP on 257 x 300 independently
+# sampled points lies 0.01 to 0.05 rad and 1 to 13 cm from the truth, depending on the sample; the seeds are ones where it lies nearer to
+# the truth than the start does (about every second one), which tests/test_registration_cpu.py asserts.
+FAR_T = (0.4, -1.2, 0.3)
+GENERAL_AXIS = (0.2, -0.3, 0.93)
+FAR_SCENES = {"half_z": (301, 257, 300, np.pi, (0, 0, 1), 0.0), "half_x": (302, 257, 300, np.pi, (1, 0, 0), 0.0),
+              "half_y": (313, 257, 300, np.pi, (0, 1, 0), 0.0), "half_g": (304, 257, 300, np.pi - 0.3, GENERAL_AXIS, 0.0),
+              "wide": (305, 257, 300, 2.2, GENERAL_AXIS, 0.0), "far": (306, 257, 300, None, None, 30.0),
+              "far_half": (307, 257, 300, np.pi, (0, 0, 1), 30.0), "half_large": (308, 1300, 1500, np.pi, (0, 0, 1), 0.0)}
+HALF_TURNS = ("half_z", "half_x", "half_y", "half_g", "far_half", "half_large")      # the trace of their rotation is below 0
+START_ANGLE, START_AXIS, START_T = 0.05, (0.5, 0.4, -0.77), (0.03, -0.04, 0.033)      # the perturbation of start_T: 0.05 rad, 6 cm
+
+
+def compose_T(A, B):
+    """12 doubles of x -> A(B(x))"""
+    Ra, Rb = np.asarray(A[:9]).reshape(3, 3), np.asarray(B[:9]).reshape(3, 3)
+    return np.concatenate([(Ra @ Rb).reshape(-1), Ra @ np.asarray(B[9:]) + np.asarray(A[9:])])
+
+
+def shifted_T(T, shift):
+    """T between two clouds after both were moved by `shift` on every axis: x + s -> R x + t + s"""
+    s = np.full(3, float(shift))
+    return np.concatenate([T[:9], T[9:] + s - np.asarray(T[:9]).reshape(3, 3) @ s])
+
+
+def far_scene(name):
+    """(target, source, T_true) of FAR_SCENES: make_scene's room under a large motion, both clouds moved by the shift before the
+    rounding to float32"""
+    seed, nt, ns, angle, axis, shift = FAR_SCENES[name]
+    T = motion_T() if angle is None else motion_T(angle, axis, FAR_T)
+    tg, sr, _ = make_scene(seed, nt, ns, T_true=T)
+    if shift:
+        tg, sr = (tg.astype(np.float64) + shift).astype(np.float32), (sr.astype(np.float64) + shift).astype(np.float32)
+    return tg, sr, shifted_T(T, shift)
+
+
+def far_pose_error(name, T):
+    """pose_error against the scene's truth with the translation measured where the clouds are (at the shift, not at an origin 50 m from
+    them, where it would be the rotation error times that lever arm)"""
+    shift = FAR_SCENES[name][5]
+    return pose_error(shifted_T(T, -shift), shifted_T(far_scene(name)[2], -shift))
+
+
+def start_T(name):
+    """the guess a far scene is registered from: the truth composed with a turn of 0.05 rad and a move of 6 cm of the source cloud about
+    its own place (for the shifted scenes: about the shifted origin, not 50 m away from the cloud)"""
+    shift = FAR_SCENES[name][5]
+    return compose_T(far_scene(name)[2], shifted_T(motion_T(START_ANGLE, START_AXIS, START_T), shift))
+
+
 def two_correspondences():
     """(target, source, max_corr2): two source points sit 1 mm from a target, the other 60 lie 10 m away: under the bound only 2 are accepted"""
     tg, sr, _ = scene("small")

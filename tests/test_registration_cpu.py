@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from fitness_ref import DBL_MAX, IDENTITY_T
-from registration_ref import (BOUNDED_MAX_CORR2, COPLANAR, ERR_NUMERIC, MAX_ITERATIONS, SCENES, correspondences, fast_pair, icp_ref, kabsch,
-                              pose_error, scene, step_ref, two_correspondences)
+from registration_ref import (BOUNDED_MAX_CORR2, COPLANAR, ERR_NUMERIC, FAR_SCENES, HALF_TURNS, MAX_ITERATIONS, SCENES, correspondences, far_pose_error,
+                              far_scene, fast_pair, icp_ref, kabsch, pose_error, scene, start_T, step_ref, two_correspondences)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NON_DEGENERATE = [n for n in SCENES if n not in COPLANAR]
@@ -68,6 +68,50 @@ def test_coplanar_scenes_need_the_determinant_correction():
         assert abs(np.linalg.det(R) - 1) < 1e-12, name
     print(dets)
     assert any(d < -0.5 for d in dets)
+
+
+# ---- the scenes far from the identity ---------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def far_runs():
+    """icp_ref from start_T on every far scene: computed once"""
+    return {name: icp_ref(*far_scene(name)[:2], T0=start_T(name), max_iterations=MAX_ITERATIONS) for name in FAR_SCENES}
+
+
+def test_far_scenes_are_what_they_claim():
+    for name, (_, nt, ns, angle, _, shift) in FAR_SCENES.items():
+        tg, sr, T_true = far_scene(name)
+        assert tg.shape == (nt, 3) and sr.shape == (ns, 3) and tg.dtype == sr.dtype == np.float32
+        tr = np.trace(T_true[:9].reshape(3, 3))
+        assert abs(tr - (1 + 2 * np.cos(0.05 if angle is None else angle))) < 1e-12   # -1 at pi, -0.91 at pi - 0.3, -0.18 at 2.2
+        assert name not in HALF_TURNS or tr < -0.9, (name, tr)
+        assert (tg.min(0) > shift - 0.02).all() and (tg.max(0) < shift + 2.02).all()   # the clouds are where the shift puts them
+        e0 = far_pose_error(name, start_T(name))
+        print(f"{name}: trace {tr:.3f}, start {e0[0]:.4f} rad {e0[1]:.4f} m")
+        assert abs(e0[0] - 0.05) < 1e-9 and 0.05 < e0[1] < 0.07                  # 0.05 rad and 6 cm
+
+
+def test_far_scenes_converge_from_their_start(far_runs):
+    for name in FAR_SCENES:
+        tg, sr, T_true = far_scene(name)
+        T, iterations, converged, status = far_runs[name]
+        e0, e1 = far_pose_error(name, start_T(name)), far_pose_error(name, T)
+        print(f"{name}: {iterations} iterations, error {e0[0]:.4f} rad {e0[1]:.4f} m -> {e1[0]:.4f} rad {e1[1]:.4f} m")
+        assert status == 0 and converged == 1 and 3 <= iterations < MAX_ITERATIONS, name
+        again, _ = step_ref(tg, sr, T)
+        assert again.tobytes() == T.tobytes(), name                           # epsilon = 0: T repeats bit for bit
+        assert e1[0] < e0[0] and e1[1] < e0[1], name
+        R = T[:9].reshape(3, 3)
+        assert abs(np.linalg.det(R) - 1) < 1e-12 and np.abs(R.T @ R - np.eye(3)).max() < 1e-12, name
+        assert name not in HALF_TURNS or np.trace(R) < 0, name
+
+
+def test_far_scenes_are_well_conditioned():
+    for name in FAR_SCENES:
+        tg, sr, _ = far_scene(name)
+        p, q, _ = correspondences(tg, sr, start_T(name))
+        _, _, S = kabsch(p, q)
+        print(name, S / S[0])
+        assert S[1] / S[0] >= 0.1 and S[2] > 1e-3 * S[0], name
 
 
 def _one_pass_longdouble(p, q):

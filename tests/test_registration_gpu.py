@@ -5,7 +5,10 @@ Bounds, stated and not tuned: the device is driven ONE iteration at a time and e
 every entry within 1e-9 -- the bar the point-to-plane ICP is held to against oracle/np_icp.py.  (The correspondences of the two are bitwise
 equal, so what differs is the rounding of two double-precision solutions of one 3 x 3 problem: about 1e-15 in practice.)  Two free-running
 trajectories are never compared: they may part at a float-rounding tie.  Everything else -- one call against many, the final pass against
-sslam_seg_fitness_scores, a pair alone against the same pair in a batch, under another target split, and repeated -- is BITWISE."""
+sslam_seg_fitness_scores, a pair alone against the same pair in a batch, under another target split, and repeated -- is BITWISE.
+The six scenes of CASES start from the identity and move by 0.05 rad; the scenes of FAR start from start_T(name), 0.05 rad from a relative
+pose of 2.2 rad to a half turn about z, x, y or a skew axis, two of them with both clouds 30 m from the origin: what loop closing hands
+the matcher when the robot comes back along its own track."""
 import ctypes as C
 import os
 import re
@@ -14,13 +17,19 @@ import subprocess
 import numpy as np
 import pytest
 
-from fitness_ref import DBL_MAX, IDENTITY_T, skew_T
-from registration_ref import BOUNDED_MAX_CORR2, ERR_NUMERIC, MAX_ITERATIONS, fast_pair, scene, step_ref, two_correspondences
+from fitness_ref import DBL_MAX, IDENTITY_T, qmat, skew_T
+from registration_ref import (BOUNDED_MAX_CORR2, ERR_NUMERIC, FAR_SCENES, HALF_TURNS, MAX_ITERATIONS, far_scene, fast_pair, scene, start_T, step_ref,
+                              two_correspondences)
 
 pytestmark = pytest.mark.gpu
 
 # (scene, max_corr2): 1500 sources span two query blocks of 1024 and six runs of 256, the last partial; 300 x 257 is one block and two runs
 CASES = [("large", None), ("small", None), ("small", BOUNDED_MAX_CORR2), ("mixed", None), ("wall", None), ("floor", None)]
+FAR = list(FAR_SCENES)      # registered from start_T(name): relative rotations of 2.2 rad to a half turn, clouds 30 m from the origin
+
+
+def _scene(name):
+    return far_scene(name) if name in FAR_SCENES else scene(name)
 
 
 @pytest.fixture(scope="module")
@@ -62,14 +71,15 @@ def _proper(T, what):
 _LOCKSTEP = {}
 
 
-def _lockstep(seg, name, max_corr2):
-    """the device driven one iteration at a time from the identity until it reports convergence: [T_0, T_1, ...], each update checked
-    against step_ref from the same T_k.  Computed once per case and shared."""
+def _lockstep(seg, name, max_corr2, start=None):
+    """the device driven one iteration at a time from `start` (the identity by default) until it reports convergence: [T_0, T_1, ...],
+    each update checked against step_ref from the same T_k.  Computed once per case and shared."""
+    cache = (name, max_corr2, None if start is None else np.asarray(start, np.float64).tobytes())
+    if cache in _LOCKSTEP:
+        return _LOCKSTEP[cache]
     key = (name, max_corr2)
-    if key in _LOCKSTEP:
-        return _LOCKSTEP[key]
-    tg, sr, _ = scene(name)
-    Ts = [IDENTITY_T.copy()]
+    tg, sr, _ = _scene(name)
+    Ts = [IDENTITY_T.copy() if start is None else np.array(start, np.float64)]
     worst = 0.0
     for k in range(MAX_ITERATIONS):
         r, _, _ = _one(seg, tg, sr, Ts[-1], max_corr2, max_iterations=1)
@@ -87,7 +97,7 @@ def _lockstep(seg, name, max_corr2):
     else:
         raise AssertionError(f"{key}: no convergence within {MAX_ITERATIONS} single iterations")
     print(f"{name} max_corr2 {max_corr2}: {len(Ts) - 1} iterations, largest |T_device - T_ref| per step {worst:.3e}")
-    _LOCKSTEP[key] = Ts
+    _LOCKSTEP[cache] = Ts
     return Ts
 
 
@@ -98,21 +108,82 @@ def test_lockstep_step_parity(seg, name, max_corr2):
     assert np.abs(Ts[-1] - IDENTITY_T).max() > 1e-2                             # the loop went somewhere
 
 
-@pytest.mark.parametrize("name,max_corr2", CASES)
-def test_one_call_equals_many(seg, name, max_corr2):
-    Ts = _lockstep(seg, name, max_corr2)
-    tg, sr, _ = scene(name)
+@pytest.mark.parametrize("name", FAR)
+def test_lockstep_step_parity_far_from_the_identity(seg, name):
+    """every update from start_T on: T0 = inverse(new) o old of a robot that comes back along its own track is nowhere near the identity"""
+    T0 = start_T(name)
+    Ts = _lockstep(seg, name, None, T0)
+    assert 3 <= len(Ts) - 1 <= MAX_ITERATIONS
+    assert np.abs(Ts[-1] - T0).max() > 1e-3                                     # the loop went somewhere
+    if name in HALF_TURNS:
+        assert np.trace(Ts[-1][:9].reshape(3, 3)) < 0
+
+
+def _one_call_equals_many(seg, name, max_corr2, T0):
+    Ts = _lockstep(seg, name, max_corr2, T0)
+    tg, sr, _ = _scene(name)
     n = len(Ts) - 1
-    r, _, _ = _one(seg, tg, sr, None, max_corr2)
+    r, _, _ = _one(seg, tg, sr, T0, max_corr2)
     assert r.T.tobytes() == Ts[-1].tobytes() and r.iterations == n and r.converged == 1 and r.status == 0
     for cap in (1, n - 1, 9):                                                   # stopped by the cap, across a chunk of 8 iterations too
         if cap < n:
-            c, _, _ = _one(seg, tg, sr, None, max_corr2, max_iterations=cap)
+            c, _, _ = _one(seg, tg, sr, T0, max_corr2, max_iterations=cap)
             assert c.T.tobytes() == Ts[cap].tobytes() and c.iterations == cap and c.converged == 0 and c.status == 0, cap
-    e, _, _ = _one(seg, tg, sr, None, max_corr2, epsilon=1e-4)                   # a real epsilon ends the same trajectory earlier
+    e, _, _ = _one(seg, tg, sr, T0, max_corr2, epsilon=1e-4)                     # a real epsilon ends the same trajectory earlier
     moved = [np.abs(Ts[k + 1] - Ts[k]).max() for k in range(n)]
     first = next(k for k, m in enumerate(moved) if m <= 1e-4)
     assert e.converged == 1 and e.iterations == first + 1 and e.T.tobytes() == Ts[first + 1].tobytes()
+
+
+@pytest.mark.parametrize("name,max_corr2", CASES)
+def test_one_call_equals_many(seg, name, max_corr2):
+    _one_call_equals_many(seg, name, max_corr2, None)
+
+
+@pytest.mark.parametrize("name", FAR)
+def test_one_call_equals_many_far_from_the_identity(seg, name):
+    _one_call_equals_many(seg, name, None, start_T(name))
+
+
+def test_mixed_batch_independence(seg):
+    """a half-turn pair, a pair 30 m from the origin, a small motion from the identity and a pair with too few correspondences in one
+    call: each bitwise what it is alone, repeated, and under another target split"""
+    htg, hsr, _ = far_scene("half_y")
+    ftg, fsr, _ = far_scene("far")
+    stg, ssr, _ = scene("small")
+    ttg, tsr, tmc = two_correspondences()
+    clouds = [htg, hsr, ftg, fsr, stg, ssr, ttg, tsr]
+    pairs = [(0, 1, start_T("half_y"), None), (2, 3, start_T("far"), None), (4, 5, None, None), (6, 7, None, tmc)]
+    res, nn = seg.register_pairs(clouds, pairs, max_iterations=MAX_ITERATIONS, return_nn=True)
+    again = seg.register_pairs(clouds, pairs, max_iterations=MAX_ITERATIONS, return_nn=True)
+    split = _with_chunk(256, lambda: seg.register_pairs(clouds, pairs, max_iterations=MAX_ITERATIONS, return_nn=True))
+    for k, (t, s, T0, mc) in enumerate(pairs):
+        got = (res[k], nn[k][0], nn[k][1])
+        if k < 3:
+            assert res[k].status == 0 and res[k].converged == 1 and res[k].iterations >= 3, k
+        else:
+            assert res[k].status == ERR_NUMERIC and res[k].iterations == 0 and res[k].T.tobytes() == IDENTITY_T.tobytes()
+        assert _same(got, _one(seg, clouds[t], clouds[s], T0, mc)), k
+        assert _same(got, (again[0][k], again[1][k][0], again[1][k][1])), k
+        assert _same(got, (split[0][k], split[1][k][0], split[1][k][1])), k
+        assert _same(got, _with_chunk(256, lambda: _one(seg, clouds[t], clouds[s], T0, mc))), k
+    assert np.trace(res[0].T[:9].reshape(3, 3)) < -0.9 and np.abs(res[1].T[9:]).max() > 1.0    # a half turn; a lever arm of 30 m
+    assert len({r.iterations for r in res}) >= 3                                 # the pairs finish at different times
+
+
+def test_sign_of_the_start_quaternion_is_not_seen(seg):
+    """T0 is a matrix: the same rotation built from q and from -q is the same twelve doubles, and nothing on the way to the result goes
+    through a quaternion whose sign could matter -- at a half turn, where w is about 0 and its sign arbitrary"""
+    from loop_ref import measurement_of_T
+    for name in ("half_z", "half_g"):
+        tg, sr, _ = far_scene(name)
+        z = measurement_of_T(start_T(name))
+        q = z[3:] / np.linalg.norm(z[3:])
+        assert abs(q[3]) < 0.2
+        plus, minus = np.array(list(qmat(q)) + list(z[:3])), np.array(list(qmat(-q)) + list(z[:3]))
+        assert plus.tobytes() == minus.tobytes() and np.abs(plus - start_T(name)).max() < 1e-12
+        a, b = _one(seg, tg, sr, plus), _one(seg, tg, sr, minus)
+        assert _same(a, b) and a[0].status == 0 and a[0].converged == 1 and np.trace(a[0].T[:9].reshape(3, 3)) < -0.9
 
 
 @pytest.mark.parametrize("name,max_corr2", CASES)
