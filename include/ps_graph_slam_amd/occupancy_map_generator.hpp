@@ -4,7 +4,8 @@
 //
 // Header-only; neither Eigen nor PCL nor OctoMap is needed.  Clouds and poses are the types map_cloud_generator.hpp accepts.  The passes
 // run on the GPU, on the process-wide frontend handle of InformationMatrixCalculator::handle() (there is no CPU fallback): a failed call
-// throws.  DEVIATIONS from OctoMap (stated at sslam_seg_occupancy_map): per-ray integration, one clamp on the sum, a flat list of cells.
+// throws.  DEVIATIONS from OctoMap (stated at sslam_seg_occupancy_map): per-ray integration, one clamp on the sum, a flat list of cells;
+// generate_scans (sslam_seg_occupancy_map_scans) is OctoMap's per-scan update and keeps only the last of the three.
 #ifndef PS_GRAPH_SLAM_AMD_OCCUPANCY_MAP_GENERATOR_HPP
 #define PS_GRAPH_SLAM_AMD_OCCUPANCY_MAP_GENERATOR_HPP
 
@@ -47,6 +48,42 @@ class OccupancyMapGenerator {
   };
 
   OccupancyMap generate(const std::vector<Item>& items, const sslam_occ_params& params) const {
+    return generate(sslam_seg_occupancy_map, "sslam_seg_occupancy_map: ", items, params);
+  }
+  // OctoMap's per-scan update (sslam_seg_occupancy_map_scans): every item is one scan, applied in the order given; a cell is updated once
+  // per scan, a hit overriding a miss, and clamped after every update.  Deviations (1) and (2) of the ray entry do not apply.
+  OccupancyMap generate_scans(const std::vector<Item>& items, const sslam_occ_params& params) const {
+    return generate(sslam_seg_occupancy_map_scans, "sslam_seg_occupancy_map_scans: ", items, params);
+  }
+  // over plain vectors: clouds[k] at poses[k]
+  template <class Cloud, class Pose>
+  OccupancyMap generate(const std::vector<Cloud>& clouds, const std::vector<Pose>& poses, const sslam_occ_params& params) const {
+    const Packed P(clouds, poses);
+    return generate(P.items, params);
+  }
+  template <class Cloud, class Pose>
+  OccupancyMap generate_scans(const std::vector<Cloud>& clouds, const std::vector<Pose>& poses, const sslam_occ_params& params) const {
+    const Packed P(clouds, poses);
+    return generate_scans(P.items, params);
+  }
+
+ private:
+  using Entry = int (*)(sslam_seg*, const float*, const int32_t*, int, const double*, const sslam_occ_params*, int32_t*, int32_t*, int32_t*, float*, int,
+                        sslam_occ_stats*);
+  struct Packed {   // clouds and poses of the caller's types as items
+    std::vector<std::vector<float>> packed;
+    std::vector<Item> items;
+    template <class Cloud, class Pose>
+    Packed(const std::vector<Cloud>& clouds, const std::vector<Pose>& poses) : packed(clouds.size()), items(clouds.size()) {
+      if (clouds.size() != poses.size()) throw std::invalid_argument("OccupancyMapGenerator::generate: one pose per cloud");
+      for (size_t k = 0; k < clouds.size(); ++k) {
+        packed[k] = InformationMatrixCalculator::packed(clouds[k]);
+        items[k].xyz = packed[k].data(); items[k].n = (int)(packed[k].size() / 3);
+        InformationMatrixCalculator::pose12(poses[k], items[k].pose);
+      }
+    }
+  };
+  OccupancyMap generate(Entry entry, const char* what, const std::vector<Item>& items, const sslam_occ_params& params) const {
     std::vector<float> xyz;
     std::vector<int32_t> start{0};
     std::vector<double> T;
@@ -59,27 +96,14 @@ class OccupancyMapGenerator {
     M.params = params;
     sslam_seg* h = InformationMatrixCalculator::handle();
     // the number of known cells is not bounded by the number of points: count first, then fetch
-    const int cap = sslam_seg_occupancy_map(h, xyz.data(), start.data(), (int)items.size(), T.data(), &params, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
-    if (cap < 0) throw std::runtime_error(std::string("sslam_seg_occupancy_map: ") + sslam_last_error());
+    const int cap = entry(h, xyz.data(), start.data(), (int)items.size(), T.data(), &params, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+    if (cap < 0) throw std::runtime_error(std::string(what) + sslam_last_error());
     M.resize((size_t)cap);
-    const int m = sslam_seg_occupancy_map(h, xyz.data(), start.data(), (int)items.size(), T.data(), &params, M.cells.data(), M.hits.data(), M.misses.data(),
-                                          M.logodds.data(), cap, &M.stats);
-    if (m < 0) throw std::runtime_error(std::string("sslam_seg_occupancy_map: ") + sslam_last_error());
+    const int m = entry(h, xyz.data(), start.data(), (int)items.size(), T.data(), &params, M.cells.data(), M.hits.data(), M.misses.data(), M.logodds.data(), cap,
+                        &M.stats);
+    if (m < 0) throw std::runtime_error(std::string(what) + sslam_last_error());
     M.resize((size_t)(m < cap ? m : cap));
     return M;
-  }
-  // over plain vectors: clouds[k] at poses[k]
-  template <class Cloud, class Pose>
-  OccupancyMap generate(const std::vector<Cloud>& clouds, const std::vector<Pose>& poses, const sslam_occ_params& params) const {
-    if (clouds.size() != poses.size()) throw std::invalid_argument("OccupancyMapGenerator::generate: one pose per cloud");
-    std::vector<std::vector<float>> packed(clouds.size());
-    std::vector<Item> items(clouds.size());
-    for (size_t k = 0; k < clouds.size(); ++k) {
-      packed[k] = InformationMatrixCalculator::packed(clouds[k]);
-      items[k].xyz = packed[k].data(); items[k].n = (int)(packed[k].size() / 3);
-      InformationMatrixCalculator::pose12(poses[k], items[k].pose);
-    }
-    return generate(items, params);
   }
 };
 

@@ -113,14 +113,10 @@ class semantic_graph_slam {
 
   // the occupancy map of the run (sslam_slam_occupancy_map; where the reference's launch file runs octomap_server): the clouds set_map_clouds
   // keeps, at the current estimates, ray-cast into the sparse grid.  Empty with map clouds off or none kept.
-  ps_graph_slam::OccupancyMap occupancy_map(const sslam_occ_params& params) {
-    ps_graph_slam::OccupancyMap M;
-    M.params = params;
-    const int cap = check(sslam_slam_occupancy_map(h_, &params, nullptr, nullptr, nullptr, nullptr, 0, nullptr), "sslam_slam_occupancy_map");   // count, then fetch
-    M.resize((size_t)cap);
-    const int m = check(sslam_slam_occupancy_map(h_, &params, M.cells.data(), M.hits.data(), M.misses.data(), M.logodds.data(), cap, &M.stats), "sslam_slam_occupancy_map");
-    M.resize((size_t)(m < cap ? m : cap));
-    return M;
+  ps_graph_slam::OccupancyMap occupancy_map(const sslam_occ_params& params) { return occupancy_map(sslam_slam_occupancy_map, "sslam_slam_occupancy_map", params); }
+  // the same through OctoMap's per-scan update (sslam_slam_occupancy_map_scans): every keyframe's cloud one scan, in keyframe order
+  ps_graph_slam::OccupancyMap occupancy_map_scans(const sslam_occ_params& params) {
+    return occupancy_map(sslam_slam_occupancy_map_scans, "sslam_slam_occupancy_map_scans", params);
   }
 
   // getRobotPose / getMap2OdomTrans (semantic_graph_slam.cpp:375-381)
@@ -159,6 +155,16 @@ class semantic_graph_slam {
   static int check(int rc, const char* what) {
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + sslam_last_error());
     return rc;
+  }
+  using OccEntry = int (*)(sslam_slam*, const sslam_occ_params*, int32_t*, int32_t*, int32_t*, float*, int, sslam_occ_stats*);
+  ps_graph_slam::OccupancyMap occupancy_map(OccEntry entry, const char* what, const sslam_occ_params& params) {
+    ps_graph_slam::OccupancyMap M;
+    M.params = params;
+    const int cap = check(entry(h_, &params, nullptr, nullptr, nullptr, nullptr, 0, nullptr), what);   // count, then fetch
+    M.resize((size_t)cap);
+    const int m = check(entry(h_, &params, M.cells.data(), M.hits.data(), M.misses.data(), M.logodds.data(), cap, &M.stats), what);
+    M.resize((size_t)(m < cap ? m : cap));
+    return M;
   }
   sslam_slam_params params_;
   sslam_slam* h_ = nullptr;

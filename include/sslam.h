@@ -742,7 +742,7 @@ typedef struct sslam_occ_params {
   float z_min, z_max;        /* a ray whose transformed end point has z' outside [z_min, z_max] takes no part */
   float sensor_origin[3];    /* in the cloud frame; the ray origin is T applied to it */
   float l_hit, l_miss;       /* log-odds added per hit (> 0) and per miss (< 0) */
-  float l_min, l_max;        /* clamp of the sum */
+  float l_min, l_max;        /* clamp of the sum (the scans entries: of every update) */
   float l_occ;               /* a cell is occupied when its log-odds >= l_occ */
   int32_t emit;              /* 0 every known cell, 1 occupied only, 2 free only */
 } sslam_occ_params;
@@ -752,7 +752,8 @@ typedef struct sslam_occ_stats {
   int32_t n_truncated, n_clipped_z;
   int32_t n_bricks, n_cells;       /* touched bricks; known cells BEFORE emit */
   int32_t reserved;
-  int64_t n_steps;                 /* cells visited, the start and end cells included: the sum of all hits and misses, the atomics of pass 2 */
+  int64_t n_steps;                 /* cells visited, the start and end cells included: the sum of all hits and misses, the atomics of pass 2
+                                      (the scans entries: the (scan, cell) updates, again the sum of all hits and misses) */
   int64_t upload_bytes;            /* host -> device bytes this call moved */
   double  kernel_ms;               /* hipEvent time of the four passes, copies excluded */
 } sslam_occ_stats;
@@ -763,6 +764,45 @@ int sslam_seg_occupancy_map(sslam_seg* s, const float* xyz, const int32_t* cloud
                             sslam_occ_stats* stats);
 /* hipEvent milliseconds of the four passes of the last call: box, bricks, accumulate, cells + records */
 int sslam_seg_last_occupancy_timing(const sslam_seg* s, double ms[4]);
+
+/* ---- occupancy map by scans: OctoMap's insertPointCloud, what octomap_server's insertScan runs [UPSTREAM, quoted from memory]: per scan a set
+ * of free cells and a set of occupied cells, a free cell dropped when the same scan also saw it occupied, every remaining cell updated ONCE
+ * and clamped after that update.  The arguments, params and stats are those of sslam_seg_occupancy_map.
+ * Unchanged from sslam_seg_occupancy_map: the rays, the z clip, the cut at max_range, the integer walk, both limits, the argument errors,
+ * the output order (bricks ascending with x fastest, then the local index), count-only calls, `emit` and max_out.
+ * New:
+ *   scans: a scan is one cloud, that is one entry of cloud_start.  Scans are applied in the order given.  A cloud that takes no part (empty,
+ *     ray origin not finite, every row clipped or not finite) is a scan without updates.  One cloud split in two is two scans, so the
+ *     split changes the result, unlike in the ray entry.
+ *   sets per scan: H = the last cells of its rays that were not truncated; M = every other cell its walks visit, the last cell of a
+ *     truncated ray included, minus H: a hit overrides a miss.
+ *   update per scan, for each cell of H or M, from lo = 0.0f the first time the cell is touched:
+ *     lo = fminf(fmaxf(lo + l, l_min), l_max), l = l_hit for H and l_miss for M, the sum rounded to float (no contraction).  A cell gets at
+ *     most one update per scan, so there is no order inside a scan.
+ *   outputs: hits_out = the number of scans with the cell in H; misses_out = the number of scans with the cell in M; logodds_out = lo after
+ *     the last scan.  The known cells, hits + misses > 0, are the cells the ray entry reports for the same input.  `emit` tests the
+ *     sequential lo against l_occ.
+ *   stats: n_rays, n_truncated, n_clipped_z, n_bricks and n_cells as in the ray entry; n_steps = the sum of hits_out and misses_out at
+ *     emit 0, the number of (scan, cell) updates; reserved 0; kernel_ms and sslam_seg_last_occupancy_timing cover the call as before, slot
+ *     2 being mark plus fold.
+ *   independence: of the order and the multiplicity of the points inside a cloud, of the launch geometry and of the chunk width below.  The
+ *     result depends on the order of the clouds, as OctoMap's does.  A repeated call repeats its bits.
+ * DEVIATIONS (1) and (2) of sslam_seg_occupancy_map are gone for these entries; (3) stays: a flat list of cells, not an octree.
+ * Passes (integer atomics only): 0 and 1 are the ray entry's.  2, per chunk of 64 consecutive clouds: mark -- every ray of the chunk is
+ * walked and bit (cloud - first cloud of the chunk) is set in the cell's 64-bit hit or miss mask by an atomic OR, issued only when a plain
+ * load shows the bit still clear (OR is idempotent, so neither a lost race nor the order matters) -- then fold: one thread per cell of the
+ * bricks the chunk entered applies the set bits in ascending order to the cell's hits, misses and lo and clears the masks.  All launches go
+ * on the handle's stream with no host round trip between chunks.  28 bytes per cell of a touched brick: hits, misses, lo, two masks (15 GB
+ * at the limit of 2^20 touched bricks).  3. the known cells that pass `emit` are compacted and written. */
+int sslam_seg_occupancy_map_scans(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds,
+                                  const double* T /* 12 per cloud: R row-major, then t; cloud -> map frame */, const sslam_occ_params* p,
+                                  int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out, int max_out,
+                                  sslam_occ_stats* stats);
+/* hipEvent milliseconds of mark and of fold, each summed over the chunks of the last scans call (their sum is slot 2 of the timing above) */
+int sslam_seg_last_occupancy_scan_timing(const sslam_seg* s, double ms[2]);
+/* counts[0]: the cells the mark launches of the last scans call visited (the ray entry's n_steps for the same input); counts[1]: the
+ * atomic ORs they issued, the rest having found their bit set by the plain load.  counts[1] varies from run to run; the result does not. */
+int sslam_seg_last_occupancy_scan_counts(const sslam_seg* s, int64_t counts[2]);
 
 /* parity hooks: per-box products of the last sslam_seg_segment call.
  * normals: w*h*4 floats (nx,ny,nz,curvature), labels: w*h int32 (-1 = no plane; otherwise the
@@ -972,6 +1012,10 @@ int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points,
  * none kept.  Errors: those of sslam_seg_occupancy_map and of sslam_slam_map_cloud. */
 int sslam_slam_occupancy_map(sslam_slam* s, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out,
                              float* logodds_out, int max_out, sslam_occ_stats* stats);
+/* sslam_seg_occupancy_map_scans over the same kept clouds, at the same poses and through the same pose upload: every keyframe's cloud is one
+ * scan, applied in keyframe order.  upload_bytes, the return value and the errors as for sslam_slam_occupancy_map. */
+int sslam_slam_occupancy_map_scans(sslam_slam* s, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out,
+                                   float* logodds_out, int max_out, sslam_occ_stats* stats);
 /* setPointCloudData (semantic_graph_slam.cpp:341-345): the cloud is copied */
 int sslam_slam_set_point_cloud(sslam_slam* s, const uint8_t* cloud, int width, int height, int point_step, int row_step,
                                int off_x, int off_y, int off_z);

@@ -149,6 +149,10 @@ def load_library():
         "sslam_seg_occupancy_map": (ci, [vp, vp, vp, ci, vp, C.POINTER(OccParams), vp, vp, vp, vp, ci, C.POINTER(OccStats)]),
         "sslam_seg_last_occupancy_timing": (ci, [vp, vp]),
         "sslam_slam_occupancy_map": (ci, [vp, C.POINTER(OccParams), vp, vp, vp, vp, ci, C.POINTER(OccStats)]),
+        "sslam_seg_occupancy_map_scans": (ci, [vp, vp, vp, ci, vp, C.POINTER(OccParams), vp, vp, vp, vp, ci, C.POINTER(OccStats)]),
+        "sslam_seg_last_occupancy_scan_timing": (ci, [vp, vp]),
+        "sslam_seg_last_occupancy_scan_counts": (ci, [vp, vp]),
+        "sslam_slam_occupancy_map_scans": (ci, [vp, C.POINTER(OccParams), vp, vp, vp, vp, ci, C.POINTER(OccStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design

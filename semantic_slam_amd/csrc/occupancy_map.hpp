@@ -1,5 +1,6 @@
-// The occupancy map over inputs that already sit on the device: the entry sslam_seg_occupancy_map stages its arguments for, and the one
-// sslam_slam_occupancy_map calls with the clouds the tick keeps resident.  Internal: a C++ symbol, not part of the exported C-ABI.
+// The occupancy map over inputs that already sit on the device: the entries sslam_seg_occupancy_map and sslam_seg_occupancy_map_scans stage
+// their arguments for, and the ones sslam_slam_occupancy_map and sslam_slam_occupancy_map_scans call with the clouds the tick keeps resident.
+// Internal: C++ symbols, not part of the exported C-ABI.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -38,4 +39,10 @@ inline int occupancy_check_args(const sslam_occ_params* p, int max_out) {
 // seg_map_cloud_device) must be complete on the device before the call.
 int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out,
                              float* logodds_out, int max_out, sslam_occ_stats* stats);
+// The same for sslam_seg_occupancy_map_scans: the same checks and passes 0 and 1 (one copy of their host code), then mark and fold per chunk
+// of clouds in place of the accumulate pass.  Per cell of a touched brick: hits, misses and log-odds (12 bytes) and the two 64-bit masks of
+// a chunk (16 bytes), 28 bytes; 2^20 touched bricks, the limit, are 2^29 cells or 15 GB of tables, which the device holds (288 GB).
+// A table that cannot be allocated fails the call with the runtime's error, as in the ray entry.
+int seg_occupancy_map_scans_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out,
+                                   int32_t* misses_out, float* logodds_out, int max_out, sslam_occ_stats* stats);
 }  // namespace sslam

@@ -2175,6 +2175,113 @@ __global__ __launch_bounds__(256) void k_occ_emit(const int* __restrict__ list, 
   out_hits[k] = hits[v]; out_misses[k] = misses[v];
   out_logodds[k] = occ_logodds(L, hits[v], misses[v]);
 }
+// ---- occupancy map by scans (sslam_seg_occupancy_map_scans in include/sslam.h; OctoMap's insertPointCloud [UPSTREAM]): passes 0, 1 and the
+// compactions are the ray entry's.  Pass 2 runs per chunk of kOccScanW consecutive clouds: k_occ_scan_mark sets bit (cloud - base) of a
+// cell's hit or miss mask, k_occ_scan_fold applies the set bits in ascending order -- the clouds' order -- to the cell's state and clears
+// the masks.  Per cell of a touched brick: hits, misses, log-odds (12 B) and two 64-bit masks (16 B), 28 B.
+constexpr int kOccScanW = 64;                 // clouds per chunk = bits of a mask word
+typedef unsigned long long OccMask;
+static_assert(kOccScanW == 8 * sizeof(OccMask), "one mask bit per cloud of a chunk");
+// The two measured alternatives (DESIGN.md section 4 has the figures), each a compile-time switch so that the measurement can be repeated:
+// 0 here issues the atomic OR of every visited cell without looking first; 1 below folds every cell of every touched brick in every chunk.
+#ifndef SSLAM_OCC_SCAN_LOAD_FIRST
+#define SSLAM_OCC_SCAN_LOAD_FIRST 1
+#endif
+#ifndef SSLAM_OCC_SCAN_FOLD_ALL
+#define SSLAM_OCC_SCAN_FOLD_ALL 0
+#endif
+// the grid of k_occ_accumulate over the clouds base .. base + gridDim.x - 1 (gridDim.x <= kOccScanW).  A plain load comes first and the
+// atomic only when the bit is still clear: thousands of rays of a cloud share the cells near its origin, and a stale load or a lost race
+// only repeats an idempotent OR.  touched[slot] = tag (the chunk's number + 1) tells the fold which bricks this chunk entered; it is never
+// cleared.  counts[0]: the cells visited, counts[1]: the atomics issued, one add per wave each.
+__global__ __launch_bounds__(256) void k_occ_scan_mark(MapIn M, OccDev P, VoxelGeom G, const int* __restrict__ slot, int base, int tag, OccMask* hmask,
+                                                      OccMask* mmask, int* touched, unsigned long long* __restrict__ counts) {
+  const int c = base + blockIdx.x, p0 = M.start[c], n = M.start[c + 1] - p0;
+  float R[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) R[k] = M.pose[12 * (size_t)c + k];
+  long long Qo[3]; bool org_far;
+  if (!occ_origin(R, P, Qo, org_far)) return;
+  const OccMask bit = (OccMask)1 << blockIdx.x;
+  long long marks = 0, issued = 0;
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+    OccRay r;
+    if (occ_ray(M, R, P, Qo, org_far, p0 + i, r) != OCC_RAY) continue;
+    size_t at = ~(size_t)0, cell0 = 0;
+    const bool cut = r.cut;
+    marks += occ_walk(r, [&](int cx, int cy, int cz, bool last) {
+      const size_t b = occ_brick(G, cx, cy, cz);
+      if (b != at) {
+        const int sl = slot[b];
+        if (touched[sl] != tag) touched[sl] = tag;
+        cell0 = (size_t)sl * 512; at = b;
+      }
+      OccMask* w = (last && !cut ? hmask : mmask) + (cell0 + (size_t)((cx & 7) | ((cy & 7) << 3) | ((cz & 7) << 6)));
+      if (!SSLAM_OCC_SCAN_LOAD_FIRST || !(*w & bit)) { atomicOr(w, bit); ++issued; }
+    });
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { marks += __shfl_down(marks, o, 64); issued += __shfl_down(issued, o, 64); }
+  if ((threadIdx.x & 63) == 0 && marks) { atomicAdd(&counts[0], (unsigned long long)marks); atomicAdd(&counts[1], (unsigned long long)issued); }
+}
+// one thread per cell of the touched bricks; a workgroup lies inside one brick (512 cells) and leaves at once when the chunk did not enter
+// it (touched == NULL: every brick is read).  The set bits of hit | miss in ascending order, a hit overriding a miss:
+// lo = fminf(fmaxf(lo + l, l_min), l_max), the sum rounded to float.  No atomics: a thread owns its cell.  (A first form counted the
+// updates here, one atomic add per wave into one word: half a million waves on one address took 4 ms where the tables take 0.3 --
+// DESIGN.md section 4; k_occ_scan_updates counts them once, at the end.)
+__global__ __launch_bounds__(256) void k_occ_scan_fold(int ncell, const int* __restrict__ touched, int tag, OccMask* __restrict__ hmask,
+                                                      OccMask* __restrict__ mmask, int* __restrict__ hits, int* __restrict__ misses,
+                                                      float* __restrict__ logodds, OccLog L) {
+  if (touched && touched[blockIdx.x >> 1] != tag) return;
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= ncell) return;
+  const OccMask h = hmask[v], m = mmask[v] & ~h;
+  OccMask left = h | m;
+  if (!left) return;
+  float lo = logodds[v];
+  while (left) {
+    const OccMask low = left & (~left + 1);
+    lo = fminf(fmaxf(lo + ((h & low) ? L.l_hit : L.l_miss), L.l_min), L.l_max);
+    left ^= low;
+  }
+  logodds[v] = lo;
+  if (h) hits[v] += __popcll(h);
+  if (m) misses[v] += __popcll(m);
+  hmask[v] = 0; mmask[v] = 0;
+}
+// n_steps of the scan entry, the sum of hits + misses over the cells of the touched bricks: at most 1024 workgroups, one add each
+__global__ __launch_bounds__(256) void k_occ_scan_updates(int ncell, const int* __restrict__ hits, const int* __restrict__ misses,
+                                                         unsigned long long* __restrict__ updates) {
+  __shared__ long long red[4];
+  long long mine = 0;
+  for (int v = blockIdx.x * 256 + threadIdx.x; v < ncell; v += gridDim.x * 256) mine += hits[v] + misses[v];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0 && red[0] + red[1] + red[2] + red[3]) atomicAdd(updates, (unsigned long long)(red[0] + red[1] + red[2] + red[3]));
+}
+struct OccScanCellPred {   // OccCellPred over the stored, sequential log-odds
+  const int* hits; const int* misses; const float* logodds; float l_occ; int emit; int* out; int max_out;
+  __device__ bool keep(int i) const {
+    if (hits[i] + misses[i] == 0) return false;
+    if (emit == 0) return true;
+    return (logodds[i] >= l_occ) == (emit == 1);
+  }
+  __device__ void put(int pos, int i) const { if (pos < max_out) out[pos] = i; }
+};
+__global__ __launch_bounds__(256) void k_occ_scan_emit(const int* __restrict__ list, int m, const int* __restrict__ bricks, VoxelGeom G, int divx, int divy,
+                                                      const int* __restrict__ hits, const int* __restrict__ misses, const float* __restrict__ logodds,
+                                                      int* __restrict__ out_cell, int* __restrict__ out_hits, int* __restrict__ out_misses,
+                                                      float* __restrict__ out_logodds) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= m) return;
+  const int v = list[k], l = v & 511, b = bricks[v >> 9];
+  const int bx = b % divx + G.minb[0], by = (b / divx) % divy + G.minb[1], bz = b / divx / divy + G.minb[2];
+  out_cell[3 * (size_t)k] = bx * 8 + (l & 7); out_cell[3 * (size_t)k + 1] = by * 8 + ((l >> 3) & 7); out_cell[3 * (size_t)k + 2] = bz * 8 + (l >> 6);
+  out_hits[k] = hits[v]; out_misses[k] = misses[v];
+  out_logodds[k] = logodds[v];
+}
 // pcl::StatisticalOutlierRemoval (meanK 50, plane_segmentation.cpp:583-605): mean distance of every point to its k nearest
 // neighbours, exact (brute force): candidates stream through LDS tiles, every thread keeps the k + 1 smallest squared distances of
 // its query in an LDS column (replace-the-maximum; after the first tiles almost every candidate is rejected by one compare)
@@ -2508,6 +2615,9 @@ struct sslam_seg {
   hipEvent_t m_ev[8] = {};            // the map cloud: start / stop around each of its four passes
   double map_pass_ms[4] = {0, 0, 0, 0};
   double occ_pass_ms[4] = {0, 0, 0, 0};   // the occupancy map's four passes (it shares the map cloud's events)
+  std::vector<hipEvent_t> occ_scan_ev;    // the occupancy map by scans: 2 * chunks + 1 events around its mark and fold launches, grows only
+  double occ_scan_ms[2] = {0, 0};         // mark, fold: summed over the chunks of the last call
+  int64_t occ_scan_counts[2] = {0, 0};    // the cells the last call's mark launches visited, the atomics they issued
   sslam_seg* twin = nullptr;
   int fifo[2] = {0, 0};            // which pipeline (0 = this, 1 = twin) holds the oldest / the newer submitted batch
   int n_inflight = 0;
@@ -2525,6 +2635,7 @@ struct sslam_seg {
     if (f_e0) (void)hipEventDestroy(f_e0);
     if (f_e1) (void)hipEventDestroy(f_e1);
     for (hipEvent_t e : m_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : occ_scan_ev) if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
   }
   void free_all() {
@@ -3564,16 +3675,31 @@ int sslam_seg_last_map_timing(const sslam_seg* s, double ms[4]) {
 
 // ---- occupancy map (the contract is at sslam_seg_occupancy_map in include/sslam.h) --------------------------------------------------------
 }  // extern "C"
-namespace sslam {
-int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out,
-                             float* logodds_out, int max_out, sslam_occ_stats* stats) {
+namespace {
+// what the checks and passes 0 and 1 leave for the passes that follow, shared by the ray entry and the scan entry
+struct OccFront {
+  MapIn M; OccDev P; OccLog L; dim3 grid; VoxelGeom G; long long div[3];
+  int* d_box;                      // [0..5] box, [6..9] rays, truncated, outside z, too far, [10] known cells before emit, [12..13] n_steps (one 64-bit word), [14..15] free
+  int *d_list, *d_slot, *d_total;  // the touched bricks ascending, brick -> slot, the compactions' counter
+  int nocc;                        // touched bricks
+  sslam_occ_stats st;
+};
+int occ_pass_ms(sslam_seg* s, sslam_occ_stats& st, int k) {
+  float ms = 0.0f;
+  SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->m_ev[2 * k], s->m_ev[2 * k + 1]));
+  s->occ_pass_ms[k] = (double)ms;
+  st.kernel_ms += (double)ms;
+  return 0;
+}
+// Returns 1 when passes 2 and 3 are to follow, 0 when the call ends here with no record (*stats is filled), an error otherwise.
+int occ_front(sslam_seg* s, const MapCloudIn& in, const sslam_occ_params* p, int max_out, sslam_occ_stats* stats, DevGuard& g, OccFront& F) {
   if (!s || in.n_clouds < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
   int rc = occupancy_check_args(p, max_out);
   if (rc) return rc;
   if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
   if (in.n_clouds > (1 << 22)) return set_error(SSLAM_ERR_UNSUPPORTED, "occupancy map: %d clouds, more than 2^22 (one launch row per cloud)", in.n_clouds);
   if ((rc = seg_device(s))) return rc;
-  sslam_occ_stats st;
+  sslam_occ_stats& st = F.st;
   std::memset(&st, 0, sizeof st);
   const int nc = in.n_clouds;
   st.n_clouds = nc;
@@ -3586,14 +3712,12 @@ int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ
   if (stats) *stats = st;
   if (max_len == 0) return 0;
   for (hipEvent_t& e : s->m_ev) if (!e) SSLAM_HIP_TRY(hipEventCreate(&e));
-  const MapIn M{in.d_xyz, in.d_start, in.d_pose};
-  const OccDev P{1.0f / p->resolution, p->z_min, p->z_max, {p->sensor_origin[0], p->sensor_origin[1], p->sensor_origin[2]}, (int)occupancy_range_units(*p)};
-  const OccLog L{p->l_hit, p->l_miss, p->l_min, p->l_max, p->l_occ};
-  const dim3 grid((unsigned)nc, (unsigned)std::min((max_len + 255) / 256, 8192)), block(256);
-  DevGuard g;
-  // pass 0: the box of the start and end cells, and the ray counters.  d_box: [0..5] box, [6..9] rays, truncated, outside z, too far,
-  // [10] known cells before emit, [12..13] the cells visited (one 64-bit word)
-  int* d_box = nullptr;
+  const MapIn M = F.M = MapIn{in.d_xyz, in.d_start, in.d_pose};
+  const OccDev P = F.P = OccDev{1.0f / p->resolution, p->z_min, p->z_max, {p->sensor_origin[0], p->sensor_origin[1], p->sensor_origin[2]}, (int)occupancy_range_units(*p)};
+  F.L = OccLog{p->l_hit, p->l_miss, p->l_min, p->l_max, p->l_occ};
+  const dim3 grid = F.grid = dim3((unsigned)nc, (unsigned)std::min((max_len + 255) / 256, 8192)), block(256);
+  // pass 0: the box of the start and end cells, and the ray counters
+  int*& d_box = F.d_box;
   if ((rc = g.alloc(&d_box, 16))) return rc;
   int h_box[16] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
   SSLAM_HIP_TRY(hipMemcpyAsync(d_box, h_box, sizeof h_box, hipMemcpyHostToDevice, s->stream));
@@ -3604,14 +3728,7 @@ int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ
   SSLAM_HIP_TRY(hipEventRecord(s->m_ev[1], s->stream));
   SSLAM_HIP_TRY(hipMemcpyAsync(h_box, d_box, 10 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
-  auto pass_ms = [&](int k) -> int {
-    float ms = 0.0f;
-    SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->m_ev[2 * k], s->m_ev[2 * k + 1]));
-    s->occ_pass_ms[k] = (double)ms;
-    st.kernel_ms += (double)ms;
-    return 0;
-  };
-  if ((rc = pass_ms(0))) return rc;
+  if ((rc = occ_pass_ms(s, st, 0))) return rc;
   if (h_box[9] > 0)
     return set_error(SSLAM_ERR_UNSUPPORTED, "occupancy map: %d rays start or end beyond 2^19 cells of %g m from the map's origin", h_box[9], (double)p->resolution);
   st.n_rays = h_box[6]; st.n_truncated = h_box[7]; st.n_clipped_z = h_box[8];
@@ -3619,13 +3736,14 @@ int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ
   if (st.n_rays == 0) return 0;
   // the cells are exact as floats (below 2^19), so with a leaf of 1 voxel_geometry's floorf(lo * inv) gives them back: its limits, its messages
   const float lo[3] = {(float)h_box[0], (float)h_box[1], (float)h_box[2]}, hi[3] = {(float)h_box[3], (float)h_box[4], (float)h_box[5]};
-  VoxelGeom G;
-  long long div[3], nbrick = 0;
+  VoxelGeom& G = F.G;
+  long long* div = F.div, nbrick = 0;
   if ((rc = voxel_geometry(lo, hi, 1.0f, &G, div, &nbrick, 3))) return rc;
   G.mul[0] = 1; G.mul[1] = (int)div[0]; G.mul[2] = (int)(div[0] * div[1]);
   // pass 1: the touched bricks, their ascending list and the brick -> slot table
   const int max_bricks = 1 << 20;
-  unsigned char* d_flag = nullptr; int *d_list = nullptr, *d_slot = nullptr, *d_blk = nullptr, *d_total = nullptr;
+  unsigned char* d_flag = nullptr; int *d_blk = nullptr;
+  int *&d_list = F.d_list, *&d_slot = F.d_slot, *&d_total = F.d_total;
   const int cap_bricks = (int)std::min<long long>(nbrick, max_bricks);
   if ((rc = g.alloc(&d_flag, (size_t)nbrick)) || (rc = g.alloc(&d_list, (size_t)cap_bricks)) || (rc = g.alloc(&d_slot, (size_t)nbrick)) ||
       (rc = g.alloc(&d_blk, (size_t)((nbrick + 255) / 256))) || (rc = g.alloc(&d_total, 1))) return rc;
@@ -3637,21 +3755,22 @@ int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ
   SSLAM_HIP_TRY(hipEventRecord(s->m_ev[3], s->stream));
   SSLAM_HIP_TRY(hipMemcpyAsync(&nocc, d_total, sizeof(int), hipMemcpyDeviceToHost, s->stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
-  if ((rc = pass_ms(1))) return rc;
+  if ((rc = occ_pass_ms(s, st, 1))) return rc;
   if (nocc > max_bricks)
     return set_error(SSLAM_ERR_UNSUPPORTED, "occupancy map: %d touched bricks of 8 x 8 x 8 cells, more than 2^20: resolution %g is too fine for these rays", nocc, (double)p->resolution);
-  st.n_bricks = nocc;
-  // pass 2: hits and misses of every cell of the touched bricks
-  const size_t ncell = (size_t)nocc * 512;
-  int *d_hits = nullptr, *d_misses = nullptr;
-  if ((rc = g.alloc(&d_hits, ncell)) || (rc = g.alloc(&d_misses, ncell))) return rc;
-  SSLAM_HIP_TRY(hipMemsetAsync(d_hits, 0, ncell * sizeof(int), s->stream));
-  SSLAM_HIP_TRY(hipMemsetAsync(d_misses, 0, ncell * sizeof(int), s->stream));
-  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[4], s->stream));
-  hipLaunchKernelGGL(k_occ_accumulate, grid, block, 0, s->stream, M, P, G, d_slot, d_hits, d_misses, (unsigned long long*)(d_box + 12));
-  SSLAM_HIP_TRY(hipGetLastError());
-  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[5], s->stream));
-  // pass 3: the known cells that pass emit, in ascending slot * 512 + local, and their records
+  st.n_bricks = F.nocc = nocc;
+  return 1;
+}
+// pass 3: the known cells that pass emit, in ascending slot * 512 + local, and their records; then the copies back, the times of passes 2
+// (pass2_ms: the caller's rule) and 3, and the stats.  pred: the predicate over the cell tables, its emit / out / max_out set here;
+// launch_emit(d_cells, m, d_oc, d_oh, d_om, d_ol) writes the m records.  Returns the number of records that pass emit.
+template <class Pred, class Emit, class Pass2>
+int occ_records(sslam_seg* s, DevGuard& g, OccFront& F, const sslam_occ_params* p, Pred pred, Emit&& launch_emit, Pass2&& pass2_ms, int32_t* cells_out,
+                int32_t* hits_out, int32_t* misses_out, float* logodds_out, int max_out, sslam_occ_stats* stats) {
+  int rc;
+  sslam_occ_stats& st = F.st;
+  int* const d_box = F.d_box;
+  const size_t ncell = (size_t)F.nocc * 512;
   const int cap_list = (int)std::min<size_t>(ncell, (size_t)max_out);
   const int nblk = (int)((ncell + 255) / 256);
   int *d_cells = nullptr, *d_vblk = nullptr;
@@ -3659,15 +3778,17 @@ int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ
   SSLAM_HIP_TRY(hipEventRecord(s->m_ev[6], s->stream));
   int total = 0;
   if (p->emit != 0) {   // n_cells counts before emit; it is read with n_steps at the end
-    hipLaunchKernelGGL(k_count_if<OccCellPred>, dim3((unsigned)nblk), dim3(256), 0, s->stream, OccCellPred{d_hits, d_misses, L, 0, nullptr, 0}, (int)ncell, d_vblk);
+    pred.emit = 0; pred.out = nullptr; pred.max_out = 0;
+    hipLaunchKernelGGL(k_count_if<Pred>, dim3((unsigned)nblk), dim3(256), 0, s->stream, pred, (int)ncell, d_vblk);
     hipLaunchKernelGGL(k_exclusive_scan_wide, dim3(1), dim3(1024), 0, s->stream, d_vblk, nblk, d_vblk, d_box + 10);
   }
-  if ((rc = compact_if(s, OccCellPred{d_hits, d_misses, L, p->emit, d_cells, cap_list}, (int)ncell, d_vblk, d_total, &total, true))) return rc;
+  pred.emit = p->emit; pred.out = d_cells; pred.max_out = cap_list;
+  if ((rc = compact_if(s, pred, (int)ncell, d_vblk, F.d_total, &total, true))) return rc;
   const int m = std::min(total, cap_list);
   int *d_oc = nullptr, *d_oh = nullptr, *d_om = nullptr; float* d_ol = nullptr;
   if (m > 0) {
     if ((rc = g.alloc(&d_oc, (size_t)m * 3)) || (rc = g.alloc(&d_oh, (size_t)m)) || (rc = g.alloc(&d_om, (size_t)m)) || (rc = g.alloc(&d_ol, (size_t)m))) return rc;
-    hipLaunchKernelGGL(k_occ_emit, dim3((m + 255) / 256), dim3(256), 0, s->stream, d_cells, m, d_list, G, (int)div[0], (int)div[1], d_hits, d_misses, L, d_oc, d_oh, d_om, d_ol);
+    launch_emit(d_cells, m, d_oc, d_oh, d_om, d_ol);
     SSLAM_HIP_TRY(hipGetLastError());
   }
   SSLAM_HIP_TRY(hipEventRecord(s->m_ev[7], s->stream));
@@ -3680,11 +3801,98 @@ int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ
     if (logodds_out) SSLAM_HIP_TRY(hipMemcpyAsync(logodds_out, d_ol, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   }
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
-  if ((rc = pass_ms(2)) || (rc = pass_ms(3))) return rc;
+  if ((rc = pass2_ms()) || (rc = occ_pass_ms(s, st, 3))) return rc;
   st.n_cells = p->emit != 0 ? tail[0] : total;
   std::memcpy(&st.n_steps, tail + 2, sizeof st.n_steps);
   if (stats) *stats = st;
   return total;
+}
+}  // namespace
+namespace sslam {
+int seg_occupancy_map_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out,
+                             float* logodds_out, int max_out, sslam_occ_stats* stats) {
+  DevGuard g;
+  OccFront F{};
+  int rc = occ_front(s, in, p, max_out, stats, g, F);
+  if (rc <= 0) return rc;
+  // pass 2: hits and misses of every cell of the touched bricks
+  const size_t ncell = (size_t)F.nocc * 512;
+  int *d_hits = nullptr, *d_misses = nullptr;
+  if ((rc = g.alloc(&d_hits, ncell)) || (rc = g.alloc(&d_misses, ncell))) return rc;
+  SSLAM_HIP_TRY(hipMemsetAsync(d_hits, 0, ncell * sizeof(int), s->stream));
+  SSLAM_HIP_TRY(hipMemsetAsync(d_misses, 0, ncell * sizeof(int), s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[4], s->stream));
+  hipLaunchKernelGGL(k_occ_accumulate, F.grid, dim3(256), 0, s->stream, F.M, F.P, F.G, F.d_slot, d_hits, d_misses, (unsigned long long*)(F.d_box + 12));
+  SSLAM_HIP_TRY(hipGetLastError());
+  SSLAM_HIP_TRY(hipEventRecord(s->m_ev[5], s->stream));
+  return occ_records(s, g, F, p, OccCellPred{d_hits, d_misses, F.L, 0, nullptr, 0},
+                     [&](const int* d_cells, int m, int* d_oc, int* d_oh, int* d_om, float* d_ol) {
+                       hipLaunchKernelGGL(k_occ_emit, dim3((m + 255) / 256), dim3(256), 0, s->stream, d_cells, m, F.d_list, F.G, (int)F.div[0], (int)F.div[1], d_hits,
+                                          d_misses, F.L, d_oc, d_oh, d_om, d_ol);
+                     },
+                     [&]() { return occ_pass_ms(s, F.st, 2); }, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
+}
+
+// The scan entry.  Pass 2 is a loop over chunks of kOccScanW clouds, mark then fold, all on the handle's stream with no host round trip
+// in between; 2 * chunks + 1 events time the launches.
+int seg_occupancy_map_scans_device(sslam_seg* s, const MapCloudIn& in, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out,
+                                   int32_t* misses_out, float* logodds_out, int max_out, sslam_occ_stats* stats) {
+  if (s) { s->occ_scan_ms[0] = s->occ_scan_ms[1] = 0; s->occ_scan_counts[0] = s->occ_scan_counts[1] = 0; }
+  DevGuard g;
+  OccFront F{};
+  int rc = occ_front(s, in, p, max_out, stats, g, F);
+  if (rc <= 0) return rc;
+  const int nc = in.n_clouds, nchunk = (nc + kOccScanW - 1) / kOccScanW;
+  const size_t ncell = (size_t)F.nocc * 512;
+  int *d_hits = nullptr, *d_misses = nullptr, *d_touched = nullptr; float* d_lo = nullptr;
+  OccMask *d_hmask = nullptr, *d_mmask = nullptr; unsigned long long* d_counts = nullptr;
+  if ((rc = g.alloc(&d_hits, ncell)) || (rc = g.alloc(&d_misses, ncell)) || (rc = g.alloc(&d_lo, ncell)) || (rc = g.alloc(&d_hmask, ncell)) ||
+      (rc = g.alloc(&d_mmask, ncell)) || (rc = g.alloc(&d_touched, (size_t)F.nocc)) || (rc = g.alloc(&d_counts, 2))) return rc;
+  while (s->occ_scan_ev.size() < 2 * (size_t)nchunk + 1) {
+    hipEvent_t e = nullptr;
+    SSLAM_HIP_TRY(hipEventCreate(&e));
+    s->occ_scan_ev.push_back(e);
+  }
+  SSLAM_HIP_TRY(hipMemsetAsync(d_hits, 0, ncell * sizeof(int), s->stream));
+  SSLAM_HIP_TRY(hipMemsetAsync(d_misses, 0, ncell * sizeof(int), s->stream));
+  SSLAM_HIP_TRY(hipMemsetAsync(d_lo, 0, ncell * sizeof(float), s->stream));          // 0.0f
+  SSLAM_HIP_TRY(hipMemsetAsync(d_hmask, 0, ncell * sizeof(OccMask), s->stream));
+  SSLAM_HIP_TRY(hipMemsetAsync(d_mmask, 0, ncell * sizeof(OccMask), s->stream));
+  SSLAM_HIP_TRY(hipMemsetAsync(d_touched, 0, (size_t)F.nocc * sizeof(int), s->stream));
+  SSLAM_HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->occ_scan_ev[0], s->stream));
+  for (int k = 0; k < nchunk; ++k) {
+    const int base = k * kOccScanW, tag = k + 1;
+    hipLaunchKernelGGL(k_occ_scan_mark, dim3((unsigned)std::min(kOccScanW, nc - base), F.grid.y), dim3(256), 0, s->stream, F.M, F.P, F.G, F.d_slot, base, tag,
+                       d_hmask, d_mmask, d_touched, d_counts);
+    SSLAM_HIP_TRY(hipEventRecord(s->occ_scan_ev[2 * k + 1], s->stream));
+    hipLaunchKernelGGL(k_occ_scan_fold, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, s->stream, (int)ncell,
+                       SSLAM_OCC_SCAN_FOLD_ALL ? (const int*)nullptr : (const int*)d_touched, tag, d_hmask, d_mmask, d_hits, d_misses, d_lo, F.L);
+    if (k == nchunk - 1)   // n_steps, inside the last fold's time
+      hipLaunchKernelGGL(k_occ_scan_updates, dim3((unsigned)std::min<size_t>((ncell + 255) / 256, 1024)), dim3(256), 0, s->stream, (int)ncell, d_hits, d_misses,
+                         (unsigned long long*)(F.d_box + 12));
+    SSLAM_HIP_TRY(hipEventRecord(s->occ_scan_ev[2 * k + 2], s->stream));
+  }
+  SSLAM_HIP_TRY(hipGetLastError());
+  unsigned long long h_counts[2] = {0, 0};   // waited for by the records' synchronisation below, before pass2 reads it
+  SSLAM_HIP_TRY(hipMemcpyAsync(h_counts, d_counts, sizeof h_counts, hipMemcpyDeviceToHost, s->stream));
+  auto pass2 = [&]() -> int {
+    for (int k = 0; k < 2 * nchunk; ++k) {
+      float ms = 0.0f;
+      SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->occ_scan_ev[k], s->occ_scan_ev[k + 1]));
+      s->occ_scan_ms[k & 1] += (double)ms;
+    }
+    s->occ_pass_ms[2] = s->occ_scan_ms[0] + s->occ_scan_ms[1];
+    F.st.kernel_ms += s->occ_pass_ms[2];
+    s->occ_scan_counts[0] = (int64_t)h_counts[0]; s->occ_scan_counts[1] = (int64_t)h_counts[1];
+    return 0;
+  };
+  return occ_records(s, g, F, p, OccScanCellPred{d_hits, d_misses, d_lo, p->l_occ, 0, nullptr, 0},
+                     [&](const int* d_cells, int m, int* d_oc, int* d_oh, int* d_om, float* d_ol) {
+                       hipLaunchKernelGGL(k_occ_scan_emit, dim3((m + 255) / 256), dim3(256), 0, s->stream, d_cells, m, F.d_list, F.G, (int)F.div[0], (int)F.div[1],
+                                          d_hits, d_misses, d_lo, d_oc, d_oh, d_om, d_ol);
+                     },
+                     pass2, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
 }
 }  // namespace sslam
 extern "C" {
@@ -3695,13 +3903,16 @@ void sslam_occ_default_params(sslam_occ_params* p) {
   *p = sslam_occ_params{0.05f, 10.0f, -1.0f, 5.0f, {0.0f, 0.0f, 0.0f}, logodds(0.7), logodds(0.4), logodds(0.1192), logodds(0.971), logodds(0.5), 0};
 }
 
-int sslam_seg_occupancy_map(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, const sslam_occ_params* p,
-                            int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out, int max_out, sslam_occ_stats* stats) {
+// sslam_seg_occupancy_map and sslam_seg_occupancy_map_scans: the same checks and staging in front of their device entries
+typedef int (*OccDeviceEntry)(sslam_seg*, const MapCloudIn&, const sslam_occ_params*, int32_t*, int32_t*, int32_t*, float*, int, sslam_occ_stats*);
+static int occupancy_map_staged(OccDeviceEntry entry, sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T,
+                                const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out, int max_out,
+                                sslam_occ_stats* stats) {
   if (!s) return set_error(SSLAM_ERR_INVALID, "bad argument");
   int n_points = 0, rc;
   if ((rc = map_check_clouds("occupancy map", xyz, cloud_start, n_clouds, T, &n_points))) return rc;
   MapCloudIn in{nullptr, nullptr, nullptr, cloud_start, n_clouds};
-  if (n_points == 0) return seg_occupancy_map_device(s, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);   // the checks, then 0
+  if (n_points == 0) return entry(s, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);   // the checks, then 0
   // the argument checks of the device entry come before anything is staged
   if ((rc = occupancy_check_args(p, max_out))) return rc;
   if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
@@ -3709,14 +3920,36 @@ int sslam_seg_occupancy_map(sslam_seg* s, const float* xyz, const int32_t* cloud
   DevGuard g;
   int64_t bytes = 0;
   if ((rc = map_stage_clouds(s, g, xyz, cloud_start, n_clouds, T, n_points, &in, &bytes))) return rc;
-  rc = seg_occupancy_map_device(s, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
+  rc = entry(s, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
   if (stats) stats->upload_bytes = bytes;
   return rc;
+}
+
+int sslam_seg_occupancy_map(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, const sslam_occ_params* p,
+                            int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out, int max_out, sslam_occ_stats* stats) {
+  return occupancy_map_staged(seg_occupancy_map_device, s, xyz, cloud_start, n_clouds, T, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
+}
+
+int sslam_seg_occupancy_map_scans(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const double* T, const sslam_occ_params* p,
+                                  int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out, int max_out, sslam_occ_stats* stats) {
+  return occupancy_map_staged(seg_occupancy_map_scans_device, s, xyz, cloud_start, n_clouds, T, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
 }
 
 int sslam_seg_last_occupancy_timing(const sslam_seg* s, double ms[4]) {
   if (!s || !ms) return set_error(SSLAM_ERR_INVALID, "null argument");
   for (int k = 0; k < 4; ++k) ms[k] = s->occ_pass_ms[k];
+  return 0;
+}
+
+int sslam_seg_last_occupancy_scan_timing(const sslam_seg* s, double ms[2]) {
+  if (!s || !ms) return set_error(SSLAM_ERR_INVALID, "null argument");
+  ms[0] = s->occ_scan_ms[0]; ms[1] = s->occ_scan_ms[1];
+  return 0;
+}
+
+int sslam_seg_last_occupancy_scan_counts(const sslam_seg* s, int64_t counts[2]) {
+  if (!s || !counts) return set_error(SSLAM_ERR_INVALID, "null argument");
+  counts[0] = s->occ_scan_counts[0]; counts[1] = s->occ_scan_counts[1];
   return 0;
 }
 

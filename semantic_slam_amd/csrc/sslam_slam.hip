@@ -1406,8 +1406,9 @@ int sslam_slam_map_cloud(sslam_slam* s, float resolution, int min_points, float*
   return rc;
 }
 
-int sslam_slam_occupancy_map(sslam_slam* s, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out,
-                             int max_out, sslam_occ_stats* stats) {
+// sslam_slam_occupancy_map and sslam_slam_occupancy_map_scans: the kept clouds at the current estimates through one of the two device entries
+static int occupancy_map_kept(decltype(&seg_occupancy_map_device) entry, sslam_slam* s, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out,
+                              int32_t* misses_out, float* logodds_out, int max_out, sslam_occ_stats* stats) {
   if (!s) return set_error(SSLAM_ERR_INVALID, "bad argument");
   int rc = occupancy_check_args(p, max_out);
   if (rc) return rc;
@@ -1417,10 +1418,20 @@ int sslam_slam_occupancy_map(sslam_slam* s, const sslam_occ_params* p, int32_t* 
   MapCloudIn in;
   int64_t sent = 0;
   if ((rc = map_poses_to_device(s, "occupancy map", nullptr, nullptr, 0, &in, &sent))) return rc;
-  rc = seg_occupancy_map_device(s->seg, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
+  rc = entry(s->seg, in, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
   if (rc >= 0) s->map_pending_bytes = 0;
   if (stats) stats->upload_bytes = sent;
   return rc;
+}
+
+int sslam_slam_occupancy_map(sslam_slam* s, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out, float* logodds_out,
+                             int max_out, sslam_occ_stats* stats) {
+  return occupancy_map_kept(seg_occupancy_map_device, s, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
+}
+
+int sslam_slam_occupancy_map_scans(sslam_slam* s, const sslam_occ_params* p, int32_t* cells_out, int32_t* hits_out, int32_t* misses_out,
+                                   float* logodds_out, int max_out, sslam_occ_stats* stats) {
+  return occupancy_map_kept(seg_occupancy_map_scans_device, s, p, cells_out, hits_out, misses_out, logodds_out, max_out, stats);
 }
 
 int sslam_slam_loop_candidates(sslam_slam* s, const double* keys, int n_keys, const double* news, int n_new, const sslam_loop_params* p,

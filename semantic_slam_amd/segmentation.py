@@ -601,14 +601,23 @@ class PointCloudSegmentation:
         :func:`occupancy_default_params`.  Returns (cells [m, 3] int32, hits [m] int32, misses [m] int32, logodds [m] float32,
         ``OccStats``) in the order the header states.  Without ``max_out`` a first call counts the records and a second one fetches them;
         with it one call writes at most that many.  The true count is left in ``last_occupancy_count``."""
+        return self._occupancy_map(self._lib.sslam_seg_occupancy_map, clouds, poses, params, max_out)
+
+    def occupancy_map_scans(self, clouds, poses, params: OccParams | None = None, max_out: int | None = None):
+        """``sslam_seg_occupancy_map_scans``: OctoMap's per-scan update.  Every cloud is one scan, applied in the order given: a cell gets at
+        most one update per scan, a hit overriding a miss, and the log-odds are clamped after every update.  Arguments and return values as
+        for :meth:`occupancy_map`; hits and misses count scans, and the log-odds are the sequential ones."""
+        return self._occupancy_map(self._lib.sslam_seg_occupancy_map_scans, clouds, poses, params, max_out)
+
+    def _occupancy_map(self, entry, clouds, poses, params, max_out):
         xyz, start, T = pack_clouds(clouds, poses)
         p = params if params is not None else occupancy_default_params()
         st = OccStats()
         head = (self._h, xyz.ctypes.data if len(xyz) else None, start.ctypes.data, len(start) - 1, T.ctypes.data, C.byref(p))
-        cap = int(max_out) if max_out is not None else self._check(self._lib.sslam_seg_occupancy_map(*head, None, None, None, None, 0, C.byref(st)))
+        cap = int(max_out) if max_out is not None else self._check(entry(*head, None, None, None, None, 0, C.byref(st)))
         cells = np.zeros((max(cap, 1), 3), np.int32); hits = np.zeros(max(cap, 1), np.int32); misses = np.zeros(max(cap, 1), np.int32)
         lo = np.zeros(max(cap, 1), np.float32)
-        m = self._check(self._lib.sslam_seg_occupancy_map(*head, cells.ctypes.data, hits.ctypes.data, misses.ctypes.data, lo.ctypes.data, cap, C.byref(st)))
+        m = self._check(entry(*head, cells.ctypes.data, hits.ctypes.data, misses.ctypes.data, lo.ctypes.data, cap, C.byref(st)))
         self.last_occupancy_count = m
         m = min(m, cap)
         return cells[:m], hits[:m], misses[:m], lo[:m], st
@@ -617,6 +626,18 @@ class PointCloudSegmentation:
         """hipEvent milliseconds of the four passes of the last occupancy map: box, bricks, accumulate, cells + records"""
         out = np.zeros(4)
         self._check(self._lib.sslam_seg_last_occupancy_timing(self._h, out.ctypes.data))
+        return out
+
+    def last_occupancy_scan_timing(self) -> np.ndarray:
+        """hipEvent milliseconds of mark and of fold, each summed over the chunks of the last :meth:`occupancy_map_scans`"""
+        out = np.zeros(2)
+        self._check(self._lib.sslam_seg_last_occupancy_scan_timing(self._h, out.ctypes.data))
+        return out
+
+    def last_occupancy_scan_counts(self) -> np.ndarray:
+        """int64 [2] of the last :meth:`occupancy_map_scans`: the cells its mark launches visited, the atomic ORs they issued"""
+        out = np.zeros(2, np.int64)
+        self._check(self._lib.sslam_seg_last_occupancy_scan_counts(self._h, out.ctypes.data))
         return out
 
     def compute2DConvexHull(self, xyz, seed: int = 0):

@@ -220,13 +220,21 @@ class SemanticGraphSLAM:
         grid.  ``params`` defaults to :func:`occupancy_default_params`.  Returns (cells [m, 3] int32, hits [m] int32, misses [m] int32,
         logodds [m] float32, ``OccStats``); the poses are those :meth:`map_cloud` reports.  Without ``max_out`` a first call counts the
         records and a second one fetches them."""
+        return self._occupancy_map(self._lib.sslam_slam_occupancy_map, params, max_out)
+
+    def occupancy_map_scans(self, params: OccParams | None = None, max_out: int | None = None):
+        """``sslam_slam_occupancy_map_scans``: the same kept clouds at the same poses through OctoMap's per-scan update -- every keyframe's cloud
+        one scan, in keyframe order, a cell updated once per scan and clamped after every update.  Arguments and return values as for
+        :meth:`occupancy_map`."""
+        return self._occupancy_map(self._lib.sslam_slam_occupancy_map_scans, params, max_out)
+
+    def _occupancy_map(self, entry, params, max_out):
         p = params if params is not None else occupancy_default_params()
         st = OccStats()
-        cap = int(max_out) if max_out is not None else self._check(self._lib.sslam_slam_occupancy_map(self._h, C.byref(p), None, None, None, None, 0, C.byref(st)))
+        cap = int(max_out) if max_out is not None else self._check(entry(self._h, C.byref(p), None, None, None, None, 0, C.byref(st)))
         cells = np.zeros((max(cap, 1), 3), np.int32); hits = np.zeros(max(cap, 1), np.int32); misses = np.zeros(max(cap, 1), np.int32)
         lo = np.zeros(max(cap, 1), np.float32)
-        m = min(cap, self._check(self._lib.sslam_slam_occupancy_map(self._h, C.byref(p), cells.ctypes.data, hits.ctypes.data, misses.ctypes.data,
-                                                                    lo.ctypes.data, cap, C.byref(st))))
+        m = min(cap, self._check(entry(self._h, C.byref(p), cells.ctypes.data, hits.ctypes.data, misses.ctypes.data, lo.ctypes.data, cap, C.byref(st))))
         return cells[:m], hits[:m], misses[:m], lo[:m], st
 
     def loop_candidates(self, keys, news, params: LoopParams | None = None, cap: int | None = None):
