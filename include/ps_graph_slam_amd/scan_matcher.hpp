@@ -30,6 +30,19 @@ class ScanMatcher {
   int max_iterations = 64;
   double transformation_epsilon = 0.0;
   double max_correspondence_distance = DBL_MAX;
+  // GICP only: neighbours per covariance and the eigenvalue along the normal (fast_gicp's setCorrespondenceRandomness and its PLANE
+  // regularisation); the covariances are computed inside the call
+  int gicp_k = 20;
+  double gicp_plane_epsilon = 1e-3;
+
+  // hdl_graph_slam's registration_method (select_registration_method): "ICP" (the default: pcl::IterativeClosestPoint), "GICP" or
+  // "FAST_GICP" (generalized ICP, sslam_seg_register_pairs_gicp).  Any other name -- "NDT", "NDT_OMP", ... have no kernel here -- throws.
+  void setMethod(const std::string& name) {
+    if (name == "ICP") gicp_ = false;
+    else if (name == "GICP" || name == "FAST_GICP") gicp_ = true;
+    else throw std::invalid_argument("ScanMatcher::setMethod: unknown registration method \"" + name + "\" (ICP, GICP, FAST_GICP)");
+  }
+  bool isGicp() const { return gicp_; }
 
   struct Result {
     std::array<double, 12> relpose;   // R row-major, then t: source -> target frame (getFinalTransformation)
@@ -74,9 +87,12 @@ class ScanMatcher {
       rp[k].max_corr2 = d < 1e154 ? d * d : DBL_MAX;
     }
     std::vector<sslam_reg_result> rr(pairs.size());
-    if (sslam_seg_register_pairs(InformationMatrixCalculator::handle(), xyz.data(), start.data(), (int)(2 * pairs.size()), rp.data(), (int)rp.size(),
-                                 max_iterations, transformation_epsilon, rr.data(), nullptr, nullptr, nullptr) < 0)
-      throw std::runtime_error(std::string("sslam_seg_register_pairs: ") + sslam_last_error());
+    const sslam_gicp_params gp{gicp_k, gicp_plane_epsilon};
+    const int rc = gicp_ ? sslam_seg_register_pairs_gicp(InformationMatrixCalculator::handle(), xyz.data(), start.data(), (int)(2 * pairs.size()), rp.data(),
+                                                         (int)rp.size(), nullptr, &gp, max_iterations, transformation_epsilon, rr.data(), nullptr, nullptr, nullptr)
+                         : sslam_seg_register_pairs(InformationMatrixCalculator::handle(), xyz.data(), start.data(), (int)(2 * pairs.size()), rp.data(),
+                                                    (int)rp.size(), max_iterations, transformation_epsilon, rr.data(), nullptr, nullptr, nullptr);
+    if (rc < 0) throw std::runtime_error(std::string(gicp_ ? "sslam_seg_register_pairs_gicp: " : "sslam_seg_register_pairs: ") + sslam_last_error());
     std::vector<Result> out(pairs.size());
     for (size_t k = 0; k < pairs.size(); ++k) {
       for (int q = 0; q < 12; ++q) out[k].relpose[q] = rr[k].T[q];
@@ -84,6 +100,9 @@ class ScanMatcher {
     }
     return out;
   }
+
+ private:
+  bool gicp_ = false;
 };
 
 }  // namespace ps_graph_slam

@@ -69,6 +69,11 @@ class semantic_graph_slam {
   // loop closing inside the tick (hdl_graph_slam's LoopDetector::detect; sslam_slam_set_loop_closure): nullptr turns it off.  After
   // init(), which needs the frontend handle for it.
   void set_loop_closure(const sslam_loop_params* params) { check(sslam_slam_set_loop_closure(h_, params), "sslam_slam_set_loop_closure"); }
+  // the scan matcher of the loop stage (hdl_graph_slam's registration_method; sslam_slam_set_loop_registration): SSLAM_REG_ICP, the
+  // default, or SSLAM_REG_GICP with its parameters (nullptr: k 20, plane_epsilon 1e-3)
+  void set_loop_registration(int method, const sslam_gicp_params* params = nullptr) {
+    check(sslam_slam_set_loop_registration(h_, method, params), "sslam_slam_set_loop_registration");
+  }
   // the records of the last run(): one per new keyframe that reached the selection with at least one candidate
   std::vector<sslam_loop> last_loops() const {
     const int n = check(sslam_slam_last_loops(h_, nullptr, 0), "sslam_slam_last_loops");

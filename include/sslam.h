@@ -645,6 +645,58 @@ typedef struct sslam_reg_result {
 int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
                              int max_iterations, double epsilon, sslam_reg_result* out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms);
 
+/* ---- generalized ICP: plane-to-plane scan matching (hdl_graph_slam's registration_method GICP / FAST_GICP: pcl::GeneralizedIterativeClosestPoint,
+ * fast_gicp::FastGICP [UPSTREAM, quoted from memory]; the reference has no scan matcher) ------------------------------------------------
+ * sslam_seg_cloud_covariances: for every point, the covariance of its k nearest neighbours inside its OWN cloud, regularised to a plane
+ * (k_knn_cov).  Clouds are laid out as for sslam_seg_fitness_scores.  cov_out: 6 doubles per point of xyz (xx xy xz yy yz zz; a point
+ * before cloud_start[0] gets zeros).  knn_index_out (optional): k int32 per point, indices inside the point's cloud, -1 padded.
+ *   Neighbours.  d2 = (dx dx + dy dy) + dz dz in float32 without fused multiply-add, dx = x_query - x_candidate.  The candidates are
+ *     the finite points of the query's cloud, the query itself included.  The set is the k smallest by (d2, index), lexicographic: ties
+ *     go to the lowest index.  It does not depend on the launch geometry, and a NumPy float32 restatement gives the same indices bit
+ *     for bit.  knn_index_out lists them in that (d2, index) order.  A cloud with m < k finite points uses all m.
+ *   Covariance, in double: mean = the sum of the neighbours in that order / m;  C = sum (q - mean)(q - mean)^T / m.
+ *   Regularisation (fast_gicp's RegularizationMethod::PLANE): C = U diag(l0 <= l1 <= l2) U^T is replaced by U diag(plane_epsilon, 1, 1) U^T,
+ *     which is I - (1 - plane_epsilon) n n^T with n the unit eigenvector of l0, and is computed that way: cyclic Jacobi sweeps on the
+ *     symmetric 3 x 3 matrix in double.  Where l0 = l1 (collinear or isotropic neighbourhoods) n is not determined: any minimiser may be
+ *     returned.
+ *   m < 3: the identity.  A non-finite point gets six zeros (and k times -1); it can never be a correspondence, so they are never read.
+ * k: 3 .. 32 (callers default to 20); plane_epsilon: finite, in (0, 1] (1e-3).  kernel_ms (optional): hipEvent time of the kernel.
+ * Returns the number of points.  SSLAM_ERR_INVALID, before any device call: the cases of sslam_seg_fitness_scores (cov_out in the place
+ * of the outputs), k or plane_epsilon outside their range.  SSLAM_ERR_NO_DEVICE without a GPU.
+ *
+ * sslam_seg_register_pairs_gicp: sslam_seg_register_pairs with the generalized-ICP update.  cov: 6 doubles per point of xyz as
+ * sslam_seg_cloud_covariances writes them, or NULL: they are computed inside the call, once per cloud that some pair names, with
+ * params (NULL: sslam_gicp_default_params: k 20, plane_epsilon 1e-3; with cov given, params is only checked).  The launch structure,
+ * the freezing of finished pairs, the convergence rule, the final fitness pass and the errors are those of sslam_seg_register_pairs.
+ * One iteration of a pair from its T = (R, t):
+ *   1. correspondences: exactly step 1 of sslam_seg_register_pairs (the indices are bitwise those of the fitness pass at T).
+ *   2. per accepted pair (source i, target j), in double:  x = R p + t,  r = q - x,  M = (C_j + R C_i R^T)^-1 by cofactors (with
+ *      regularised covariances its eigenvalues lie in [1 / 2, 1 / (2 plane_epsilon)]),  J = [ [x]x | -I ]  for the left perturbation
+ *      T <- exp(delta) T, delta = (w, v).  29 sums: the upper triangle of J^T M J, J^T M r, r^T M r and the count, in the fixed order
+ *      of step 3 of sslam_seg_register_pairs.
+ *   3. H delta = -b by Cholesky.  Fewer than 3 accepted, a pivot that is not positive or a sum or result that is not finite:
+ *      status = SSLAM_ERR_NUMERIC, the pair is finished and T is left as it stood before this pass.
+ *   4. R_new = exp([w]x) R, passed through its unit quaternion (largest-pivot branch) and back, so that R stays a proper rotation to
+ *      1e-12 after any number of iterations;  t_new = exp([w]x) t + v.
+ *   5. iterations += 1; converged when max |T_new - T| <= epsilon over the 12 entries.  Unlike the closed form of the point-to-point
+ *      update, a Gauss-Newton step keeps moving T in its last bits: epsilon = 0 runs a pair to max_iterations.
+ * DEVIATION: M is held fixed within an iteration and rebuilt at the next, and the step is plain Gauss-Newton.  fast_gicp wraps the same
+ * step in Levenberg-Marquardt and PCL's GICP minimises with BFGS; neither was needed on the scenes this project tests.
+ * score is the EUCLIDEAN fitness score at out.T, bitwise what sslam_seg_fitness_scores returns (hdl's getFitnessScore for every method),
+ * so fitness_score_thresh and sslam_information_from_fitness apply unchanged.  max_iterations = 0: T = T0, the fitness pass at T0, and
+ * the covariances are neither read nor computed.  kernel_ms does not include a covariance pass made inside the call.
+ * SSLAM_ERR_INVALID also for params with k or plane_epsilon out of range. */
+typedef struct sslam_gicp_params {
+  int32_t k;                   /* 20    neighbours per covariance, 3 .. 32 */
+  double  plane_epsilon;       /* 1e-3  the eigenvalue along the normal, in (0, 1] */
+} sslam_gicp_params;
+void sslam_gicp_default_params(sslam_gicp_params* p);
+int sslam_seg_cloud_covariances(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, int k, double plane_epsilon, double* cov_out,
+                                int32_t* knn_index_out, double* kernel_ms);
+int sslam_seg_register_pairs_gicp(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
+                                  const double* cov, const sslam_gicp_params* params, int max_iterations, double epsilon, sslam_reg_result* out,
+                                  int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms);
+
 /* ---- map cloud: every cloud at its pose, reduced to one cloud over a SPARSE voxel grid (hdl_graph_slam's
  * MapCloudGenerator::generate(keyframes, resolution) [UPSTREAM, quoted from memory]: transform, concatenate, octree-downsample; the
  * reference planned the call -- mapping::generateMap / opitmizeMap at semantic_graph_slam.cpp:36-40, 72-73, 85-86, commented out) ------
@@ -959,6 +1011,19 @@ int sslam_slam_last_loops(const sslam_slam* s, sslam_loop* out, int max);
 /* wall seconds inside the last sslam_slam_run: [0] the candidate launch with its copies, [1] sslam_seg_register_pairs, [2] sslam_graph_gate,
  * [3] the whole loop stage, the downsampling of the new clouds included.  All zero with loop closure off. */
 int sslam_slam_last_loop_timing(const sslam_slam* s, double seconds[4]);
+/* The scan matcher of step 4 (hdl_graph_slam's registration_method).  SSLAM_REG_ICP, the default: sslam_seg_register_pairs.
+ * SSLAM_REG_GICP: step 0 also computes the covariances of every new keyframe's downsampled cloud (sslam_seg_cloud_covariances with p; NULL:
+ * sslam_gicp_default_params), ONCE per keyframe, and keeps them with the cloud; step 4 calls sslam_seg_register_pairs_gicp with them.  A
+ * keyframe downsampled before GICP was chosen gets its covariances the first time it is packed for a match.  Selection, score test, gate
+ * and edge are untouched, and [1] of sslam_slam_last_loop_timing is the matcher, whichever it is.  A separate call so that
+ * sslam_loop_params keeps its layout; a handle on which it was never made, or made with SSLAM_REG_ICP, runs its ticks bit for bit as
+ * before.  Changing the method or its parameters drops the kept covariances.  Returns 0; SSLAM_ERR_INVALID: a NULL handle, another
+ * method, k outside 3 .. 32, a plane_epsilon that is not finite or not in (0, 1].  Host only: needs no device. */
+#define SSLAM_REG_ICP 0
+#define SSLAM_REG_GICP 1
+int sslam_slam_set_loop_registration(sslam_slam* s, int method, const sslam_gicp_params* p);
+/* *clouds = the keyframe clouds that went through sslam_seg_cloud_covariances since the handle was created.  Returns 0. */
+int sslam_slam_loop_covariance_passes(const sslam_slam* s, int64_t* clouds);
 /* LoopDetector::find_candidates for all new keyframes of a tick in one launch (k_loop_candidates), on its own.  keys: x, y, accum_distance
  * per old keyframe; news: the same per new keyframe.  Old keyframe k passes for new keyframe n when
  *   accum_n - accum_k >= accum_distance_thresh,   d2 <= distance_thresh * distance_thresh with d2 = dx dx + dy dy,

@@ -136,6 +136,11 @@ def load_library():
         "sslam_batch_kernel_time": (ci, [vp, C.c_char_p, dp, C.POINTER(i64)]),
         "sslam_seg_fitness_scores": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, dp]),
         "sslam_seg_register_pairs": (ci, [vp, vp, vp, ci, vp, ci, ci, cd, vp, vp, vp, dp]),
+        "sslam_gicp_default_params": (None, [vp]),
+        "sslam_seg_cloud_covariances": (ci, [vp, vp, vp, ci, ci, cd, vp, vp, dp]),
+        "sslam_seg_register_pairs_gicp": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, ci, cd, vp, vp, vp, dp]),
+        "sslam_slam_set_loop_registration": (ci, [vp, ci, vp]),
+        "sslam_slam_loop_covariance_passes": (ci, [vp, C.POINTER(i64)]),
         "sslam_inf_default_params": (None, [vp]),
         "sslam_information_from_fitness": (ci, [vp, cd, dp]),
         "sslam_slam_set_fitness_information": (ci, [vp, vp, C.c_float, cd]),

@@ -16,6 +16,14 @@ inline int set_error(int code, const char* fmt, ...) {
   last_error_ref() = buf;
   return code;
 }
+// The parameter ranges of generalized ICP (sslam_gicp_params), one copy for the frontend's entry points and the tick's setter
+constexpr int kGicpMinK = 3, kGicpMaxK = 32;
+inline int gicp_check_params(int k, double plane_epsilon) {
+  if (k < kGicpMinK || k > kGicpMaxK) return set_error(-1 /* SSLAM_ERR_INVALID */, "generalized ICP: k = %d outside %d .. %d", k, kGicpMinK, kGicpMaxK);
+  if (!(plane_epsilon > 0.0) || !(plane_epsilon <= 1.0))   // NaN fails both
+    return set_error(-1, "generalized ICP: plane_epsilon must be finite and in (0, 1]");
+  return 0;
+}
 // Largest dynamic-LDS opt-in a kernel may ask for on `device`: the device's own limit (hipDeviceProp_t::sharedMemPerBlockOptin /
 // maxSharedMemoryPerBlock) minus `reserve` bytes for the kernels' static LDS, never more than `want` (the gfx950 figure the plans were
 // sized for).  A part with less LDS than an MI355X then fails with "needs N B of LDS" instead of a failed hipFuncSetAttribute.

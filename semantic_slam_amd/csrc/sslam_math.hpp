@@ -345,4 +345,145 @@ SSLAM_HD bool icp_gn_step(const double sums[29], double T[12]) {
   return true;
 }
 
+// ---- generalized ICP (sslam_seg_cloud_covariances, sslam_seg_register_pairs_gicp) ----------------------------------------------------
+// jacobi4_rotate for a symmetric 3 x 3 matrix
+template <int P, int Q>
+SSLAM_HD void jacobi3_rotate(double (&A)[3][3], double (&V)[3][3]) {
+  const double apq = A[P][Q];
+  if (apq == 0.0) return;
+  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double akp = A[k][P], akq = A[k][Q];
+    A[k][P] = c * akp - s * akq; A[k][Q] = s * akp + c * akq;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double apk = A[P][k], aqk = A[Q][k];
+    A[P][k] = c * apk - s * aqk; A[Q][k] = s * apk + c * aqk;
+  }
+  A[P][Q] = 0.0; A[Q][P] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double vkp = V[k][P], vkq = V[k][Q];
+    V[k][P] = c * vkp - s * vkq; V[k][Q] = s * vkp + c * vkq;
+  }
+}
+// fast_gicp's PLANE regularisation of a neighbourhood covariance C (xx xy xz yy yz zz): U diag(l) U^T -> U diag(eps, 1, 1) U^T with eps
+// at the smallest eigenvalue, which is I - (1 - eps) n n^T for the unit eigenvector n of that eigenvalue (the first among equal
+// diagonal entries after the sweeps: with l0 = l1 any minimiser may come out).  Cyclic Jacobi sweeps, as horn_rigid runs them.
+SSLAM_HD void gicp_plane_covariance(const double C[6], double eps, double out[6]) {
+  double A[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
+  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+    const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+    if (off <= 1e-40 * dia) break;
+    jacobi3_rotate<0, 1>(A, V); jacobi3_rotate<0, 2>(A, V); jacobi3_rotate<1, 2>(A, V);
+  }
+  double best = A[0][0];
+  int kb = 0;
+  if (A[1][1] < best) { best = A[1][1]; kb = 1; }
+  if (A[2][2] < best) { best = A[2][2]; kb = 2; }
+  const double m0 = kb == 0 ? 1.0 : 0.0, m1 = kb == 1 ? 1.0 : 0.0, m2 = kb == 2 ? 1.0 : 0.0;   // 0 / 1 weights: see horn_rigid
+  double x = (m0 * V[0][0] + m1 * V[0][1]) + m2 * V[0][2];
+  double y = (m0 * V[1][0] + m1 * V[1][1]) + m2 * V[1][2];
+  double z = (m0 * V[2][0] + m1 * V[2][1]) + m2 * V[2][2];
+  const double nn = sqrt(x * x + y * y + z * z);
+  x /= nn; y /= nn; z /= nn;
+  const double w = 1.0 - eps;
+  out[0] = 1.0 - w * x * x; out[1] = -w * x * y; out[2] = -w * x * z;
+  out[3] = 1.0 - w * y * y; out[4] = -w * y * z; out[5] = 1.0 - w * z * z;
+}
+// The contribution of one correspondence to a Gauss-Newton pass of generalized ICP.  x = R p + t, r = q - x, M = (Ct + R Cs R^T)^-1 by
+// cofactors (both covariances as xx xy xz yy yz zz), J = [ [x]x | -I ] for the left perturbation T <- exp(delta) T, delta = (w, v):
+// a[0..20] = J^T M J (upper triangle by rows), a[21..26] = J^T M r, a[27] = r^T M r, a[28] = 1 -- the layout icp_gn_step reads.
+SSLAM_HD void gicp_point_sums(const double T[12], const double p[3], const double q[3], const double Cs[6], const double Ct[6], double (&a)[29]) {
+  const double x[3] = {(T[0] * p[0] + T[1] * p[1]) + T[2] * p[2] + T[9], (T[3] * p[0] + T[4] * p[1]) + T[5] * p[2] + T[10],
+                       (T[6] * p[0] + T[7] * p[1]) + T[8] * p[2] + T[11]};
+  const double r[3] = {q[0] - x[0], q[1] - x[1], q[2] - x[2]};
+  // B = R Cs, S = Ct + B R^T (symmetric)
+  const double cs[3][3] = {{Cs[0], Cs[1], Cs[2]}, {Cs[1], Cs[3], Cs[4]}, {Cs[2], Cs[4], Cs[5]}};
+  double B[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) B[i][j] = (T[3 * i] * cs[0][j] + T[3 * i + 1] * cs[1][j]) + T[3 * i + 2] * cs[2][j];
+  auto brt = [&](int i, int j) { return (B[i][0] * T[3 * j] + B[i][1] * T[3 * j + 1]) + B[i][2] * T[3 * j + 2]; };
+  const double sxx = Ct[0] + brt(0, 0), sxy = Ct[1] + brt(0, 1), sxz = Ct[2] + brt(0, 2), syy = Ct[3] + brt(1, 1), syz = Ct[4] + brt(1, 2),
+               szz = Ct[5] + brt(2, 2);
+  const double cxx = syy * szz - syz * syz, cxy = sxz * syz - sxy * szz, cxz = sxy * syz - sxz * syy;
+  const double cyy = sxx * szz - sxz * sxz, cyz = sxy * sxz - sxx * syz, czz = sxx * syy - sxy * sxy;
+  const double det = (sxx * cxx + sxy * cxy) + sxz * cxz;
+  const double M[3][3] = {{cxx / det, cxy / det, cxz / det}, {cxy / det, cyy / det, cyz / det}, {cxz / det, cyz / det, czz / det}};
+  const double J[3][6] = {{0.0, -x[2], x[1], -1.0, 0.0, 0.0}, {x[2], 0.0, -x[0], 0.0, -1.0, 0.0}, {-x[1], x[0], 0.0, 0.0, 0.0, -1.0}};
+  double MJ[3][6], Mr[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) MJ[i][c] = (M[i][0] * J[0][c] + M[i][1] * J[1][c]) + M[i][2] * J[2][c];
+    Mr[i] = (M[i][0] * r[0] + M[i][1] * r[1]) + M[i][2] * r[2];
+  }
+  int m = 0;
+#pragma unroll
+  for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+    for (int cc = rr; cc < 6; ++cc) a[m++] = (J[0][rr] * MJ[0][cc] + J[1][rr] * MJ[1][cc]) + J[2][rr] * MJ[2][cc];
+#pragma unroll
+  for (int rr = 0; rr < 6; ++rr) a[21 + rr] = (J[0][rr] * Mr[0] + J[1][rr] * Mr[1]) + J[2][rr] * Mr[2];
+  a[27] = (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
+  a[28] = 1.0;
+}
+// Unit quaternion of a rotation matrix (row-major), the branch with the largest pivot, as INTEGRATION.md section 2 spells it out
+SSLAM_HD Quat quat_of_rotation(const double R[9]) {
+  Quat q;
+  const double tr = R[0] + R[4] + R[8];
+  if (tr > 0)                          { const double s = 2 * sqrt(1 + tr);                 q.w = s / 4; q.x = (R[7] - R[5]) / s; q.y = (R[2] - R[6]) / s; q.z = (R[3] - R[1]) / s; }
+  else if (R[0] > R[4] && R[0] > R[8]) { const double s = 2 * sqrt(1 + R[0] - R[4] - R[8]); q.x = s / 4; q.w = (R[7] - R[5]) / s; q.y = (R[1] + R[3]) / s; q.z = (R[2] + R[6]) / s; }
+  else if (R[4] > R[8])                { const double s = 2 * sqrt(1 + R[4] - R[0] - R[8]); q.y = s / 4; q.w = (R[2] - R[6]) / s; q.x = (R[1] + R[3]) / s; q.z = (R[5] + R[7]) / s; }
+  else                                 { const double s = 2 * sqrt(1 + R[8] - R[0] - R[4]); q.z = s / 4; q.w = (R[3] - R[1]) / s; q.x = (R[2] + R[6]) / s; q.y = (R[5] + R[7]) / s; }
+  const double n = sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+  return {q.x / n, q.y / n, q.z / n, q.w / n};
+}
+// One Gauss-Newton step of generalized ICP from the 29 sums of a pass: H delta = -b by Cholesky (no damping: M is held fixed within the
+// pass), R_new = exp([w]x) R passed through its unit quaternion and qmat (R stays a proper rotation after any number of steps),
+// t_new = exp([w]x) t + v.  false, with Tn unwritten: a sum that is not finite, fewer than 3 correspondences, a pivot that is not positive.
+SSLAM_HD bool gicp_gn_step(const double sums[29], const double T[12], double Tn[12]) {
+  bool fin = true;
+  for (int k = 0; k < 29; ++k) fin = fin && isfinite(sums[k]);
+  if (!fin || sums[28] < 3.0) return false;
+  double A[36], L[36];
+  for (int k = 0; k < 36; ++k) L[k] = 0;
+  int m = 0;
+  for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { A[r * 6 + c] = A[c * 6 + r] = sums[m++]; }
+  for (int j = 0; j < 6; ++j) {
+    double dsum = A[j * 6 + j];
+    for (int k = 0; k < j; ++k) dsum -= L[j * 6 + k] * L[j * 6 + k];
+    if (!(dsum > 0)) return false;
+    L[j * 6 + j] = sqrt(dsum);
+    for (int i = j + 1; i < 6; ++i) { double v = A[i * 6 + j]; for (int k = 0; k < j; ++k) v -= L[i * 6 + k] * L[j * 6 + k]; L[i * 6 + j] = v / L[j * 6 + j]; }
+  }
+  double y[6], dx[6];
+  for (int i = 0; i < 6; ++i) { double v = -sums[21 + i]; for (int k = 0; k < i; ++k) v -= L[i * 6 + k] * y[k]; y[i] = v / L[i * 6 + i]; }
+  for (int i = 5; i >= 0; --i) { double v = y[i]; for (int k = i + 1; k < 6; ++k) v -= L[k * 6 + i] * dx[k]; dx[i] = v / L[i * 6 + i]; }
+  const double wx = dx[0], wy = dx[1], wz = dx[2], th = sqrt(wx * wx + wy * wy + wz * wz);
+  double E[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (th > 0) {
+    const double sa = sin(th) / th, bq = (1.0 - cos(th)) / (th * th);
+    const double K[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { double kk = 0; for (int q = 0; q < 3; ++q) kk += K[r * 3 + q] * K[q * 3 + c]; E[r * 3 + c] += sa * K[r * 3 + c] + bq * kk; }
+  }
+  double Rn[9];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) Rn[r * 3 + c] = E[r * 3] * T[c] + E[r * 3 + 1] * T[3 + c] + E[r * 3 + 2] * T[6 + c];
+    Tn[9 + r] = E[r * 3] * T[9] + E[r * 3 + 1] * T[10] + E[r * 3 + 2] * T[11] + dx[3 + r];
+  }
+  const Mat3 Rq = qmat(quat_of_rotation(Rn));
+  for (int k = 0; k < 9; ++k) Tn[k] = Rq.m[k];
+  for (int k = 0; k < 12; ++k) if (!isfinite(Tn[k])) return false;
+  return true;
+}
+
 }  // namespace sslam

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <cstdio>
@@ -2530,6 +2531,170 @@ __global__ __launch_bounds__(64) void k_reg_step(const int* __restrict__ seg0, c
   }
 }
 
+// ---- generalized ICP (fast_gicp / pcl::GeneralizedIterativeClosestPoint [UPSTREAM]: hdl_graph_slam's registration_method GICP / FAST_GICP) ----
+// k_knn_cov: the covariance of every point's k nearest neighbours inside its own cloud, regularised to a plane (gicp_plane_covariance).
+// One workgroup per block of kKnnThreads consecutive query points of ONE cloud (the KnnBlock table), one thread per query.  The cloud
+// streams through LDS kKnnThreads points at a time; every thread keeps the k smallest (d2, index) of its query in two LDS columns
+// (replace-the-maximum, as k_sor_mean_distance keeps its distances).  Candidates arrive in ascending index, so a candidate enters only
+// with a strictly smaller d2 than the column's maximum or into an empty slot (+inf, INT_MAX): the set is the k smallest by (d2, index)
+// whatever the tile or block size.  The columns are then sorted ascending; mean and covariance run in double in that order.
+constexpr int kKnnThreads = 128;
+static_assert(SSLAM_ERR_INVALID == -1, "gicp_check_params (csrc/sslam_common.hpp) returns it by value");
+static_assert(kKnnThreads * (3 * sizeof(float) + kGicpMaxK * (sizeof(float) + sizeof(int))) <= 64 * 1024, "the columns of the largest k fit the LDS of a workgroup");
+struct KnnBlock { int c0, n, q0; };   // first point of the cloud in xyz, its points, the block's first query inside the cloud
+__global__ __launch_bounds__(kKnnThreads) void k_knn_cov(const float* __restrict__ xyz, const KnnBlock* __restrict__ blocks, int k, double eps,
+                                                        double* __restrict__ cov, int* __restrict__ knn) {
+  extern __shared__ float sm[];
+  float* tile = sm;                                   // [kKnnThreads][3]
+  float* bd = sm + kKnnThreads * 3;                   // [k][kKnnThreads]
+  int* bi = (int*)(bd + k * kKnnThreads);             // [k][kKnnThreads]
+  const KnnBlock B = blocks[blockIdx.x];
+  const int tid = threadIdx.x, i = B.q0 + tid;
+  const float* pts = xyz + 3 * (size_t)B.c0;
+  const bool valid_i = i < B.n;
+  float qx = 0, qy = 0, qz = 0;
+  bool fin = false;
+  if (valid_i) { qx = pts[3 * (size_t)i]; qy = pts[3 * (size_t)i + 1]; qz = pts[3 * (size_t)i + 2]; fin = isfinite(qx) && isfinite(qy) && isfinite(qz); }
+  const float inf = __int_as_float(0x7f800000), nanf_ = __int_as_float(0x7fc00000);
+  for (int j = 0; j < k; ++j) { bd[j * kKnnThreads + tid] = inf; bi[j * kKnnThreads + tid] = INT_MAX; }
+  float max_d = inf;
+  int max_i = INT_MAX, arg_max = 0;
+  for (int t0 = 0; t0 < B.n; t0 += kKnnThreads) {
+    __syncthreads();
+    const int c = t0 + tid;
+    float cx = nanf_, cy = nanf_, cz = nanf_;
+    if (c < B.n) {
+      const float x = pts[3 * (size_t)c], y = pts[3 * (size_t)c + 1], z = pts[3 * (size_t)c + 2];
+      if (isfinite(x) && isfinite(y) && isfinite(z)) { cx = x; cy = y; cz = z; }
+    }
+    tile[tid * 3] = cx; tile[tid * 3 + 1] = cy; tile[tid * 3 + 2] = cz;
+    __syncthreads();
+    if (!fin) continue;
+    const int m = min(kKnnThreads, B.n - t0);
+    for (int j = 0; j < m; ++j) {
+      const float dx = qx - tile[j * 3], dy = qy - tile[j * 3 + 1], dz = qz - tile[j * 3 + 2];
+      const float d = (dx * dx + dy * dy) + dz * dz;
+      if (d < max_d || (d == max_d && t0 + j < max_i)) {    // a NaN candidate (not a finite point) fails both
+        bd[arg_max * kKnnThreads + tid] = d; bi[arg_max * kKnnThreads + tid] = t0 + j;
+        max_d = bd[tid]; max_i = bi[tid]; arg_max = 0;
+        for (int q = 1; q < k; ++q) {
+          const float v = bd[q * kKnnThreads + tid];
+          const int w = bi[q * kKnnThreads + tid];
+          if (v > max_d || (v == max_d && w > max_i)) { max_d = v; max_i = w; arg_max = q; }
+        }
+      }
+    }
+  }
+  if (!valid_i) return;
+  double* out = cov + 6 * ((size_t)B.c0 + i);
+  int* kout = knn ? knn + (size_t)k * ((size_t)B.c0 + i) : nullptr;
+  if (!fin) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) out[q] = 0.0;
+    if (kout) for (int q = 0; q < k; ++q) kout[q] = -1;
+    return;
+  }
+  for (int a = 1; a < k; ++a) {          // ascending insertion sort by (d2, index); the empty slots end up last
+    const float v = bd[a * kKnnThreads + tid];
+    const int w = bi[a * kKnnThreads + tid];
+    int b = a - 1;
+    while (b >= 0 && (bd[b * kKnnThreads + tid] > v || (bd[b * kKnnThreads + tid] == v && bi[b * kKnnThreads + tid] > w))) {
+      bd[(b + 1) * kKnnThreads + tid] = bd[b * kKnnThreads + tid]; bi[(b + 1) * kKnnThreads + tid] = bi[b * kKnnThreads + tid]; --b;
+    }
+    bd[(b + 1) * kKnnThreads + tid] = v; bi[(b + 1) * kKnnThreads + tid] = w;
+  }
+  int m = 0;
+  while (m < k && bi[m * kKnnThreads + tid] != INT_MAX) ++m;
+  if (kout) for (int q = 0; q < k; ++q) kout[q] = q < m ? bi[q * kKnnThreads + tid] : -1;
+  if (m < 3) { out[0] = 1.0; out[1] = 0.0; out[2] = 0.0; out[3] = 1.0; out[4] = 0.0; out[5] = 1.0; return; }
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (int q = 0; q < m; ++q) {
+    const float* p = pts + 3 * (size_t)bi[q * kKnnThreads + tid];
+    sx += (double)p[0]; sy += (double)p[1]; sz += (double)p[2];
+  }
+  const double mx = sx / (double)m, my = sy / (double)m, mz = sz / (double)m;
+  double C[6] = {0, 0, 0, 0, 0, 0};
+  for (int q = 0; q < m; ++q) {
+    const float* p = pts + 3 * (size_t)bi[q * kKnnThreads + tid];
+    const double ax = (double)p[0] - mx, ay = (double)p[1] - my, az = (double)p[2] - mz;
+    C[0] += ax * ax; C[1] += ax * ay; C[2] += ax * az; C[3] += ay * ay; C[4] += ay * az; C[5] += az * az;
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) C[q] /= (double)m;
+  double P[6];
+  gicp_plane_covariance(C, eps, P);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) out[q] = P[q];
+}
+// One iteration of ALL pairs is  reset best -> k_nn_pairs -> k_gicp_sums -> k_gicp_step: the structure of the point-to-point loop above.
+//   k_gicp_sums  the run table and the reduction tree of k_reg_sums; an accepted point i with its target j contributes gicp_point_sums
+//                (csrc/sslam_math.hpp) at the pair's double T with the covariances of source point i and target point j: 29 sums.
+//   k_gicp_step  one wave per pair: lanes 0..28 add the run records in ascending run order, lane 0 takes gicp_gn_step and applies the
+//                status and convergence rules of k_reg_step.
+__global__ __launch_bounds__(kNnSeg) void k_gicp_sums(const float* __restrict__ xyz, const double* __restrict__ cov, const NnPair* __restrict__ pairs,
+                                                     const NnSeg* __restrict__ segs, const unsigned long long* __restrict__ best,
+                                                     const RegState* __restrict__ st, double* __restrict__ part) {
+  __shared__ double red[kNnSeg / 64][kIcpSums];
+  const NnSeg sg = segs[blockIdx.x];
+  if (st[sg.pair].done) return;          // the same for the whole workgroup
+  const NnPair P = pairs[sg.pair];
+  const int tid = threadIdx.x, i = sg.seg * kNnSeg + tid;
+  double a[kIcpSums];
+#pragma unroll
+  for (int k = 0; k < kIcpSums; ++k) a[k] = 0.0;
+  if (i < P.ns) {
+    const unsigned long long key = best[P.qoff + i];
+    if (key != ~0ull && (double)__uint_as_float((unsigned)(key >> 32)) <= P.max_range) {
+      const int j = (int)(unsigned)(key & 0xffffffffull);   // < P.nt: k_nn_pairs only ever writes indices of the pair's target cloud
+      const float* ps = xyz + 3 * (size_t)(P.s0 + i);
+      const float* qt = xyz + 3 * (size_t)(P.t0 + j);
+      const double* cs = cov + 6 * (size_t)(P.s0 + i);
+      const double* ct = cov + 6 * (size_t)(P.t0 + j);
+      const double p[3] = {(double)ps[0], (double)ps[1], (double)ps[2]}, q[3] = {(double)qt[0], (double)qt[1], (double)qt[2]};
+      const double Cs[6] = {cs[0], cs[1], cs[2], cs[3], cs[4], cs[5]}, Ct[6] = {ct[0], ct[1], ct[2], ct[3], ct[4], ct[5]};
+      double T[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) T[k] = st[sg.pair].T[k];
+      gicp_point_sums(T, p, q, Cs, Ct, a);
+    }
+  }
+  block_sum4(a, red, part + (size_t)blockIdx.x * kIcpSums);
+}
+__global__ __launch_bounds__(64) void k_gicp_step(const int* __restrict__ seg0, const double* __restrict__ part, double epsilon, NnPair* __restrict__ pairs,
+                                                  RegState* __restrict__ st, int* __restrict__ live) {
+  __shared__ double sums[kIcpSums];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  if (st[p].done) return;
+  if (tid < kIcpSums) {
+    double v = 0.0;
+    for (int r = seg0[p]; r < seg0[p + 1]; ++r) v += part[(size_t)r * kIcpSums + tid];   // ascending run order
+    sums[tid] = v;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double Tn[12], moved = 0.0;
+  if (!gicp_gn_step(sums, st[p].T, Tn)) {   // T stays as it stood before this pass
+    st[p].status = SSLAM_ERR_NUMERIC;
+    st[p].done = 1;
+    atomicSub(live, 1);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) moved = fmax(moved, fabs(Tn[k] - st[p].T[k]));
+#pragma unroll
+  for (int k = 0; k < 12; ++k) st[p].T[k] = Tn[k];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) pairs[p].R[k] = (float)Tn[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pairs[p].t[k] = (float)Tn[9 + k];
+  st[p].iterations += 1;
+  if (moved <= epsilon) {
+    st[p].converged = 1;
+    st[p].done = 1;
+    atomicSub(live, 1);
+  }
+}
+
 // ---- k-means of the legacy path (plane_segmentation::computeKmeans -> cv::kmeans, plane_segmentation.cpp:524-535) -----------------
 // assignment step: nearest centre in float32 (squared distance accumulated coordinate by coordinate; ties -> lowest centre), and for
 // the next centre update the coordinate sums / counts per cluster and the compactness, all in 2^-20 fixed point (integer atomics)
@@ -4221,11 +4386,81 @@ int sslam_seg_fitness_scores(sslam_seg* s, const float* xyz, const int32_t* clou
   return n_pairs;
 }
 
-// ---- scan matching: nearest-neighbour ICP of cloud pairs (k_nn_pairs, k_reg_sums, k_reg_step; k_nn_finish at the end) ----------------
-int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
-                             int max_iterations, double epsilon, sslam_reg_result* out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
+// ---- per-point covariances of generalized ICP (k_knn_cov) ----------------------------------------------------------------------------
+void sslam_gicp_default_params(sslam_gicp_params* p) {
+  if (!p) return;
+  p->k = 20; p->plane_epsilon = 1e-3;   // fast_gicp's k_correspondences and its PLANE regularisation [UPSTREAM, quoted from memory]
+}
+// k_knn_cov over the clouds that `wanted` marks (NULL: all) of the device's point table: the block table goes up, one launch; with
+// `timed`, f_e0 and f_e1 are recorded right before and right after the launch (nothing but the kernel lies between them)
+static int knn_cov_launch(sslam_seg* s, DevGuard& g, const float* d_xyz, const int32_t* cloud_start, int n_clouds, const unsigned char* wanted, int k,
+                          double plane_epsilon, double* d_cov, int* d_knn, bool timed) {
+  std::vector<KnnBlock> blocks;
+  for (int c = 0; c < n_clouds; ++c) {
+    if (wanted && !wanted[c]) continue;
+    const int n = cloud_start[c + 1] - cloud_start[c];
+    for (int q0 = 0; q0 < n; q0 += kKnnThreads) blocks.push_back(KnnBlock{cloud_start[c], n, q0});
+  }
+  if (blocks.empty()) {
+    if (timed) { SSLAM_HIP_TRY(hipEventRecord(s->f_e0, s->stream)); SSLAM_HIP_TRY(hipEventRecord(s->f_e1, s->stream)); }
+    return 0;
+  }
+  KnnBlock* d_blocks = nullptr;
+  int rc;
+  if ((rc = g.alloc(&d_blocks, blocks.size()))) return rc;
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(KnnBlock), hipMemcpyHostToDevice, s->stream));
+  const size_t lds = (size_t)kKnnThreads * (3 * sizeof(float) + (size_t)k * (sizeof(float) + sizeof(int)));   // 21.5 KB at k = 20, 33.5 KB at 32
+  if (timed) SSLAM_HIP_TRY(hipEventRecord(s->f_e0, s->stream));
+  hipLaunchKernelGGL(k_knn_cov, dim3((unsigned)blocks.size()), dim3(kKnnThreads), lds, s->stream, d_xyz, d_blocks, k, plane_epsilon, d_cov, d_knn);
+  if (timed) SSLAM_HIP_TRY(hipEventRecord(s->f_e1, s->stream));
+  SSLAM_HIP_TRY(hipGetLastError());
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));   // the block table leaves scope with the caller's vector
+  return 0;
+}
+int sslam_seg_cloud_covariances(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, int k, double plane_epsilon, double* cov_out,
+                                int32_t* knn_index_out, double* kernel_ms) {
+  if (!s || !cloud_start || n_clouds < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = nn_check_clouds(xyz, cloud_start, n_clouds, nullptr, 0);
+  if (rc) return rc;
+  const int n_points = cloud_start[n_clouds];
+  if (n_points > 0 && !cov_out) return set_error(SSLAM_ERR_INVALID, "null cov_out");
+  if ((rc = gicp_check_params(k, plane_epsilon))) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  rc = seg_device(s);
+  if (rc) return rc;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (n_points == 0) return 0;
+  DevGuard g;
+  float* d_xyz = nullptr;
+  double* d_cov = nullptr;
+  int* d_knn = nullptr;
+  if ((rc = g.alloc(&d_xyz, (size_t)n_points * 3)) || (rc = g.alloc(&d_cov, (size_t)n_points * 6)) ||
+      (knn_index_out && (rc = g.alloc(&d_knn, (size_t)n_points * k)))) return rc;
+  if (!s->f_e0) { SSLAM_HIP_TRY(hipEventCreate(&s->f_e0)); SSLAM_HIP_TRY(hipEventCreate(&s->f_e1)); }
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_xyz, xyz, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  // points before cloud_start[0] belong to no cloud: their entries are zeros
+  SSLAM_HIP_TRY(hipMemsetAsync(d_cov, 0, (size_t)n_points * 6 * sizeof(double), s->stream));
+  if (d_knn) SSLAM_HIP_TRY(hipMemsetAsync(d_knn, 0xff, (size_t)n_points * k * sizeof(int), s->stream));
+  if ((rc = knn_cov_launch(s, g, d_xyz, cloud_start, n_clouds, nullptr, k, plane_epsilon, d_cov, d_knn, true))) return rc;
+  SSLAM_HIP_TRY(hipMemcpyAsync(cov_out, d_cov, (size_t)n_points * 6 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  if (d_knn) SSLAM_HIP_TRY(hipMemcpyAsync(knn_index_out, d_knn, (size_t)n_points * k * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if (kernel_ms) {
+    float ms = 0.0f;
+    SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->f_e0, s->f_e1));
+    *kernel_ms = (double)ms;
+  }
+  return n_points;
+}
+
+// ---- scan matching: nearest-neighbour ICP of cloud pairs (k_nn_pairs, k_reg_sums, k_reg_step; k_nn_finish at the end), and its
+// generalized form (k_gicp_sums, k_gicp_step in their place; gp != NULL): one host loop for both ------------------------------------------
+static int register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
+                          const double* cov, const sslam_gicp_params* gp, int max_iterations, double epsilon, sslam_reg_result* out,
+                          int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
   if (!s || !cloud_start || n_clouds < 0 || n_pairs < 0 || (n_pairs > 0 && (!pairs || !out)) || max_iterations < 0 || !(epsilon >= 0.0))
     return set_error(SSLAM_ERR_INVALID, "bad argument");
+  if (gp) { const int rcp = gicp_check_params(gp->k, gp->plane_epsilon); if (rcp) return rcp; }
   std::vector<sslam_fitness_pair> fp(n_pairs);   // the search reads a pair as the fitness pass does: T = the initial guess, max_range = max_corr2
   for (int p = 0; p < n_pairs; ++p) {
     fp[p].target = pairs[p].target; fp[p].source = pairs[p].source; fp[p].max_range = pairs[p].max_corr2;
@@ -4253,8 +4488,21 @@ int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* clou
   RegState* d_st = nullptr;
   int *d_seg0 = nullptr, *d_live = nullptr;
   double* d_part = nullptr;
+  const int n_sums = gp ? kIcpSums : kRegSums;
+  const size_t n_points = (size_t)cloud_start[n_clouds];
+  double* d_cov = nullptr;
   if ((rc = nn_upload(s, g, pl, xyz, cloud_start[n_clouds], d)) || (rc = g.alloc(&d_st, (size_t)n_pairs)) || (rc = g.alloc(&d_seg0, seg0.size())) ||
-      (rc = g.alloc(&d_live, 1)) || (rc = g.alloc(&d_part, pl.segs.size() * kRegSums))) return rc;
+      (rc = g.alloc(&d_live, 1)) || (rc = g.alloc(&d_part, pl.segs.size() * n_sums)) || (gp && (rc = g.alloc(&d_cov, n_points * 6)))) return rc;
+  if (gp && max_iterations > 0 && n_points > 0) {   // the covariances: the caller's, or those of every cloud a pair names, each cloud once
+    if (cov) {
+      SSLAM_HIP_TRY(hipMemcpyAsync(d_cov, cov, n_points * 6 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    } else {
+      std::vector<unsigned char> wanted(n_clouds, 0);
+      for (int p = 0; p < n_pairs; ++p) wanted[pairs[p].target] = wanted[pairs[p].source] = 1;
+      SSLAM_HIP_TRY(hipMemsetAsync(d_cov, 0, n_points * 6 * sizeof(double), s->stream));
+      if ((rc = knn_cov_launch(s, g, d.xyz, cloud_start, n_clouds, wanted.data(), gp->k, gp->plane_epsilon, d_cov, nullptr, false))) return rc;
+    }
+  }
   int live = n_pairs;
   SSLAM_HIP_TRY(hipMemcpyAsync(d_st, h_st.data(), h_st.size() * sizeof(RegState), hipMemcpyHostToDevice, s->stream));
   SSLAM_HIP_TRY(hipMemcpyAsync(d_seg0, seg0.data(), seg0.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
@@ -4266,6 +4514,11 @@ int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* clou
     const int n = std::min(8, max_iterations - it);
     for (int k = 0; k < n; ++k) {
       if ((rc = nn_search(s, pl, d))) return rc;
+      if (gp) {
+        if (!pl.segs.empty()) hipLaunchKernelGGL(k_gicp_sums, dim3((unsigned)pl.segs.size()), dim3(kNnSeg), 0, s->stream, d.xyz, d_cov, d.pairs, d.segs, d.best, d_st, d_part);
+        hipLaunchKernelGGL(k_gicp_step, dim3((unsigned)n_pairs), dim3(64), 0, s->stream, d_seg0, d_part, epsilon, d.pairs, d_st, d_live);
+        continue;
+      }
       if (!pl.segs.empty()) hipLaunchKernelGGL(k_reg_sums, dim3((unsigned)pl.segs.size()), dim3(kNnSeg), 0, s->stream, d.xyz, d.pairs, d.segs, d.best, d_st, d_part);
       hipLaunchKernelGGL(k_reg_step, dim3((unsigned)n_pairs), dim3(64), 0, s->stream, d_seg0, d_part, epsilon, d.pairs, d_st, d_live);
     }
@@ -4286,6 +4539,18 @@ int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* clou
     out[p].iterations = S.iterations; out[p].converged = S.converged; out[p].status = S.status;
   }
   return n_pairs;
+}
+int sslam_seg_register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
+                             int max_iterations, double epsilon, sslam_reg_result* out, int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
+  return register_pairs(s, xyz, cloud_start, n_clouds, pairs, n_pairs, nullptr, nullptr, max_iterations, epsilon, out, nn_index_out, nn_dist2_out, kernel_ms);
+}
+int sslam_seg_register_pairs_gicp(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
+                                  const double* cov, const sslam_gicp_params* params, int max_iterations, double epsilon, sslam_reg_result* out,
+                                  int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
+  sslam_gicp_params gp;
+  sslam_gicp_default_params(&gp);
+  if (params) gp = *params;
+  return register_pairs(s, xyz, cloud_start, n_clouds, pairs, n_pairs, cov, &gp, max_iterations, epsilon, out, nn_index_out, nn_dist2_out, kernel_ms);
 }
 
 void sslam_inf_default_params(sslam_inf_params* p) {

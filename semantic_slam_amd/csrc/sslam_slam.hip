@@ -346,6 +346,7 @@ struct KeyFrame {
   bool presegmented = false;
   std::vector<float> ds;                  // loop closure: the downsampled cloud (xyz), kept for the rest of the run
   bool has_ds = false;
+  std::vector<double> cov;                // loop registration GICP: 6 doubles per point of ds, computed once, kept with it
   bool map_done = false;                  // map clouds: this keyframe's cloud has been looked at (appended, or found empty)
 };
 
@@ -413,6 +414,9 @@ struct sslam_slam {
   // sslam_slam_set_loop_closure: candidate search, scan match, gate and loop edge inside the tick
   bool loop_on = false;
   sslam_loop_params loop_P{};
+  int loop_method = SSLAM_REG_ICP;        // sslam_slam_set_loop_registration
+  sslam_gicp_params loop_gicp{20, 1e-3};
+  int64_t loop_cov_passes = 0;            // clouds that went through sslam_seg_cloud_covariances so far
   double last_edge_accum = 0;             // accum_distance of the keyframe that got the last loop edge (hdl's last_edge_accum_distance)
   std::vector<sslam_loop> loops;          // records of the last run()
   double loop_seconds[4] = {0, 0, 0, 0};  // candidates, registration, gate, the whole stage (downsampling included) of the last run()
@@ -838,13 +842,25 @@ void measurement_of_T(const double* R, double z[7]) {
   else                                 { const double q = 2 * std::sqrt(1 + R[8] - R[0] - R[4]); z[5] = q / 4; z[6] = (R[3] - R[1]) / q; z[3] = (R[2] + R[6]) / q; z[4] = (R[5] + R[7]) / q; }
 }
 
+// loop registration GICP: the covariances of a keyframe's downsampled cloud, once per keyframe
+int keyframe_covariances(sslam_slam* s, KeyFrame& kf) {
+  if (s->loop_method != SSLAM_REG_GICP || !kf.has_ds || kf.cov.size() == 2 * kf.ds.size()) return 0;
+  const int32_t start[2] = {0, (int32_t)(kf.ds.size() / 3)};
+  kf.cov.resize(2 * kf.ds.size());
+  const int rc = sslam_seg_cloud_covariances(s->seg, kf.ds.data(), start, 1, s->loop_gicp.k, s->loop_gicp.plane_epsilon, kf.cov.data(), nullptr, nullptr);
+  if (rc < 0) { kf.cov.clear(); return rc; }
+  s->loop_cov_passes += 1;
+  return 0;
+}
+
 // the downsampled cloud of every new keyframe that carries one; before the association loop, which drops the raw clouds
 int downsample_new_keyframes(sslam_slam* s) {
   for (auto& kf : s->new_keyframes) {
     if (kf->cloud.empty() || kf->has_ds) continue;
-    const int rc = downsampled_cloud(s, *kf, s->loop_P.voxel_leaf, kf->ds);
+    int rc = downsampled_cloud(s, *kf, s->loop_P.voxel_leaf, kf->ds);
     if (rc < 0) return rc;
     kf->has_ds = !kf->ds.empty();
+    if ((rc = keyframe_covariances(s, *kf)) < 0) return rc;      // nothing to do without a cloud or with SSLAM_REG_ICP
   }
   return 0;
 }
@@ -929,17 +945,27 @@ int close_loops(sslam_slam* s) {
   std::vector<float> xyz;
   std::vector<int32_t> start{0};
   std::vector<int> cloud_of_old(n_keys, -1), first_pair(n_new, 0);
-  auto pack = [&](const std::vector<float>& ds) { xyz.insert(xyz.end(), ds.begin(), ds.end()); start.push_back((int32_t)(xyz.size() / 3)); return (int)start.size() - 2; };
+  const bool gicp = s->loop_method == SSLAM_REG_GICP;
+  std::vector<double> cov;                // GICP: the kept covariances of the packed clouds, in step with xyz
+  auto pack = [&](KeyFrame& kf) -> int {
+    if (gicp) {                           // a keyframe downsampled before GICP was chosen gets its covariances here, once
+      const int rcc = keyframe_covariances(s, kf);
+      if (rcc < 0) return rcc;
+      cov.insert(cov.end(), kf.cov.begin(), kf.cov.end());
+    }
+    xyz.insert(xyz.end(), kf.ds.begin(), kf.ds.end()); start.push_back((int32_t)(xyz.size() / 3)); return (int)start.size() - 2;
+  };
   std::vector<sslam_reg_pair> pairs;
   for (int j = 0; j < n_new; ++j) {
     first_pair[j] = (int)pairs.size();
     const int nc = std::min<int>(count[j], cap);
     if (nc == 0) continue;
-    const int target = pack(s->new_keyframes[news[j].kf]->ds);
+    const int target = pack(*s->new_keyframes[news[j].kf]);
+    if (target < 0) return target;
     const Pose inv = inverse(news[j].est);
     for (int c = 0; c < nc; ++c) {
       const int k = cand[(size_t)j * cap + c];
-      if (cloud_of_old[k] < 0) cloud_of_old[k] = pack(s->keyframes[olds[k].kf]->ds);
+      if (cloud_of_old[k] < 0 && (cloud_of_old[k] = pack(*s->keyframes[olds[k].kf])) < 0) return cloud_of_old[k];
       const Pose rel = compose(inv, olds[k].est);
       sslam_reg_pair R;
       R.target = target; R.source = cloud_of_old[k];
@@ -953,8 +979,12 @@ int close_loops(sslam_slam* s) {
   if (pairs.empty()) return 0;
   std::vector<sslam_reg_result> reg(pairs.size());
   t0 = now_s();
-  rc = sslam_seg_register_pairs(s->seg, xyz.data(), start.data(), (int)start.size() - 1, pairs.data(), (int)pairs.size(), P.max_iterations, P.epsilon,
-                                reg.data(), nullptr, nullptr, nullptr);
+  if (gicp)
+    rc = sslam_seg_register_pairs_gicp(s->seg, xyz.data(), start.data(), (int)start.size() - 1, pairs.data(), (int)pairs.size(), cov.data(), &s->loop_gicp,
+                                       P.max_iterations, P.epsilon, reg.data(), nullptr, nullptr, nullptr);
+  else
+    rc = sslam_seg_register_pairs(s->seg, xyz.data(), start.data(), (int)start.size() - 1, pairs.data(), (int)pairs.size(), P.max_iterations, P.epsilon,
+                                  reg.data(), nullptr, nullptr, nullptr);
   s->loop_seconds[1] = now_s() - t0;
   if (rc < 0) return rc;
   // the best pair of every new keyframe; its measurement and information where it passes the score test
@@ -1308,7 +1338,7 @@ int sslam_slam_set_loop_closure(sslam_slam* s, const sslam_loop_params* p) {
     s->loop_on = false;
     s->last_edge_accum = 0;
     for (auto* list : {&s->keyframes, &s->new_keyframes})
-      for (auto& kf : *list) { kf->ds.clear(); kf->ds.shrink_to_fit(); kf->has_ds = false; }
+      for (auto& kf : *list) { kf->ds.clear(); kf->ds.shrink_to_fit(); kf->has_ds = false; kf->cov.clear(); kf->cov.shrink_to_fit(); }
     return 0;
   }
   const int rc = check_loop_params(p, true);
@@ -1317,6 +1347,28 @@ int sslam_slam_set_loop_closure(sslam_slam* s, const sslam_loop_params* p) {
   s->loop_on = true;
   s->loop_P = *p;
   if (s->loop_P.voxel_leaf == 0) s->loop_P.voxel_leaf = 0.1f;
+  return 0;
+}
+
+int sslam_slam_set_loop_registration(sslam_slam* s, int method, const sslam_gicp_params* p) {
+  if (!s) return set_error(SSLAM_ERR_INVALID, "null handle");
+  if (method != SSLAM_REG_ICP && method != SSLAM_REG_GICP) return set_error(SSLAM_ERR_INVALID, "loop registration: method %d: SSLAM_REG_ICP or SSLAM_REG_GICP", method);
+  sslam_gicp_params g;
+  sslam_gicp_default_params(&g);
+  if (p) g = *p;
+  const int rc = gicp_check_params(g.k, g.plane_epsilon);
+  if (rc) return rc;
+  if (method != s->loop_method || g.k != s->loop_gicp.k || g.plane_epsilon != s->loop_gicp.plane_epsilon)   // kept covariances belong to other parameters
+    for (auto* list : {&s->keyframes, &s->new_keyframes})
+      for (auto& kf : *list) { kf->cov.clear(); kf->cov.shrink_to_fit(); }
+  s->loop_method = method;
+  s->loop_gicp = g;
+  return 0;
+}
+
+int sslam_slam_loop_covariance_passes(const sslam_slam* s, int64_t* clouds) {
+  if (!s || !clouds) return set_error(SSLAM_ERR_INVALID, "null argument");
+  *clouds = s->loop_cov_passes;
   return 0;
 }
 

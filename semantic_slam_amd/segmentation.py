@@ -90,6 +90,11 @@ class RegResult(C.Structure):
                 ("status", C.c_int32)]
 
 
+class GicpParams(C.Structure):
+    """``sslam_gicp_params`` (include/sslam.h)"""
+    _fields_ = [("k", C.c_int32), ("plane_epsilon", C.c_double)]
+
+
 @dataclasses.dataclass
 class Registration:
     """one pair's result of ``PointCloudSegmentation.register_pairs``"""
@@ -532,6 +537,34 @@ class PointCloudSegmentation:
         cuts = np.cumsum(n_src)[:-1] if n_src else []
         return score, used, list(zip(np.split(idx[:sum(n_src)], cuts), np.split(d2[:sum(n_src)], cuts)))
 
+    def cloud_covariances(self, clouds, k: int = 20, plane_epsilon: float = 1e-3, return_knn: bool = False):
+        """``sslam_seg_cloud_covariances``: per point the covariance of its ``k`` nearest neighbours inside its own cloud, regularised to
+        a plane (fast_gicp's PLANE method: eigenvalues ``plane_epsilon``, 1, 1), as generalized ICP reads it.  ``clouds``: a sequence of
+        [n, 3] float arrays.  Returns one [n, 6] float64 array per cloud (xx xy xz yy yz zz), with ``return_knn`` also one [n, k] int32
+        array per cloud: the neighbours in (d2, index) order, indices inside the cloud, -1 padded.  The hipEvent time of the kernel is
+        left in ``last_covariance_ms``."""
+        cl = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in clouds]
+        start = np.zeros(len(cl) + 1, np.int32)
+        start[1:] = np.cumsum([len(c) for c in cl])
+        xyz = np.ascontiguousarray(np.concatenate(cl, 0)) if cl else np.zeros((0, 3), np.float32)
+        n = int(start[-1])
+        cov = np.zeros((max(n, 1), 6))
+        knn = np.zeros((max(n, 1), max(int(k), 1)), np.int32) if return_knn else None
+        ms = C.c_double(0)
+        self._check(self._lib.sslam_seg_cloud_covariances(self._h, xyz.ctypes.data, start.ctypes.data, len(cl), int(k), float(plane_epsilon),
+                                                          cov.ctypes.data, knn.ctypes.data if return_knn else None, C.byref(ms)))
+        self.last_covariance_ms = ms.value
+        covs = np.split(cov[:n], start[1:-1]) if cl else []
+        return (covs, np.split(knn[:n], start[1:-1]) if cl else []) if return_knn else covs
+
+    def register_pairs_gicp(self, clouds, pairs, covariances=None, k: int = 20, plane_epsilon: float = 1e-3, max_iterations: int = 50,
+                            epsilon: float = 0.0, return_nn: bool = False):
+        """``sslam_seg_register_pairs_gicp``: :meth:`register_pairs` with the generalized-ICP (plane-to-plane) update, hdl_graph_slam's
+        registration_method GICP / FAST_GICP.  ``covariances``: what :meth:`cloud_covariances` returned for ``clouds``, or None: they are
+        computed inside the call with ``k`` and ``plane_epsilon``, once per cloud that a pair names.  Arguments and return types are those
+        of :meth:`register_pairs`; the score is the Euclidean fitness score at the final T."""
+        return self._register_pairs(clouds, pairs, max_iterations, epsilon, return_nn, (covariances, GicpParams(int(k), float(plane_epsilon))))
+
     def register_pairs(self, clouds, pairs, max_iterations: int = 50, epsilon: float = 0.0, return_nn: bool = False):
         """``sslam_seg_register_pairs``: nearest-neighbour ICP of several cloud pairs, the whole loop on the device (what
         LoopDetector::matching does with pcl::IterativeClosestPoint).  ``clouds``: a sequence of [n, 3] float arrays.  ``pairs``:
@@ -540,6 +573,10 @@ class PointCloudSegmentation:
         (None: none).  ``epsilon``: a pair has converged when an update moves no entry of T by more than it (0: T repeats bit for bit).
         Returns one ``Registration`` per pair, with ``return_nn`` also per pair (nearest target index, squared distance) of every source
         point at the final T.  The hipEvent time of the loop is left in ``last_registration_ms``."""
+        return self._register_pairs(clouds, pairs, max_iterations, epsilon, return_nn, None)
+
+    def _register_pairs(self, clouds, pairs, max_iterations, epsilon, return_nn, gicp):
+        # gicp: None (point-to-point) or (covariances or None, GicpParams)
         cl = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in clouds]
         start = np.zeros(len(cl) + 1, np.int32)
         start[1:] = np.cumsum([len(c) for c in cl])
@@ -561,9 +598,19 @@ class PointCloudSegmentation:
         idx = np.zeros(total, np.int32) if return_nn else None
         d2 = np.zeros(total, np.float32) if return_nn else None
         ms = C.c_double(0)
-        self._check(self._lib.sslam_seg_register_pairs(self._h, xyz.ctypes.data, start.ctypes.data, len(cl), C.cast(rec, C.c_void_p), len(pairs),
-                                                       int(max_iterations), float(epsilon), C.cast(res, C.c_void_p),
-                                                       idx.ctypes.data if return_nn else None, d2.ctypes.data if return_nn else None, C.byref(ms)))
+        tail = (int(max_iterations), float(epsilon), C.cast(res, C.c_void_p), idx.ctypes.data if return_nn else None,
+                d2.ctypes.data if return_nn else None, C.byref(ms))
+        if gicp is None:
+            self._check(self._lib.sslam_seg_register_pairs(self._h, xyz.ctypes.data, start.ctypes.data, len(cl), C.cast(rec, C.c_void_p), len(pairs), *tail))
+        else:
+            covs, gp = gicp
+            cov = None
+            if covs is not None:
+                if len(covs) != len(cl) or any(np.shape(a) != (len(c), 6) for a, c in zip(covs, cl)):
+                    raise ValueError("covariances: one [n, 6] array per cloud")
+                cov = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64).reshape(-1, 6) for a in covs], 0)) if cl else np.zeros((1, 6))
+            self._check(self._lib.sslam_seg_register_pairs_gicp(self._h, xyz.ctypes.data, start.ctypes.data, len(cl), C.cast(rec, C.c_void_p), len(pairs),
+                                                                cov.ctypes.data if cov is not None else None, C.byref(gp), *tail))
         self.last_registration_ms = ms.value
         out = [Registration(np.array(res[k].T[:], np.float64), res[k].score, res[k].used, res[k].iterations, res[k].converged, res[k].status)
                for k in range(len(pairs))]

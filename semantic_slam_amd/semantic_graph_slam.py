@@ -12,7 +12,7 @@ import numpy as np
 
 from ._lib import load_library, MapStats, OccParams, OccStats, OptStats
 from .graph_slam import SslamError, _pose7
-from .segmentation import DBL_MAX, InfParams, Plane, PointCloudSegmentation, default_inf_params, occupancy_default_params  # noqa: F401
+from .segmentation import DBL_MAX, GicpParams, InfParams, Plane, PointCloudSegmentation, default_inf_params, occupancy_default_params  # noqa: F401
 
 
 class SlamParams(C.Structure):   # sslam_slam_params
@@ -52,6 +52,8 @@ class Loop(C.Structure):         # sslam_loop
 
 
 LOOP_ADDED, LOOP_SCORE, LOOP_GATE, LOOP_NO_MATCH = 0, 1, 2, 3   # SSLAM_LOOP_*
+REG_ICP, REG_GICP = 0, 1                                        # SSLAM_REG_*
+REG_METHODS = {"ICP": REG_ICP, "GICP": REG_GICP, "FAST_GICP": REG_GICP}   # hdl_graph_slam's registration_method names
 
 _BOUND = False
 
@@ -181,6 +183,23 @@ class SemanticGraphSLAM:
         if isinstance(params, str):
             params = default_loop_params()
         self._check(self._lib.sslam_slam_set_loop_closure(self._h, None if params is None else C.byref(params)))
+
+    def set_loop_registration(self, method="ICP", k: int = 20, plane_epsilon: float = 1e-3) -> None:
+        """``sslam_slam_set_loop_registration``: the scan matcher of the loop stage, hdl_graph_slam's ``registration_method``.  ``method``:
+        "ICP" / ``REG_ICP`` (the default of a handle) or "GICP" / "FAST_GICP" / ``REG_GICP``; with GICP every keyframe's downsampled
+        cloud gets its covariances (``k`` neighbours, ``plane_epsilon``) once and the pairs go through ``register_pairs_gicp``."""
+        if isinstance(method, str):
+            if method not in REG_METHODS:
+                raise ValueError(f"registration method {method!r}: one of {sorted(REG_METHODS)}")
+            method = REG_METHODS[method]
+        gp = GicpParams(int(k), float(plane_epsilon))
+        self._check(self._lib.sslam_slam_set_loop_registration(self._h, int(method), C.byref(gp)))
+
+    def loop_covariance_passes(self) -> int:
+        """``sslam_slam_loop_covariance_passes``: keyframe clouds whose covariances were computed so far (GICP: one per keyframe with a cloud)"""
+        n = C.c_int64(0)
+        self._check(self._lib.sslam_slam_loop_covariance_passes(self._h, C.byref(n)))
+        return n.value
 
     def last_loops(self):
         """the ``Loop`` records of the last ``run``: one per new keyframe that reached the selection with at least one candidate"""
