@@ -1112,6 +1112,117 @@ sslam_graph* sslam_slam_graph(sslam_slam* s);
  * covariance keeps its value, no error is returned. */
 int sslam_slam_find_matches(sslam_slam* s, const sslam_plane* objects, int n, const float robot_pose[6], sslam_landmark* out);
 
+/* ---- scan-matching odometry (hdl_graph_slam's prefiltering_nodelet and scan_matching_odometry_nodelet [UPSTREAM, quoted from memory]):
+ * the pose the orchestrator's sslam_slam_vio takes, computed from the clouds alone ----------------------------------------------------
+ * pcl::RadiusOutlierRemoval (hdl's outlier_removal_method RADIUS; radius 0.8, 2 neighbours there).  The project's own rule, PCL's boundary
+ * sense being [UPSTREAM, quoted from memory]: a finite point is kept when at least min_neighbors OTHER finite points lie within radius,
+ * that is d2 <= r2 with d2 = (dx dx + dy dy) + dz dz in float32 without fused multiply-add, dx = x_query - x_candidate (the arithmetic of
+ * the nearest-neighbour kernels), and r2 = (float)(radius * radius).  Duplicates of a point count as its neighbours.  A non-finite point
+ * is never kept and never a neighbour.  keep_out: the ascending indices of the kept points, at most max_out of them; the return value is
+ * the true count.  count_out (optional, n entries): the neighbours of every point, -1 for a non-finite one.  n = 0 returns 0.
+ * SSLAM_ERR_INVALID: a NULL handle or xyz, n < 0, keep_out NULL with max_out > 0, a radius that is not finite and positive, a negative
+ * min_neighbors.  SSLAM_ERR_NO_DEVICE without a GPU. */
+int sslam_seg_radius_outlier_removal(sslam_seg* s, const float* xyz, int n, double radius, int min_neighbors, int32_t* keep_out, int max_out,
+                                     int32_t* count_out);
+
+/* The prefilter chain in hdl's order -- distance filter, downsample, outlier removal -- on ONE upload of xyz: the intermediate clouds stay on
+ * the device (every stage's kept points go through the ordered compaction there), xyz_out comes back once.  The host reads back only what
+ * sizes a launch: a count per stage, the bounding box of the voxel grid, the three moments (sum, sum of squares, number) of the
+ * statistical stage.  The result is bit for bit the composition of sslam_seg_distance_filter + gather, sslam_seg_voxel_grid on the result,
+ * and sslam_seg_statistical_outlier_removal or sslam_seg_radius_outlier_removal + gather.
+ * A stage that is off passes its input on.  Non-finite points are dropped by the first stage that runs; where none has run when the chain
+ * ends (all off, or the statistical stage skipped), the chain ends in a compaction of the finite points.  The statistical stage is
+ * SKIPPED when fewer than mean_k + 1 finite points reach it (the stand-alone call refuses those), so a sparse frame is no error.
+ * counts (optional): the points after each of the three stages.  An empty result is valid.  At most max_out points are written to
+ * xyz_out; the return value is the true count.  kernel_ms (optional): hipEvent time from the first kernel to the last.
+ * SSLAM_ERR_INVALID, before any device call: a NULL handle or params, xyz NULL with n > 0, n < 0, max_out < 0, xyz_out NULL with max_out > 0,
+ * distance_near / distance_far NaN (with the distance filter on), leaf not positive and finite (VOXELGRID), mean_k outside 1 .. 63
+ * or stddev_mul NaN (STATISTICAL), radius not finite and positive or min_neighbors < 0 (RADIUS), downsample or outlier not one of the
+ * values below, a batch in flight.  SSLAM_ERR_UNSUPPORTED from the voxel geometry is passed on.  SSLAM_ERR_NO_DEVICE without a GPU. */
+#define SSLAM_DOWNSAMPLE_NONE 0
+#define SSLAM_DOWNSAMPLE_VOXELGRID 1
+#define SSLAM_OUTLIER_NONE 0
+#define SSLAM_OUTLIER_STATISTICAL 1
+#define SSLAM_OUTLIER_RADIUS 2
+typedef struct sslam_prefilter_params {
+  int32_t use_distance_filter;      /* 1 */
+  double  distance_near, distance_far;   /* 1.0, 100.0: kept when near < |p| < far, the rule of sslam_seg_distance_filter */
+  int32_t downsample;               /* SSLAM_DOWNSAMPLE_VOXELGRID */
+  float   leaf;                     /* 0.1 */
+  int32_t outlier;                  /* SSLAM_OUTLIER_STATISTICAL */
+  int32_t mean_k;                   /* 20 */
+  double  stddev_mul;               /* 1.0 */
+  double  radius;                   /* 0.8 */
+  int32_t min_neighbors;            /* 2 */
+} sslam_prefilter_params;
+void sslam_prefilter_default_params(sslam_prefilter_params* p);
+int sslam_seg_prefilter(sslam_seg* s, const float* xyz, int n, const sslam_prefilter_params* p, float* xyz_out, int max_out, int32_t counts[3],
+                        double* kernel_ms);
+
+/* The odometry handle: every frame is matched against the current KEYFRAME cloud, starting from the last relative transform; a new
+ * keyframe is taken when the relative motion or the time since the last one passes a threshold (hdl's matching()).  On the host:
+ * keyframe_pose and prev_trans (keyframe -> last accepted frame; 12 doubles each, R row-major then t) and the keyframe's stamp.  On the
+ * device: the keyframe's filtered cloud and, under GICP, its covariances; the frame goes up once as raw points and only its 12 doubles
+ * come back.  One push:
+ *   1. the prefilter chain above on the frame; under GICP the covariances of the filtered frame, once (sslam_seg_cloud_covariances' kernel).
+ *   2. no keyframe yet: an empty filtered frame returns SSLAM_ERR_NUMERIC and the handle stays without one; otherwise the frame becomes
+ *      the keyframe, keyframe_pose = prev_trans = I, pose = I, new_keyframe = 1, accepted = 1, matched = 0.
+ *   3. match: target = keyframe, source = frame, T0 = prev_trans, max_corr2 = max_correspondence_distance squared -- one pair of
+ *      sslam_seg_register_pairs(_gicp) exactly (kernels, chunks of 8 iterations, the final fitness pass); under GICP the keyframe's
+ *      covariances are those computed when it was a frame.  T: keyframe -> frame.
+ *   4. status != 0 (fewer than 3 correspondences, a failed step) is "not converged" in hdl's sense; a match that merely reached
+ *      max_iterations counts as converged, as PCL's criterion does (a deviation from a strict reading of hasConverged).  Not converged:
+ *      pose = keyframe_pose * prev_trans, accepted = 0, nothing else changes.
+ *   5. with transform_thresholding: delta = inverse(prev_trans) * T; |t(delta)| > max_acceptable_trans or angle(delta) >
+ *      max_acceptable_angle: the frame is handled as in 4.
+ *   6. otherwise pose = keyframe_pose * T, prev_trans = T, accepted = 1; delta_trans = |t(T)|, delta_angle = angle(T), delta_time =
+ *      (sec - keyframe sec) + 1e-9 * (nsec - keyframe nsec) in double.
+ *   7. any of the three STRICTLY above its keyframe_delta_* threshold: the frame's device cloud and covariances become the keyframe's
+ *      (the two slots of the device arena swap roles; nothing crosses the host), keyframe_pose = pose, the stamp is kept, prev_trans = I,
+ *      new_keyframe = 1.
+ * angle(T) is upstream's acos(Quaternionf(R).w()), HALF the rotation angle -- an upstream quirk kept so that hdl's threshold values mean
+ * what they mean there; here acos(min(1, |w|)) with w from the unit quaternion of R by the largest-pivot branch.
+ * Products are plain double on the host, no fused multiply-add: C = A * B has R_C[i][j] = (A[i][0] B[0][j] + A[i][1] B[1][j]) + A[i][2] B[2][j]
+ * and t_C[i] = ((A[i][0] t_B[0] + A[i][1] t_B[1]) + A[i][2] t_B[2]) + t_A[i]; inverse(A) has R = transpose(R_A) and
+ * t[i] = -((A[0][i] t_A[0] + A[1][i] t_A[1]) + A[2][i] t_A[2]); |t| = sqrt((t0 t0 + t1 t1) + t2 t2).
+ * Several odometry handles may share one frontend handle; they share no state.  A failed push leaves the handle as it was.
+ * SSLAM_ERR_INVALID: NULL arguments (stats may be NULL), n < 0, parameters out of range (the checks of the prefilter and of the
+ * generalized-ICP parameters; max_iterations < 0; epsilon, the correspondence distance or one of the five thresholds not finite and
+ * >= 0; a method other than the two), a frontend batch in flight.  create checks the handle and the parameters and returns NULL on a
+ * bad one, with the reason in sslam_last_error.
+ * SSLAM_ERR_NO_DEVICE without a GPU: create succeeds and push fails. */
+typedef struct sslam_odom sslam_odom;
+typedef struct sslam_odom_params {
+  sslam_prefilter_params prefilter;
+  int32_t method;                   /* SSLAM_REG_GICP (hdl's default is FAST_GICP) | SSLAM_REG_ICP */
+  sslam_gicp_params gicp;           /* 20, 1e-3 */
+  int32_t max_iterations;           /* 64 */
+  double  epsilon;                  /* 0.01: the rule of sslam_seg_register_pairs, the largest change of an entry of T */
+  double  max_correspondence_distance;   /* 2.5; squared before use */
+  double  keyframe_delta_trans, keyframe_delta_angle, keyframe_delta_time;   /* 0.25 m, 0.15 (see angle), 1.0 s */
+  int32_t transform_thresholding;   /* 0 */
+  double  max_acceptable_trans, max_acceptable_angle;   /* 1.0, 1.0 */
+} sslam_odom_params;
+typedef struct sslam_odom_stats {
+  int32_t n_raw, n_filtered;        /* points of the frame before and after the prefilter */
+  int32_t matched;                  /* 1 when the frame was matched against a keyframe (0 for the frame that became the first one) */
+  int32_t iterations, converged, status, used;   /* as sslam_reg_result has them; 0 without a match */
+  int32_t accepted, new_keyframe, keyframes;     /* keyframes: taken so far, this call included */
+  int64_t covariance_passes;        /* covariance launches of the handle so far: one per pushed frame under GICP, none per keyframe */
+  double  fitness;                  /* the Euclidean fitness score at the final T; 0 without a match */
+  double  T[12];                    /* keyframe -> frame, what the pose was built from: the match's T when accepted, else prev_trans */
+  double  delta_trans, delta_angle, delta_time;  /* of an accepted frame; 0 otherwise */
+  double  prefilter_ms, covariance_ms, registration_ms;   /* hipEvent times */
+  double  total_ms;                 /* the whole call, wall clock */
+} sslam_odom_stats;
+void        sslam_odom_default_params(sslam_odom_params* p);
+sslam_odom* sslam_odom_create(sslam_seg* seg, const sslam_odom_params* p);   /* p NULL: the defaults; seg is borrowed and must outlive the handle */
+void        sslam_odom_destroy(sslam_odom* o);
+int         sslam_odom_reset(sslam_odom* o);                                 /* forgets the keyframe and the counters; returns 0 */
+int         sslam_odom_push(sslam_odom* o, const float* xyz, int n, int32_t stamp_sec, int32_t stamp_nsec, double pose_out[12], sslam_odom_stats* stats);
+/* the current keyframe's filtered cloud (at most max_out points; returns the true count, 0 without a keyframe) and its pose (optional) */
+int         sslam_odom_keyframe(const sslam_odom* o, float* xyz_out, int max_out, double pose_out[12]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,15 @@ def load_library():
         "sslam_seg_last_occupancy_scan_timing": (ci, [vp, vp]),
         "sslam_seg_last_occupancy_scan_counts": (ci, [vp, vp]),
         "sslam_slam_occupancy_map_scans": (ci, [vp, C.POINTER(OccParams), vp, vp, vp, vp, ci, C.POINTER(OccStats)]),
+        "sslam_seg_radius_outlier_removal": (ci, [vp, vp, ci, cd, ci, vp, ci, vp]),
+        "sslam_prefilter_default_params": (None, [vp]),
+        "sslam_seg_prefilter": (ci, [vp, vp, ci, vp, vp, ci, vp, dp]),
+        "sslam_odom_default_params": (None, [vp]),
+        "sslam_odom_create": (vp, [vp, vp]),
+        "sslam_odom_destroy": (None, [vp]),
+        "sslam_odom_reset": (ci, [vp]),
+        "sslam_odom_push": (ci, [vp, vp, ci, C.c_int32, C.c_int32, vp, vp]),
+        "sslam_odom_keyframe": (ci, [vp, vp, ci, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design

@@ -26,6 +26,7 @@
 #include "../../include/sslam.h"
 #include "map_cloud.hpp"
 #include "occupancy_map.hpp"
+#include "odometry.hpp"
 #include "sslam_common.hpp"
 #include "sslam_math.hpp"
 
@@ -3616,16 +3617,15 @@ int sslam_debug_voxel_geometry(const float lo[3], const float hi[3], float leaf,
   return 0;
 }
 
-int sslam_seg_voxel_grid(sslam_seg* s, const float* xyz, int n, float leaf, float* centroids_out, int32_t* counts_out, int max_out) {
-  if (!s || !xyz || n < 0 || !(leaf > 0) || (!centroids_out && max_out > 0)) return set_error(SSLAM_ERR_INVALID, "bad argument");
-  int rc = seg_device(s);
-  if (rc) return rc;
-  if (n == 0) return 0;
-  DevGuard g;
-  float *d_pts = nullptr, *d_part = nullptr;
+// the voxel grid over n > 0 points that sit on the device: min / max, geometry, accumulate, the ascending list of the occupied cells, the
+// centroids.  *d_out (3 floats per voxel) and *d_oc (points per voxel) are the guard's and stay NULL with *nocc = 0 (no finite point).
+// The host reads back the bounding box and the number of occupied cells; everything else stays on the device.
+static int voxel_grid_device(sslam_seg* s, DevGuard& g, const float* d_pts, int n, float leaf, float** d_out, int** d_oc, int* nocc_out) {
+  int rc;
+  *d_out = nullptr; *d_oc = nullptr; *nocc_out = 0;
+  float* d_part = nullptr;
   const int nblk = std::min(256, (n + 255) / 256);
-  if ((rc = g.alloc(&d_pts, (size_t)n * 3)) || (rc = g.alloc(&d_part, (size_t)nblk * 6))) return rc;
-  SSLAM_HIP_TRY(hipMemcpyAsync(d_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  if ((rc = g.alloc(&d_part, (size_t)nblk * 6))) return rc;
   hipLaunchKernelGGL(k_voxel_minmax, dim3(nblk), dim3(256), 0, s->stream, d_pts, n, d_part);
   std::vector<float> part((size_t)nblk * 6);
   SSLAM_HIP_TRY(hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(float), hipMemcpyDeviceToHost, s->stream));
@@ -3646,10 +3646,25 @@ int sslam_seg_voxel_grid(sslam_seg* s, const float* xyz, int n, float leaf, floa
   int nocc = 0;
   if ((rc = compact_flags(s, g, d_flag, (int)ncell, d_cells, (int)ncell, &nocc))) return rc;
   if (nocc == 0) return 0;
-  float* d_out = nullptr; int* d_oc = nullptr;
-  if ((rc = g.alloc(&d_out, (size_t)nocc * 3)) || (rc = g.alloc(&d_oc, nocc))) return rc;
-  hipLaunchKernelGGL(k_voxel_centroids, dim3((nocc + 255) / 256), dim3(256), 0, s->stream, d_cells, nocc, d_count, d_sums, d_out, d_oc);
+  if ((rc = g.alloc(d_out, (size_t)nocc * 3)) || (rc = g.alloc(d_oc, nocc))) return rc;
+  hipLaunchKernelGGL(k_voxel_centroids, dim3((nocc + 255) / 256), dim3(256), 0, s->stream, d_cells, nocc, d_count, d_sums, *d_out, *d_oc);
   SSLAM_HIP_TRY(hipGetLastError());
+  *nocc_out = nocc;
+  return 0;
+}
+int sslam_seg_voxel_grid(sslam_seg* s, const float* xyz, int n, float leaf, float* centroids_out, int32_t* counts_out, int max_out) {
+  if (!s || !xyz || n < 0 || !(leaf > 0) || (!centroids_out && max_out > 0)) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = seg_device(s);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  DevGuard g;
+  float *d_pts = nullptr, *d_out = nullptr;
+  int* d_oc = nullptr;
+  if ((rc = g.alloc(&d_pts, (size_t)n * 3))) return rc;
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  int nocc = 0;
+  if ((rc = voxel_grid_device(s, g, d_pts, n, leaf, &d_out, &d_oc, &nocc))) return rc;
+  if (nocc == 0) return 0;
   const int m = std::min(nocc, max_out);
   if (m > 0) {
     SSLAM_HIP_TRY(hipMemcpyAsync(centroids_out, d_out, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
@@ -4118,6 +4133,20 @@ int sslam_seg_last_occupancy_scan_counts(const sslam_seg* s, int64_t counts[2]) 
   return 0;
 }
 
+// the mean distance of every one of n > 0 device points to its mean_k nearest neighbours -> d_md (-1 for a non-finite point)
+static_assert(kSorMaxMeanK == kSorMaxK, "prefilter_check_params (csrc/odometry.hpp) bounds mean_k by it");
+static int sor_mean_distance_device(sslam_seg* s, const float* d_pts, int n, int mean_k, float* d_md) {
+  const size_t lds = (size_t)(128 * 3 + (mean_k + 1) * 128) * sizeof(float);
+  hipLaunchKernelGGL(k_sor_mean_distance, dim3((n + 127) / 128), dim3(128), lds, s->stream, d_pts, n, mean_k, d_md);
+  SSLAM_HIP_TRY(hipGetLastError());
+  return 0;
+}
+// pcl::StatisticalOutlierRemoval::applyFilterIndices: the threshold from the moments of the valid mean distances (sequential double sums
+// in index order); one expression for the host wrapper and the resident chain
+static double sor_threshold(double sum, double sq, int valid, double stddev_mul) {
+  const double mean = sum / valid, variance = (sq - sum * sum / valid) / (valid - 1.0), stddev = std::sqrt(variance);
+  return mean + stddev_mul * stddev;
+}
 int sslam_seg_statistical_outlier_removal(sslam_seg* s, const float* xyz, int n, int mean_k, double stddev_mul, int32_t* keep_out, int max_out,
                                           float* mean_dist_out) {
   if (!s || !xyz || n < 0 || mean_k < 1 || mean_k >= kSorMaxK || (!keep_out && max_out > 0)) return set_error(SSLAM_ERR_INVALID, "bad argument (mean_k must be in [1, %d))", kSorMaxK);
@@ -4131,9 +4160,7 @@ int sslam_seg_statistical_outlier_removal(sslam_seg* s, const float* xyz, int n,
   float *d_pts = nullptr, *d_md = nullptr;
   if ((rc = g.alloc(&d_pts, (size_t)n * 3)) || (rc = g.alloc(&d_md, n))) return rc;
   SSLAM_HIP_TRY(hipMemcpyAsync(d_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  const size_t lds = (size_t)(128 * 3 + (mean_k + 1) * 128) * sizeof(float);
-  hipLaunchKernelGGL(k_sor_mean_distance, dim3((n + 127) / 128), dim3(128), lds, s->stream, d_pts, n, mean_k, d_md);
-  SSLAM_HIP_TRY(hipGetLastError());
+  if ((rc = sor_mean_distance_device(s, d_pts, n, mean_k, d_md))) return rc;
   std::vector<float> md(n);
   SSLAM_HIP_TRY(hipMemcpyAsync(md.data(), d_md, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
@@ -4143,8 +4170,7 @@ int sslam_seg_statistical_outlier_removal(sslam_seg* s, const float* xyz, int n,
   for (int i = 0; i < n; ++i) if (md[i] >= 0) { sum += md[i]; sq += (double)md[i] * md[i]; ++valid; }
   if (mean_dist_out) for (int i = 0; i < n; ++i) mean_dist_out[i] = md[i];
   if (valid < 2) return 0;
-  const double mean = sum / valid, variance = (sq - sum * sum / valid) / (valid - 1.0), stddev = std::sqrt(variance);
-  const double thr = mean + stddev_mul * stddev;
+  const double thr = sor_threshold(sum, sq, valid, stddev_mul);
   int kept = 0;
   for (int i = 0; i < n; ++i)
     if (md[i] >= 0 && !((double)md[i] > thr)) { if (kept < max_out) keep_out[kept] = i; ++kept; }
@@ -4312,15 +4338,17 @@ static int nn_plan(sslam_seg* s, const int32_t* cloud_start, const sslam_fitness
   }
   return 0;
 }
-// buffers and the copies to the device, all on the handle's stream; f_e0 is NOT recorded here
+// buffers and the copies to the device, all on the handle's stream; f_e0 is NOT recorded here.  With d.xyz set by the caller the points
+// already sit on the device (the odometry's arena): xyz is not read and nothing is allocated for them.
 static int nn_upload(sslam_seg* s, DevGuard& g, const NnPlan& pl, const float* xyz, int n_points, NnDev& d) {
   int rc;
   const size_t total_q = (size_t)pl.total_q;
-  if ((rc = g.alloc(&d.xyz, (size_t)n_points * 3)) || (rc = g.alloc(&d.pairs, pl.hp.size())) || (rc = g.alloc(&d.items, pl.items.size())) ||
+  const bool resident = d.xyz != nullptr;
+  if ((!resident && (rc = g.alloc(&d.xyz, (size_t)n_points * 3))) || (rc = g.alloc(&d.pairs, pl.hp.size())) || (rc = g.alloc(&d.items, pl.items.size())) ||
       (rc = g.alloc(&d.segs, pl.segs.size())) || (rc = g.alloc(&d.best, total_q)) || (rc = g.alloc(&d.idx, total_q)) ||
       (rc = g.alloc(&d.d2, total_q)) || (rc = g.alloc(&d.sum, pl.segs.size())) || (rc = g.alloc(&d.used, pl.segs.size()))) return rc;
   if (!s->f_e0) { SSLAM_HIP_TRY(hipEventCreate(&s->f_e0)); SSLAM_HIP_TRY(hipEventCreate(&s->f_e1)); }
-  if (n_points > 0) SSLAM_HIP_TRY(hipMemcpyAsync(d.xyz, xyz, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  if (!resident && n_points > 0) SSLAM_HIP_TRY(hipMemcpyAsync(d.xyz, xyz, (size_t)n_points * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
   SSLAM_HIP_TRY(hipMemcpyAsync(d.pairs, pl.hp.data(), pl.hp.size() * sizeof(NnPair), hipMemcpyHostToDevice, s->stream));
   if (!pl.items.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(d.items, pl.items.data(), pl.items.size() * sizeof(NnItem), hipMemcpyHostToDevice, s->stream));
   if (!pl.segs.empty()) SSLAM_HIP_TRY(hipMemcpyAsync(d.segs, pl.segs.data(), pl.segs.size() * sizeof(NnSeg), hipMemcpyHostToDevice, s->stream));
@@ -4455,9 +4483,11 @@ int sslam_seg_cloud_covariances(sslam_seg* s, const float* xyz, const int32_t* c
 
 // ---- scan matching: nearest-neighbour ICP of cloud pairs (k_nn_pairs, k_reg_sums, k_reg_step; k_nn_finish at the end), and its
 // generalized form (k_gicp_sums, k_gicp_step in their place; gp != NULL): one host loop for both ------------------------------------------
+// d_xyz / d_cov_resident: NULL, or the points (and, with gp, the covariances of every cloud a pair names) where they already sit on the
+// device -- the odometry's arena; xyz and cov are then not read.  Everything after the staging is the same code for both callers.
 static int register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_start, int n_clouds, const sslam_reg_pair* pairs, int n_pairs,
                           const double* cov, const sslam_gicp_params* gp, int max_iterations, double epsilon, sslam_reg_result* out,
-                          int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms) {
+                          int32_t* nn_index_out, float* nn_dist2_out, double* kernel_ms, float* d_xyz = nullptr, double* d_cov_resident = nullptr) {
   if (!s || !cloud_start || n_clouds < 0 || n_pairs < 0 || (n_pairs > 0 && (!pairs || !out)) || max_iterations < 0 || !(epsilon >= 0.0))
     return set_error(SSLAM_ERR_INVALID, "bad argument");
   if (gp) { const int rcp = gicp_check_params(gp->k, gp->plane_epsilon); if (rcp) return rcp; }
@@ -4466,7 +4496,7 @@ static int register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_s
     fp[p].target = pairs[p].target; fp[p].source = pairs[p].source; fp[p].max_range = pairs[p].max_corr2;
     for (int k = 0; k < 12; ++k) fp[p].T[k] = pairs[p].T0[k];
   }
-  int rc = nn_check_clouds(xyz, cloud_start, n_clouds, fp.data(), n_pairs);
+  int rc = nn_check_clouds(d_xyz ? d_xyz : xyz, cloud_start, n_clouds, fp.data(), n_pairs);
   if (rc) return rc;
   if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
   rc = seg_device(s);
@@ -4490,10 +4520,11 @@ static int register_pairs(sslam_seg* s, const float* xyz, const int32_t* cloud_s
   double* d_part = nullptr;
   const int n_sums = gp ? kIcpSums : kRegSums;
   const size_t n_points = (size_t)cloud_start[n_clouds];
-  double* d_cov = nullptr;
+  double* d_cov = d_cov_resident;
+  d.xyz = d_xyz;
   if ((rc = nn_upload(s, g, pl, xyz, cloud_start[n_clouds], d)) || (rc = g.alloc(&d_st, (size_t)n_pairs)) || (rc = g.alloc(&d_seg0, seg0.size())) ||
-      (rc = g.alloc(&d_live, 1)) || (rc = g.alloc(&d_part, pl.segs.size() * n_sums)) || (gp && (rc = g.alloc(&d_cov, n_points * 6)))) return rc;
-  if (gp && max_iterations > 0 && n_points > 0) {   // the covariances: the caller's, or those of every cloud a pair names, each cloud once
+      (rc = g.alloc(&d_live, 1)) || (rc = g.alloc(&d_part, pl.segs.size() * n_sums)) || (gp && !d_cov && (rc = g.alloc(&d_cov, n_points * 6)))) return rc;
+  if (gp && !d_cov_resident && max_iterations > 0 && n_points > 0) {   // the covariances: the caller's, or those of every cloud a pair names, each cloud once
     if (cov) {
       SSLAM_HIP_TRY(hipMemcpyAsync(d_cov, cov, n_points * 6 * sizeof(double), hipMemcpyHostToDevice, s->stream));
     } else {
@@ -4551,6 +4582,327 @@ int sslam_seg_register_pairs_gicp(sslam_seg* s, const float* xyz, const int32_t*
   sslam_gicp_default_params(&gp);
   if (params) gp = *params;
   return register_pairs(s, xyz, cloud_start, n_clouds, pairs, n_pairs, cov, &gp, max_iterations, epsilon, out, nn_index_out, nn_dist2_out, kernel_ms);
+}
+
+// ---- scan-matching odometry: radius outlier removal, the resident prefilter chain, the odometry handle (kernels and host rules in
+// csrc/odometry.hpp; the contract is at sslam_seg_prefilter / sslam_odom_push in include/sslam.h) ----------------------------------------
+static int radius_count_device(sslam_seg* s, const float* d_pts, int n, double radius, int* d_count) {
+  const float r2 = (float)(radius * radius);
+  hipLaunchKernelGGL(k_radius_count, dim3((n + kRadThreads - 1) / kRadThreads), dim3(kRadThreads), 0, s->stream, d_pts, n, r2, d_count);
+  SSLAM_HIP_TRY(hipGetLastError());
+  return 0;
+}
+int sslam_seg_radius_outlier_removal(sslam_seg* s, const float* xyz, int n, double radius, int min_neighbors, int32_t* keep_out, int max_out,
+                                     int32_t* count_out) {
+  if (!s || !xyz || n < 0 || (!keep_out && max_out > 0) || !(radius > 0 && std::isfinite(radius)) || min_neighbors < 0)
+    return set_error(SSLAM_ERR_INVALID, "bad argument (radius must be finite and positive, min_neighbors >= 0)");
+  int rc = seg_device(s);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  DevGuard g;
+  float* d_pts = nullptr; int *d_cnt = nullptr, *d_out = nullptr; unsigned char* d_flag = nullptr;
+  if ((rc = g.alloc(&d_pts, (size_t)n * 3)) || (rc = g.alloc(&d_cnt, n)) || (rc = g.alloc(&d_flag, n)) || (rc = g.alloc(&d_out, n))) return rc;
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_pts, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  if ((rc = radius_count_device(s, d_pts, n, radius, d_cnt))) return rc;
+  hipLaunchKernelGGL(k_radius_flag, dim3((n + 255) / 256), dim3(256), 0, s->stream, d_cnt, n, min_neighbors, d_flag);
+  int total = 0;
+  if ((rc = compact_flags(s, g, d_flag, n, d_out, n, &total))) return rc;
+  const int m = std::min(total, max_out);
+  if (m > 0) SSLAM_HIP_TRY(hipMemcpy(keep_out, d_out, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+  if (count_out) SSLAM_HIP_TRY(hipMemcpy(count_out, d_cnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  return total;
+}
+
+void sslam_prefilter_default_params(sslam_prefilter_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof *p);
+  p->use_distance_filter = 1; p->distance_near = 1.0; p->distance_far = 100.0;   // hdl's prefiltering_nodelet [UPSTREAM, quoted from memory]
+  p->downsample = SSLAM_DOWNSAMPLE_VOXELGRID; p->leaf = 0.1f;
+  p->outlier = SSLAM_OUTLIER_STATISTICAL; p->mean_k = 20; p->stddev_mul = 1.0;
+  p->radius = 0.8; p->min_neighbors = 2;
+}
+// The chain over n points that sit on the device (d_in is only read).  *d_res: the result, *m_out points -- a buffer of the guard's, or
+// d_in itself where nothing was dropped.  Each stage's kept points go through compact_if with GatherPred: the index list of the host entry
+// point and its gather in one.  `clean`: the non-finite points are gone.
+static int prefilter_device(sslam_seg* s, DevGuard& g, const float* d_in, int n, const sslam_prefilter_params* p, const float** d_res, int* m_out,
+                            int32_t counts[3]) {
+  const float* cur = d_in;
+  int m = n, rc;
+  bool clean = false;
+  unsigned char* d_flag = nullptr; int *d_blk = nullptr, *d_total = nullptr;
+  if ((rc = g.alloc(&d_flag, n)) || (rc = g.alloc(&d_blk, (n + 255) / 256)) || (rc = g.alloc(&d_total, 1))) return rc;
+  auto keep_flagged = [&]() -> int {     // m > 0
+    float* dst = nullptr;
+    int total = 0, rc2;
+    if ((rc2 = g.alloc(&dst, (size_t)m * 3)) || (rc2 = compact_if(s, GatherPred{d_flag, cur, dst}, m, d_blk, d_total, &total))) return rc2;
+    cur = dst; m = total; clean = true;
+    return 0;
+  };
+  if (p->use_distance_filter && m > 0) {
+    hipLaunchKernelGGL(k_range_flag, dim3((m + 255) / 256), dim3(256), 0, s->stream, cur, m, p->distance_near, p->distance_far, d_flag);
+    if ((rc = keep_flagged())) return rc;
+  }
+  counts[0] = m;
+  if (p->downsample == SSLAM_DOWNSAMPLE_VOXELGRID && m > 0) {
+    float* d_out = nullptr; int* d_oc = nullptr;
+    int nocc = 0;
+    if ((rc = voxel_grid_device(s, g, cur, m, p->leaf, &d_out, &d_oc, &nocc))) return rc;
+    cur = d_out; m = nocc; clean = true;
+  }
+  counts[1] = m;
+  if (!clean && m > 0) {                 // no stage has run: the compaction of the finite points
+    hipLaunchKernelGGL(k_finite_flag, dim3((m + 255) / 256), dim3(256), 0, s->stream, cur, m, d_flag);
+    if ((rc = keep_flagged())) return rc;
+  }
+  if (p->outlier == SSLAM_OUTLIER_STATISTICAL && m >= p->mean_k + 1) {
+    float* d_md = nullptr; double* d_mom = nullptr;
+    double mom[3] = {0, 0, 0};
+    if ((rc = g.alloc(&d_md, m)) || (rc = g.alloc(&d_mom, 3)) || (rc = sor_mean_distance_device(s, cur, m, p->mean_k, d_md))) return rc;
+    hipLaunchKernelGGL(k_sor_moments, dim3(1), dim3(64), 0, s->stream, d_md, m, d_mom);
+    SSLAM_HIP_TRY(hipMemcpyAsync(mom, d_mom, sizeof mom, hipMemcpyDeviceToHost, s->stream));
+    SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+    const int valid = (int)mom[2];
+    if (valid < 2) m = 0;                // the stand-alone call keeps nothing there
+    else {
+      hipLaunchKernelGGL(k_sor_flag, dim3((m + 255) / 256), dim3(256), 0, s->stream, d_md, m, sor_threshold(mom[0], mom[1], valid, p->stddev_mul), d_flag);
+      if ((rc = keep_flagged())) return rc;
+    }
+  } else if (p->outlier == SSLAM_OUTLIER_RADIUS && m > 0) {
+    int* d_cnt = nullptr;
+    if ((rc = g.alloc(&d_cnt, m)) || (rc = radius_count_device(s, cur, m, p->radius, d_cnt))) return rc;
+    hipLaunchKernelGGL(k_radius_flag, dim3((m + 255) / 256), dim3(256), 0, s->stream, d_cnt, m, p->min_neighbors, d_flag);
+    if ((rc = keep_flagged())) return rc;
+  }
+  counts[2] = m;
+  SSLAM_HIP_TRY(hipGetLastError());
+  *d_res = cur; *m_out = m;
+  return 0;
+}
+int sslam_seg_prefilter(sslam_seg* s, const float* xyz, int n, const sslam_prefilter_params* p, float* xyz_out, int max_out, int32_t counts[3],
+                        double* kernel_ms) {
+  if (!s || !p || n < 0 || (!xyz && n > 0) || max_out < 0 || (!xyz_out && max_out > 0)) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  int rc = prefilter_check_params(p);
+  if (rc) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  if ((rc = seg_device(s))) return rc;
+  if (kernel_ms) *kernel_ms = 0.0;
+  int32_t cnt[3] = {0, 0, 0};
+  if (counts) memcpy(counts, cnt, sizeof cnt);
+  if (n == 0) return 0;
+  DevGuard g;
+  float* d_in = nullptr;
+  const float* d_res = nullptr;
+  int m = 0;
+  if ((rc = g.alloc(&d_in, (size_t)n * 3))) return rc;
+  if (!s->f_e0) { SSLAM_HIP_TRY(hipEventCreate(&s->f_e0)); SSLAM_HIP_TRY(hipEventCreate(&s->f_e1)); }
+  SSLAM_HIP_TRY(hipMemcpyAsync(d_in, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(s->f_e0, s->stream));
+  if ((rc = prefilter_device(s, g, d_in, n, p, &d_res, &m, cnt))) return rc;
+  SSLAM_HIP_TRY(hipEventRecord(s->f_e1, s->stream));
+  const int w = std::min(m, max_out);
+  if (w > 0) SSLAM_HIP_TRY(hipMemcpyAsync(xyz_out, d_res, (size_t)w * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  if (kernel_ms) {
+    float ms = 0.0f;
+    SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->f_e0, s->f_e1));
+    *kernel_ms = (double)ms;
+  }
+  if (counts) memcpy(counts, cnt, sizeof cnt);
+  return m;
+}
+
+}  // extern "C"
+// The odometry handle.  The device arena holds TWO slots of `cap` points each (and, under GICP, of 6 doubles per point): the keyframe's
+// filtered cloud in one, the frame's in the other, so that one base pointer serves the pair table of the registration kernels; a frame
+// that becomes the keyframe swaps the roles of the slots.
+struct sslam_odom {
+  sslam_seg* seg = nullptr;
+  sslam_odom_params P;
+  bool has_kf = false;
+  double kf_pose[12], prev[12];
+  int32_t kf_sec = 0, kf_nsec = 0;
+  float* d_xyz = nullptr;
+  double* d_cov = nullptr;
+  size_t cap = 0;
+  int kf_slot = 0, kf_n = 0, keyframes = 0;
+  int64_t cov_passes = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};   // around the prefilter
+  ~sslam_odom() {
+    if (!d_xyz && !d_cov && !ev[0]) return;
+    (void)hipSetDevice(seg_device_index(seg));
+    if (d_xyz) (void)hipFree(d_xyz);
+    if (d_cov) (void)hipFree(d_cov);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+// room for `need` points per slot; the keyframe's slot moves with the arena (device to device)
+static int odom_reserve(sslam_odom* o, size_t need) {
+  if (need <= o->cap) return 0;
+  sslam_seg* s = o->seg;
+  const bool gicp = o->P.method == SSLAM_REG_GICP;
+  const size_t cap = std::max<size_t>(std::max<size_t>(need, 2 * o->cap), 1024);
+  DevGuard g;
+  float* nx = nullptr; double* nc = nullptr;
+  int rc;
+  if ((rc = g.alloc(&nx, 2 * cap * 3)) || (gicp && (rc = g.alloc(&nc, 2 * cap * 6)))) return rc;
+  if (o->has_kf && o->kf_n > 0) {
+    SSLAM_HIP_TRY(hipMemcpyAsync(nx + (size_t)o->kf_slot * cap * 3, o->d_xyz + (size_t)o->kf_slot * o->cap * 3, (size_t)o->kf_n * 3 * sizeof(float),
+                                 hipMemcpyDeviceToDevice, s->stream));
+    if (gicp) SSLAM_HIP_TRY(hipMemcpyAsync(nc + (size_t)o->kf_slot * cap * 6, o->d_cov + (size_t)o->kf_slot * o->cap * 6, (size_t)o->kf_n * 6 * sizeof(double),
+                                           hipMemcpyDeviceToDevice, s->stream));
+    SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  if (o->d_xyz) (void)hipFree(o->d_xyz);
+  if (o->d_cov) (void)hipFree(o->d_cov);
+  o->d_xyz = nx; o->d_cov = nc; o->cap = cap;
+  g.ptrs.clear();                        // the handle owns them now
+  return 0;
+}
+extern "C" {
+void sslam_odom_default_params(sslam_odom_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof *p);
+  sslam_prefilter_default_params(&p->prefilter);
+  p->method = SSLAM_REG_GICP;            // hdl's default is FAST_GICP
+  sslam_gicp_default_params(&p->gicp);
+  p->max_iterations = 64; p->epsilon = 0.01; p->max_correspondence_distance = 2.5;
+  p->keyframe_delta_trans = 0.25; p->keyframe_delta_angle = 0.15; p->keyframe_delta_time = 1.0;
+  p->transform_thresholding = 0; p->max_acceptable_trans = 1.0; p->max_acceptable_angle = 1.0;
+}
+sslam_odom* sslam_odom_create(sslam_seg* seg, const sslam_odom_params* p) {
+  if (!seg) { set_error(SSLAM_ERR_INVALID, "bad argument"); return nullptr; }
+  sslam_odom_params P;
+  if (p) P = *p; else sslam_odom_default_params(&P);
+  if (odom_check_params(&P)) return nullptr;
+  sslam_odom* o = new sslam_odom();
+  o->seg = seg; o->P = P;
+  odom_identity(o->kf_pose); odom_identity(o->prev);
+  return o;
+}
+void sslam_odom_destroy(sslam_odom* o) { delete o; }
+int sslam_odom_reset(sslam_odom* o) {
+  if (!o) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  o->has_kf = false; o->kf_n = 0; o->keyframes = 0; o->cov_passes = 0; o->kf_sec = o->kf_nsec = 0;
+  odom_identity(o->kf_pose); odom_identity(o->prev);
+  return 0;
+}
+int sslam_odom_push(sslam_odom* o, const float* xyz, int n, int32_t stamp_sec, int32_t stamp_nsec, double pose_out[12], sslam_odom_stats* stats) {
+  const auto t_start = std::chrono::steady_clock::now();
+  if (!o || !xyz || !pose_out || n < 0) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  sslam_seg* s = o->seg;
+  const sslam_odom_params& P = o->P;
+  int rc = odom_check_params(&P);
+  if (rc) return rc;
+  if (s->q_busy || s->n_inflight > 0) return set_error(SSLAM_ERR_INVALID, "a batch is in flight: collect it first");
+  if ((rc = seg_device(s))) return rc;
+  const bool gicp = P.method == SSLAM_REG_GICP;
+  if (!o->ev[0]) { SSLAM_HIP_TRY(hipEventCreate(&o->ev[0])); SSLAM_HIP_TRY(hipEventCreate(&o->ev[1])); }
+  if (!s->f_e0) { SSLAM_HIP_TRY(hipEventCreate(&s->f_e0)); SSLAM_HIP_TRY(hipEventCreate(&s->f_e1)); }
+  sslam_odom_stats st;
+  memset(&st, 0, sizeof st);
+  st.n_raw = n;
+  // 1. the frame goes up once; the chain; its result into the frame's slot of the arena; its covariances
+  DevGuard g;
+  float* d_in = nullptr;
+  const float* d_res = nullptr;
+  int m = 0;
+  int32_t cnt[3] = {0, 0, 0};
+  if ((rc = g.alloc(&d_in, (size_t)n * 3))) return rc;
+  if (n > 0) SSLAM_HIP_TRY(hipMemcpyAsync(d_in, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  SSLAM_HIP_TRY(hipEventRecord(o->ev[0], s->stream));
+  if (n > 0 && (rc = prefilter_device(s, g, d_in, n, &P.prefilter, &d_res, &m, cnt))) return rc;
+  SSLAM_HIP_TRY(hipEventRecord(o->ev[1], s->stream));
+  st.n_filtered = m;
+  if (!o->has_kf && m == 0) {
+    SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+    return set_error(SSLAM_ERR_NUMERIC, "odometry: the first frame is empty after the prefilter (%d raw points): no keyframe", n);
+  }
+  if ((rc = odom_reserve(o, (size_t)m))) return rc;
+  const int fs = o->has_kf ? 1 - o->kf_slot : 0;
+  const size_t f0 = (size_t)fs * o->cap;
+  if (m > 0) SSLAM_HIP_TRY(hipMemcpyAsync(o->d_xyz + f0 * 3, d_res, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+  int64_t cov_passes = o->cov_passes;
+  if (gicp && m > 0) {
+    const int32_t one[2] = {(int32_t)f0, (int32_t)(f0 + m)};
+    if ((rc = knn_cov_launch(s, g, o->d_xyz, one, 1, nullptr, P.gicp.k, P.gicp.plane_epsilon, o->d_cov, nullptr, true))) return rc;
+    float ms = 0.0f;
+    SSLAM_HIP_TRY(hipEventElapsedTime(&ms, s->f_e0, s->f_e1));
+    st.covariance_ms = (double)ms;
+    ++cov_passes;
+  } else {
+    SSLAM_HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  {
+    float ms = 0.0f;
+    SSLAM_HIP_TRY(hipEventElapsedTime(&ms, o->ev[0], o->ev[1]));
+    st.prefilter_ms = (double)ms;
+  }
+  double pose[12], T[12];
+  bool promote = false;
+  if (!o->has_kf) {                      // 2. the first keyframe
+    odom_identity(pose); odom_identity(T);
+    st.accepted = 1;
+    promote = true;
+  } else {                               // 3. the match: one pair of register_pairs over the arena
+    const int n_slot[2] = {fs == 0 ? m : o->kf_n, fs == 1 ? m : o->kf_n};
+    const int32_t starts[4] = {0, n_slot[0], (int32_t)o->cap, (int32_t)o->cap + n_slot[1]};   // clouds 0 and 2 are the slots, 1 is the gap
+    sslam_reg_pair pr;
+    pr.target = 2 * o->kf_slot; pr.source = 2 * fs;
+    for (int k = 0; k < 12; ++k) pr.T0[k] = o->prev[k];
+    pr.max_corr2 = P.max_correspondence_distance * P.max_correspondence_distance;
+    sslam_reg_result res;
+    memset(&res, 0, sizeof res);
+    if ((rc = register_pairs(s, nullptr, starts, 3, &pr, 1, nullptr, gicp ? &P.gicp : nullptr, P.max_iterations, P.epsilon, &res, nullptr, nullptr,
+                             &st.registration_ms, o->d_xyz, gicp ? o->d_cov : nullptr)) < 0) return rc;
+    st.matched = 1; st.iterations = res.iterations; st.converged = res.converged; st.status = res.status; st.used = res.used; st.fitness = res.score;
+    bool ok = res.status == 0;           // 4. hdl's hasConverged
+    if (ok && P.transform_thresholding) {   // 5.
+      double inv[12], delta[12];
+      odom_inverse(o->prev, inv);
+      odom_mul(inv, res.T, delta);
+      if (odom_trans(delta) > P.max_acceptable_trans || odom_angle(delta) > P.max_acceptable_angle) ok = false;
+    }
+    if (!ok) {
+      for (int k = 0; k < 12; ++k) T[k] = o->prev[k];
+      odom_mul(o->kf_pose, o->prev, pose);
+    } else {                             // 6.
+      for (int k = 0; k < 12; ++k) T[k] = res.T[k];
+      odom_mul(o->kf_pose, T, pose);
+      st.accepted = 1;
+      st.delta_trans = odom_trans(T);
+      st.delta_angle = odom_angle(T);
+      st.delta_time = ((double)stamp_sec - (double)o->kf_sec) + 1e-9 * ((double)stamp_nsec - (double)o->kf_nsec);
+      promote = st.delta_trans > P.keyframe_delta_trans || st.delta_angle > P.keyframe_delta_angle || st.delta_time > P.keyframe_delta_time;   // 7.
+    }
+  }
+  // nothing can fail from here on: the state changes
+  o->cov_passes = cov_passes;
+  if (st.accepted) for (int k = 0; k < 12; ++k) o->prev[k] = T[k];
+  if (promote) {
+    o->has_kf = true; o->kf_slot = fs; o->kf_n = m;
+    for (int k = 0; k < 12; ++k) o->kf_pose[k] = pose[k];
+    o->kf_sec = stamp_sec; o->kf_nsec = stamp_nsec;
+    odom_identity(o->prev);
+    ++o->keyframes;
+    st.new_keyframe = 1;
+  }
+  st.keyframes = o->keyframes;
+  st.covariance_passes = o->cov_passes;
+  for (int k = 0; k < 12; ++k) { pose_out[k] = pose[k]; st.T[k] = T[k]; }
+  st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  if (stats) *stats = st;
+  return 0;
+}
+int sslam_odom_keyframe(const sslam_odom* o, float* xyz_out, int max_out, double pose_out[12]) {
+  if (!o || max_out < 0 || (!xyz_out && max_out > 0)) return set_error(SSLAM_ERR_INVALID, "bad argument");
+  if (!o->has_kf) return 0;
+  if (pose_out) for (int k = 0; k < 12; ++k) pose_out[k] = o->kf_pose[k];
+  const int w = std::min(o->kf_n, max_out);
+  if (w > 0) {
+    SSLAM_HIP_TRY(hipSetDevice(seg_device_index(o->seg)));
+    SSLAM_HIP_TRY(hipMemcpy(xyz_out, o->d_xyz + (size_t)o->kf_slot * o->cap * 3, (size_t)w * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return o->kf_n;
 }
 
 void sslam_inf_default_params(sslam_inf_params* p) {

@@ -445,6 +445,35 @@ class PointCloudSegmentation:
                                                                         len(pts), md.ctypes.data))
         return out[:n], md[:len(pts)]
 
+    def radius_outlier_removal(self, xyz, radius: float = 0.8, min_neighbors: int = 2, max_out: int | None = None):
+        """``sslam_seg_radius_outlier_removal`` (pcl::RadiusOutlierRemoval, hdl's outlier_removal_method RADIUS): (ascending indices of the
+        points with at least ``min_neighbors`` other finite points within ``radius``, neighbour count per point, -1 for a non-finite one).
+        ``max_out`` caps the indices written; the true count is left in ``last_radius_count``."""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        cap = len(pts) if max_out is None else int(max_out)
+        out = np.zeros(max(cap, 1), np.int32); cnt = np.zeros(max(len(pts), 1), np.int32)
+        buf = pts if len(pts) else np.zeros((1, 3), np.float32)
+        n = self._check(self._lib.sslam_seg_radius_outlier_removal(self._h, buf.ctypes.data, len(pts), float(radius), int(min_neighbors),
+                                                                   out.ctypes.data, cap, cnt.ctypes.data))
+        self.last_radius_count = n
+        return out[:min(n, cap)], cnt[:len(pts)]
+
+    def prefilter(self, xyz, params=None, max_out: int | None = None, **kw):
+        """``sslam_seg_prefilter``: hdl's prefiltering chain (distance filter, downsample, outlier removal) on one upload, the intermediate
+        clouds resident on the device.  ``params``: a ``PrefilterParams`` (odometry.py), or None with the fields to change as keywords.
+        Returns (filtered cloud [m, 3] float32, counts after each stage [3] int32); the hipEvent time is left in ``last_prefilter_ms``."""
+        from .odometry import prefilter_params
+        p = params if params is not None else prefilter_params(**kw)
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        cap = len(pts) if max_out is None else int(max_out)
+        out = np.zeros((max(cap, 1), 3), np.float32); counts = np.zeros(3, np.int32)
+        ms = C.c_double(0)
+        m = self._check(self._lib.sslam_seg_prefilter(self._h, pts.ctypes.data if len(pts) else None, len(pts), C.addressof(p), out.ctypes.data, cap,
+                                                      counts.ctypes.data, C.byref(ms)))
+        self.last_prefilter_ms = ms.value
+        self.last_prefilter_count = m
+        return out[:min(m, cap)], counts
+
     def computeKmeans(self, points, num_centroids: int, seed: int = 0):
         """plane_segmentation::computeKmeans (plane_segmentation.cpp:524-535) -> (labels, centroids, compactness)"""
         pts = np.ascontiguousarray(points, np.float32)
